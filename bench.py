@@ -6,12 +6,20 @@
 
 One "step" = forward -> 0.4*CE + 0.6*Dice -> backward (-> RCCL all-reduce) -> SGD(momentum) update on a synthetic
 224x224 9-class minibatch of 24 images per GPU (BASELINE.json configs[1]; weak scaling), fp32, inputs resident in HBM.
-Rank 0 prints ONE JSON line.  At N=1 it also carries
+Rank 0 prints ONE JSON line.  A plain run measures the headline and nothing else: set-up, `--warmup` untimed steps, exactly
+`--steps` timed steps, the line.  `--dump-outputs DIR` then writes what the last timed step computed as DIR/<name>.npy
+(float32): "loss" = the [loss, ce, dice] the step returns, "params" / "grads" = the same fixed seeded sample of positions of
+the flat weight buffer after the update and of the flat gradient buffer the update read.  Inputs are seeded, so two builds
+given the same arguments can be compared file for file.
+With --full, at N=1 the line also carries
   * "roofline": the stripe-attention kernels (the kernels north_star names), timed live with HIP events on the launch
     stream, algorithmic FLOPs from SURVEY.md 8(d): 4*L*N*C per block per image forward, x2 more for backward;
   * "roofline_dominant_by_time": the same measurement for the GEMM family (every Linear of the 26 blocks, fwd + dgrad +
     wgrad), which is ~73 % of the step;
-  * "cpu_baseline": the CPU oracle's identical training step timed on this host's cores (kind "port").
+  * "cpu_baseline": the CPU oracle's identical training step timed on this host's cores (kind "port");
+  * "bf16_mode": the same workload in the bf16 matmul mode (headline configuration only);
+and at N>1 "dp_diagnostics" (five instrumented steps after the timed region).  --skip-roofline / --skip-cpu / --skip-bf16 drop
+single parts of a --full run.
 """
 import argparse
 import json
@@ -259,6 +267,27 @@ def _median(v):
     return 0.5 * (v[(n - 1) // 2] + v[n // 2])
 
 
+DUMP_SAMPLE = 1 << 22        # positions kept of each flat buffer: 2 x 16 MB of float32, inside the 64 MB a dump may take
+
+
+def dump_outputs(trainer, stats, out_dir):
+    """--dump-outputs: the last timed step's results as float32 .npy files (see the module docstring).  The sampled positions
+    depend only on the buffer length (seed 0), so runs with the same arguments dump the same positions."""
+    import numpy as np
+    opt = trainer.engine.opt
+    idx = None
+    if opt.numel > DUMP_SAMPLE:
+        g = torch.Generator().manual_seed(0)
+        idx = torch.randperm(opt.numel, generator=g)[:DUMP_SAMPLE].sort().values.to(opt.flat_param.device)
+    arrays = {"loss": stats, "params": opt.flat_param, "grads": opt.flat_grad}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        if idx is not None and name != "loss":
+            t = t[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+    log(f"[bench] outputs of the last timed step written to {out_dir}: {', '.join(arrays)}")
+
+
 def bf16_mode_line(args, config, num_classes, dev):
     """BASELINE configs[2]'s per-GPU workload (same model, batch and step; bf16 MFMA for every Linear / conv and the attention
     products, bf16 block activations and weight shadow, fp32 accumulation / residual stream / statistics / master weights) for 20
@@ -307,7 +336,15 @@ def main():
                          "for every Linear / conv, block activations and a weight shadow stored as bf16, fp32 accumulation, "
                          "residual stream, attention arithmetic, statistics and master weights")
     ap.add_argument("--img-size", type=int, default=None, help="override DATA.IMG_SIZE (384 uses split [1,2,12,12])")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the secondary measurements: attention / GEMM-family rooflines, the bf16-mode "
+                         "line and the CPU-oracle baseline at N=1, per-phase data-parallel diagnostics at N>1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss statistics and seeded samples of the updated weights and the gradients "
+                         "as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(_spawn_ranks(args.gpus, sys.argv[1:]))
@@ -347,8 +384,10 @@ def main():
     elapsed, step_ms, stats = _timed_steps(trainer, img, lab, args.steps, args.warmup, world, dev)
     loss = [float(v) for v in stats.tolist()]
     log(f"[bench] timed region done: {elapsed / args.steps * 1e3:.3f} ms/step")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(trainer, stats, args.dump_outputs)
     dp_diag = None
-    if world > 1:
+    if world > 1 and args.full:
         # outside the timed region: five more steps with a HIP event after every backward phase, around the wait for the
         # collectives and after the update, so that one multi-GPU run says where its time went (rank 0's view)
         trainer.enable_timing()
@@ -379,17 +418,18 @@ def main():
                                "shallow encoder; each phase's gradient buckets go on the wire when it ends), the time the compute stream then "
                                "waited for the collectives (+ bf16 unpack), and the SGD update")
             out["dp_diagnostics"] = dp_diag
-        if world == 1 and not args.skip_roofline:
+        extras = world == 1 and args.full
+        if extras and not args.skip_roofline:
             log("[bench] attention roofline sub-benchmark ...")
             out["roofline"] = attention_roofline(args.batch, config.MODEL.CSWIN, config.DATA.IMG_SIZE, bf16=args.matmul == "bf16")
             if args.matmul == "fp32":
                 log("[bench] GEMM family roofline sub-benchmark ...")
                 out["roofline_dominant_by_time"] = gemm_family_roofline(args.batch, config.MODEL.CSWIN, config.DATA.IMG_SIZE)
-        if world == 1 and headline and args.matmul == "fp32" and not args.skip_bf16:
+        if extras and headline and args.matmul == "fp32" and not args.skip_bf16:
             log("[bench] bf16 mode (BASELINE configs[2] per-GPU workload), 20 steps ...")
             del trainer
             out["bf16_mode"] = bf16_mode_line(args, config, num_classes, dev)
-        if world == 1 and not args.skip_cpu:
+        if extras and not args.skip_cpu:
             out["cpu_baseline"] = cpu_baseline(args.cpu_batch)
         print(json.dumps(out), flush=True)
     if world > 1:
