@@ -5,20 +5,16 @@ current stream.  All arithmetic of the hot path happens in libcswin_hip.so.  Eve
 CswinHipError on a non-HIP tensor -- there is no CPU / eager fallback.
 """
 import ctypes
+import math
 
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from ._lib import ReduceJob, WgradDesc, act_bf16, call, dev_f32, lib, precision, ptr, shadow_ptr, stream
+from ._lib import CswinHipError, ReduceJob, WgradDesc, act_bf16, call, dev_f32, lib, precision, ptr, shadow_ptr, stream
 
 __all__ = ["layer_norm", "linear", "linear_pair", "mlp", "stripe_attention", "cswin_block", "conv_tokens", "patch_embed_conv", "carafe_reassemble",
            "tokens_to_nchw", "matmul_nn", "ce_dice_loss", "dropout", "img2windows", "windows2img"]
-
-
-def join_wgrad_stream():
-    """Kept for callers of round-2 code: weight gradients run on the calling stream (the side-stream variants measured slower
-    under hipGraphs and were removed in round 3), so there is nothing to join."""
 
 
 # ------------------------------------------------------------------------------------------------
@@ -28,108 +24,109 @@ def join_wgrad_stream():
 # default an op launches its own (a CSWinBlock: its six to eight in one launch) so that the gradient tensors it returns are
 # complete when autograd sees them (accumulation into an existing .grad, hooks).  Inside `engine_backward(opt)` -- the HipEngine
 # wraps each of its backward phases in it, and owns what happens to the gradients afterwards -- two things change:
-#   * the jobs are QUEUED and reduced when the context exits, one launch per 48 jobs instead of 77 launches of ~7 us per step
-#     (30 per-block batches + 47 stand-alone ones, most of that launch floor);
-#   * parameter gradients are WRITTEN IN PLACE into the optimiser's flat gradient buffer (the reduction's output pointer is the
-#     parameter's slot), so the pass that packed them afterwards (three launches, 2 x 94 MB per step) has nothing left to copy.
-# Both rely on nobody reading a returned gradient before the context exits and on .grad being None when the pass starts.
-_rq = {"on": False, "jobs": [], "keep": [], "slots": None}
+#   * gradients of opt's leaf parameters are WRITTEN IN PLACE into the optimiser's flat gradient buffer (the reduction's output
+#     pointer is the parameter's slot), so the pass that packed them afterwards (three launches, 2 x 94 MB per step) has nothing
+#     left to copy;
+#   * a reduction WAITS -- for a block-tail launch that carries it, or for the exit of the context: one launch per 48 jobs instead
+#     of 77 launches of ~7 us per step -- if and only if everything it writes lies inside that flat buffer.  Nothing in the pass
+#     reads a slot, and the buffer outlives the pass; any other output (a composed weight's gradient feeds the next backward node,
+#     a frozen parameter's is dropped by autograd at once) is reduced before the op returns.
+# Both rely on nobody reading opt.flat_grad before the context exits and on .grad being None when the pass starts.
 MAX_REDUCE_JOBS = 48
+TAIL_RIDER_JOBS = 16
 
 
 class engine_backward:
     """with engine_backward(opt): ... one backward pass whose parameter gradients go straight to opt.flat_grad and whose slab
-    reductions run once, at exit."""
+    reductions run late, at exit at the latest.  The ops talk to the innermost open pass (`_pass`); outside any, and for
+    engine_backward(None), that is a pass without a buffer: every gradient is a fresh tensor and no reduction waits."""
 
     def __init__(self, opt=None):
-        self.opt = opt
+        self._flat = opt.flat_grad if opt is not None else None
+        self._slots = {p.data_ptr(): (o, p.numel()) for p, o in zip(opt.params, opt.offsets)} if opt is not None else {}
+        self._queue = []             # (ReduceJob copy, the tensors it reads), oldest first
+        self._given = set()          # offsets of the slots handed out in this pass
 
     def __enter__(self):
-        self.prev = (_rq["on"], _rq["slots"])
-        _rq["on"] = True
-        if self.opt is not None:
-            base = self.opt.flat_grad
-            _rq["slots"] = (base, {p.data_ptr(): (o, p.numel()) for p, o in zip(self.opt.params, self.opt.offsets)})
+        global _pass
+        self._outer, _pass = _pass, self
         return self
 
     def __exit__(self, *exc):
-        _rq["on"], _rq["slots"] = self.prev
-        if exc[0] is None:
-            flush_reductions()
-        else:
-            _rq["jobs"], _rq["keep"] = [], []
+        global _pass
+        _pass = self._outer
+        if exc[0] is None:           # an exception drops the queue unlaunched
+            self.flush()
         return False
 
+    def grad(self, param_key, shape, device):
+        """The tensor a parameter gradient is written to: the parameter's slot of the flat gradient buffer if `param_key` (what
+        _param_keys() recorded in forward) is a leaf parameter of this pass's optimiser, a fresh tensor otherwise."""
+        n = math.prod(shape)
+        o, numel = self._slots.get(param_key, (0, -1)) if param_key else (0, -1)
+        if numel != n:
+            return torch.empty(tuple(shape), dtype=torch.float32, device=device)
+        if o in self._given:
+            raise CswinHipError(f"engine_backward: two ops of one backward pass use the leaf parameter at offset {o} of flat_grad; "
+                                f"the first gradient is already placed there and its reduction may still be waiting")
+        self._given.add(o)
+        return self._flat[o:o + n].view(shape)
 
-def flush_reductions():
-    jobs, _rq["jobs"] = _rq["jobs"], []
-    keep, _rq["keep"] = _rq["keep"], []
-    st = stream()
-    for i in range(0, len(jobs), MAX_REDUCE_JOBS):
-        chunk = jobs[i:i + MAX_REDUCE_JOBS]
-        arr = (ReduceJob * len(chunk))(*chunk)
-        call("cswin_rows_sum_multi", ctypes.cast(arr, ctypes.c_void_p), len(chunk), st)
-    del keep
+    def _in_flat(self, address):
+        return self._flat is not None and 0 <= address - self._flat.data_ptr() < 4 * self._flat.numel()
 
+    def reduce(self, jobs, reads):
+        """jobs: ReduceJob structs filled by entry points called with `deferred` (one that had nothing to reduce leaves its slot
+        zeroed); reads: the workspaces they read.  A job that writes nothing but flat_grad slots joins the queue, the others run
+        now, in one launch."""
+        now = []
+        for j in jobs:
+            if j.part and all(self._in_flat(a) for a in (j.out, j.out2) if a):
+                self._queue.append((ReduceJob.from_buffer_copy(j), reads))
+            elif j.part:
+                now.append(j)
+        if now:
+            arr = (ReduceJob * len(now))(*now)
+            call("cswin_rows_sum_multi", _job_ptr(arr), len(now), stream())
 
-TAIL_RIDER_JOBS = 16
+    def queued_outputs(self):
+        """Every address a waiting reduction will write."""
+        return [a for j, _ in self._queue for a in (j.out, j.out2) if a]
 
+    def take_pending(self, maxn=TAIL_RIDER_JOBS):
+        """Up to `maxn` waiting reductions (oldest first) for a launch that can carry them at the end of its grid
+        (cswin_linear_bwd_tail): (pointer to the jobs or None, count, owner).  They leave the queue: the caller holds `owner`
+        until that launch is enqueued; what the jobs read is released with it (the allocator reuses it in stream order)."""
+        taken, self._queue = self._queue[:maxn], self._queue[maxn:]
+        arr = (ReduceJob * len(taken))(*[j for j, _ in taken])
+        return (_job_ptr(arr) if taken else None), len(taken), (arr, taken)
 
-def take_pending_reductions(maxn=TAIL_RIDER_JOBS):
-    """Up to `maxn` queued reductions (oldest first) for a launch that can carry them at the end of its grid (cswin_linear_bwd_tail):
-    (ctypes array or None, count).  The workspaces they read stay in the queue's keep-alive list until the next flush."""
-    n = min(len(_rq["jobs"]), maxn) if _rq["on"] else 0
-    if n == 0:
-        return None, 0
-    chunk = _rq["jobs"][:n]
-    del _rq["jobs"][:n]
-    return (ReduceJob * n)(*chunk), n
-
-
-def _reduce_jobs(jobs, keep, leaf=True):
-    """jobs: ReduceJob structs filled by entry points called with `deferred`; keep: the workspaces they read.  leaf: every output
-    is the gradient of a leaf parameter (nothing else in this backward pass reads it), so the jobs may wait for the flush."""
-    jobs = [j for j in jobs if j.part]                    # an entry point that had nothing to reduce leaves its slot zeroed
-    if not jobs:
-        return
-    if not (leaf and _rq["on"]):                          # needed now (a composed weight's gradient feeds the next backward node)
-        arr = (ReduceJob * len(jobs))(*jobs)
-        call("cswin_rows_sum_multi", ctypes.cast(arr, ctypes.c_void_p), len(jobs), stream())
-        return
-    for j in jobs:
-        c = ReduceJob()
-        ctypes.memmove(ctypes.byref(c), ctypes.byref(j), ctypes.sizeof(ReduceJob))
-        _rq["jobs"].append(c)
-    _rq["keep"] += [t for t in keep if t is not None]
-
-
-def _all_leaf(*ts):
-    """True when every given tensor is a leaf of the autograd graph (a module parameter passed as it is, not a view or a
-    function of one): only then is its gradient final when the op returns it -- and nobody's input."""
-    return all(t is None or t.is_leaf for t in ts)
-
-
-def _grad_like(w, leaf=True):
-    """The tensor a parameter gradient is written to: the parameter's slot of the flat gradient buffer inside engine_backward (leaf
-    parameters only), a fresh tensor otherwise."""
-    return _grad_at(w.data_ptr() if leaf else 0, w.shape, w.device)
+    def flush(self):
+        while self._queue:
+            jobs, n, _owner = self.take_pending(MAX_REDUCE_JOBS)
+            call("cswin_rows_sum_multi", jobs, n, stream())
 
 
-def _grad_at(param_ptr, shape, device):
-    """Same for a parameter known by its address only (biases are not saved for backward; their data_ptr is; 0 = no slot)."""
-    slots = _rq["slots"]
-    if slots is not None and param_ptr:
-        n = 1
-        for d in shape:
-            n *= int(d)
-        hit = slots[1].get(param_ptr)
-        if hit is not None and hit[1] == n:
-            return slots[0][hit[0]:hit[0] + n].view(shape)
-    return torch.empty(tuple(shape), dtype=torch.float32, device=device)
+_pass = engine_backward()
 
 
-def _pptr(t):
-    return t.data_ptr() if t is not None else 0
+def _param_keys(*ts):
+    """Per parameter, what engine_backward.grad() finds its slot by: the address of a leaf of the autograd graph (a module
+    parameter passed as it is), 0 for anything else -- a view or a function of a parameter shares or lacks its address, but its
+    gradient is somebody's input, not final."""
+    return tuple(t.data_ptr() if t is not None and t.is_leaf else 0 for t in ts)
+
+
+def _job_ptr(jobs, i=0):
+    """Pointer to slot i of a ctypes array of ReduceJob."""
+    return ctypes.c_void_p(ctypes.addressof(jobs) + i * ctypes.sizeof(ReduceJob))
+
+
+def _fill_wgrad(d, dy, x, row_scale, dw, dbias, workspace, ws_bytes, rows_per_sample, M, N, K, io_bf16=0):
+    """One WgradDesc of cswin_linear_bwd_weight_batch / _tail.  workspace: device address."""
+    d.dy, d.x, d.row_scale, d.dw, d.dbias = (t.data_ptr() if t is not None else None for t in (dy, x, row_scale, dw, dbias))
+    d.workspace, d.ws_bytes, d.rows_per_sample, d.M, d.N, d.K = workspace, ws_bytes, rows_per_sample, M, N, K
+    d.precision, d.io_bf16 = precision(), io_bf16
 
 
 def _ws(nbytes, device):
@@ -158,8 +155,7 @@ class _LayerNorm(Function):
         rstd = torch.empty_like(mean)
         call("cswin_layernorm_fwd", ptr(x), ptr(gamma), ptr(beta), ptr(y), ptr(mean), ptr(rstd), M, C, eps, 0, stream())
         ctx.save_for_backward(x, gamma, mean, rstd)
-        ctx.leaf = _all_leaf(gamma, beta)
-        ctx.beta_ptr = _pptr(beta) if ctx.leaf else 0
+        ctx.keys = _param_keys(gamma, beta)
         return y
 
     @staticmethod
@@ -170,14 +166,13 @@ class _LayerNorm(Function):
         C = x.shape[-1]
         M = x.numel() // C
         dx = torch.empty_like(x)
-        dg = _grad_like(gamma, ctx.leaf)
-        db = _grad_at(ctx.beta_ptr, gamma.shape, gamma.device)
+        dg, db = (_pass.grad(k, gamma.shape, gamma.device) for k in ctx.keys)
         nbytes = lib().cswin_layernorm_bwd_workspace(M, C)
         ws = _ws(nbytes, x.device)
         job = (ReduceJob * 1)()
         call("cswin_layernorm_bwd", ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), None, ptr(dx), ptr(dg), ptr(db),
-             ptr(ws), nbytes, M, C, ctypes.cast(job, ctypes.c_void_p), None, stream())
-        _reduce_jobs(job, (ws,), ctx.leaf)
+             ptr(ws), nbytes, M, C, _job_ptr(job), None, stream())
+        _pass.reduce(job, (ws,))
         return dx, dg, db, None
 
 
@@ -239,8 +234,7 @@ class _Linear(Function):
         call("cswin_linear_fwd", ptr(x), ptr(x2), K1 if x2 is not None else 0, pw, ptr(b), ptr(y), None, ptr(residual),
              ptr(row_scale), rps, M, N, K, precision(), fw, stream())
         ctx.save_for_backward(x, w, x2, row_scale)
-        ctx.leaf = _all_leaf(w, b)
-        ctx.has_bias, ctx.has_res, ctx.rps, ctx.bias_ptr = b is not None, residual is not None, rps, _pptr(b) if ctx.leaf else 0
+        ctx.has_bias, ctx.has_res, ctx.rps, ctx.keys = b is not None, residual is not None, rps, _param_keys(w, b)
         return y
 
     @staticmethod
@@ -260,15 +254,14 @@ class _Linear(Function):
             call("cswin_linear_bwd_data", ptr(dy), pw, ptr(dx), ptr(dx2), K1 if x2 is not None else 0, None,
                  ptr(row_scale), ctx.rps, None, M, N, K, precision(), fw, stream())
         if need[1]:
-            if True:
-                dw = _grad_like(w, ctx.leaf)
-                db = _grad_at(ctx.bias_ptr, (N,), w.device) if ctx.has_bias else None
-                nbytes = lib().cswin_linear_bwd_weight_workspace(M, N, K)
-                ws = _ws(nbytes, w.device)
-                job = (ReduceJob * 1)()
-                call("cswin_linear_bwd_weight", ptr(dy), ptr(x), ptr(x2), K1 if x2 is not None else 0, ptr(row_scale), ctx.rps,
-                     ptr(dw), ptr(db), ptr(ws), nbytes, M, N, K, ctypes.cast(job, ctypes.c_void_p), precision(), stream())
-                _reduce_jobs(job, (ws,), ctx.leaf)
+            dw = _pass.grad(ctx.keys[0], w.shape, w.device)
+            db = _pass.grad(ctx.keys[1], (N,), w.device) if ctx.has_bias else None
+            nbytes = lib().cswin_linear_bwd_weight_workspace(M, N, K)
+            ws = _ws(nbytes, w.device)
+            job = (ReduceJob * 1)()
+            call("cswin_linear_bwd_weight", ptr(dy), ptr(x), ptr(x2), K1 if x2 is not None else 0, ptr(row_scale), ctx.rps,
+                 ptr(dw), ptr(db), ptr(ws), nbytes, M, N, K, _job_ptr(job), precision(), stream())
+            _pass.reduce(job, (ws,))
         dres = dy if ctx.has_res else None
         return dx, dw, db, dx2, dres, None
 
@@ -296,8 +289,7 @@ class _LinearPair(Function):
             ys.append(y)
         ctx.save_for_backward(x, w1, w2)
         ctx.has_b = (b1 is not None, b2 is not None)
-        ctx.leaf = _all_leaf(w1, b1, w2, b2)
-        ctx.bias_ptrs = (_pptr(b1), _pptr(b2)) if ctx.leaf else (0, 0)
+        ctx.keys = _param_keys(w1, b1, w2, b2)
         return tuple(ys)
 
     @staticmethod
@@ -317,17 +309,15 @@ class _LinearPair(Function):
         wg, jobs = (WgradDesc * 2)(), (ReduceJob * 2)()
         for i, (dy, w, has_b) in enumerate(((dy1, w1, ctx.has_b[0]), (dy2, w2, ctx.has_b[1]))):
             N = w.shape[0]
-            dw = _grad_like(w, ctx.leaf)
-            db = _grad_at(ctx.bias_ptrs[i], (N,), w.device) if has_b else None
+            dw = _pass.grad(ctx.keys[2 * i], w.shape, w.device)
+            db = _pass.grad(ctx.keys[2 * i + 1], (N,), w.device) if has_b else None
             nbytes = lib().cswin_linear_bwd_weight_workspace(M, N, K)
             ws = _ws(nbytes, w.device)
             keep.append(ws)
-            wg[i].dy, wg[i].x, wg[i].row_scale, wg[i].dw = dy.data_ptr(), x.data_ptr(), None, dw.data_ptr()
-            wg[i].dbias, wg[i].workspace, wg[i].ws_bytes = (db.data_ptr() if has_b else None), ws.data_ptr(), nbytes
-            wg[i].rows_per_sample, wg[i].M, wg[i].N, wg[i].K, wg[i].precision = 1, M, N, K, precision()
+            _fill_wgrad(wg[i], dy, x, None, dw, db, ws.data_ptr(), nbytes, 1, M, N, K)
             grads += [dw, db]
-        call("cswin_linear_bwd_weight_batch", ctypes.cast(wg, ctypes.c_void_p), 2, ctypes.cast(jobs, ctypes.c_void_p), None, 0, st)
-        _reduce_jobs(jobs, keep, ctx.leaf)
+        call("cswin_linear_bwd_weight_batch", ctypes.cast(wg, ctypes.c_void_p), 2, _job_ptr(jobs), None, 0, st)
+        _pass.reduce(jobs, keep)
         return (dx,) + tuple(grads)
 
 
@@ -363,8 +353,7 @@ class _Mlp(Function):
                  M, N, Hd, precision(), f2, stream())
         ctx.save_for_backward(x, w1, w2, pre, act, row_scale)
         ctx.has_res, ctx.rps, ctx.has_b1, ctx.has_b2 = residual is not None, rps, b1 is not None, b2 is not None
-        ctx.leaf = _all_leaf(w1, b1, w2, b2)
-        ctx.bias_ptrs = (_pptr(b1), _pptr(b2)) if ctx.leaf else (0, 0)
+        ctx.keys = _param_keys(w1, b1, w2, b2)
         ctx.drop = (float(drop_p), seeds)
         return y
 
@@ -394,19 +383,20 @@ class _Mlp(Function):
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             call("cswin_linear_bwd_data", ptr(dpre), ptr(w1), ptr(dx), None, 0, None, None, 1, None, M, Hd, K, precision(), 0, st)
-        if True:                                                # both weight gradients
-            dw2 = _grad_like(w2, ctx.leaf)
-            db2 = _grad_at(ctx.bias_ptrs[1], (N,), dev) if ctx.has_b2 else None
-            nbytes = max(lib().cswin_linear_bwd_weight_workspace(M, N, Hd), lib().cswin_linear_bwd_weight_workspace(M, Hd, K))
-            ws, ws1 = _ws(nbytes, dev), _ws(nbytes, dev)
-            jobs = (ReduceJob * 2)()
-            call("cswin_linear_bwd_weight", ptr(dyl), ptr(act), None, 0, ptr(rs_gemm), ctx.rps, ptr(dw2), ptr(db2), ptr(ws),
-                 nbytes, M, N, Hd, ctypes.cast(ctypes.byref(jobs[0]), ctypes.c_void_p), precision(), stream())
-            dw1 = _grad_like(w1, ctx.leaf)
-            db1 = _grad_at(ctx.bias_ptrs[0], (Hd,), dev) if ctx.has_b1 else None
-            call("cswin_linear_bwd_weight", ptr(dpre), ptr(x), None, 0, None, 1, ptr(dw1), ptr(db1), ptr(ws1), nbytes, M, Hd, K,
-                 ctypes.cast(ctypes.byref(jobs[1]), ctypes.c_void_p), precision(), stream())
-            _reduce_jobs(jobs, (ws, ws1), ctx.leaf)
+        # both weight gradients
+        k1, kb1, k2, kb2 = ctx.keys
+        dw2 = _pass.grad(k2, w2.shape, dev)
+        db2 = _pass.grad(kb2, (N,), dev) if ctx.has_b2 else None
+        nbytes = max(lib().cswin_linear_bwd_weight_workspace(M, N, Hd), lib().cswin_linear_bwd_weight_workspace(M, Hd, K))
+        ws, ws1 = _ws(nbytes, dev), _ws(nbytes, dev)
+        jobs = (ReduceJob * 2)()
+        call("cswin_linear_bwd_weight", ptr(dyl), ptr(act), None, 0, ptr(rs_gemm), ctx.rps, ptr(dw2), ptr(db2), ptr(ws),
+             nbytes, M, N, Hd, _job_ptr(jobs, 0), precision(), stream())
+        dw1 = _pass.grad(k1, w1.shape, dev)
+        db1 = _pass.grad(kb1, (Hd,), dev) if ctx.has_b1 else None
+        call("cswin_linear_bwd_weight", ptr(dpre), ptr(x), None, 0, None, 1, ptr(dw1), ptr(db1), ptr(ws1), nbytes, M, Hd, K,
+             _job_ptr(jobs, 1), precision(), stream())
+        _pass.reduce(jobs, (ws, ws1))
         return dx, dw1, db1, dw2, db2, (dy if ctx.has_res else None), None, None, None
 
 
@@ -463,8 +453,8 @@ class _MatmulNN(Function):
         ws = _ws(nbytes, a.device)
         job = (ReduceJob * 1)()
         call("cswin_linear_bwd_weight", ptr(a), ptr(dc), None, 0, None, 1, ptr(db), None, ptr(ws), nbytes, M, N, K,
-             ctypes.cast(job, ctypes.c_void_p), precision(), stream())
-        _reduce_jobs(job, (ws,), False)
+             _job_ptr(job), precision(), stream())
+        _pass.reduce(job, (ws,))
         return da, db
 
 
@@ -495,7 +485,7 @@ class _StripeAttention(Function):
              _int_array(heads), _int_array(idx), split, float(scale or 0.0), drop[0], drop[1], ptr(dropout_epoch(qkv.device)) if drop[0] > 0 else None,
              int(q16), stream())
         ctx.save_for_backward(qkv, lse, y0, *ws_, *bs_)
-        ctx.leaf = _all_leaf(*wb)
+        ctx.keys = _param_keys(*wb)
         ctx.meta = (reso, split, tuple(idx), tuple(heads), float(scale or 0.0), drop)
         return y
 
@@ -510,16 +500,16 @@ class _StripeAttention(Function):
         B, L, C3 = qkv.shape
         C = C3 // 3
         dqkv = torch.empty_like(qkv)
-        dws = [_grad_like(w, ctx.leaf) for w in ws_]
-        dbs = [_grad_like(b, ctx.leaf) for b in bs_]
+        dws = [_pass.grad(k, t.shape, t.device) for k, t in zip(ctx.keys[:nb], ws_)]
+        dbs = [_pass.grad(k, t.shape, t.device) for k, t in zip(ctx.keys[nb:], bs_)]
         ha, ia = _int_array(heads), _int_array(idx)
         nbytes = lib().cswin_attn_bwd_workspace(B, reso, C, nb, ha, ia, split)
         ws = _ws(nbytes, qkv.device)
         jobs = (ReduceJob * 2)()
         call("cswin_attn_bwd", ptr(qkv), _ptr_array(ws_), _ptr_array(bs_), ptr(lse), ptr(y0), ptr(dy), ptr(dqkv), _ptr_array(dws),
-             _ptr_array(dbs), ptr(ws), nbytes, B, reso, C, nb, ha, ia, split, scale, ctypes.cast(jobs, ctypes.c_void_p), drop[0], drop[1],
+             _ptr_array(dbs), ptr(ws), nbytes, B, reso, C, nb, ha, ia, split, scale, _job_ptr(jobs), drop[0], drop[1],
              ptr(dropout_epoch(qkv.device)) if drop[0] > 0 else None, int(qkv.dtype == torch.bfloat16), stream())
-        _reduce_jobs(jobs, [ws], ctx.leaf)
+        _pass.reduce(jobs, (ws,))
         return (dqkv, None, None, None, None, None, None) + tuple(d.view(d.shape[0], 1, 3, 3) for d in dws) + tuple(dbs)
 
 
@@ -588,8 +578,7 @@ class _CSWinBlock(Function):
         call("cswin_linear_fwd", ptr(act), None, 0, p2, ptr(bb2), ptr(y), None, ptr(x1), ptr(rs2), L, M, C, Hd, precision(), io_x | f2, st)
         ctx.save_for_backward(x, m1, r1, h1, qkv, lse, att, att0, x1, m2, r2, h2, pre, act, rs1, rs2, g1, wqkv, wp, g2, w1, w2, *lw, *lb)
         ctx.meta = (reso, split, tuple(idx), tuple(heads), float(scale or 0.0), bqkv is not None, s16, drop)
-        ctx.leaf = _all_leaf(g1, b1, wqkv, bqkv, wp, bp, g2, b2, w1, bb1, w2, bb2, *lepe)
-        ctx.bptrs = tuple(_pptr(t) if ctx.leaf else 0 for t in (b1, bqkv, bp, b2, bb1, bb2))     # parameters that are not saved: where their gradients go
+        ctx.keys = _param_keys(g1, b1, wqkv, bqkv, wp, bp, g2, b2, w1, bb1, w2, bb2, *lepe)
         return y
 
     @staticmethod
@@ -612,7 +601,6 @@ class _CSWinBlock(Function):
         ws = _ws(sum(sizes), dev)
         wsp = [ctypes.c_void_p(ws.data_ptr() + sum(sizes[:i])) for i in range(6)]
         jobs = (ReduceJob * 8)()
-        J = lambda i: ctypes.cast(ctypes.byref(jobs[i]), ctypes.c_void_p)
         (pq, fq), (pp, fp), (p1, f1), (p2, f2) = [_wsrc(w) if s16 else (ptr(w), 0) for w in (wqkv, wp, w1, w2)]
         E16 = lambda *shape: torch.empty(*shape, dtype=torch.bfloat16, device=dev)
         dy16 = _twin_take(dy) if s16 else None          # rounded copy of dy left by the backward that produced it (see _twins)
@@ -624,65 +612,62 @@ class _CSWinBlock(Function):
         wg = (WgradDesc * 4)()
 
         def defer_wgrad(slot, dy_, x_, rs_, dw_, db_, wsi, N_, K_, io=0):
-            wg[slot].io_bf16 = io if s16 else 0
-            wg[slot].dy, wg[slot].x, wg[slot].row_scale = dy_.data_ptr(), x_.data_ptr(), (rs_.data_ptr() if rs_ is not None else None)
-            wg[slot].dw, wg[slot].dbias = dw_.data_ptr(), (db_.data_ptr() if db_ is not None else None)
-            wg[slot].workspace, wg[slot].ws_bytes = wsp[wsi].value, sizes[wsi]
-            wg[slot].rows_per_sample, wg[slot].M, wg[slot].N, wg[slot].K, wg[slot].precision = L, M, N_, K_, precision()
+            _fill_wgrad(wg[slot], dy_, x_, rs_, dw_, db_, wsp[wsi].value, sizes[wsi], L, M, N_, K_, io if s16 else 0)
 
-        pb1, pbqkv, pbp, pb2, pbb1, pbb2 = ctx.bptrs
-        leaf = ctx.leaf
-        dw2, db2 = _grad_like(w2, leaf), _grad_at(pbb2, (C,), dev)
+        kg1, kb1, kwqkv, kbqkv, kwp, kbp, kg2, kb2, kw1, kbb1, kw2, kbb2, *klepe = ctx.keys
+        G = lambda key, *shape: _pass.grad(key, shape, dev)
+        dw2, db2 = G(kw2, *w2.shape), G(kbb2, C)
         if dy16 is not None:
             defer_wgrad(0, dy16, act, rs2, dw2, db2, 0, C, Hd, io=3)   # dy's twin and x = act are stored as bf16
         else:
             defer_wgrad(0, dy, act, rs2, dw2, db2, 0, C, Hd, io=2)     # x = act is stored as bf16
-        dw1, db1 = _grad_like(w1, leaf), _grad_at(pbb1, (Hd,), dev)
+        dw1, db1 = G(kw1, *w1.shape), G(kbb1, Hd)
         defer_wgrad(1, dpre, h2, None, dw1, db1, 1, Hd, C, io=3)        # dy = dpre and x = h2 are stored as bf16
         dh2 = torch.empty_like(x)                                      # fp32 (x is)
         call("cswin_linear_bwd_data", ptr(dpre), p1, ptr(dh2), None, 0, None, None, 1, None, M, Hd, C, precision(), (1 if s16 else 0) | f1, st)
-        dx1, dg2, dbt2 = torch.empty_like(x), _grad_like(g2, leaf), _grad_at(pb2, (C,), dev)
+        dx1, dg2, dbt2 = torch.empty_like(x), G(kg2, C), G(kb2, C)
         dx1_16 = E16(B, L, C) if s16 else None                         # the GEMMs below read the twin, the residual path dx1
         call("cswin_layernorm_bwd", ptr(dh2), ptr(x1), ptr(m2), ptr(r2), ptr(g2), ptr(dy), ptr(dx1), ptr(dg2), ptr(dbt2), wsp[2],
-             sizes[2], M, C, J(2), ptr(dx1_16), st)
+             sizes[2], M, C, _job_ptr(jobs, 2), ptr(dx1_16), st)
         # ---- attention branch ----
         datt = dh2                                                     # reuse
         call("cswin_linear_bwd_data", ptr(dx1_16 if s16 else dx1), pp, ptr(datt), None, 0, None, ptr(rs1), L, None, M, C, C, precision(),
              fp | (1 if s16 else 0), st)
-        dwp, dbp = _grad_like(wp, leaf), _grad_at(pbp, (C,), dev)
+        dwp, dbp = G(kwp, *wp.shape), G(kbp, C)
         defer_wgrad(2, dx1_16 if s16 else dx1, att, rs1, dwp, dbp, 3, C, C, io=3)      # dx1's twin and x = att are stored as bf16
         dqkv = torch.empty_like(qkv)
-        dlw = [_grad_like(t, leaf) for t in lw]
-        dlb = [_grad_like(t, leaf) for t in lb]
+        dlw = [G(k, *t.shape) for k, t in zip(klepe[:nb], lw)]
+        dlb = [G(k, *t.shape) for k, t in zip(klepe[nb:], lb)]
         ha, ia = _int_array(heads), _int_array(idx)
         naw = h.cswin_attn_bwd_workspace(B, reso, C, nb, ha, ia, split)
         aws = _ws(naw, dev)
         call("cswin_attn_bwd", ptr(qkv), _ptr_array(lw), _ptr_array(lb), ptr(lse), ptr(att0), ptr(datt), ptr(dqkv),
-             _ptr_array(dlw), _ptr_array(dlb), ptr(aws), naw, B, reso, C, nb, ha, ia, split, scale, J(6), drop[0], drop[1],
+             _ptr_array(dlw), _ptr_array(dlb), ptr(aws), naw, B, reso, C, nb, ha, ia, split, scale, _job_ptr(jobs, 6), drop[0], drop[1],
              ptr(dropout_epoch(dev)) if drop[0] > 0 else None, 7 if s16 else 0, st)
-        dwqkv = _grad_like(wqkv, leaf)
-        dbqkv = _grad_at(pbqkv, (3 * C,), dev) if has_qkv_bias else None
+        dwqkv = G(kwqkv, *wqkv.shape)
+        dbqkv = G(kbqkv, 3 * C) if has_qkv_bias else None
         defer_wgrad(3, dqkv, h1, None, dwqkv, dbqkv, 4, 3 * C, C, io=3)  # dy = dqkv and x = h1 are stored as bf16
         wjobs = (ReduceJob * 4)()
         dh1 = datt                                                     # reuse again
-        pend, npend = take_pending_reductions()              # the previous blocks' slab reductions ride at the end of this grid
-        pend = ctypes.cast(pend, ctypes.c_void_p) if npend else None
+        # the previous blocks' slab reductions ride at the end of this grid; `riders` owns them and what they read until the
+        # launch is enqueued (the end of this function)
+        pend, npend, riders = _pass.take_pending()
         if precision() == 0:
             # fp32: the qkv data gradient rides in the weight-gradient batch's launch as well (both only wait for dqkv)
             call("cswin_linear_bwd_tail", ptr(dqkv), pq, ptr(dh1), M, 3 * C, C, ctypes.cast(wg, ctypes.c_void_p), 4,
-                 ctypes.cast(wjobs, ctypes.c_void_p), pend, npend, st)
+                 _job_ptr(wjobs), pend, npend, st)
         else:
-            call("cswin_linear_bwd_weight_batch", ctypes.cast(wg, ctypes.c_void_p), 4, ctypes.cast(wjobs, ctypes.c_void_p), pend, npend, st)
+            call("cswin_linear_bwd_weight_batch", ctypes.cast(wg, ctypes.c_void_p), 4, _job_ptr(wjobs), pend, npend, st)
             call("cswin_linear_bwd_data", ptr(dqkv), pq, ptr(dh1), None, 0, None, None, 1, None, M, 3 * C, C, precision(), (1 if s16 else 0) | fq, st)
         for slot, ji in enumerate((0, 1, 3, 4)):
             jobs[ji] = wjobs[slot]
-        dx, dg1, dbt1 = torch.empty_like(x), _grad_like(g1, leaf), _grad_at(pb1, (C,), dev)
+        dx, dg1, dbt1 = torch.empty_like(x), G(kg1, C), G(kb1, C)
         dx16 = E16(B, L, C) if s16 else None
         call("cswin_layernorm_bwd", ptr(dh1), ptr(x), ptr(m1), ptr(r1), ptr(g1), ptr(dx1), ptr(dx), ptr(dg1), ptr(dbt1), wsp[5],
-             sizes[5], M, C, J(5), ptr(dx16), st)
+             sizes[5], M, C, _job_ptr(jobs, 5), ptr(dx16), st)
         if s16:
             _twin_put(dx, dx16)
-        _reduce_jobs(jobs, [ws, aws], leaf)
+        _pass.reduce(jobs, (ws, aws))
         grads = (dx, None, None, None, None, None, None, None, None, None, None, dg1, dbt1, dwqkv, dbqkv, dwp, dbp, dg2, dbt2, dw1, db1,
                  dw2, db2)
         return grads + tuple(d.view(d.shape[0], 1, 3, 3) for d in dlw) + tuple(dlb)
@@ -723,8 +708,7 @@ class _ConvTokens(Function):
         call("cswin_conv_tok_fwd", ptr(x), ptr(wp), ptr(b), ptr(y), B, H, W, Cin, Cout, ks, stride, pad, precision(), stream())
         ctx.save_for_backward(x, w, wpt)
         ctx.meta = (H, W, stride, pad, b is not None)
-        ctx.leaf = _all_leaf(w, b)
-        ctx.bias_ptr = _pptr(b) if ctx.leaf else 0
+        ctx.keys = _param_keys(w, b)
         return y
 
     @staticmethod
@@ -749,15 +733,14 @@ class _ConvTokens(Function):
                 if wpt is None:
                     _, wpt = _permute_w(w, Cin, True)
                 call("cswin_conv_tok_bwd_data", ptr(dy), ptr(wpt), ptr(dx), B, H, W, Cin, Cout, ks, stride, pad, precision(), st)
-        if True:
-            dw = _grad_like(w, ctx.leaf)                # written in the parameter layout by the slab reduction itself
-            db = _grad_at(ctx.bias_ptr, (Cout,), x.device) if has_b else None
-            nbytes = lib().cswin_conv_tok_bwd_weight_workspace(B, H, W, Cin, Cout, ks, stride, pad)
-            ws = _ws(nbytes, x.device)
-            job = (ReduceJob * 1)()
-            call("cswin_conv_tok_bwd_weight", ptr(dy), ptr(x), ptr(dw), ptr(db), ptr(ws), nbytes, B, H, W, Cin, Cout, ks,
-                 stride, pad, 1, ctypes.cast(job, ctypes.c_void_p), precision(), stream())
-            _reduce_jobs(job, (ws,), ctx.leaf)
+        dw = _pass.grad(ctx.keys[0], w.shape, x.device)      # written in the parameter layout by the slab reduction itself
+        db = _pass.grad(ctx.keys[1], (Cout,), x.device) if has_b else None
+        nbytes = lib().cswin_conv_tok_bwd_weight_workspace(B, H, W, Cin, Cout, ks, stride, pad)
+        ws = _ws(nbytes, x.device)
+        job = (ReduceJob * 1)()
+        call("cswin_conv_tok_bwd_weight", ptr(dy), ptr(x), ptr(dw), ptr(db), ptr(ws), nbytes, B, H, W, Cin, Cout, ks,
+             stride, pad, 1, _job_ptr(job), precision(), stream())
+        _pass.reduce(job, (ws,))
         return dx, dw, db, None, None, None, None
 
 
@@ -784,8 +767,7 @@ class _PatchEmbedConv(Function):
         call("cswin_conv_tok_fwd", ptr(x), ptr(wp), ptr(b), ptr(y), B, H, W, cpad, Cout, ks, stride, pad, precision(), st)
         ctx.save_for_backward(x, w)
         ctx.meta = (H, W, stride, pad, cpad, b is not None)
-        ctx.leaf = _all_leaf(w, b)
-        ctx.bias_ptr = _pptr(b) if ctx.leaf else 0
+        ctx.keys = _param_keys(w, b)
         return y
 
     @staticmethod
@@ -798,12 +780,12 @@ class _PatchEmbedConv(Function):
         Cout, Cin, ks, _ = w.shape
         st = stream()
         dwp = torch.empty(Cout, ks * ks, cpad, dtype=torch.float32, device=x.device)
-        db = _grad_at(ctx.bias_ptr, (Cout,), x.device) if has_b else None
+        db = _pass.grad(ctx.keys[1], (Cout,), x.device) if has_b else None
         nbytes = lib().cswin_conv_tok_bwd_weight_workspace(B, H, W, cpad, Cout, ks, stride, pad)
         ws = _ws(nbytes, x.device)
         call("cswin_conv_tok_bwd_weight", ptr(dy), ptr(x), ptr(dwp), ptr(db), ptr(ws), nbytes, B, H, W, cpad, Cout, ks, stride,
              pad, 0, None, precision(), st)                          # channel-padded image (3 -> 4): unpermuted separately, right away
-        dw = _grad_like(w, ctx.leaf)
+        dw = _pass.grad(ctx.keys[0], w.shape, x.device)
         call("cswin_conv_weight_unpermute", ptr(dwp), ptr(dw), Cout, Cin, ks, cpad, st)
         return None, dw, db, None, None
 
@@ -826,7 +808,7 @@ class _CarafeReassemble(Function):
         call("cswin_carafe_fwd", ptr(e), ptr(z), ptr(bias), ptr(out), ptr(wt), B, H, W, Cz, S, stream())
         ctx.save_for_backward(z, wt)
         ctx.meta = (H, W, S, bias is not None)
-        ctx.bias_ptr = _pptr(bias) if _all_leaf(bias) else 0
+        ctx.keys = _param_keys(bias)
         return out
 
     @staticmethod
@@ -838,13 +820,13 @@ class _CarafeReassemble(Function):
         B, L, Cz = z.shape
         de = torch.empty_like(wt)
         dz = torch.empty_like(z)
-        db = _grad_at(ctx.bias_ptr, (Cz,), z.device) if has_b else None
+        db = _pass.grad(ctx.keys[0], (Cz,), z.device) if has_b else None
         nbytes = lib().cswin_carafe_bwd_workspace(B, H, W, Cz, S)
         ws = _ws(nbytes, z.device)
         job = (ReduceJob * 1)()
         call("cswin_carafe_bwd", ptr(dout), ptr(z), ptr(wt), ptr(de), ptr(dz), ptr(db), ptr(ws), nbytes, B, H, W, Cz, S,
-             ctypes.cast(job, ctypes.c_void_p), stream())
-        _reduce_jobs(job, [ws], leaf=ctx.bias_ptr != 0)      # the bias gradient's partial sums: queued when the bias is a leaf parameter
+             _job_ptr(job), stream())
+        _pass.reduce(job, (ws,))                             # the bias gradient's partial sums
         return de, dz, db, None, None, None
 
 

@@ -65,8 +65,10 @@ class FlatSGD:
         return lo, hi
 
     def _gather_table(self, first, last):
+        """(device table of {src, dst, n} rows, row count) that packs p.grad of parameters first..last-1 into flat_grad; rebuilt
+        when a gradient has moved.  Gradients that already are their slot (ops.engine_backward) need no row."""
         key = tuple(p.grad.data_ptr() if p.grad is not None else 0 for p in self.params[first:last])
-        slot = self._tables.setdefault((first, last), {"key": None})
+        slot = self._tables.setdefault((first, last), {"key": None, "n": 0, "host": None, "dev": None})
         if key != slot["key"]:
             rows = []
             base = self.flat_grad.data_ptr()
@@ -74,36 +76,33 @@ class FlatSGD:
                 if src == 0:
                     raise RuntimeError("FlatSGD.step(): a parameter has no gradient")
                 if src == base + 4 * o:
-                    continue                          # written in place (ops.engine_backward): nothing to pack
+                    continue                          # written in place: nothing to pack
                 if not p.grad.is_contiguous():
                     raise RuntimeError("FlatSGD.step(): non-contiguous gradient")
                 n = p.numel()
                 for c in range(0, n, _CHUNK):
                     rows.append((src + 4 * c, base + 4 * (o + c), min(_CHUNK, n - c)))
-            slot["empty"] = not rows
-            if not rows:
-                slot["key"] = key
-                return None
-            if "host" not in slot:
-                # pinned host side allocated once per range (outside any capture: the first call is an eager warm-up)
-                slot["host"] = torch.zeros(len(rows), 3, dtype=torch.int64).pin_memory()
-                slot["dev"] = torch.zeros(len(rows), 3, dtype=torch.int64, device=self.flat_grad.device)
-            if not torch.cuda.is_current_stream_capturing():
-                torch.cuda.current_stream().synchronize()      # a previous async upload may still read the host buffer
-            slot["host"].numpy()[:] = np.asarray(rows, dtype=np.int64)
-            # async upload from pinned memory: a memcpy node when captured (the host buffer lives with the optimiser)
-            slot["dev"].copy_(slot["host"], non_blocking=True)
-            slot["key"] = key
-        return None if slot.get("empty") else slot["dev"]
+            if rows:
+                capturing = torch.cuda.is_current_stream_capturing()
+                if slot["host"] is None or slot["host"].shape[0] != len(rows):
+                    # the row count depends on how many gradients were placed; the tables are sized in an eager warm-up
+                    if capturing:
+                        raise RuntimeError("FlatSGD: the gather table would have to be reallocated inside a stream capture")
+                    slot["host"] = torch.zeros(len(rows), 3, dtype=torch.int64).pin_memory()
+                    slot["dev"] = torch.zeros(len(rows), 3, dtype=torch.int64, device=self.flat_grad.device)
+                if not capturing:
+                    torch.cuda.current_stream().synchronize()      # a previous async upload may still read the host buffer
+                slot["host"].numpy()[:] = np.asarray(rows, dtype=np.int64)
+                # async upload from pinned memory: a memcpy node when captured (the host buffer lives with the optimiser)
+                slot["dev"].copy_(slot["host"], non_blocking=True)
+            slot["key"], slot["n"] = key, len(rows)
+        return slot["dev"], slot["n"]
 
     def gather_grads(self, first=0, last=None):
         """Pack p.grad of parameters first..last-1 into self.flat_grad (one launch)."""
-        from .ops import join_wgrad_stream
-        join_wgrad_stream()          # weight gradients may have been produced on the side stream
-        last = len(self.params) if last is None else last
-        t = self._gather_table(first, last)
-        if t is not None:
-            call("cswin_multi_copy", ptr(t), t.shape[0], stream())
+        table, rows = self._gather_table(first, len(self.params) if last is None else last)
+        if rows:
+            call("cswin_multi_copy", ptr(table), rows, stream())
         return self.flat_grad
 
     def apply(self, grad_scale=1.0):

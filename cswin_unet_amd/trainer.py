@@ -27,6 +27,7 @@ import torch
 import torch.distributed as dist
 
 from ._lib import call, lib, ptr, stream
+from .ops import engine_backward
 from .optim import FlatSGD
 
 
@@ -130,52 +131,39 @@ class HipEngine:
              self.w_ce / float(B * hw), self.w_dice / ncls * dice_grad_scale, B, ncls, hw, 0, stream())
         return dlogits
 
+    def _backward(self, outputs, grad_outputs, lo, hi, extra_inputs=()):
+        """One backward phase: the gradients of parameters lo..hi-1 end in their range of opt.flat_grad (placed there by the ops,
+        the rest gathered); returns the gradients of `extra_inputs`."""
+        params = self.opt.params[lo:hi]
+        with engine_backward(self.opt):
+            grads = torch.autograd.grad(outputs, params + list(extra_inputs), grad_outputs)
+        for p, g in zip(params, grads):
+            p.grad = g
+        self.opt.gather_grads(lo, hi)
+        return list(grads[len(params):])
+
     def _backward_decoder(self, logits, lab, dice_grad_scale):
         """loss backward + decoder half; returns the gradients of the boundary tensors."""
         dlogits = self._loss_grad(logits, lab, dice_grad_scale)
-        params, n_enc = self.opt.params, self.n_enc
+        n, n_enc = len(self.opt.params), self.n_enc
         self.opt.zero_grad()
-        from .ops import engine_backward
         if not self.split_backward:
-            with engine_backward(self.opt):
-                grads = torch.autograd.grad([logits], params, [dlogits])
-            for p, g in zip(params, grads):
-                p.grad = g
-            self.opt.gather_grads()
+            self._backward([logits], [dlogits], 0, n)
             return None
         core = self.core
-        dec_in = list(core.dec_in)                    # detached leaves the decoder consumed (detach_decoder_inputs)
-        with engine_backward(self.opt):
-            grads = torch.autograd.grad([logits], params[n_enc:] + dec_in, [dlogits])
-        for p, g in zip(params[n_enc:], grads):
-            p.grad = g
-        self.opt.gather_grads(n_enc, len(params))
-        return [core.xb, core.x1, core.x2, core.x3], list(grads[len(params) - n_enc:])
+        # core.dec_in: the detached leaves the decoder consumed (detach_decoder_inputs)
+        return [core.xb, core.x1, core.x2, core.x3], self._backward([logits], [dlogits], n_enc, n, core.dec_in)
 
     def _backward_encoder_deep(self, boundary):
         """merge2 .. norm (92 % of the encoder's parameters): from the bottleneck and the stage-3 skip back to the
         detached stage-2 output.  Returns what the shallow phase needs."""
         (xb, x1, x2, x3), (dxb, dx1, dx2, dx3) = boundary
-        params, lo, hi = self.opt.params, self.n_mid, self.n_enc
-        mid = self.core.enc_mid_in
-        from .ops import engine_backward
-        with engine_backward(self.opt):
-            grads = torch.autograd.grad([xb, x3], params[lo:hi] + [mid], [dxb, dx3])
-        for p, g in zip(params[lo:hi], grads):
-            p.grad = g
-        self.opt.gather_grads(lo, hi)
-        return [x2, x1], [dx2 + grads[-1], dx1]
+        (dmid,) = self._backward([xb, x3], [dxb, dx3], self.n_mid, self.n_enc, [self.core.enc_mid_in])
+        return [x2, x1], [dx2 + dmid, dx1]
 
     def _backward_encoder(self, boundary, lo=0, hi=None):
         bound, dbound = boundary
-        params = self.opt.params
-        hi = self.n_enc if hi is None else hi
-        from .ops import engine_backward
-        with engine_backward(self.opt):
-            grads = torch.autograd.grad(bound, params[lo:hi], dbound)
-        for p, g in zip(params[lo:hi], grads):
-            p.grad = g
-        self.opt.gather_grads(lo, hi)
+        self._backward(bound, dbound, lo, self.n_enc if hi is None else hi)
 
     def _phase_ranges(self):
         n = len(self.opt.params)

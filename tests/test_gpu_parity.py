@@ -1488,6 +1488,111 @@ def test_engine_backward_places_the_gradients_autograd_would_accumulate(N, ops):
         assert _rel_l2(got, want[n]) < 1e-6, (n, _rel_l2(got, want[n]))       # same slabs; the batched reduction may sum them in another order
 
 
+def _engine_model(N, frozen=()):
+    net = N.CSWinTransformer(img_size=224, num_classes=9, embed_dim=64, depth=[1, 2, 2, 1], split_size=[1, 2, 7, 7],
+                             num_heads=[2, 4, 8, 16], qkv_bias=True, drop_path_rate=0.0).to(DEV)
+    fill_state_dict(net).train()
+    params = dict(net.named_parameters())
+    for n in frozen:
+        params[n].requires_grad_(False)
+    return net
+
+
+def _engine_reference(N, ops, img, lab, frozen=()):
+    """name -> gradient a plain loss.backward() leaves on every trainable parameter."""
+    net = _engine_model(N, frozen)
+    loss, _ = ops.ce_dice_loss(net(img), lab)
+    loss.backward()
+    return {n: p.grad.clone() for n, p in net.named_parameters() if p.requires_grad}
+
+
+def _assert_flat_grad(net, opt, want):
+    torch.cuda.synchronize()
+    names = [n for n, p in net.named_parameters() if p.requires_grad]
+    assert names == list(want) and len(names) == len(opt.params)
+    for n, p, o in zip(names, opt.params, opt.offsets):
+        got = opt.flat_grad[o:o + p.numel()].view(p.shape)
+        assert _rel_l2(got, want[n]) < 1e-6, (n, _rel_l2(got, want[n]))
+
+
+def test_engine_backward_with_frozen_parameters(N, ops):
+    """Partial fine-tuning through the engine: a frozen parameter is a leaf without a slot in the optimiser's flat buffer.  Its
+    gradient goes to a fresh tensor that autograd drops as soon as the op returns, so a reduction writing there must not wait
+    (it would write into memory the allocator has handed to somebody else): while the pass is open, every waiting reduction
+    writes inside flat_grad only, and the trainable parameters' gradients are those of a plain loss.backward()."""
+    from cswin_unet_amd.optim import FlatSGD
+    frozen = ("stage3.0.qkv.weight", "stage3.1.norm1.weight", "stage3.1.norm1.bias", "stage3.0.mlp.fc2.bias")
+    img = T(det_normal("eng.x", (2, 3, 224, 224)))
+    lab = T(det_labels("eng.lab", (2, 224, 224), 9))
+    want = _engine_reference(N, ops, img, lab, frozen)
+
+    net = _engine_model(N, frozen)
+    assert set(frozen) <= set(dict(net.named_parameters())) and len(want) == len(list(net.parameters())) - len(frozen)
+    opt = FlatSGD(net.parameters(), lr=0.0)
+    loss, _ = ops.ce_dice_loss(net(img), lab)
+    opt.zero_grad()
+    with ops.engine_backward(opt) as bwd:
+        grads = torch.autograd.grad(loss, opt.params)
+        lo, waiting = opt.flat_grad.data_ptr(), bwd.queued_outputs()
+        assert waiting and all(lo <= a < lo + 4 * opt.numel for a in waiting)
+    for p, g in zip(opt.params, grads):
+        p.grad = g
+    opt.gather_grads()
+    _assert_flat_grad(net, opt, want)
+
+
+def test_flat_sgd_alternates_between_plain_and_engine_backward(N, ops):
+    """One FlatSGD, stepped after a plain loss.backward() (every gradient gathered), after an engine pass (only the composed
+    weights' gradients gathered) and after a plain one again: the gather table follows the number of rows each time.  lr = 0, so
+    the three steps see the same weights and must leave the same gradients in flat_grad."""
+    from cswin_unet_amd.optim import FlatSGD
+    img = T(det_normal("eng.x", (2, 3, 224, 224)))
+    lab = T(det_labels("eng.lab", (2, 224, 224), 9))
+    want = _engine_reference(N, ops, img, lab)
+    net = _engine_model(N)
+    opt = FlatSGD(net.parameters(), lr=0.0)
+    for engine in (False, True, False):
+        loss, _ = ops.ce_dice_loss(net(img), lab)
+        opt.zero_grad()
+        if engine:
+            with ops.engine_backward(opt):
+                grads = torch.autograd.grad(loss, opt.params)
+            for p, g in zip(opt.params, grads):
+                p.grad = g
+        else:
+            loss.backward()
+        opt.step()
+        _assert_flat_grad(net, opt, want)
+
+
+def test_engine_backward_refuses_a_leaf_parameter_used_twice(ops):
+    """Two ops sharing one leaf weight: outside a pass autograd accumulates the two gradients (bit-equal to the sum of the same
+    two ops run on separate copies of the weight); inside engine_backward both would be written to the one slot, the second
+    over the first while its reduction may still wait, so the pass refuses."""
+    from cswin_unet_amd._lib import CswinHipError
+    from cswin_unet_amd.optim import FlatSGD
+    x = T(det_normal("twice.x", (4, 49, 64)))
+    w, w1, w2 = (torch.nn.Parameter(T(det_normal("twice.w", (64, 64)))) for _ in range(3))
+    b = torch.nn.Parameter(T(det_normal("twice.b", (64,))))
+
+    def loss(wa, wb):
+        return ops.linear(ops.linear(x, wa, b), wb).square().sum()
+
+    loss(w1, w2).backward()
+    separate, b_want = w1.grad + w2.grad, b.grad.clone()
+    b.grad = None
+    loss(w, w).backward()
+    assert torch.equal(w.grad, separate) and torch.equal(b.grad, b_want)
+
+    opt = FlatSGD([w, b], lr=0.0)
+    opt.zero_grad()
+    with pytest.raises(CswinHipError, match="offset 0"):
+        with ops.engine_backward(opt):
+            torch.autograd.grad(loss(w, w), opt.params)
+    loss(w, w).backward()                              # the refused pass left nothing behind
+    assert torch.equal(w.grad, separate) and torch.equal(b.grad, b_want)
+
+
 def test_use_chk_in_bf16_mode_matches_plain_backward(N, ops, bf16_matmul):
     """The same in the bf16 mode: the recompute runs the bf16-storage forward again, the backward finds (or does not find) the bf16
     gradient twins in another order than without checkpointing; with identical DropPath draws the gradients must agree to the
