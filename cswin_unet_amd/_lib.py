@@ -44,11 +44,18 @@ SIGNATURES = {
     "cswin_conv_weight_permute": (I, [P, P, P, I, I, I, I, P]),
     "cswin_conv_weight_unpermute": (I, [P, P, I, I, I, I, P]),
     "cswin_conv_weight_flipT": (I, [P, P, I, I, I, P]),
+    "cswin_conv_weight_images": (I, [P, I, P]),
+    "cswin_conv_tok_bwd_weight_cpad": (I, [P, P, P, P, P, SZ, I, I, I, I, I, I, I, I, I, P, I, P]),
     "cswin_nchw_to_tokens": (I, [P, P, I, I, I, I, I, P]),
     "cswin_tokens_to_nchw": (I, [P, P, I, I, I, I, I, P]),
     "cswin_carafe_fwd": (I, [P, P, P, P, P, I, I, I, I, I, P]),
     "cswin_carafe_bwd_workspace": (SZ, [I, I, I, I, I]),
     "cswin_carafe_bwd": (I, [P, P, P, P, P, P, P, SZ, I, I, I, I, I, P, P]),
+    "cswin_carafe_fwd_nchw": (I, [P, P, P, P, P, I, I, I, I, I, I, P]),
+    "cswin_carafe_bwd_nchw_ok": (I, [I, I, I, I]),
+    "cswin_carafe_bwd_nchw": (I, [P, P, P, P, P, P, P, SZ, I, I, I, I, I, I, P, P]),
+    "cswin_head_compose": (I, [P, P, P, P, P, I, I, I, I, P]),
+    "cswin_head_compose_bwd": (I, [P, P, P, P, P, P, P, P, I, I, I, P]),
     "cswin_loss_workspace": (SZ, [I, I, L]),
     "cswin_loss_sums": (I, [P, P, P, P, SZ, I, I, L, I, P]),
     "cswin_loss_finalize": (I, [P, P, P, D, I, F, F, P, P]),
@@ -75,6 +82,12 @@ class ReduceJob(ctypes.Structure):
     _fields_ = [("part", c_void_p), ("out", c_void_p), ("out2", c_void_p), ("n_first", ctypes.c_longlong),
                 ("n", ctypes.c_longlong), ("stride", ctypes.c_longlong), ("rows", c_int), ("reserved", c_int),
                 ("conv_kk", c_int), ("conv_cin", c_int)]
+
+
+class ConvImageJob(ctypes.Structure):
+    """Mirror of cswin_conv_image_job (include/cswin_hip.h)."""
+    _fields_ = [("w", c_void_p), ("w_perm", c_void_p), ("w_permT", c_void_p), ("w_flipT", c_void_p), ("Cout", c_int),
+                ("Cin", c_int), ("ks", c_int), ("Cpad", c_int)]
 
 
 _lib = None

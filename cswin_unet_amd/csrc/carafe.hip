@@ -72,6 +72,61 @@ __global__ __launch_bounds__(256) void carafe_fwd_kernel(const float* __restrict
     }
 }
 
+// The same reassembly written STRAIGHT to (B, C, S*H, S*W) planes, first C of the Cz channels (the segmentation head: C classes in
+// 16-channel tokens).  One lane per OUTPUT pixel; a workgroup covers 256 / S^2 consecutive low-resolution pixels and all their
+// sub-pixels with sx fastest, so a wave's stores are contiguous runs of one output row in every class plane, and the padded
+// (B, (S*H)*(S*W), Cz) token tensor with the transposing pass after it never exists.  Arithmetic and its order are those of
+// carafe_fwd_kernel (bit-identical results).
+template <int S>
+__global__ __launch_bounds__(256) void carafe_fwd_nchw_kernel(const float* __restrict__ e, const float* __restrict__ z,
+                                                               const float* __restrict__ bias, float* __restrict__ out,
+                                                               float* __restrict__ wt_save, int B, int H, int W, int Cz, int C) {
+    constexpr int S2 = S * S, PPB = 256 / S2;
+    const int sy = threadIdx.x / (PPB * S), rem = threadIdx.x % (PPB * S);
+    const int pl = rem / S, sx = rem % S, s = sy * S + sx;
+    const long npix = (long)B * H * W, plane = (long)H * S * W * S;
+    for (long p0 = (long)blockIdx.x * PPB; p0 < npix; p0 += (long)gridDim.x * PPB) {
+        const long pix = p0 + pl;
+        if (pix >= npix) continue;
+        const int w = (int)(pix % W);
+        const int h = (int)((pix / W) % H);
+        const int b = (int)(pix / ((long)W * H));
+        float wt[9];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            wt[k] = e[pix * (9 * S2) + k * S2 + s];
+            mx = fmaxf(mx, wt[k]);
+        }
+        float sum = 0.f;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            wt[k] = __expf(wt[k] - mx);
+            sum += wt[k];
+        }
+        const float inv = 1.0f / sum;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) wt[k] *= inv;
+        if (wt_save) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) wt_save[pix * (9 * S2) + k * S2 + s] = wt[k];
+        }
+        float* o = out + (long)b * C * plane + ((long)h * S + sy) * (W * S) + w * S + sx;
+        for (int c = 0; c < C; c += 4) {
+            f32x4 acc = bias ? *reinterpret_cast<const f32x4*>(bias + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int k = 0; k < 9; ++k) {
+                const int hh = h + k / 3 - 1, ww = w + k % 3 - 1;
+                if ((unsigned)hh < (unsigned)H && (unsigned)ww < (unsigned)W)
+                    acc += wt[k] * *reinterpret_cast<const f32x4*>(z + (((long)b * H + hh) * W + ww) * Cz + c);
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (c + q < C) o[(c + q) * plane] = acc[q];
+        }
+    }
+}
+
 // de[b,hw,k*S2+s] = Wt[k] * (dWt[k] - sum_j Wt[j] dWt[j]),  dWt[k] = sum_c dout[pix(s), c] * z[nbr_k, c]
 // dbias_part != NULL (Cz <= 512): the kernel streams over dout anyway, so it also leaves the per-workgroup column sums of dout
 // in dbias_part[block][Cz] (dbias = their sum), which saves the separate column-sum pass over dout.
@@ -197,12 +252,29 @@ constexpr int C4_NP = C4_HALO * C4_HALO;      // 100 pixels whose G is needed
 
 __device__ __forceinline__ f32x4 carafe_mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
+// 4 x 4 transpose of (lane group kq = bits 4-5 of the lane) x (element of v) among the four lanes 16 apart
+__device__ __forceinline__ f32x4 lane_transpose4(f32x4 v, int kq) {
+    const bool hi = kq & 2, odd = kq & 1;
+    float s0 = hi ? v[0] : v[2], s1 = hi ? v[1] : v[3];
+    s0 = __shfl_xor(s0, 32, 64);
+    s1 = __shfl_xor(s1, 32, 64);
+    if (hi) { v[0] = s0; v[1] = s1; } else { v[2] = s0; v[3] = s1; }
+    float t0 = odd ? v[0] : v[1], t1 = odd ? v[2] : v[3];
+    t0 = __shfl_xor(t0, 16, 64);
+    t1 = __shfl_xor(t1, 16, 64);
+    if (odd) { v[0] = t0; v[2] = t1; } else { v[1] = t0; v[3] = t1; }
+    return v;
+}
+
 constexpr int C4_WAVES = 8;                   // waves per workgroup (two workgroups of 64 KB LDS share a CU)
 
+// NCHW: dout is the (B, C, 4H, 4W) gradient of the logits themselves (C <= 16 planes; channels >= C read as zero, which is
+// what the padded tokens held) instead of (B, (4H)*(4W), 16) tokens: same values in the same registers, no re-layout pass.
+template <bool NCHW>
 __global__ __launch_bounds__(64 * C4_WAVES) void carafe4_bwd_fused_kernel(const float* __restrict__ dout, const float* __restrict__ z,
                                                                  const float* __restrict__ wt_save, float* __restrict__ de,
                                                                  float* __restrict__ dz, float* __restrict__ dbias_part,
-                                                                 int B, int H, int W, int tiles_x, int tiles_y) {
+                                                                 int B, int H, int W, int tiles_x, int tiles_y, int C) {
     constexpr int S = 4, S2 = 16, Cz = 16;
     __shared__ __attribute__((aligned(16))) float Gs[C4_NP * 9 * Cz];      // [pixel][tap][channel]   57.6 KB
     __shared__ __attribute__((aligned(16))) float zt[C4_NP * Cz];          // z of the tile + halo       6.4 KB
@@ -248,18 +320,49 @@ __global__ __launch_bounds__(64 * C4_WAVES) void carafe4_bwd_fused_kernel(const 
             for (int j = 0; j < 4; ++j) av[u][j] = dv[u][j] = wv[u][j] = 0.f;
             if (!inside[u]) continue;
             const float* wp = wt_save + pix[u] * (9 * S2);
-            const float* drow = dout + (((long)b * H * S + h * S) * (W * S) + w * S) * Cz;   // hi-res pixel (4h, 4w)
+            const float* drow = dout + (((long)b * H * S + h * S) * (W * S) + w * S) * Cz;   // hi-res pixel (4h, 4w) of the tokens
             const long hstride = (long)W * S * Cz;                                           // one hi-res row down
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (li < 9) av[u][j] = wp[li * S2 + 4 * j + kq];                              // A: tap li, sub-pixel 4j + kq
-                dv[u][j] = drow[j * hstride + kq * Cz + li];      // B: channel li, sub-pixel (row j, column kq): 256-B segments
+                if (!NCHW) dv[u][j] = drow[j * hstride + kq * Cz + li];  // B: channel li, sub-pixel (row j, column kq): 256-B segments
             }
             if (interior[u]) {
-                db[u] = *reinterpret_cast<const f32x4*>(drow + (li >> 2) * hstride + (li & 3) * Cz + 4 * kq);
+                if (!NCHW) db[u] = *reinterpret_cast<const f32x4*>(drow + (li >> 2) * hstride + (li & 3) * Cz + 4 * kq);
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
                     if (4 * kq + r < 9) wv[u][r] = wp[(4 * kq + r) * S2 + li];
+            }
+        }
+        if (NCHW) {
+            // In planes a pixel's block is 16-B pieces of C x 4 different rows.  Lane (li = channel, kq = pixel of the group)
+            // fetches row j of its pixel's block as one 16-B load -- the four pixels of a group are neighbours, so a load
+            // instruction reads 64 contiguous bytes per class plane --, then the four lanes of a channel transpose (pixel x
+            // column) among themselves, which leaves dv exactly as the token form loads it ...
+            const int plm = pl0 + kq, phm = plm / C4_HALO, pwm = plm - phm * C4_HALO;
+            const int hm = h0 + phm, wm = w0 + pwm;
+            const bool okm = plm < C4_NP && (unsigned)hm < (unsigned)H && (unsigned)wm < (unsigned)W && li < C;
+            const float* src = dout + ((long)b * C + li) * ((long)H * S * W * S) + ((long)hm * S) * (W * S) + wm * S;
+            f32x4 X[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                X[j] = okm ? *reinterpret_cast<const f32x4*>(src + (long)j * (W * S)) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                X[j] = lane_transpose4(X[j], kq);
+#pragma unroll
+                for (int u = 0; u < PB; ++u) dv[u][j] = X[j][u];
+            }
+            // ... and the second operand layout (lane: sub-pixel li, channels 4 kq + r) is the transpose of the block.  The matrix
+            // pipe does it: with dv as the A operand (channel x sub-pixel) and the identity as B, the accumulator layout of
+            // D^T . I is that operand, and x * 1 + 0 + 0 + 0 is exact.
+#pragma unroll
+            for (int u = 0; u < PB; ++u) {
+                if (!interior[u]) continue;                                                  // wave-uniform
+                f32x4 t = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) t = carafe_mfma4(dv[u][j], 4 * j + kq == li ? 1.f : 0.f, t);
+                db[u] = t;
             }
         }
 #pragma unroll
@@ -389,6 +492,19 @@ int cswin_carafe_fwd(const float* e, const float* z, const float* bias, float* o
     return CSWIN_OK;
 }
 
+// As cswin_carafe_fwd, but out is (B, C, S*H, S*W): the first C <= Cz channels, one plane each (the logits of the fused head)
+int cswin_carafe_fwd_nchw(const float* e, const float* z, const float* bias, float* out, float* wt_save, int B, int H, int W,
+                          int Cz, int C, int S, void* stream) {
+    CSWIN_REQUIRE(e && z && out, CSWIN_ERR_SHAPE, "carafe_fwd_nchw: null pointer");
+    CSWIN_REQUIRE(carafe_args_ok(B, H, W, Cz, S) && C > 0 && C <= Cz, CSWIN_ERR_UNSUPPORTED, "carafe_fwd_nchw: unsupported shape B=%d H=%d W=%d Cz=%d C=%d S=%d (Cz %% 4 == 0, 0 < C <= Cz, S in {2,4})", B, H, W, Cz, C, S);
+    hipStream_t st = (hipStream_t)stream;
+    const long pixels = (long)B * H * W;
+    if (S == 2) hipLaunchKernelGGL(carafe_fwd_nchw_kernel<2>, dim3(grid_for(pixels, 64)), dim3(256), 0, st, e, z, bias, out, wt_save, B, H, W, Cz, C);
+    else hipLaunchKernelGGL(carafe_fwd_nchw_kernel<4>, dim3(grid_for(pixels, 16)), dim3(256), 0, st, e, z, bias, out, wt_save, B, H, W, Cz, C);
+    CSWIN_LAUNCH_CHECK();
+    return CSWIN_OK;
+}
+
 static bool carafe4_fused_ok(int H, int W, int Cz, int S) { return S == 4 && Cz == 16 && H % C4_T == 0 && W % C4_T == 0; }
 
 size_t cswin_carafe_bwd_workspace(int B, int H, int W, int Cz, int S) {
@@ -412,8 +528,8 @@ int cswin_carafe_bwd(const float* dout, const float* z, const float* wt_save, fl
     const bool no_fused = cswin_tuning().carafe_generic != 0;                                // tuning aid
     if (carafe4_fused_ok(H, W, Cz, S) && !no_fused) {
         const int tx = W / C4_T, ty = H / C4_T, nblk = B * tx * ty;
-        hipLaunchKernelGGL(carafe4_bwd_fused_kernel, dim3(nblk), dim3(64 * C4_WAVES), 0, st, dout, z, wt_save, de, dz,
-                           dbias ? (float*)workspace : nullptr, B, H, W, tx, ty);
+        hipLaunchKernelGGL(carafe4_bwd_fused_kernel<false>, dim3(nblk), dim3(64 * C4_WAVES), 0, st, dout, z, wt_save, de, dz,
+                           dbias ? (float*)workspace : nullptr, B, H, W, tx, ty, Cz);
         CSWIN_LAUNCH_CHECK();
         if (dbias) {
             reduce_now_or_defer(cswin_reduce_job{(const float*)workspace, dbias, nullptr, 0, Cz, Cz, nblk, 0, 0, 0}, deferred, st);
@@ -438,6 +554,32 @@ int cswin_carafe_bwd(const float* dout, const float* z, const float* wt_save, fl
     } else if (dbias) {
         int nblk = colsum_blocks(items, Cz);
         hipLaunchKernelGGL(colsum_partial_kernel, dim3(nblk), dim3(256), 0, st, dout, (float*)workspace, items, Cz);
+        reduce_now_or_defer(cswin_reduce_job{(const float*)workspace, dbias, nullptr, 0, Cz, Cz, nblk, 0, 0, 0}, deferred, st);
+        CSWIN_LAUNCH_CHECK();
+    }
+    return CSWIN_OK;
+}
+
+// 1 where cswin_carafe_bwd_nchw exists: the fused S = 4, Cz = 16 kernel on whole 8 x 8 tiles (the model's head at 56 x 56)
+int cswin_carafe_bwd_nchw_ok(int H, int W, int Cz, int S) { return carafe4_fused_ok(H, W, Cz, S) ? 1 : 0; }
+
+// cswin_carafe_bwd for a gradient that arrives as (B, C, 4H, 4W) planes, C <= Cz = 16 (channels >= C count as zero).  Workspace,
+// dbias and deferred as for cswin_carafe_bwd.
+int cswin_carafe_bwd_nchw(const float* dout, const float* z, const float* wt_save, float* de, float* dz, float* dbias,
+                          void* workspace, size_t ws_bytes, int B, int H, int W, int Cz, int C, int S, cswin_reduce_job* deferred,
+                          void* stream) {
+    if (deferred) *deferred = cswin_reduce_job{};
+    CSWIN_REQUIRE(dout && z && wt_save && de && dz, CSWIN_ERR_SHAPE, "carafe_bwd_nchw: null pointer");
+    CSWIN_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && C <= Cz && carafe4_fused_ok(H, W, Cz, S), CSWIN_ERR_UNSUPPORTED,
+                  "carafe_bwd_nchw: needs S = 4, Cz = 16, C <= 16, H and W multiples of %d (got B=%d H=%d W=%d Cz=%d C=%d S=%d)", C4_T, B, H, W, Cz, C, S);
+    CSWIN_REQUIRE(!dbias || (workspace && ws_bytes >= cswin_carafe_bwd_workspace(B, H, W, Cz, S)), CSWIN_ERR_WORKSPACE, "carafe_bwd_nchw: workspace too small");
+    CSWIN_REQUIRE(((uintptr_t)dout & 15) == 0, CSWIN_ERR_ALIGN, "carafe_bwd_nchw: dout must be 16-B aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int tx = W / C4_T, ty = H / C4_T, nblk = B * tx * ty;
+    hipLaunchKernelGGL(carafe4_bwd_fused_kernel<true>, dim3(nblk), dim3(64 * C4_WAVES), 0, st, dout, z, wt_save, de, dz,
+                       dbias ? (float*)workspace : nullptr, B, H, W, tx, ty, C);
+    CSWIN_LAUNCH_CHECK();
+    if (dbias) {
         reduce_now_or_defer(cswin_reduce_job{(const float*)workspace, dbias, nullptr, 0, Cz, Cz, nblk, 0, 0, 0}, deferred, st);
         CSWIN_LAUNCH_CHECK();
     }

@@ -96,13 +96,27 @@ typedef struct cswin_reduce_job {
     long long n_first, n, stride;
     int rows, reserved;      // reserved: set by the library (bit 0 = 16-B loads are legal)
     int conv_kk, conv_cin;   // != 0: columns [0, n_first) are a conv weight gradient in the implicit-GEMM order [Cout][k*k][Cin],
-                             // stored to `out` in the nn.Conv2d order [Cout][Cin][k][k] (conv_kk = k*k, conv_cin = Cin)
+                             // stored to `out` in the nn.Conv2d order [Cout][Cin][k][k] (conv_kk = k*k, conv_cin = Cin; with a
+                             // channel-padded input, conv_cin = Cin | Cin_param << 16 and `out` is [Cout][Cin_param][k][k])
 } cswin_reduce_job;
 }
 
 static inline int reduce_job_vec_ok(const cswin_reduce_job& j) {
     return ((uintptr_t)j.part % 16 == 0) && j.stride % 4 == 0 && j.n % 4 == 0 && (!j.out2 || j.n_first % 4 == 0);
 }
+
+// store of column i < n_first of a convolution job: slab order [Cout][k*k][Cin] -> parameter order [Cout][Cin_param][k][k].
+// conv_cin: bits 0-15 the slab's Cin, bits 16-31 the parameter's Cin where the slab's is a zero-padded image of it (0: same);
+// the padded channels' columns are dropped.
+__device__ __forceinline__ void reduce_conv_store(const cswin_reduce_job& j, long i, float t) {
+    const int kk = j.conv_kk, Cin = j.conv_cin & 0xFFFF, Cpar = (j.conv_cin >> 16) ? (j.conv_cin >> 16) : Cin;
+    const long co = i / ((long)kk * Cin);
+    const int rem = (int)(i - co * kk * Cin), tap = rem / Cin, ci = rem - tap * Cin;
+    if (ci < Cpar) j.out[(co * Cpar + ci) * kk + tap] = t;
+}
+// A channel-padded convolution job keeps the summation order of a plain job (rows_sum_block / rows_sum_few: what reduced its
+// slabs before the re-layout moved into the reduction); the others run rows_sum_conv_block as they always did.
+__device__ __host__ __forceinline__ bool reduce_job_conv_padded(const cswin_reduce_job& j) { return j.conv_kk && (j.conv_cin >> 16); }
 
 // One workgroup (256 threads) = 64 columns x 16 row groups: a wave reads 4 slab rows x 256 contiguous bytes per
 // instruction with up to four 16-B loads in flight per lane; the 16 row-group sums meet in LDS.
@@ -139,6 +153,7 @@ __device__ __forceinline__ void rows_sum_block(const cswin_reduce_job& job, long
 #pragma unroll
         for (int k = 0; k < RS_G; ++k) t += red[k][threadIdx.x];
         if (job.out2 && i >= job.n_first) job.out2[i - job.n_first] = t;
+        else if (job.conv_kk) reduce_conv_store(job, i, t);
         else job.out[i] = t;
     }
 }
@@ -147,8 +162,6 @@ __device__ __forceinline__ void rows_sum_block(const cswin_reduce_job& job, long
 // the parameter is [Cout][Cin][k][k]: slabs are read along their columns (coalesced), the nn.Conv2d layout is produced by the
 // 4-B stores of the (small) result.  Columns >= n_first are the bias gradient as usual.
 __device__ __forceinline__ void rows_sum_conv_block(const cswin_reduce_job& j, long blk, float (*red)[RS_COLS + 1]) {
-    const int kk = j.conv_kk, Cin = j.conv_cin;
-    float* out = j.out;
     // reduce into LDS exactly like rows_sum_block, then remap the store
     const int c4 = threadIdx.x & 15, g = threadIdx.x >> 4;
     const long i0 = blk * RS_COLS + 4 * c4;
@@ -179,11 +192,7 @@ __device__ __forceinline__ void rows_sum_conv_block(const cswin_reduce_job& j, l
 #pragma unroll
         for (int k = 0; k < RS_G; ++k) t += red[k][threadIdx.x];
         if (j.out2 && i >= j.n_first) j.out2[i - j.n_first] = t;
-        else if (i < j.n_first) {
-            const long co = i / ((long)kk * Cin);
-            const int rem = (int)(i - co * kk * Cin), tap = rem / Cin, ci = rem - tap * Cin;
-            out[(co * Cin + ci) * kk + tap] = t;
-        }
+        else if (i < j.n_first) reduce_conv_store(j, i, t);
     }
 }
 
@@ -201,6 +210,18 @@ typedef struct cswin_wgrad_desc {
     int io_bf16;             /* precision 1 only: bit 0 = dy is stored as bf16, bit 1 = x is stored as bf16 */
 } cswin_wgrad_desc;
 }
+
+// one convolution weight and the images of it to (re)write (cswin_conv_weight_images); NULL images are skipped
+extern "C" {
+typedef struct cswin_conv_image_job {
+    const float* w;          // nn.Conv2d parameter [Cout][Cin][ks][ks]
+    float* w_perm;           // [Cout][ks*ks][Cpad]
+    float* w_permT;          // [ks*ks][Cout][Cpad]
+    float* w_flipT;          // [Cin][ks*ks (mirrored)][Cout]
+    int Cout, Cin, ks, Cpad;
+} cswin_conv_image_job;
+}
+constexpr int CSWIN_MAX_CONV_IMAGE_JOBS = 16;      // 16 x 48 B + 18 x 4 B of kernel arguments
 
 constexpr int CSWIN_MAX_REDUCE_JOBS = 48;          // one launch's kernel arguments: 48 x 64 B + 49 x 4 B < 4 KB
 struct ReduceJobs {
@@ -226,17 +247,20 @@ __device__ __forceinline__ void rows_sum_few(const cswin_reduce_job& job, long b
     if (r < job.rows) s0 += *reinterpret_cast<const f32x4*>(base + (long)r * job.stride);
     s0 += s1;
     if (job.out2 && i0 >= job.n_first) *reinterpret_cast<f32x4*>(job.out2 + (i0 - job.n_first)) = s0;
-    else *reinterpret_cast<f32x4*>(job.out + i0) = s0;
+    else if (job.conv_kk) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) reduce_conv_store(job, i0 + e, s0[e]);
+    } else *reinterpret_cast<f32x4*>(job.out + i0) = s0;
 }
 // reserved bit 1 (set by cswin_rows_sum_multi): this job runs in the few-rows mode (needs bit 0 and 16-B aligned outputs)
 static inline int reduce_job_few_ok(const cswin_reduce_job& j) {
-    return !j.conv_kk && reduce_job_vec_ok(j) && j.rows <= RS_FEW_ROWS && j.n >= 4 * RS_FEW_COLS && ((uintptr_t)j.out % 16 == 0) &&
+    return (!j.conv_kk || reduce_job_conv_padded(j)) && reduce_job_vec_ok(j) && j.rows <= RS_FEW_ROWS && j.n >= 4 * RS_FEW_COLS && ((uintptr_t)j.out % 16 == 0) &&
            (!j.out2 || ((uintptr_t)j.out2 % 16 == 0));
 }
 
 static __global__ __launch_bounds__(256) void rows_sum_kernel(cswin_reduce_job job) {
     __shared__ float red[RS_G][RS_COLS + 1];
-    if (job.conv_kk) rows_sum_conv_block(job, blockIdx.x, red);
+    if (job.conv_kk && !reduce_job_conv_padded(job)) rows_sum_conv_block(job, blockIdx.x, red);
     else if (job.reserved & 2) rows_sum_few(job, blockIdx.x);
     else rows_sum_block(job, blockIdx.x, red);
 }
@@ -260,7 +284,7 @@ __device__ __forceinline__ void rows_sum_dispatch(const cswin_reduce_job* j, con
         else hi = mid - 1;
     }
     const int k = lo;
-    if (j[k].conv_kk) rows_sum_conv_block(j[k], blk - first_block[k], red);
+    if (j[k].conv_kk && !reduce_job_conv_padded(j[k])) rows_sum_conv_block(j[k], blk - first_block[k], red);
     else if (j[k].reserved & 2) rows_sum_few(j[k], blk - first_block[k]);
     else rows_sum_block(j[k], blk - first_block[k], red);
 }

@@ -1166,12 +1166,13 @@ size_t cswin_conv_tok_bwd_weight_workspace(int B, int H, int W, int Cin, int Cou
 }
 
 // dw_perm: [Cout][ks*ks][Cin], or the nn.Conv2d parameter layout [Cout][Cin][ks][ks] when torch_layout != 0; dbias: [Cout]
-int cswin_conv_tok_bwd_weight(const float* dy, const float* x, float* dw_perm, float* dbias, void* workspace,
-                              size_t ws_bytes, int B, int H, int W, int Cin, int Cout, int ks, int stride, int pad,
-                              int torch_layout, cswin_reduce_job* deferred, int precision, void* stream) {
+static int conv_wgrad_impl(const float* dy, const float* x, float* dw_perm, float* dbias, void* workspace,
+                           size_t ws_bytes, int B, int H, int W, int Cin, int Cout, int ks, int stride, int pad,
+                           int torch_layout, int Cin_param, cswin_reduce_job* deferred, int precision, void* stream) {
     CSWIN_CHECK_PRECISION(precision, "conv_tok_bwd_weight");
     CSWIN_REQUIRE(dy && x && dw_perm, CSWIN_ERR_SHAPE, "conv_tok_bwd_weight: null pointer");
     CSWIN_REQUIRE(Cin % 4 == 0 && Cout % 4 == 0 && aligned16(dy) && aligned16(x), CSWIN_ERR_ALIGN, "conv_tok_bwd_weight: channels %% 4 and 16-B alignment required");
+    CSWIN_REQUIRE(!torch_layout || Cin < 65536, CSWIN_ERR_UNSUPPORTED, "conv_tok_bwd_weight: torch_layout needs Cin < 65536");
     int OH = (H + 2 * pad - ks) / stride + 1, OW = (W + 2 * pad - ks) / stride + 1;
     int M = B * OH * OW, K = ks * ks * Cin;
     size_t need = cswin_linear_bwd_weight_workspace(M, Cout, K);
@@ -1190,19 +1191,40 @@ int cswin_conv_tok_bwd_weight(const float* dy, const float* x, float* dw_perm, f
     launch_gemm<false, false, 4, EPI_PLAIN, false>(A, Bm, e, Cout, K, M, splits, rps, precision, st);
     CSWIN_LAUNCH_CHECK();
     long n = (long)Cout * K;
-    cswin_reduce_job job = {slab, dw_perm, dbias, n, n + (dbias ? Cout : 0), slab_stride, splits, 0, torch_layout ? ks * ks : 0, torch_layout ? Cin : 0};
+    cswin_reduce_job job = {slab, dw_perm, dbias, n, n + (dbias ? Cout : 0), slab_stride, splits, 0, torch_layout ? ks * ks : 0,
+                            torch_layout ? (Cin | (Cin_param != Cin ? Cin_param << 16 : 0)) : 0};
     if (deferred) {
         *deferred = job;
         return CSWIN_OK;
     }
     if (torch_layout) {
-        job.reserved = reduce_job_vec_ok(job);
-        hipLaunchKernelGGL(rows_sum_kernel, dim3((unsigned)((job.n + RS_COLS - 1) / RS_COLS)), dim3(256), 0, st, job);
+        const int few = reduce_job_few_ok(job);                  // a channel-padded job only: it reduces as a plain one does
+        job.reserved = reduce_job_vec_ok(job) | (few ? 2 : 0);
+        const long cols = few ? RS_FEW_COLS : RS_COLS;
+        hipLaunchKernelGGL(rows_sum_kernel, dim3((unsigned)((job.n + cols - 1) / cols)), dim3(256), 0, st, job);
     } else {
         launch_rows_sum(slab, dw_perm, dbias, n, n + (dbias ? Cout : 0), splits, slab_stride, st);
     }
     CSWIN_LAUNCH_CHECK();
     return CSWIN_OK;
+}
+
+int cswin_conv_tok_bwd_weight(const float* dy, const float* x, float* dw_perm, float* dbias, void* workspace,
+                              size_t ws_bytes, int B, int H, int W, int Cin, int Cout, int ks, int stride, int pad,
+                              int torch_layout, cswin_reduce_job* deferred, int precision, void* stream) {
+    return conv_wgrad_impl(dy, x, dw_perm, dbias, workspace, ws_bytes, B, H, W, Cin, Cout, ks, stride, pad, torch_layout, Cin, deferred,
+                           precision, stream);
+}
+
+// The same for an input whose Cin channels are a zero-padded image of the parameter's Cin_param < Cin (the patch embedding: 3
+// image channels in 4-channel tokens): dw is the nn.Conv2d parameter [Cout][Cin_param][ks][ks], written by the slab reduction
+// itself, which drops the padded channels' columns -- no [Cout][ks*ks][Cin] image and no unpermute launch
+int cswin_conv_tok_bwd_weight_cpad(const float* dy, const float* x, float* dw, float* dbias, void* workspace, size_t ws_bytes,
+                                   int B, int H, int W, int Cin, int Cin_param, int Cout, int ks, int stride, int pad,
+                                   cswin_reduce_job* deferred, int precision, void* stream) {
+    CSWIN_REQUIRE(Cin_param > 0 && Cin_param <= Cin && Cin < 65536, CSWIN_ERR_SHAPE, "conv_tok_bwd_weight_cpad: 0 < Cin_param <= Cin < 65536");
+    return conv_wgrad_impl(dy, x, dw, dbias, workspace, ws_bytes, B, H, W, Cin, Cout, ks, stride, pad, 1, Cin_param, deferred, precision,
+                           stream);
 }
 
 // jobs: HOST array of njobs (<= CSWIN_MAX_REDUCE_JOBS = 48) reductions left pending by *_bwd_weight / layernorm_bwd calls with `deferred` set

@@ -213,14 +213,21 @@ class _SumInputChannels(torch.autograd.Function):
 class _PatchEmbed(nn.Sequential):
     """Conv2d(in, E, 7, 4, 2) -> 'b c h w -> b (h w) c' -> LayerNorm(E); keys '0.*' and '2.*' as in the reference."""
 
-    def forward(self, img):
-        conv, norm = self[0], self[2]
-        w = conv.weight
+    def conv_weight(self, img):
+        """The kernel this image is convolved with."""
+        w = self[0].weight
         if img.shape[1] == 1 and w.shape[1] > 1:
             # a grey image that the reference repeats to in_chans identical channels (vision_transformer.py:40-41): the
             # convolution over identical channels is the convolution of the one channel with the kernel summed over its
             # input channels -- the repeated (B, 3, H, W) tensor is never built
             w = _SumInputChannels.apply(w)
+        return w
+
+    def forward(self, img, w=None):
+        """w: conv_weight(img) if the caller already has it (it prepared the weight images of the pass with it)."""
+        conv, norm = self[0], self[2]
+        if w is None:
+            w = self.conv_weight(img)
         tok = ops.patch_embed_conv(img, w, conv.bias, conv.stride[0], conv.padding[0])
         return ops.layer_norm(tok, norm.weight, norm.bias, norm.eps)
 
@@ -324,10 +331,10 @@ class CSWinTransformer(nn.Module):
             b._dp_preset = [scales[2 * i], scales[2 * i + 1]]
 
     # encoder and bottleneck
-    def forward_features(self, x):
+    def forward_features(self, x, pe_weight=None):
         self._predraw_drop_path(x.shape[0], x.device)
         ops.clear_twins()                      # bf16 gradient twins of a previous backward that nobody consumed
-        x = self.stage1_conv_embed(x)
+        x = self.stage1_conv_embed(x, pe_weight)
         if self.pos_drop.p > 0 and self.training:
             x = ops.dropout(x, self.pos_drop.p)
         x = self._run(self.stage1, x)
@@ -363,18 +370,30 @@ class CSWinTransformer(nn.Module):
         side = _square_side(x.shape[1])
         ncls = head.out_channels
         cpad = max(16, 1 << (ncls - 1).bit_length())
-        w_head = head.weight.flatten(1)                                        # (ncls, 64)
-        w_fused = ops.matmul_nn(w_head, up.out.weight.flatten(1))              # (ncls, C) = W_head @ W_out
-        b_fused = ops.linear(up.out.bias[None, :], w_head)[0]                  # (ncls,)   = W_head @ b_out
-        w_fused = nn.functional.pad(w_fused, (0, 0, 0, cpad - ncls))           # zero rows -> 16-channel tokens
-        b_fused = nn.functional.pad(b_fused, (0, cpad - ncls))
+        # (cpad, C) = [W_head @ W_out ; 0] and (cpad,) = [W_head @ b_out ; 0]: zero rows -> 16-channel tokens; one launch
+        w_fused, b_fused = ops.head_compose(head.weight, up.out.weight, up.out.bias, cpad)
         mid, z = ops.linear_pair(x, up.down.weight.flatten(1), up.down.bias, w_fused, None)
         e = ops.conv_tokens(mid, up.encoder.weight, up.encoder.bias, side, side, 1, 1)
-        tok = ops.carafe_reassemble(e, z, b_fused, side, side, up.up_factor)   # (B, (4 side)^2, cpad)
-        return ops.tokens_to_nchw(tok, ncls, up.up_factor * side, up.up_factor * side)
+        # the reassembly kernel stores the ncls class planes itself: (B, ncls, 4 side, 4 side), no padded token tensor
+        return ops.carafe_reassemble_nchw(e, z, b_fused, side, side, up.up_factor, ncls)
+
+    def _conv_specs(self, pe_weight):
+        """(weight, cpad, stride, pad) of every convolution of a forward pass, for ops.conv_weight_images."""
+        pe = self.stage1_conv_embed[0]
+        specs = [(pe_weight, (pe_weight.shape[1] + 3) // 4 * 4, pe.stride[0], pe.padding[0])]
+        specs += [(m.conv.weight, m.conv.weight.shape[1], 2, 1) for m in (self.merge1, self.merge2, self.merge3)]
+        specs += [(u.encoder.weight, u.encoder.weight.shape[1], 1, 1)
+                  for u in (self.upsample4, self.upsample3, self.upsample2, self.upsample1)]
+        return specs
 
     def forward(self, x):
-        x = self.forward_features(x)
+        # all eight convolutions' weight images in one launch (they were twelve, one per convolution and direction)
+        pe_weight = self.stage1_conv_embed.conv_weight(x)
+        with ops.conv_weight_images(self._conv_specs(pe_weight)):
+            return self._forward(x, pe_weight)
+
+    def _forward(self, x, pe_weight):
+        x = self.forward_features(x, pe_weight)
         # Encoder/decoder boundary = the bottleneck and the three skips.  A trainer that back-propagates the two halves
         # separately (to overlap the decoder's gradient all-reduce with the encoder's backward) sets
         # `detach_decoder_inputs`: the decoder then consumes detached leaves (self.dec_in) and the trainer feeds their

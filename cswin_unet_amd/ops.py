@@ -11,10 +11,10 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from ._lib import CswinHipError, ReduceJob, WgradDesc, act_bf16, call, dev_f32, lib, precision, ptr, shadow_ptr, stream
+from ._lib import ConvImageJob, CswinHipError, ReduceJob, WgradDesc, act_bf16, call, dev_f32, lib, precision, ptr, shadow_ptr, stream
 
 __all__ = ["layer_norm", "linear", "linear_pair", "mlp", "stripe_attention", "cswin_block", "conv_tokens", "patch_embed_conv", "carafe_reassemble",
-           "tokens_to_nchw", "matmul_nn", "ce_dice_loss", "dropout", "img2windows", "windows2img"]
+           "carafe_reassemble_nchw", "conv_weight_images", "head_compose", "tokens_to_nchw", "matmul_nn", "ce_dice_loss", "dropout", "img2windows", "windows2img"]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -684,6 +684,62 @@ def cswin_block(x, reso, split, idx, heads, scale, norm1, qkv, proj, norm2, fc1,
 # ------------------------------------------------------------------------------------------------
 # convolutions on tokens
 # ------------------------------------------------------------------------------------------------
+MAX_CONV_IMAGE_JOBS = 16
+_conv_images = {}        # weight address -> (weight, cpad, w_perm, w_permT, w_flipT) of the open conv_weight_images context
+
+
+def _same_conv(w, stride, pad):
+    """A stride-1 "same" convolution: its data gradient is a forward convolution of dy with the mirrored / transposed image."""
+    return stride == 1 and 2 * pad == w.shape[2] - 1 and w.shape[0] % 4 == 0
+
+
+class conv_weight_images:
+    """with conv_weight_images(specs): ... -- the implicit-GEMM weight images of every convolution the body will run, written by
+    ONE launch on entry instead of one launch per convolution and direction.  specs: (weight, cpad, stride, pad) per convolution
+    (weight (Cout, Cin, ks, ks) on the HIP device, cpad >= Cin the channel count of its input tokens).  conv_tokens /
+    patch_embed_conv called inside with one of these very weights take its images from here (and keep the backward's in their
+    context, as they keep their own); any other weight gets its images the usual way.  The images are fresh tensors of this
+    pass: what a backward needs is what its forward saw."""
+
+    def __init__(self, specs):
+        self._specs = [sp for sp in specs if sp[0] is not None and sp[0].is_cuda and sp[0].dtype == torch.float32 and sp[0].is_contiguous()]
+
+    def __enter__(self):
+        global _conv_images
+        self._outer = _conv_images
+        images, jobs = {}, []
+        grad = torch.is_grad_enabled()
+        for w, cpad, stride, pad in self._specs[:MAX_CONV_IMAGE_JOBS]:
+            Cout, Cin, ks, _ = w.shape
+            E = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=w.device)
+            same = _same_conv(w, stride, pad)
+            need_dx = grad and cpad == Cin                   # channel-padded input tokens are an image: no input gradient
+            wp = E(Cout, ks * ks, cpad)
+            wpt = E(ks * ks, Cout, cpad) if need_dx and not same else None
+            wf = E(Cin, ks * ks, Cout) if need_dx and same else None
+            images[w.data_ptr()] = (w, cpad, wp, wpt, wf)
+            jobs.append(ConvImageJob(w.data_ptr(), wp.data_ptr(), wpt.data_ptr() if wpt is not None else None,
+                                     wf.data_ptr() if wf is not None else None, Cout, Cin, ks, cpad))
+        if jobs:
+            arr = (ConvImageJob * len(jobs))(*jobs)
+            call("cswin_conv_weight_images", ctypes.cast(arr, ctypes.c_void_p), len(jobs), stream())
+        _conv_images = images
+        return self
+
+    def __exit__(self, *exc):
+        global _conv_images
+        _conv_images = self._outer
+        return False
+
+
+def _images_of(w, cpad):
+    """(w_perm, w_permT, w_flipT) of the open conv_weight_images context for this very weight, or None."""
+    e = _conv_images.get(w.data_ptr())
+    if e is not None and e[0].shape == w.shape and e[1] == cpad:
+        return e[2:]
+    return None
+
+
 def _permute_w(w, cpad, want_t):
     Cout, Cin, ks, _ = w.shape
     wp = torch.empty(Cout, ks * ks, cpad, dtype=torch.float32, device=w.device)
@@ -702,11 +758,16 @@ class _ConvTokens(Function):
         OH, OW = (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
         need_dx = ctx.needs_input_grad[0]
         # stride-1 "same" convolutions take their data gradient as a forward convolution of dy (see backward): no transposed image
-        same = stride == 1 and 2 * pad == ks - 1 and Cout % 4 == 0
-        wp, wpt = _permute_w(w, Cin, need_dx and not same)   # both weight images in one launch; the transposed one is kept
+        same = _same_conv(w, stride, pad)
+        img = _images_of(w, Cin)
+        wf = None
+        if img is not None and (img[1] is not None or same or not need_dx):
+            wp, wpt, wf = img                                # made with every other convolution's at the start of the pass
+        else:
+            wp, wpt = _permute_w(w, Cin, need_dx and not same)   # both weight images in one launch; the transposed one is kept
         y = torch.empty(B, OH * OW, Cout, dtype=torch.float32, device=x.device)
         call("cswin_conv_tok_fwd", ptr(x), ptr(wp), ptr(b), ptr(y), B, H, W, Cin, Cout, ks, stride, pad, precision(), stream())
-        ctx.save_for_backward(x, w, wpt)
+        ctx.save_for_backward(x, w, wpt, wf if need_dx else None)
         ctx.meta = (H, W, stride, pad, b is not None)
         ctx.keys = _param_keys(w, b)
         return y
@@ -714,7 +775,7 @@ class _ConvTokens(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
-        x, w, wpt = ctx.saved_tensors
+        x, w, wpt, wf = ctx.saved_tensors
         H, W, stride, pad, has_b = ctx.meta
         dy = dev_f32(dy)
         B, L, Cin = x.shape
@@ -723,11 +784,12 @@ class _ConvTokens(Function):
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
-            if stride == 1 and 2 * pad == ks - 1 and Cout % 4 == 0:
+            if _same_conv(w, stride, pad):
                 # dx = conv(dy, mirrored / transposed weights): both operands r-contiguous on the forward kernel, instead of
                 # the generic transposed gather (CARAFE4 encoder, 16 -> 144 channels at 56 x 56: 13.41 -> 13.36 ms per step)
-                wf = torch.empty(Cin, ks * ks, Cout, dtype=torch.float32, device=x.device)
-                call("cswin_conv_weight_flipT", ptr(w), ptr(wf), Cout, Cin, ks, st)
+                if wf is None:
+                    wf = torch.empty(Cin, ks * ks, Cout, dtype=torch.float32, device=x.device)
+                    call("cswin_conv_weight_flipT", ptr(w), ptr(wf), Cout, Cin, ks, st)
                 call("cswin_conv_tok_fwd", ptr(dy), ptr(wf), None, ptr(dx), B, H, W, Cout, Cin, ks, 1, pad, precision(), st)
             else:
                 if wpt is None:
@@ -761,7 +823,8 @@ class _PatchEmbedConv(Function):
         st = stream()
         x = torch.empty(B, H * W, cpad, dtype=torch.float32, device=img.device)
         call("cswin_nchw_to_tokens", ptr(img), ptr(x), B, Cin, H, W, cpad, st)
-        wp, _ = _permute_w(w, cpad, False)
+        images = _images_of(w, cpad)
+        wp = images[0] if images is not None else _permute_w(w, cpad, False)[0]
         OH, OW = (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
         y = torch.empty(B, OH * OW, Cout, dtype=torch.float32, device=img.device)
         call("cswin_conv_tok_fwd", ptr(x), ptr(wp), ptr(b), ptr(y), B, H, W, cpad, Cout, ks, stride, pad, precision(), st)
@@ -779,14 +842,15 @@ class _PatchEmbedConv(Function):
         B = x.shape[0]
         Cout, Cin, ks, _ = w.shape
         st = stream()
-        dwp = torch.empty(Cout, ks * ks, cpad, dtype=torch.float32, device=x.device)
+        dw = _pass.grad(ctx.keys[0], w.shape, x.device)
         db = _pass.grad(ctx.keys[1], (Cout,), x.device) if has_b else None
         nbytes = lib().cswin_conv_tok_bwd_weight_workspace(B, H, W, cpad, Cout, ks, stride, pad)
         ws = _ws(nbytes, x.device)
-        call("cswin_conv_tok_bwd_weight", ptr(dy), ptr(x), ptr(dwp), ptr(db), ptr(ws), nbytes, B, H, W, cpad, Cout, ks, stride,
-             pad, 0, None, precision(), st)                          # channel-padded image (3 -> 4): unpermuted separately, right away
-        dw = _pass.grad(ctx.keys[0], w.shape, x.device)
-        call("cswin_conv_weight_unpermute", ptr(dwp), ptr(dw), Cout, Cin, ks, cpad, st)
+        job = (ReduceJob * 1)()
+        # channel-padded input (3 -> 4): the slab reduction drops the padded columns as it writes the parameter layout
+        call("cswin_conv_tok_bwd_weight_cpad", ptr(dy), ptr(x), ptr(dw), ptr(db), ptr(ws), nbytes, B, H, W, cpad, Cin, Cout, ks,
+             stride, pad, _job_ptr(job), precision(), st)
+        _pass.reduce(job, (ws,))
         return None, dw, db, None, None
 
 
@@ -832,6 +896,89 @@ class _CarafeReassemble(Function):
 
 def carafe_reassemble(e, z, bias, H, W, S):
     return _CarafeReassemble.apply(e, z, bias, H, W, S)
+
+
+class _CarafeReassembleNchw(Function):
+    """carafe_reassemble whose output is (B, C, S*H, S*W): the first C channels as planes, written by the reassembly kernel and
+    read by its backward -- for the segmentation head, whose C class maps travel in Cz = 16 channel tokens."""
+
+    @staticmethod
+    def forward(ctx, e, z, bias, H, W, S, C):
+        e, z, bias = dev_f32(e, "carafe kernel logits"), dev_f32(z, "carafe features"), dev_f32(bias)
+        B, L, Cz = z.shape
+        assert L == H * W and e.shape == (B, L, 9 * S * S) and 0 < C <= Cz
+        out = torch.empty(B, C, S * H, S * W, dtype=torch.float32, device=z.device)
+        wt = torch.empty_like(e)
+        call("cswin_carafe_fwd_nchw", ptr(e), ptr(z), ptr(bias), ptr(out), ptr(wt), B, H, W, Cz, C, S, stream())
+        ctx.save_for_backward(z, wt)
+        ctx.meta = (H, W, S, C, bias is not None)
+        ctx.keys = _param_keys(bias)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        z, wt = ctx.saved_tensors
+        H, W, S, C, has_b = ctx.meta
+        dout = dev_f32(dout)
+        B, L, Cz = z.shape
+        de = torch.empty_like(wt)
+        dz = torch.empty_like(z)
+        db = _pass.grad(ctx.keys[0], (Cz,), z.device) if has_b else None
+        nbytes = lib().cswin_carafe_bwd_workspace(B, H, W, Cz, S)
+        ws = _ws(nbytes, z.device)
+        job = (ReduceJob * 1)()
+        call("cswin_carafe_bwd_nchw", ptr(dout), ptr(z), ptr(wt), ptr(de), ptr(dz), ptr(db), ptr(ws), nbytes, B, H, W, Cz, C, S,
+             _job_ptr(job), stream())
+        _pass.reduce(job, (ws,))
+        return de, dz, db, None, None, None, None
+
+
+def carafe_reassemble_nchw(e, z, bias, H, W, S, C):
+    """carafe_reassemble(e, z, bias, H, W, S)[..., :C] as (B, C, S*H, S*W).  Where the NCHW backward kernel does not exist (it
+    is the fused S = 4, Cz = 16 one) the token form and the layout adapter run instead: same values either way."""
+    if lib().cswin_carafe_bwd_nchw_ok(H, W, z.shape[-1], S):
+        return _CarafeReassembleNchw.apply(e, z, bias, H, W, S, C)
+    return tokens_to_nchw(carafe_reassemble(e, z, bias, H, W, S), C, S * H, S * W)
+
+
+class _HeadCompose(Function):
+    """(W_head W_out, W_head b_out), zero-padded to cpad rows: the weights of `output` (1x1, no bias) applied after CARAFE4's
+    `out` (1x1), as ONE small launch, and one more for the three gradients."""
+
+    @staticmethod
+    def forward(ctx, w_head, w_out, b_out, cpad):
+        w_head, w_out, b_out = dev_f32(w_head, "head weight"), dev_f32(w_out, "out weight"), dev_f32(b_out)
+        ncls, E = w_head.shape[0], w_head.numel() // w_head.shape[0]
+        C = w_out.numel() // w_out.shape[0]
+        assert w_out.shape[0] == E and cpad >= ncls and (b_out is None or b_out.numel() == E)
+        wf = torch.empty(cpad, C, dtype=torch.float32, device=w_head.device)
+        bf = torch.empty(cpad, dtype=torch.float32, device=w_head.device)
+        call("cswin_head_compose", ptr(w_head), ptr(w_out), ptr(b_out), ptr(wf), ptr(bf), ncls, E, C, cpad, stream())
+        ctx.save_for_backward(w_head, w_out, b_out)
+        ctx.keys = _param_keys(w_head, w_out, b_out)
+        return wf, bf
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dwf, dbf):
+        w_head, w_out, b_out = ctx.saved_tensors
+        ncls, E = w_head.shape[0], w_head.numel() // w_head.shape[0]
+        C = w_out.numel() // w_out.shape[0]
+        dev = w_head.device
+        dwf = dev_f32(dwf) if dwf is not None else torch.zeros(ncls, C, dtype=torch.float32, device=dev)
+        dbf = dev_f32(dbf)
+        dwh = _pass.grad(ctx.keys[0], w_head.shape, dev)
+        dwo = _pass.grad(ctx.keys[1], w_out.shape, dev)
+        dbo = _pass.grad(ctx.keys[2], b_out.shape, dev) if b_out is not None else None
+        call("cswin_head_compose_bwd", ptr(w_head), ptr(w_out), ptr(b_out), ptr(dwf), ptr(dbf), ptr(dwh), ptr(dwo), ptr(dbo),
+             ncls, E, C, stream())
+        return dwh, dwo, dbo, None
+
+
+def head_compose(w_head, w_out, b_out, cpad):
+    """w_head (ncls, E[, 1, 1]), w_out (E, C[, 1, 1]), b_out (E) or None -> (w_fused (cpad, C), b_fused (cpad))."""
+    return _HeadCompose.apply(w_head, w_out, b_out, int(cpad))
 
 
 class _TokensToNchw(Function):

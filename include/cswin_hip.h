@@ -42,7 +42,9 @@ extern "C" {
  * cswin_rows_sum_multi (a CSWinBlock backward has six to eight: four weight gradients, two LayerNorm dgamma/dbeta, the LePE conv
  * gradients; cswin_unet_amd.ops queues the jobs of a whole backward pass and reduces them in one or two launches).
  * conv_kk / conv_cin != 0: columns [0, n_first) are a convolution weight gradient in the implicit-GEMM order [Cout][k*k][Cin] and
- * are stored to `out` in the nn.Conv2d order [Cout][Cin][k][k]. */
+ * are stored to `out` in the nn.Conv2d order [Cout][Cin][k][k].  For an input whose channels are a zero-padded image of the
+ * parameter's (cswin_conv_tok_bwd_weight_cpad) conv_cin = Cin | Cin_param << 16: the padded channels' columns are dropped and `out`
+ * is [Cout][Cin_param][k][k]. */
 typedef struct cswin_reduce_job {
     const float* part;
     float* out;
@@ -194,6 +196,24 @@ int cswin_conv_weight_unpermute(const float* dw_perm, float* dw, int Cout, int C
 /* w [Cout][Cin][ks][ks] -> wf [Cin][ks*ks (mirrored)][Cout]: with it the data gradient of a stride-1, pad = ks/2 convolution is
  * cswin_conv_tok_fwd(dy, wf, NULL, dx, B, H, W, Cout, Cin, ks, 1, pad) (CARAFE encoder, cswin_unet.py:228,241) */
 int cswin_conv_weight_flipT(const float* w, float* wf, int Cout, int Cin, int ks, void* stream);
+/* Every weight image of a step in ONE launch: jobs = host array of 1..16 records; each non-NULL image of each job is written,
+ * bit for bit what the three entry points above write (the model refreshes all its convolutions' images at the start of a
+ * forward pass instead of one launch per convolution and direction). */
+typedef struct cswin_conv_image_job {
+    const float* w;          /* nn.Conv2d parameter [Cout][Cin][ks][ks] */
+    float* w_perm;           /* [Cout][ks*ks][Cpad] or NULL */
+    float* w_permT;          /* [ks*ks][Cout][Cpad] or NULL */
+    float* w_flipT;          /* [Cin][ks*ks (mirrored)][Cout] or NULL */
+    int Cout, Cin, ks, Cpad;
+} cswin_conv_image_job;
+int cswin_conv_weight_images(const cswin_conv_image_job* jobs, int njobs, void* stream);
+/* cswin_conv_tok_bwd_weight for an input whose Cin channels are a zero-padded image of the parameter's Cin_param <= Cin (the
+ * patch embedding: 3 image channels in 4-channel tokens).  dw is the nn.Conv2d parameter [Cout][Cin_param][ks][ks]; the slab
+ * reduction writes it and drops the padded channels (its job carries conv_cin = Cin | Cin_param << 16): no cswin_conv_weight_unpermute
+ * launch.  Workspace and deferred as for cswin_conv_tok_bwd_weight. */
+int cswin_conv_tok_bwd_weight_cpad(const float* dy, const float* x, float* dw, float* dbias, void* workspace, size_t ws_bytes,
+                                   int B, int H, int W, int Cin, int Cin_param, int Cout, int ks, int stride, int pad,
+                                   cswin_reduce_job* deferred, int precision, void* stream);
 
 /* ---- layout adapters at the ends of the token pipeline (Rearrange 'b c h w -> b (h w) c', cswin_unet.py:340;
  *      view/permute of up_x4, :540-541) ---- */
@@ -211,6 +231,25 @@ size_t cswin_carafe_bwd_workspace(int B, int H, int W, int Cz, int S);
  * layernorm_bwd (NULL: reduced immediately; else the job is returned, zeroed when there is no bias) */
 int cswin_carafe_bwd(const float* dout, const float* z, const float* wt_save, float* de, float* dz, float* dbias,
                      void* workspace, size_t ws_bytes, int B, int H, int W, int Cz, int S, cswin_reduce_job* deferred, void* stream);
+/* The reassembly written to / differentiated from (B, C, S*H, S*W) planes, the first C <= Cz channels (the logits of the fused
+ * segmentation head: C classes carried in Cz = 16 channel tokens) -- the (B, (S*H)*(S*W), Cz) token tensor and the
+ * cswin_tokens_to_nchw / cswin_nchw_to_tokens passes around the loss do not exist.  Same bits as the token forms followed by
+ * those adapters.  The backward form exists where cswin_carafe_bwd_nchw_ok() returns 1 (S = 4, Cz = 16, H and W multiples of 8). */
+int cswin_carafe_fwd_nchw(const float* e, const float* z, const float* bias, float* out, float* wt_save, int B, int H, int W,
+                          int Cz, int C, int S, void* stream);
+int cswin_carafe_bwd_nchw_ok(int H, int W, int Cz, int S);
+int cswin_carafe_bwd_nchw(const float* dout, const float* z, const float* wt_save, float* de, float* dz, float* dbias,
+                          void* workspace, size_t ws_bytes, int B, int H, int W, int Cz, int C, int S, cswin_reduce_job* deferred,
+                          void* stream);
+
+/* ---- the fused segmentation head's weights (up_x4: `output` 1x1 applied after upsample1.out 1x1, cswin_unet.py:540-543) ----
+ * w_head (ncls, E), w_out (E, C), b_out (E) or NULL -> w_fused (Cpad, C) = [W_head W_out ; 0], b_fused (Cpad) = [W_head b_out ; 0];
+ * and the gradients of the three from dw_fused (>= ncls rows of C) and db_fused (>= ncls, or NULL).  One small launch each. */
+int cswin_head_compose(const float* w_head, const float* w_out, const float* b_out, float* w_fused, float* b_fused, int ncls,
+                       int E, int C, int Cpad, void* stream);
+int cswin_head_compose_bwd(const float* w_head, const float* w_out, const float* b_out, const float* dw_fused,
+                           const float* db_fused, float* dw_head, float* dw_out, float* db_out, int ncls, int E, int C,
+                           void* stream);
 
 /* ---- loss of the training step: 0.4*CE + 0.6*Dice (trainer.py:55-57, utils.py:9-45) ----
  * logits (B, ncls, HW) fp32, labels (B, HW) int64.  sums[1 + 3*ncls] = {sum -log p[label], intersect_c, y_sum_c,
