@@ -66,6 +66,9 @@ SIGNATURES = {
     "cswin_pack_bf16": (I, [P, P, L, P]),
     "cswin_pack_bf16_scaled": (I, [P, P, L, F, P]),
     "cswin_unpack_bf16": (I, [P, P, L, P]),
+    "cswin_seg_metrics_nbins": (I, [I, I, I]),
+    "cswin_seg_metrics_workspace": (SZ, [I, I, I, I, I]),
+    "cswin_seg_metrics": (I, [P, P, P, P, P, SZ, I, I, I, I, I, P]),
 }
 
 

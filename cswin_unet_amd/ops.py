@@ -14,7 +14,8 @@ from torch.autograd.function import once_differentiable
 from ._lib import ConvImageJob, CswinHipError, ReduceJob, WgradDesc, act_bf16, call, dev_f32, lib, precision, ptr, shadow_ptr, stream
 
 __all__ = ["layer_norm", "linear", "linear_pair", "mlp", "stripe_attention", "cswin_block", "conv_tokens", "patch_embed_conv", "carafe_reassemble",
-           "carafe_reassemble_nchw", "conv_weight_images", "head_compose", "tokens_to_nchw", "matmul_nn", "ce_dice_loss", "dropout", "img2windows", "windows2img"]
+           "carafe_reassemble_nchw", "conv_weight_images", "head_compose", "tokens_to_nchw", "matmul_nn", "ce_dice_loss", "dropout", "img2windows", "windows2img",
+           "seg_metrics"]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1084,6 +1085,35 @@ def ce_dice_loss(logits, labels, w_ce=0.4, w_dice=0.6, group=None, inputs_are_pr
     if inputs_are_probs and w_ce != 0.0:
         raise ValueError("ce_dice_loss: cross entropy needs logits; with inputs_are_probs pass w_ce=0")
     return _CeDiceLoss.apply(logits, labels, float(w_ce), float(w_dice), group, bool(inputs_are_probs), class_weight)
+
+
+# ------------------------------------------------------------------------------------------------
+# evaluation metrics of a label volume
+# ------------------------------------------------------------------------------------------------
+def seg_metrics(pred, label, ncls, ndim=None):
+    """Per-class Dice / HD95 ingredients of a prediction / label pair of class ids (csrc/metrics.hip).  pred, label: uint8 HIP
+    tensors (D, H, W) or (H, W) with ids < ncls; ndim (default: the tensors' rank) picks the 6- or 4-neighbourhood of the border
+    rule.  Returns device tensors (counts int64 [ncls, 4] = |P|, |G|, |P n G|, |dP| + |dG|; hist int32 [ncls, nbins] of squared
+    surface distances), no host sync; utils.metrics_from_counts_hist turns them into (dice, hd95) pairs."""
+    for t, what in ((pred, "seg_metrics prediction"), (label, "seg_metrics label")):
+        if not t.is_cuda:
+            raise CswinHipError(f"{what} is on {t.device}: the cswin_unet_amd ops run on a HIP device only (no CPU fallback)")
+        if t.dtype != torch.uint8:
+            raise CswinHipError(f"{what} has dtype {t.dtype}; class ids are passed as uint8")
+    if pred.shape != label.shape or pred.dim() not in (2, 3):
+        raise CswinHipError(f"seg_metrics: prediction {tuple(pred.shape)} and label {tuple(label.shape)} must be equal (D, H, W) or (H, W) shapes")
+    ndim = pred.dim() if ndim is None else int(ndim)
+    pred, label = pred.contiguous(), label.contiguous()
+    D, H, W = (1,) * (3 - pred.dim()) + tuple(pred.shape)
+    h = lib()
+    nbins, nbytes = h.cswin_seg_metrics_nbins(D, H, W), h.cswin_seg_metrics_workspace(D, H, W, ndim, int(ncls))
+    if nbins == 0 or nbytes == 0:
+        raise CswinHipError(f"seg_metrics: {h.cswin_last_error().decode()}")
+    counts = torch.empty(int(ncls), 4, dtype=torch.int64, device=pred.device)
+    hist = torch.empty(int(ncls), nbins, dtype=torch.int32, device=pred.device)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=pred.device)
+    call("cswin_seg_metrics", ptr(pred), ptr(label), ptr(counts), ptr(hist), ptr(ws), nbytes, D, H, W, ndim, int(ncls), stream())
+    return counts, hist
 
 
 # ------------------------------------------------------------------------------------------------

@@ -9,8 +9,12 @@ Mirrors the reference's utils.py names and call signatures:
     their outputs); tests check them against hand-computed cases only.
   * ``test_single_volume(image, label, net, classes, patch_size, ...)``  (utils.py:61-102)  -- same per-slice arithmetic
     (cubic zoom in, argmax, nearest zoom out), but the slices of a volume go through the network in batches instead of
-    one launch per slice.
+    one launch per slice.  ``metrics="hip"`` takes Dice / HD95 of all classes from one device call (``volume_metrics``:
+    ops.seg_metrics returns integer counts and an integer histogram of squared surface distances, the host finishes in
+    float64) instead of the per-class scipy loop; ``evaluate_volumes`` is the aggregating loop of test.py:155-164.
 """
+import logging
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -80,6 +84,76 @@ def calculate_metric_percase(pred, gt):
     return 0, 0
 
 
+def _hist_percentile(hist, q=95.0):
+    """np.percentile(x, q) (linear interpolation) of the multiset x that holds hist[s] copies of sqrt(s), from the cumulative
+    histogram: the two order statistics around the virtual index q/100 * (n - 1) and numpy's own lerp."""
+    hist = np.asarray(hist, np.int64)
+    cum = np.cumsum(hist)
+    n = int(cum[-1]) if cum.size else 0
+    if n == 0:
+        raise RuntimeError('empty histogram')
+    idx = (n - 1) * (q / 100.0)
+    lo = int(np.floor(idx))
+    hi = min(lo + 1, n - 1)
+    t = idx - lo
+    a = np.sqrt(np.float64(np.searchsorted(cum, lo, side="right")))          # order statistic k lies in the first bin with cum > k
+    b = np.sqrt(np.float64(np.searchsorted(cum, hi, side="right")))
+    d = b - a
+    return float(a + d * t if t < 0.5 else b - d * (1 - t))
+
+
+def metrics_from_counts_hist(counts, hist):
+    """[(dice, hd95)] for classes 1 .. ncls-1 from what ops.seg_metrics returns (numpy: counts [ncls, 4] = |P|, |G|, |P n G|,
+    |dP| + |dG|; hist [ncls, >= largest used bin + 1] of squared surface distances), with the three branches of
+    calculate_metric_percase."""
+    counts, hist = np.asarray(counts), np.asarray(hist)
+    out = []
+    for c in range(1, counts.shape[0]):
+        npred, ngt, inter = int(counts[c, 0]), int(counts[c, 1]), int(counts[c, 2])
+        if npred > 0 and ngt > 0:
+            out.append((2.0 * inter / float(npred + ngt), _hist_percentile(hist[c])))
+        elif npred > 0:
+            out.append((1, 0))
+        else:
+            out.append((0, 0))
+    return out
+
+
+def _class_ids_u8(a, classes, what, device):
+    """Integral class ids in [0, classes) of any dtype (numpy or tensor) -> uint8 tensor on `device`; ValueError otherwise."""
+    if isinstance(a, torch.Tensor) and a.is_cuda:
+        t = a
+        bad = bool((t != t.round()).any()) if t.is_floating_point() else False
+        lo, hi = (float(t.min()), float(t.max())) if t.numel() else (0.0, 0.0)
+    else:
+        t = a.detach().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        bad = bool(np.any(t != np.rint(t))) if t.dtype.kind == "f" else t.dtype.kind not in "biu"
+        lo, hi = (float(t.min()), float(t.max())) if t.size else (0.0, 0.0)
+    if bad:
+        raise ValueError(f"{what}: class ids must be integral")
+    if lo < 0 or hi >= classes:
+        raise ValueError(f"{what}: class ids span [{lo:g}, {hi:g}], outside [0, {classes})")
+    if isinstance(t, torch.Tensor):
+        return t.to(torch.uint8).to(device)
+    return torch.from_numpy(np.ascontiguousarray(t.astype(np.uint8))).to(device)
+
+
+def volume_metrics(pred, label, classes, device="cuda"):
+    """[(dice, hd95)] for classes 1 .. classes-1 of a (D, H, W) or (H, W) prediction / label pair -- what the loop of
+    calculate_metric_percase(pred == i, label == i) returns -- from one ops.seg_metrics call.  pred / label: numpy arrays or
+    tensors of any dtype holding integral ids in [0, classes) (ValueError otherwise).  HIP device only."""
+    classes = int(classes)
+    if not 2 <= classes <= 255:
+        raise ValueError(f"volume_metrics: classes={classes} outside 2..255")
+    if tuple(pred.shape) != tuple(label.shape):
+        raise ValueError(f"volume_metrics: prediction {tuple(pred.shape)} and label {tuple(label.shape)} differ in shape")
+    p8, l8 = _class_ids_u8(pred, classes, "prediction", device), _class_ids_u8(label, classes, "label", device)
+    counts, hist = ops.seg_metrics(p8, l8, classes)
+    used = (hist != 0).any(dim=0).nonzero()
+    last = int(used.max()) if used.numel() else 0                  # download only the bins in use
+    return metrics_from_counts_hist(counts.cpu().numpy(), hist[:, :last + 1].cpu().numpy())
+
+
 @torch.no_grad()
 def predict_volume(image, net, patch_size=(224, 224), batch_slices=16, device="cuda"):
     """image (D, H, W) or (H, W) numpy -> integer class map of the same shape.  Per slice: cubic zoom to patch_size if the
@@ -103,13 +177,19 @@ def predict_volume(image, net, patch_size=(224, 224), batch_slices=16, device="c
 
 
 def test_single_volume(image, label, net, classes, patch_size=[256, 256], test_save_path=None, case=None, z_spacing=1,
-                       batch_slices=16, device="cuda"):
+                       batch_slices=16, device="cuda", metrics="host"):
     """Per-class (dice, hd95) of one volume, classes 1..classes-1 (utils.py:61-102).  image / label: (1, D, H, W) tensors
     as the DataLoader yields them.  With test_save_path the volumes are written as .npz (SimpleITK, which the reference
-    uses for .nii.gz, is not installed here)."""
+    uses for .nii.gz, is not installed here).  metrics: "host" = the per-class scipy loop, "hip" = one volume_metrics call on
+    the device (same values)."""
+    if metrics not in ("host", "hip"):
+        raise ValueError(f'test_single_volume: metrics must be "host" or "hip", got {metrics!r}')
     image, label = image.squeeze(0).cpu().detach().numpy(), label.squeeze(0).cpu().detach().numpy()
     prediction = predict_volume(image, net, tuple(patch_size), batch_slices, device).astype(label.dtype)
-    metric_list = [calculate_metric_percase(prediction == i, label == i) for i in range(1, classes)]
+    if metrics == "hip":
+        metric_list = volume_metrics(prediction, label, classes, device)
+    else:
+        metric_list = [calculate_metric_percase(prediction == i, label == i) for i in range(1, classes)]
     if test_save_path is not None:
         np.savez_compressed(f"{test_save_path}/{case}_pred.npz", image=image.astype(np.float32),
                             prediction=prediction.astype(np.float32), label=label.astype(np.float32),
@@ -118,3 +198,29 @@ def test_single_volume(image, label, net, classes, patch_size=[256, 256], test_s
 
 
 test_single_volume.__test__ = False     # not a pytest test (the name is the reference's)
+
+
+def evaluate_volumes(loader, net, classes, patch_size, metrics="hip", test_save_path=None, z_spacing=1, batch_slices=16,
+                     device="cuda"):
+    """The volume loop of the reference's inference() (test.py:155-164): test_single_volume per batch of `loader` (dicts with
+    "image", "label" (1, D, H, W) and "case_name", batch size 1), the per-volume and final lines it logs.  Returns
+    (per_volume, class_mean, mean_dice, mean_hd95): the metric list of every volume, the (classes-1, 2) table of per-class
+    means over the volumes, and that table's column means."""
+    per_volume = []
+    for i_batch, batch in enumerate(loader):
+        name = batch["case_name"]
+        name = name if isinstance(name, str) else name[0]
+        metric_i = test_single_volume(batch["image"], batch["label"], net, classes=classes, patch_size=list(patch_size),
+                                      test_save_path=test_save_path, case=name, z_spacing=z_spacing, batch_slices=batch_slices,
+                                      device=device, metrics=metrics)
+        per_volume.append(metric_i)
+        m = np.mean(metric_i, axis=0)
+        logging.info('idx %d case %s mean_dice %f mean_hd95 %f' % (i_batch, name, m[0], m[1]))
+    if not per_volume:
+        raise ValueError("evaluate_volumes: the loader yielded no volume")
+    class_mean = sum(np.array(m, dtype=np.float64) for m in per_volume) / len(per_volume)
+    for i in range(1, classes):
+        logging.info('Mean class %d mean_dice %f mean_hd95 %f' % (i, class_mean[i - 1][0], class_mean[i - 1][1]))
+    mean_dice, mean_hd95 = (float(v) for v in np.mean(class_mean, axis=0))
+    logging.info('Testing performance in best val model: mean_dice : %f mean_hd95 : %f' % (mean_dice, mean_hd95))
+    return per_volume, class_mean, mean_dice, mean_hd95

@@ -28,7 +28,8 @@ extern "C" {
 
 /* Bumped whenever a prototype or struct below changes (1: round 1; 2: round 2 -- stream / precision / storage arguments; 3: round 3 --
  * cswin_attn_fwd writes y0, cswin_attn_bwd reads it).  cswin_abi_version() returns the value the library was built with: a consumer
- * compiled against another header must refuse to call it. */
+ * compiled against another header must refuse to call it.  Entry points that are only ADDED (cswin_seg_metrics*) do not bump
+ * it: every prototype an older consumer binds is unchanged. */
 #define CSWIN_ABI_VERSION 4
 
 #define CSWIN_OK 0
@@ -293,6 +294,24 @@ int cswin_pack_bf16(const float* src, void* dst_bf16, long n, void* stream);
    mean (eight ranks' sum would otherwise spend three of bf16's eight mantissa bits on the factor 8 it is divided by afterwards) */
 int cswin_pack_bf16_scaled(const float* src, void* dst_bf16, long n, float scale, void* stream);
 int cswin_unpack_bf16(const void* src_bf16, float* dst, long n, void* stream);
+
+/* ---- evaluation: per-class Dice / HD95 ingredients of a label volume (utils.py:48-58; medpy.metric.binary dc / hd95,
+ *      connectivity 1, unit voxel spacing) ----
+ * pred, label: dense (D, H, W) class ids, every id < ncls, 2 <= ncls <= 255; each of D, H, W in 1..2048 (3 * 2047^2 stays
+ * inside int32).  ndim = 3: the six face neighbours decide what a border voxel is; ndim = 2 requires D == 1 and uses the four
+ * in-plane neighbours (a (1, H, W) volume with ndim = 3 is legal: there every set voxel is a border voxel, as scipy's
+ * binary_erosion(border_value=0) has it).
+ * counts[ncls][4] (64-bit) = {|P_c|, |G_c|, |P_c n G_c|, |dP_c| + |dG_c|};  hist[ncls][nbins] (32-bit unsigned), nbins =
+ * cswin_seg_metrics_nbins(D, H, W) = (D-1)^2 + (H-1)^2 + (W-1)^2 + 1: hist[c][s] = border voxels of P_c whose nearest border
+ * voxel of G_c lies at squared distance s, plus the same with P and G exchanged.  Both are zeroed by the call; rows of classes
+ * with an empty side, and row 0 (background), stay zero.  Squared distances are exact integers (true Euclidean minimum) and only
+ * integer atomics are used: the result is bit-reproducible.  hd95_c = 95th percentile of the multiset with hist[c][s] copies of
+ * sqrt(s); dice_c = 2 counts[c][2] / (counts[c][0] + counts[c][1]).
+ * The size queries are host-only and return 0 with a message for an unsupported shape. */
+int    cswin_seg_metrics_nbins(int D, int H, int W);
+size_t cswin_seg_metrics_workspace(int D, int H, int W, int ndim, int ncls);
+int    cswin_seg_metrics(const unsigned char* pred, const unsigned char* label, long long* counts, unsigned int* hist,
+                         void* workspace, size_t ws_bytes, int D, int H, int W, int ndim, int ncls, void* stream);
 
 #ifdef __cplusplus
 }
