@@ -265,13 +265,18 @@ static __global__ __launch_bounds__(256) void rows_sum_kernel(cswin_reduce_job j
     else rows_sum_block(job, blockIdx.x, red);
 }
 
-static inline void launch_rows_sum(const float* part, float* out, float* out2, long n_first, long n, int rows, long stride,
-                                   hipStream_t st) {
-    cswin_reduce_job job = {part, out, out2, n_first, n, stride, rows, 0, 0, 0};
+// The one place that decides how a job is reduced: sets its `reserved` flags (bit 0 = 16-B loads are legal, bit 1 = few-rows mode)
+// and returns its workgroup count.  Every kind of job passes through here, stand-alone or as an entry of a table; a convolution
+// job in the unpadded layout never takes the few-rows mode (reduce_job_few_ok) and runs rows_sum_conv_block.
+static inline int flag_reduce_job(cswin_reduce_job& job) {
     const int few = reduce_job_few_ok(job);
     job.reserved = reduce_job_vec_ok(job) | (few ? 2 : 0);
     const long cols = few ? RS_FEW_COLS : RS_COLS;
-    hipLaunchKernelGGL(rows_sum_kernel, dim3((unsigned)((n + cols - 1) / cols)), dim3(256), 0, st, job);
+    return (int)((job.n + cols - 1) / cols);
+}
+static inline void launch_reduce_job(cswin_reduce_job job, hipStream_t st) {
+    const int blocks = flag_reduce_job(job);
+    hipLaunchKernelGGL(rows_sum_kernel, dim3(blocks), dim3(256), 0, st, job);
 }
 
 // workgroup `blk` of a job table (256 threads; `red` = 16 x 65 floats of LDS): the job is the last k with first_block[k] <= blk
@@ -309,17 +314,18 @@ static inline int fill_reduce_table(const cswin_reduce_job* jobs, int njobs, csw
         if (!(jobs[i].part && jobs[i].out && jobs[i].n > 0 && jobs[i].rows > 0)) return -1;
         if ((jobs[i].conv_kk == 0) != (jobs[i].conv_cin == 0) || jobs[i].conv_kk < 0) return -1;
         out[i] = jobs[i];
-        const int few = reduce_job_few_ok(jobs[i]);
-        out[i].reserved = reduce_job_vec_ok(jobs[i]) | (few ? 2 : 0);
         first_block[i] = blocks;
-        blocks += few ? (int)((jobs[i].n + RS_FEW_COLS - 1) / RS_FEW_COLS) : (int)((jobs[i].n + RS_COLS - 1) / RS_COLS);
+        blocks += flag_reduce_job(out[i]);
     }
     first_block[njobs] = blocks;
     return blocks;
 }
 
-// run `job` now, or hand it to the caller (deferred != NULL) to be batched by cswin_rows_sum_multi
+// run `job` now, or hand it to the caller (deferred != NULL) to be batched by cswin_rows_sum_multi: the same job either way
 static inline void reduce_now_or_defer(const cswin_reduce_job& job, cswin_reduce_job* deferred, hipStream_t st) {
     if (deferred) *deferred = job;
-    else launch_rows_sum(job.part, job.out, job.out2, (long)job.n_first, (long)job.n, job.rows, (long)job.stride, st);
+    else launch_reduce_job(job, st);
 }
+
+// floats between the split-M slabs of a weight gradient dw[N,K]: slab s = [dw partial (N*K) | dbias partial (N)] (gemm.hip's WgradSlabs)
+static inline long wgrad_slab_stride(int N, int K) { return (long)N * K + N; }

@@ -548,8 +548,11 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
     if (do_colsum && m0 + tid < M) epi.colsum[(long)split * epi.colsum_stride + m0 + tid] = csum;
 }
 
+// threads of a workgroup: KW groups of 2 x 2 (64 x 32 tile: 2 x 1) waves
+constexpr int gemm_threads(int BM, int BN, int KW) { return 64 * (BM >= 64 ? 2 : 1) * (BN >= 64 ? 2 : 1) * KW; }
+
 template <int BM, int BN, int BK, int KW, bool A_RC, bool B_RC, int VEC, int EPI, bool SCALE_A, int PREC, class ASrc, class BSrc>
-__global__ __launch_bounds__(64 * (BM >= 64 ? 2 : 1) * (BN >= 64 ? 2 : 1) * KW) void gemm_kernel(ASrc A, BSrc B, Epilogue epi, int M, int N, int R,
+__global__ __launch_bounds__(gemm_threads(BM, BN, KW)) void gemm_kernel(ASrc A, BSrc B, Epilogue epi, int M, int N, int R,
                                                     int r_per_split, int tiles_m, int tiles_n) {
     __shared__ __attribute__((aligned(16))) float lds[gemm_lds_floats<BM, BN, BK, KW, A_RC, B_RC>()];
     gemm_body<BM, BN, BK, KW, A_RC, B_RC, VEC, EPI, SCALE_A, PREC, ASrc, BSrc>(lds, A, B, epi, M, N, R, r_per_split, tiles_m, tiles_n,
@@ -629,18 +632,31 @@ __global__ __launch_bounds__(256 * KW) void gemm_conv_s2_dgrad_batch_kernel(Gemm
         b.first[p + 1] - b.first[p], (int)blockIdx.x);
 }
 
+// ======================================================================================
+// host side: launch policy (tile, k-groups, splits, batches), then the C ABI
+// ======================================================================================
 template <int BM, int BN, int BK, int KW, bool A_RC, bool B_RC, int VEC, int EPI, bool SCALE_A, int PREC, class ASrc, class BSrc>
 void launch_cfg(const ASrc& A, const BSrc& B, const Epilogue& epi, int M, int N, int R, int splits, int r_per_split,
                 hipStream_t st) {
     int tm = cdiv(M, BM), tn = cdiv(N, BN);
     dim3 grid(tm * tn * splits);
     const int pad_lds = cswin_tuning().gemm_pad_lds;                                                    // tuning aid: caps residency
-    hipLaunchKernelGGL((gemm_kernel<BM, BN, BK, KW, A_RC, B_RC, VEC, EPI, SCALE_A, PREC, ASrc, BSrc>), grid, dim3(64 * (BM >= 64 ? 2 : 1) * (BN >= 64 ? 2 : 1) * KW), pad_lds, st, A, B, epi,
+    hipLaunchKernelGGL((gemm_kernel<BM, BN, BK, KW, A_RC, B_RC, VEC, EPI, SCALE_A, PREC, ASrc, BSrc>), grid, dim3(gemm_threads(BM, BN, KW)), pad_lds, st, A, B, epi,
                        M, N, R, r_per_split, tm, tn);
 }
 
-// tile choice (measured on MI355X, tools/gemm_bench.py): the largest tile that still yields >= ~1.5 workgroups per CU
+// Wave groups (KW) for a launch of `blocks` workgroups whose reduction is r_len long: with fewer than ~2 workgroups per CU and
+// a long reduction, split the k-range of each tile over 2 or 4 wave groups so every SIMD still has independent MFMA chains.
+int k_groups(long blocks, int r_len) {
+    if (blocks < 320 && r_len >= 512) return 4;
+    if (blocks < 640 && r_len >= 256) return 2;
+    return 1;
+}
 
+// a reduction of R in one split: r_per_split is a whole number of k-tiles
+int one_split(int R) { return cdiv(R, BKMAX) * BKMAX; }
+
+// tile choice (measured on MI355X, tools/gemm_bench.py): the largest tile that still yields >= ~1.5 workgroups per CU
 template <bool A_RC, bool B_RC, int VEC, int EPI, bool SCALE_A, class ASrc, class BSrc>
 void launch_gemm(const ASrc& A, const BSrc& B, const Epilogue& epi_in, int M, int N, int R, int splits, int r_per_split,
                  int precision, hipStream_t st) {
@@ -661,31 +677,34 @@ void launch_gemm(const ASrc& A, const BSrc& B, const Epilogue& epi_in, int M, in
     if (splits == 1 && cost(64, 32, pen2) < cost(64, 64, 1.0)) tile = 2;
     if (forced_tile) tile = forced_tile;
     const int r_len = r_per_split < R ? r_per_split : R;
+    const bool wgrad = !A_RC && !B_RC;
     if (precision == 1) {
         // bf16 operands: 16x fewer MFMA cycles per tile, the kernel is bound by staging and barriers: one k-tile of 64,
         // and two wave groups only where a long reduction meets few workgroups
-        const long nb = blocks(64, 64);
-        if ((nb < 640 && r_len >= 256) || (!A_RC && !B_RC && r_len >= 256))
+        if (k_groups(blocks(64, 64), r_len) >= 2 || (wgrad && r_len >= 256))
             launch_cfg<64, 64, 64, 2, A_RC, B_RC, VEC, EPI, SCALE_A, 1>(A, B, epi, M, N, R, splits, r_per_split, st);
         else launch_cfg<64, 64, 64, 1, A_RC, B_RC, VEC, EPI, SCALE_A, 1>(A, B, epi, M, N, R, splits, r_per_split, st);
         return;
     }
     if (tile == 2) {
-        if (blocks(64, 32) < 640 && r_len >= 256)
+        if (k_groups(blocks(64, 32), r_len) >= 2)
             return launch_cfg<64, 32, 64, 2, A_RC, B_RC, VEC, EPI, SCALE_A, 0>(A, B, epi, M, N, R, splits, r_per_split, st);
         return launch_cfg<64, 32, 32, 1, A_RC, B_RC, VEC, EPI, SCALE_A, 0>(A, B, epi, M, N, R, splits, r_per_split, st);
     }
-    // 64 x 64: with fewer than ~2 workgroups per CU and a long reduction, split the k-range of each tile over 2 or 4 wave
-    // groups so every SIMD still has independent MFMA chains.
-    const long nb = blocks(64, 64);
-    int kw = 1;
-    if (nb < 640 && r_len >= 256) kw = 2;
-    if (nb < 320 && r_len >= 512) kw = 4;
-    if (!A_RC && !B_RC && r_len >= 256 && kw < 2) kw = 2;      // weight gradients: measured 5-8 % faster
+    int kw = k_groups(blocks(64, 64), r_len);
+    if (wgrad && r_len >= 256 && kw < 2) kw = 2;               // weight gradients: measured 5-8 % faster
     if (forced_kw) kw = forced_kw;
     if (kw == 4) launch_cfg<64, 64, 64, 4, A_RC, B_RC, VEC, EPI, SCALE_A, 0>(A, B, epi, M, N, R, splits, r_per_split, st);
     else if (kw == 2) launch_cfg<64, 64, 64, 2, A_RC, B_RC, VEC, EPI, SCALE_A, 0>(A, B, epi, M, N, R, splits, r_per_split, st);
     else launch_cfg<64, 64, 32, 1, A_RC, B_RC, VEC, EPI, SCALE_A, 0>(A, B, epi, M, N, R, splits, r_per_split, st);
+}
+
+// launch_gemm with the loaders' width chosen at run time: vec = 16-B loads are legal (alignment, sizes multiples of 4)
+template <bool A_RC, bool B_RC, int EPI, bool SCALE_A, class ASrc, class BSrc>
+void launch_gemm_vec(bool vec, const ASrc& A, const BSrc& B, const Epilogue& epi, int M, int N, int R, int splits, int r_per_split,
+                     int precision, hipStream_t st) {
+    if (vec) launch_gemm<A_RC, B_RC, 4, EPI, SCALE_A>(A, B, epi, M, N, R, splits, r_per_split, precision, st);
+    else launch_gemm<A_RC, B_RC, 1, EPI, SCALE_A>(A, B, epi, M, N, R, splits, r_per_split, precision, st);
 }
 
 long long* g_stamps = nullptr;     // debug only (cswin_debug_set_stamps)
@@ -696,6 +715,18 @@ Epilogue plain_epilogue(float* C, long ldc) {
     e.ldc = ldc;
     e.stamps = g_stamps;
     return e;
+}
+
+// problem (A, B, e) with M x N outputs and a reduction of R in `splits` slices of rps as the next slot of a batch; its 64 x 64
+// tiles take the next workgroups (first[b.n] is the launch's workgroup count so far)
+template <class ASrc, class BSrc>
+void push(GemmBatch<ASrc, BSrc>& b, const ASrc& A, const BSrc& B, Epilogue e, int M, int N, int R, int rps, int splits) {
+    const int i = b.n++;
+    e.vec_store = epilogue_vec_ok(e, N);
+    b.A[i] = A; b.B[i] = B; b.e[i] = e;
+    b.M[i] = M; b.N[i] = N; b.R[i] = R; b.rps[i] = rps;
+    b.tm[i] = cdiv(M, 64); b.tn[i] = cdiv(N, 64);
+    b.first[i + 1] = b.first[i] + b.tm[i] * b.tn[i] * splits;
 }
 
 // split count for the M-reduction of a weight gradient: enough workgroups to fill the chip
@@ -716,6 +747,237 @@ void choose_split(int M, int out_rows, int out_cols, int* splits, int* r_per_spl
     *r_per_split = rps;
 }
 
+// The workspace of a split-M weight gradient dw[N,K] (+ dbias[N]): slab s = [dw partial (N*K) | dbias partial (N)], the slabs
+// wgrad_slab_stride(N, K) apart, so that one reduction launch serves both.  The GEMM's epilogue writes the slabs, the job sums them.
+struct WgradSlabs {
+    float* base; long stride; int N, K;
+    WgradSlabs(void* workspace, int N_, int K_) : base((float*)workspace), stride(wgrad_slab_stride(N_, K_)), N(N_), K(K_) {}
+    // covers the stand-alone split policy and the batched one (up to 1024 workgroups for a single problem)
+    static size_t bytes(int M, int N, int K) {
+        int s0, s1, rps;
+        choose_split(M, N, K, &s0, &rps);
+        choose_split(M, N, K, &s1, &rps, 1024);
+        return (size_t)(s0 > s1 ? s0 : s1) * wgrad_slab_stride(N, K) * sizeof(float);
+    }
+    Epilogue epilogue(bool with_dbias) const {
+        Epilogue e = plain_epilogue(base, K);
+        e.split_stride = stride;
+        e.colsum = with_dbias ? base + (long)N * K : nullptr;
+        e.colsum_stride = (int)stride;
+        return e;
+    }
+    // conv_kk / conv_cin: a convolution's dw goes to the nn.Conv2d layout (see cswin_reduce_job)
+    cswin_reduce_job job(float* dw, float* dbias, int splits, int conv_kk = 0, int conv_cin = 0) const {
+        const long nk = (long)N * K;
+        return cswin_reduce_job{base, dw, dbias, nk, nk + (dbias ? N : 0), stride, splits, 0, conv_kk, conv_cin};
+    }
+};
+
+// jobs: HOST array of njobs (<= CSWIN_MAX_REDUCE_JOBS = 48) reductions left pending by *_bwd_weight / layernorm_bwd calls with `deferred` set
+int rows_sum_multi(const cswin_reduce_job* jobs, int njobs, void* stream) {
+    CSWIN_REQUIRE(jobs && njobs > 0 && njobs <= CSWIN_MAX_REDUCE_JOBS, CSWIN_ERR_SHAPE, "rows_sum_multi: 1..%d jobs", CSWIN_MAX_REDUCE_JOBS);
+    ReduceJobs J = {};
+    const int blocks = fill_reduce_table(jobs, njobs, J.j, J.first_block);
+    CSWIN_REQUIRE(blocks >= 0, CSWIN_ERR_SHAPE, "rows_sum_multi: bad job (part / out / n / rows, or conv_kk without conv_cin)");
+    J.njobs = njobs;
+    hipLaunchKernelGGL(rows_sum_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, J);
+    CSWIN_LAUNCH_CHECK();
+    return CSWIN_OK;
+}
+
+// One weight gradient dw[N,K] = (row_scale . dy)^T @ [x | x2] through the tiled GEMM (arguments checked by the caller); its slab
+// reduction runs at once or goes to *deferred
+int wgrad_tiled(const float* dy, const float* x, const float* x2, int k_split, const float* row_scale, int rows_per_sample, float* dw,
+                float* dbias, void* workspace, int M, int N, int K, cswin_reduce_job* deferred, int precision, hipStream_t st) {
+    int splits, rps;
+    choose_split(M, N, K, &splits, &rps);
+    const WgradSlabs slabs(workspace, N, K);
+    const Epilogue e = slabs.epilogue(dbias != nullptr);
+    PlainSrc A = {dy, N, M, N, row_scale, rows_per_sample};      // S(i = m (reduction), j = n)
+    if (x2) {
+        ConcatSrc B = {x, x2, k_split, K - k_split, M, K, k_split};
+        bool vec = (N % 4 == 0) && (K % 4 == 0) && (k_split % 4 == 0) && aligned16(dy) && aligned16(x) && aligned16(x2);
+        launch_gemm_vec<false, false, EPI_PLAIN, true>(vec, A, B, e, N, K, M, splits, rps, precision, st);
+    } else {
+        PlainSrc B = {x, K, M, K, nullptr, 1};
+        bool vec = (N % 4 == 0) && (K % 4 == 0) && aligned16(dy) && aligned16(x);
+        if (row_scale) launch_gemm_vec<false, false, EPI_PLAIN, true>(vec, A, B, e, N, K, M, splits, rps, precision, st);
+        else launch_gemm_vec<false, false, EPI_PLAIN, false>(vec, A, B, e, N, K, M, splits, rps, precision, st);
+    }
+    CSWIN_LAUNCH_CHECK();
+    reduce_now_or_defer(slabs.job(dw, dbias, splits), deferred, st);
+    CSWIN_LAUNCH_CHECK();
+    return CSWIN_OK;
+}
+
+// what the batch kernels require of a problem: 16-B loads of both operands and 16-B stores to the slabs
+bool wgrad_aligned(const cswin_wgrad_desc& p) {
+    return p.N % 4 == 0 && p.K % 4 == 0 && aligned16(p.dy) && aligned16(p.x) && aligned16(p.workspace);
+}
+
+// what may ride at the end of the weight-gradient batch's grid: a plain fp32 data gradient dx[M,K] = dy[M,N] @ w[N,K] (dy == NULL:
+// none; cswin_linear_bwd_tail) and reductions left pending by earlier launches.  who: the entry point, for its error text.
+struct TailExtras { const char* who; const float* dy; const float* w; float* dx; int M, N, K; const cswin_reduce_job* jobs; int njobs; };
+
+int wgrad_batch_impl(const cswin_wgrad_desc* d, int n, cswin_reduce_job* deferred, const TailExtras& x, void* stream) {
+    CSWIN_REQUIRE(x.njobs >= 0 && x.njobs <= CSWIN_TAIL_RIDER_JOBS && (x.njobs == 0 || x.jobs), CSWIN_ERR_SHAPE,
+                  "%s: 0..%d pending reductions", x.who, CSWIN_TAIL_RIDER_JOBS);
+    CSWIN_REQUIRE(d && deferred && n >= 1 && n <= WGRAD_BATCH, CSWIN_ERR_SHAPE, "linear_bwd_weight_batch: 1..%d problems and their deferred slots", WGRAD_BATCH);
+    bool fast = true, any_bf16 = false;
+    const int precision = d[0].precision;
+    CSWIN_CHECK_PRECISION(precision, "linear_bwd_weight_batch");
+    for (int i = 0; i < n; ++i) {
+        CSWIN_REQUIRE(d[i].precision == precision, CSWIN_ERR_UNSUPPORTED, "linear_bwd_weight_batch: problems of one launch share one precision");
+        CSWIN_REQUIRE(d[i].io_bf16 == 0 || (precision == 1 && (d[i].io_bf16 & ~3) == 0), CSWIN_ERR_UNSUPPORTED, "linear_bwd_weight_batch: bf16 storage needs precision 1");
+        CSWIN_REQUIRE(d[i].dy && d[i].x && d[i].dw && d[i].M > 0 && d[i].N > 0 && d[i].K > 0, CSWIN_ERR_SHAPE, "linear_bwd_weight_batch: bad problem %d", i);
+        CSWIN_REQUIRE(!d[i].row_scale || d[i].rows_per_sample > 0, CSWIN_ERR_SHAPE, "linear_bwd_weight_batch: rows_per_sample must be > 0");
+        size_t need = WgradSlabs::bytes(d[i].M, d[i].N, d[i].K);
+        CSWIN_REQUIRE(d[i].workspace && d[i].ws_bytes >= need, CSWIN_ERR_WORKSPACE, "linear_bwd_weight_batch: workspace %zu < %zu", d[i].ws_bytes, need);
+        fast = fast && wgrad_aligned(d[i]);
+        any_bf16 = any_bf16 || d[i].io_bf16;
+    }
+    const bool has_dgrad = x.dy != nullptr, extra = has_dgrad || x.njobs > 0;
+    // the data gradient as a GEMM problem (as cswin_linear_bwd_data poses it): M x K outputs, reduction N in one split
+    const PlainSrc gA = {x.dy, x.N, x.M, x.N, nullptr, 1, 0}, gB = {x.w, x.K, x.N, x.K, nullptr, 1, 0};      // gB: S(i = n (reduction), j = k)
+    const bool g_vec = x.N % 4 == 0 && x.K % 4 == 0 && aligned16(x.dy) && aligned16(x.w);
+    const bool merge_on = cswin_tuning().gemm_tail_merge != 0;                                                  // tuning aid
+    const bool ride = extra && merge_on && fast && precision == 0 && (!has_dgrad || (g_vec && aligned16(x.dx)));
+    const bool w16_path = fast && precision == 1 && (cswin_tuning().wgrad16_on || any_bf16);
+    const bool jobs_ride16 = merge_on && w16_path && x.njobs > 0;                     // bf16 mode: the reductions ride in wgrad16's grid
+    if (extra && !ride) {                   // the data gradient (and the pending reductions) as launches of their own, then the batch as usual
+        if (has_dgrad) {
+            launch_gemm_vec<true, false, EPI_PLAIN, false>(g_vec, gA, gB, plain_epilogue(x.dx, x.K), x.M, x.K, x.N, 1, one_split(x.N), precision,
+                                                           (hipStream_t)stream);
+            CSWIN_LAUNCH_CHECK();
+        }
+        if (x.njobs > 0 && !jobs_ride16) {
+            int rc = rows_sum_multi(x.jobs, x.njobs, stream);
+            if (rc) return rc;
+        }
+    }
+    if (!fast) {
+        // Separate launches.  In bf16 mode a problem that is aligned by itself still goes through the batch path, as a batch of one.
+        for (int i = 0; i < n; ++i) CSWIN_REQUIRE(d[i].io_bf16 == 0, CSWIN_ERR_ALIGN, "linear_bwd_weight_batch: bf16 storage needs N, K multiples of 4 and 16-B alignment");
+        const TailExtras none = {x.who};
+        for (int i = 0; i < n; ++i) {
+            int rc = precision == 1 && wgrad_aligned(d[i])
+                         ? wgrad_batch_impl(&d[i], 1, &deferred[i], none, stream)
+                         : wgrad_tiled(d[i].dy, d[i].x, nullptr, 0, d[i].row_scale, d[i].rows_per_sample, d[i].dw, d[i].dbias, d[i].workspace,
+                                       d[i].M, d[i].N, d[i].K, &deferred[i], precision, (hipStream_t)stream);
+            if (rc) return rc;
+        }
+        return CSWIN_OK;
+    }
+    if (w16_path) {
+        // bf16 operands: 128 x 128 tiles, ~3 workgroups per CU over the whole batch (load-bound: see wgrad16.hip)
+        // Workgroups are shared out in proportion to the work (rows x tiles), so that every workgroup of the launch walks the same
+        // number of rows: with equal shares per problem the C x C problem's workgroups finished after 10 k cycles and the C x 4C
+        // ones after 37 k (in-kernel stamps, tools/wgrad16_stamps.py), and the launch lasts as long as its slowest workgroup.
+        int splits[WGRAD_BATCH], rps[WGRAD_BATCH];
+        double work_total = 0.0;
+        for (int i = 0; i < n; ++i) work_total += (double)d[i].M * cdiv(d[i].N, 128) * cdiv(d[i].K, 128);
+        for (int i = 0; i < n; ++i) {
+            const int M = d[i].M, N = d[i].N, K = d[i].K;
+            const WgradSlabs slabs(d[i].workspace, N, K);
+            const int tiles = cdiv(N, 128) * cdiv(K, 128);
+            const int w16_wgs = cswin_tuning().w16_wgs, w16_even = cswin_tuning().w16_even;                // tuning aids (1 = equal share per problem)
+            int s = w16_even ? (w16_wgs / n) / tiles : (int)(w16_wgs * ((double)M * tiles / work_total) / tiles + 0.5);
+            const int cap = (int)(d[i].ws_bytes / (slabs.stride * (long)sizeof(float)));
+            if (s > cap) s = cap;
+            if (s > M / 64) s = M / 64;
+            if (s < 1) s = 1;
+            rps[i] = cdiv(cdiv(M, s), 32) * 32;
+            splits[i] = cdiv(M, rps[i]);
+            deferred[i] = slabs.job(d[i].dw, d[i].dbias, splits[i]);
+        }
+        CSWIN_REQUIRE(cswin_wgrad16_batch(d, n, splits, rps, jobs_ride16 ? x.jobs : nullptr, jobs_ride16 ? x.njobs : 0, stream, g_stamps) == 0,
+                      CSWIN_ERR_SHAPE, "linear_bwd_weight_batch: bad pending reduction");
+        CSWIN_LAUNCH_CHECK();
+        return CSWIN_OK;
+    }
+    WgradBatch b = {};
+    for (int i = 0; i < n; ++i) {
+        const int M = d[i].M, N = d[i].N, K = d[i].K;
+        int splits, rps;
+        // 1024 workgroups per launch, i.e. exactly 4 per CU, shared by the problems (measured with four problems: 192 / 256 /
+        // 320 per problem -> 13.80 / 13.55 / 14.09 ms per step); a quarter of the slab traffic of four stand-alone launches
+        const int batch_env = cswin_tuning().gemm_batch_wgs;                                                      // tuning aid
+        // Equal shares per problem (the C x C problem then has 294-row workgroups beside the 1176-row ones of the C x 4C problems).
+        // Shares in proportion to the work (CSWIN_GEMM_BATCH_EVEN=0), which pays for the load-bound bf16 kernel above, measured
+        // SLOWER here: 13.70 against 13.28 ms/step -- this kernel is matrix-pipe bound and the extra slabs cost more than the tail.
+        const int batch_even = cswin_tuning().gemm_batch_even;                                                      // tuning aid
+        const int total_wgs = batch_env > 0 ? (batch_env < 1024 ? batch_env : 1024) * n : 1024;
+        int batch_target = total_wgs / n;                                                            // the workspace query covers <= 1024
+        if (!batch_even) {
+            double work = 0.0;
+            for (int j = 0; j < n; ++j) work += (double)d[j].M * cdiv(d[j].N, 64) * cdiv(d[j].K, 64);
+            batch_target = (int)(total_wgs * ((double)M * cdiv(N, 64) * cdiv(K, 64) / work) + 0.5);
+            if (batch_target > 1024) batch_target = 1024;
+            if (batch_target < 1) batch_target = 1;
+        }
+        choose_split(M, N, K, &splits, &rps, batch_target);
+        const WgradSlabs slabs(d[i].workspace, N, K);
+        CSWIN_REQUIRE((size_t)splits * slabs.stride * sizeof(float) <= d[i].ws_bytes, CSWIN_ERR_WORKSPACE,
+                      "linear_bwd_weight_batch: %d slabs do not fit problem %d's workspace", splits, i);
+        push(b, PlainSrc{d[i].dy, N, M, N, d[i].row_scale, d[i].row_scale ? d[i].rows_per_sample : 1},   // S(i = m (reduction), j = n)
+             PlainSrc{d[i].x, K, M, K, nullptr, 1}, slabs.epilogue(d[i].dbias != nullptr), N, K, M, rps, splits);
+        deferred[i] = slabs.job(d[i].dw, d[i].dbias, splits);
+    }
+    const int blocks = b.first[n];
+    if (ride) {
+        BlockTail t = {};
+        if (has_dgrad) {       // one more problem, in fields of its own: 64 x 64 tiles
+            t.dA = gA; t.dB = gB;
+            t.de = plain_epilogue(x.dx, x.K);
+            t.de.vec_store = epilogue_vec_ok(t.de, x.K);
+            t.dM = x.M; t.dN = x.K; t.dR = x.N; t.drps = one_split(x.N);
+            t.dtm = cdiv(x.M, 64); t.dtn = cdiv(x.K, 64);
+            t.nd = t.dtm * t.dtn;
+        }
+        t.w = b;
+        int rblocks = 0;
+        if (x.njobs > 0) {
+            rblocks = fill_reduce_table(x.jobs, x.njobs, t.r.j, t.r.first_block);
+            CSWIN_REQUIRE(rblocks >= 0, CSWIN_ERR_SHAPE, "linear_bwd_tail: bad pending reduction");
+            t.r.njobs = x.njobs;
+        }
+        static_assert(sizeof(BlockTail) <= 4096, "kernel argument block");
+        hipLaunchKernelGGL(gemm_block_tail_kernel, dim3(blocks + t.nd + rblocks), dim3(512), 0, (hipStream_t)stream, t);
+    } else if (precision == 1) {
+        hipLaunchKernelGGL(gemm_wgrad_batch_kernel<1>, dim3(blocks), dim3(512), 0, (hipStream_t)stream, b);
+    } else {
+        hipLaunchKernelGGL(gemm_wgrad_batch_kernel<0>, dim3(blocks), dim3(512), 0, (hipStream_t)stream, b);
+    }
+    CSWIN_LAUNCH_CHECK();
+    return CSWIN_OK;
+}
+
+// dw_perm: [Cout][ks*ks][Cin], or the nn.Conv2d parameter layout [Cout][Cin_param][ks][ks] when torch_layout != 0; dbias: [Cout]
+int conv_wgrad_impl(const float* dy, const float* x, float* dw_perm, float* dbias, void* workspace, size_t ws_bytes, int B, int H,
+                    int W, int Cin, int Cout, int ks, int stride, int pad, int torch_layout, int Cin_param,
+                    cswin_reduce_job* deferred, int precision, void* stream) {
+    CSWIN_CHECK_PRECISION(precision, "conv_tok_bwd_weight");
+    CSWIN_REQUIRE(dy && x && dw_perm, CSWIN_ERR_SHAPE, "conv_tok_bwd_weight: null pointer");
+    CSWIN_REQUIRE(Cin % 4 == 0 && Cout % 4 == 0 && aligned16(dy) && aligned16(x), CSWIN_ERR_ALIGN, "conv_tok_bwd_weight: channels %% 4 and 16-B alignment required");
+    CSWIN_REQUIRE(!torch_layout || Cin < 65536, CSWIN_ERR_UNSUPPORTED, "conv_tok_bwd_weight: torch_layout needs Cin < 65536");
+    int OH = (H + 2 * pad - ks) / stride + 1, OW = (W + 2 * pad - ks) / stride + 1;
+    int M = B * OH * OW, K = ks * ks * Cin;
+    size_t need = WgradSlabs::bytes(M, Cout, K);
+    CSWIN_REQUIRE(workspace && ws_bytes >= need, CSWIN_ERR_WORKSPACE, "conv_tok_bwd_weight: workspace %zu < %zu", ws_bytes, need);
+    hipStream_t st = (hipStream_t)stream;
+    int splits, rps;
+    choose_split(M, Cout, K, &splits, &rps);
+    const WgradSlabs slabs(workspace, Cout, K);
+    PlainSrc A = {dy, Cout, M, Cout, nullptr, 1};
+    ConvSrc Bm = {x, B, H, W, Cin, OH, OW, ks, stride, pad, M, K};   // S(i = pixel m (reduction), j = (tap, ci))
+    launch_gemm<false, false, 4, EPI_PLAIN, false>(A, Bm, slabs.epilogue(dbias != nullptr), Cout, K, M, splits, rps, precision, st);
+    CSWIN_LAUNCH_CHECK();
+    reduce_now_or_defer(slabs.job(dw_perm, dbias, splits, torch_layout ? ks * ks : 0,
+                                  torch_layout ? (Cin | (Cin_param != Cin ? Cin_param << 16 : 0)) : 0), deferred, st);
+    CSWIN_LAUNCH_CHECK();
+    return CSWIN_OK;
+}
+
 }  // namespace
 
 // ======================================================================================
@@ -723,7 +985,9 @@ void choose_split(int M, int out_rows, int out_cols, int* splits, int* r_per_spl
 // ======================================================================================
 extern "C" {
 
-// debug aid (not part of include/cswin_hip.h): device buffer [nblk][4] of int64 that GEMM workgroups stamp with s_memtime
+// debug aid (not part of include/cswin_hip.h): device buffer [workgroups][8] of int64; workgroup w of a GEMM launch stamps row w:
+// slots 0-3 s_memtime at start / first tile staged / main loop done / epilogue done, 4 the hardware id register, 5-6 s_memrealtime
+// at start / end (7 unused)
 void cswin_debug_set_stamps(void* p) { g_stamps = (long long*)p; }
 
 int cswin_linear_fwd(const float* x, const float* x2, int k_split, const float* w, const float* bias, float* y,
@@ -744,19 +1008,14 @@ int cswin_linear_fwd(const float* x, const float* x2, int k_split, const float* 
     e.c_bf16 = (io_bf16 & 2) != 0;
     PlainSrc B = {w, K, N, K, nullptr, 1, (io_bf16 >> 2) & 1};
     CSWIN_REQUIRE(!(y_act && residual), CSWIN_ERR_UNSUPPORTED, "linear_fwd: activation and residual epilogues are exclusive");
-    const int rk = cdiv(K, BKMAX) * BKMAX;
+    const int rk = one_split(K);
     if (x2) {
         CSWIN_REQUIRE(!y_act, CSWIN_ERR_UNSUPPORTED, "linear_fwd: concat input does not support the activation epilogue");
         ConcatSrc A = {x, x2, k_split, K - k_split, M, K, k_split};
         bool vec = (k_split % 4 == 0) && (K % 4 == 0) && aligned16(x) && aligned16(x2) && aligned16(w);
         CSWIN_REQUIRE(io_bf16 == 0 || (io_bf16 == 4 && vec), CSWIN_ERR_UNSUPPORTED, "linear_fwd: a concat input takes only the bf16 weight flag (4), with 16-B aligned operands");
-        if (residual) {
-            if (vec) launch_gemm<true, true, 4, EPI_RES, false>(A, B, e, M, N, K, 1, rk, precision, st);
-            else launch_gemm<true, true, 1, EPI_RES, false>(A, B, e, M, N, K, 1, rk, precision, st);
-        } else {
-            if (vec) launch_gemm<true, true, 4, EPI_PLAIN, false>(A, B, e, M, N, K, 1, rk, precision, st);
-            else launch_gemm<true, true, 1, EPI_PLAIN, false>(A, B, e, M, N, K, 1, rk, precision, st);
-        }
+        if (residual) launch_gemm_vec<true, true, EPI_RES, false>(vec, A, B, e, M, N, K, 1, rk, precision, st);
+        else launch_gemm_vec<true, true, EPI_PLAIN, false>(vec, A, B, e, M, N, K, 1, rk, precision, st);
     } else {
         if (precision == 1 && (io_bf16 & 5) == 5) {             // both operands stored as bf16: LDS-DMA kernel (gemm16.hip)
             if (cswin_gemm16(0, y_act ? EPI_ACT : (residual ? EPI_RES : EPI_PLAIN), x, w, &e, M, N, K, stream) == 0) {
@@ -768,16 +1027,9 @@ int cswin_linear_fwd(const float* x, const float* x2, int k_split, const float* 
         bool vec = (K % 4 == 0) && aligned16(x) && aligned16(w);
         CSWIN_REQUIRE(io_bf16 == 0 || (vec && aligned16(y) && (!y_act || aligned16(y_act)) && (!bias || aligned16(bias))), CSWIN_ERR_ALIGN,
                       "linear_fwd: bf16 storage needs 16-B aligned operands");
-        if (y_act) {
-            if (vec) launch_gemm<true, true, 4, EPI_ACT, false>(A, B, e, M, N, K, 1, rk, precision, st);
-            else launch_gemm<true, true, 1, EPI_ACT, false>(A, B, e, M, N, K, 1, rk, precision, st);
-        } else if (residual) {
-            if (vec) launch_gemm<true, true, 4, EPI_RES, false>(A, B, e, M, N, K, 1, rk, precision, st);
-            else launch_gemm<true, true, 1, EPI_RES, false>(A, B, e, M, N, K, 1, rk, precision, st);
-        } else {
-            if (vec) launch_gemm<true, true, 4, EPI_PLAIN, false>(A, B, e, M, N, K, 1, rk, precision, st);
-            else launch_gemm<true, true, 1, EPI_PLAIN, false>(A, B, e, M, N, K, 1, rk, precision, st);
-        }
+        if (y_act) launch_gemm_vec<true, true, EPI_ACT, false>(vec, A, B, e, M, N, K, 1, rk, precision, st);
+        else if (residual) launch_gemm_vec<true, true, EPI_RES, false>(vec, A, B, e, M, N, K, 1, rk, precision, st);
+        else launch_gemm_vec<true, true, EPI_PLAIN, false>(vec, A, B, e, M, N, K, 1, rk, precision, st);
     }
     CSWIN_LAUNCH_CHECK();
     return CSWIN_OK;
@@ -807,7 +1059,7 @@ int cswin_linear_bwd_data(const float* dy, const float* w, float* dx, float* dx2
     PlainSrc B = {w, K, N, K, nullptr, 1, (io_bf16 >> 2) & 1};     // S(i = n (reduction), j = k): row-contiguous image
     bool vec = (N % 4 == 0) && (K % 4 == 0) && aligned16(dy) && aligned16(w);
     // output rows = M, output cols = K, reduction = N
-    const int rn = cdiv(N, BKMAX) * BKMAX;
+    const int rn = one_split(N);
     const int modes = (dx2 != nullptr) + (gelu_pre != nullptr) + (add != nullptr);
     CSWIN_REQUIRE(modes <= 1, CSWIN_ERR_UNSUPPORTED, "linear_bwd_data: dx2 / gelu_pre / add are mutually exclusive");
     if (precision == 1 && !dx2 && !add && (io_bf16 & 5) == 5) {  // both operands stored as bf16: LDS-DMA kernel (gemm16.hip)
@@ -816,42 +1068,15 @@ int cswin_linear_bwd_data(const float* dy, const float* w, float* dx, float* dx2
             return CSWIN_OK;
         }
     }
-    if (dx2) {
-        if (vec) launch_gemm<true, false, 4, EPI_SPLIT2, false>(A, B, e, M, K, N, 1, rn, precision, st);
-        else launch_gemm<true, false, 1, EPI_SPLIT2, false>(A, B, e, M, K, N, 1, rn, precision, st);
-    } else if (gelu_pre) {
-        if (vec) launch_gemm<true, false, 4, EPI_GELUBWD, false>(A, B, e, M, K, N, 1, rn, precision, st);
-        else launch_gemm<true, false, 1, EPI_GELUBWD, false>(A, B, e, M, K, N, 1, rn, precision, st);
-    } else if (add) {
-        if (vec) launch_gemm<true, false, 4, EPI_RES, false>(A, B, e, M, K, N, 1, rn, precision, st);
-        else launch_gemm<true, false, 1, EPI_RES, false>(A, B, e, M, K, N, 1, rn, precision, st);
-    } else {
-        if (vec) launch_gemm<true, false, 4, EPI_PLAIN, false>(A, B, e, M, K, N, 1, rn, precision, st);
-        else launch_gemm<true, false, 1, EPI_PLAIN, false>(A, B, e, M, K, N, 1, rn, precision, st);
-    }
+    if (dx2) launch_gemm_vec<true, false, EPI_SPLIT2, false>(vec, A, B, e, M, K, N, 1, rn, precision, st);
+    else if (gelu_pre) launch_gemm_vec<true, false, EPI_GELUBWD, false>(vec, A, B, e, M, K, N, 1, rn, precision, st);
+    else if (add) launch_gemm_vec<true, false, EPI_RES, false>(vec, A, B, e, M, K, N, 1, rn, precision, st);
+    else launch_gemm_vec<true, false, EPI_PLAIN, false>(vec, A, B, e, M, K, N, 1, rn, precision, st);
     CSWIN_LAUNCH_CHECK();
     return CSWIN_OK;
 }
 
-size_t cswin_linear_bwd_weight_workspace(int M, int N, int K) {
-    // covers the stand-alone split policy and the batched one (up to 1024 workgroups for a single problem)
-    int s0, s1, rps;
-    choose_split(M, N, K, &s0, &rps);
-    choose_split(M, N, K, &s1, &rps, 1024);
-    return (size_t)(s0 > s1 ? s0 : s1) * ((size_t)N * K + N) * sizeof(float);
-}
-
-int cswin_linear_bwd_weight_batch(const cswin_wgrad_desc* d, int n, cswin_reduce_job* deferred, const cswin_reduce_job* pending, int npending,
-                                  void* stream);
-int cswin_rows_sum_multi(const cswin_reduce_job* jobs, int njobs, void* stream);
-}  // extern "C"
-namespace {
-// what may ride at the end of the weight-gradient batch's grid: a plain fp32 data gradient dx[M,K] = dy[M,N] @ w[N,K] (dy == NULL:
-// none; cswin_linear_bwd_tail) and reductions left pending by earlier launches
-struct TailExtras { const float* dy; const float* w; float* dx; int M, N, K; const cswin_reduce_job* jobs; int njobs; };
-int wgrad_batch_impl(const cswin_wgrad_desc* d, int n, cswin_reduce_job* deferred, const TailExtras* extra, void* stream);
-}  // namespace
-extern "C" {
+size_t cswin_linear_bwd_weight_workspace(int M, int N, int K) { return WgradSlabs::bytes(M, N, K); }
 
 // dw[N,K] = (row_scale . dy)^T @ [x | x2];  dbias[N] = colsum(row_scale . dy)
 int cswin_linear_bwd_weight(const float* dy, const float* x, const float* x2, int k_split, const float* row_scale,
@@ -861,51 +1086,20 @@ int cswin_linear_bwd_weight(const float* dy, const float* x, const float* x2, in
     CSWIN_REQUIRE(dy && x && dw && M > 0 && N > 0 && K > 0, CSWIN_ERR_SHAPE, "linear_bwd_weight: bad arguments");
     CSWIN_REQUIRE(!x2 || (k_split > 0 && k_split < K), CSWIN_ERR_SHAPE, "linear_bwd_weight: bad concat split");
     CSWIN_REQUIRE(!row_scale || rows_per_sample > 0, CSWIN_ERR_SHAPE, "linear_bwd_weight: rows_per_sample must be > 0");
-    size_t need = cswin_linear_bwd_weight_workspace(M, N, K);
+    size_t need = WgradSlabs::bytes(M, N, K);
     CSWIN_REQUIRE(workspace && ws_bytes >= need, CSWIN_ERR_WORKSPACE, "linear_bwd_weight: workspace %zu < %zu", ws_bytes, need);
     hipStream_t st = (hipStream_t)stream;
-    if (precision == 1 && !x2 && N % 4 == 0 && K % 4 == 0 && aligned16(dy) && aligned16(x) && aligned16(workspace)) {
-        // bf16 mode: the transposing-read kernel (wgrad16.hip) through the batch entry, as a batch of one
-        cswin_wgrad_desc d1 = {dy, x, row_scale, dw, dbias, workspace, ws_bytes, rows_per_sample, M, N, K, 1, 0};
+    const cswin_wgrad_desc d1 = {dy, x, row_scale, dw, dbias, workspace, ws_bytes, rows_per_sample, M, N, K, precision, 0};
+    if (precision == 1 && !x2 && wgrad_aligned(d1)) {
+        // bf16 mode: the transposing-read kernel (wgrad16.hip) through the batch path, as a batch of one
         cswin_reduce_job job;
-        int rc = cswin_linear_bwd_weight_batch(&d1, 1, &job, nullptr, 0, stream);
+        int rc = wgrad_batch_impl(&d1, 1, &job, TailExtras{"linear_bwd_weight_batch"}, stream);
         if (rc) return rc;
         reduce_now_or_defer(job, deferred, st);
         CSWIN_LAUNCH_CHECK();
         return CSWIN_OK;
     }
-    int splits, rps;
-    choose_split(M, N, K, &splits, &rps);
-    // slab s = [dw partial (N*K) | dbias partial (N)]: one reduction launch serves both
-    float* slab = (float*)workspace;
-    const long slab_stride = (long)N * K + N;
-    Epilogue e = plain_epilogue(slab, K);
-    e.split_stride = slab_stride;
-    e.colsum = dbias ? slab + (long)N * K : nullptr;
-    e.colsum_stride = (int)slab_stride;
-    PlainSrc A = {dy, N, M, N, row_scale, rows_per_sample};      // S(i = m (reduction), j = n)
-    if (x2) {
-        ConcatSrc B = {x, x2, k_split, K - k_split, M, K, k_split};
-        bool vec = (N % 4 == 0) && (K % 4 == 0) && (k_split % 4 == 0) && aligned16(dy) && aligned16(x) && aligned16(x2);
-        if (vec) launch_gemm<false, false, 4, EPI_PLAIN, true>(A, B, e, N, K, M, splits, rps, precision, st);
-        else launch_gemm<false, false, 1, EPI_PLAIN, true>(A, B, e, N, K, M, splits, rps, precision, st);
-    } else {
-        PlainSrc B = {x, K, M, K, nullptr, 1};
-        bool vec = (N % 4 == 0) && (K % 4 == 0) && aligned16(dy) && aligned16(x);
-        if (row_scale) {
-            if (vec) launch_gemm<false, false, 4, EPI_PLAIN, true>(A, B, e, N, K, M, splits, rps, precision, st);
-            else launch_gemm<false, false, 1, EPI_PLAIN, true>(A, B, e, N, K, M, splits, rps, precision, st);
-        } else {
-            if (vec) launch_gemm<false, false, 4, EPI_PLAIN, false>(A, B, e, N, K, M, splits, rps, precision, st);
-            else launch_gemm<false, false, 1, EPI_PLAIN, false>(A, B, e, N, K, M, splits, rps, precision, st);
-        }
-    }
-    CSWIN_LAUNCH_CHECK();
-    long n = (long)N * K;
-    cswin_reduce_job job = {slab, dw, dbias, n, n + (dbias ? N : 0), slab_stride, splits, 0};
-    reduce_now_or_defer(job, deferred, st);
-    CSWIN_LAUNCH_CHECK();
-    return CSWIN_OK;
+    return wgrad_tiled(dy, x, x2, k_split, row_scale, rows_per_sample, dw, dbias, workspace, M, N, K, deferred, precision, st);
 }
 
 // n (<= 4) weight gradients without concat sources in one launch (see gemm_wgrad_batch_kernel); deferred[i] receives problem
@@ -913,10 +1107,7 @@ int cswin_linear_bwd_weight(const float* dy, const float* x, const float* x2, in
 // aligned / a multiple of 4 in N and K.
 int cswin_linear_bwd_weight_batch(const cswin_wgrad_desc* d, int n, cswin_reduce_job* deferred, const cswin_reduce_job* pending, int npending,
                                   void* stream) {
-    CSWIN_REQUIRE(npending >= 0 && npending <= CSWIN_TAIL_RIDER_JOBS && (npending == 0 || pending), CSWIN_ERR_SHAPE,
-                  "linear_bwd_weight_batch: 0..%d pending reductions", CSWIN_TAIL_RIDER_JOBS);
-    TailExtras r = {nullptr, nullptr, nullptr, 0, 0, 0, pending, npending};
-    return wgrad_batch_impl(d, n, deferred, npending > 0 ? &r : nullptr, stream);
+    return wgrad_batch_impl(d, n, deferred, TailExtras{"linear_bwd_weight_batch", nullptr, nullptr, nullptr, 0, 0, 0, pending, npending}, stream);
 }
 
 // The tail of a CSWinBlock's backward: dx[M,K] = dy[M,N] @ w[N,K] (the qkv Linear's data gradient, plain fp32, no epilogue extras)
@@ -925,156 +1116,8 @@ int cswin_linear_bwd_weight_batch(const cswin_wgrad_desc* d, int n, cswin_reduce
 int cswin_linear_bwd_tail(const float* dy, const float* w, float* dx, int M, int N, int K, const cswin_wgrad_desc* d, int n,
                           cswin_reduce_job* deferred, const cswin_reduce_job* pending, int npending, void* stream) {
     CSWIN_REQUIRE(dy && w && dx && M > 0 && N > 0 && K > 0, CSWIN_ERR_SHAPE, "linear_bwd_tail: bad data-gradient arguments");
-    CSWIN_REQUIRE(npending >= 0 && npending <= CSWIN_TAIL_RIDER_JOBS && (npending == 0 || pending), CSWIN_ERR_SHAPE,
-                  "linear_bwd_tail: 0..%d pending reductions", CSWIN_TAIL_RIDER_JOBS);
-    TailExtras r = {dy, w, dx, M, N, K, pending, npending};
-    return wgrad_batch_impl(d, n, deferred, &r, stream);
+    return wgrad_batch_impl(d, n, deferred, TailExtras{"linear_bwd_tail", dy, w, dx, M, N, K, pending, npending}, stream);
 }
-
-}  // extern "C"
-namespace {
-int wgrad_batch_impl(const cswin_wgrad_desc* d, int n, cswin_reduce_job* deferred, const TailExtras* extra, void* stream) {
-    CSWIN_REQUIRE(d && deferred && n >= 1 && n <= WGRAD_BATCH, CSWIN_ERR_SHAPE, "linear_bwd_weight_batch: 1..%d problems and their deferred slots", WGRAD_BATCH);
-    bool fast = true;
-    const int precision = d[0].precision;
-    CSWIN_CHECK_PRECISION(precision, "linear_bwd_weight_batch");
-    for (int i = 0; i < n; ++i) {
-        CSWIN_REQUIRE(d[i].precision == precision, CSWIN_ERR_UNSUPPORTED, "linear_bwd_weight_batch: problems of one launch share one precision");
-        CSWIN_REQUIRE(d[i].io_bf16 == 0 || (precision == 1 && (d[i].io_bf16 & ~3) == 0), CSWIN_ERR_UNSUPPORTED, "linear_bwd_weight_batch: bf16 storage needs precision 1");
-        CSWIN_REQUIRE(d[i].dy && d[i].x && d[i].dw && d[i].M > 0 && d[i].N > 0 && d[i].K > 0, CSWIN_ERR_SHAPE, "linear_bwd_weight_batch: bad problem %d", i);
-        CSWIN_REQUIRE(!d[i].row_scale || d[i].rows_per_sample > 0, CSWIN_ERR_SHAPE, "linear_bwd_weight_batch: rows_per_sample must be > 0");
-        size_t need = cswin_linear_bwd_weight_workspace(d[i].M, d[i].N, d[i].K);
-        CSWIN_REQUIRE(d[i].workspace && d[i].ws_bytes >= need, CSWIN_ERR_WORKSPACE, "linear_bwd_weight_batch: workspace %zu < %zu", d[i].ws_bytes, need);
-        fast = fast && d[i].N % 4 == 0 && d[i].K % 4 == 0 && aligned16(d[i].dy) && aligned16(d[i].x) && aligned16(d[i].workspace);
-    }
-    const bool has_dgrad = extra && extra->dy;
-    const bool merge_on = cswin_tuning().gemm_tail_merge != 0;                                                  // tuning aid
-    const bool ride = extra && merge_on && fast && precision == 0 &&
-                      (!has_dgrad || (extra->N % 4 == 0 && extra->K % 4 == 0 && aligned16(extra->dy) && aligned16(extra->w) && aligned16(extra->dx)));
-    const bool w16_path = fast && precision == 1 && (cswin_tuning().wgrad16_on || d[0].io_bf16 || (n > 1 && d[1].io_bf16) || (n > 2 && d[2].io_bf16) || (n > 3 && d[3].io_bf16));
-    const bool jobs_ride16 = extra && merge_on && w16_path && extra->njobs > 0;       // bf16 mode: the reductions ride in wgrad16's grid
-    if (extra && !ride) {                   // the data gradient (and the pending reductions) as launches of their own, then the batch as usual
-        if (has_dgrad) {
-            int rc = cswin_linear_bwd_data(extra->dy, extra->w, extra->dx, nullptr, 0, nullptr, nullptr, 1, nullptr, extra->M, extra->N,
-                                           extra->K, precision == 1 ? 1 : 0, 0, stream);
-            if (rc) return rc;
-        }
-        if (extra->njobs > 0 && !jobs_ride16) {
-            int rc = cswin_rows_sum_multi(extra->jobs, extra->njobs, stream);
-            if (rc) return rc;
-        }
-    }
-    if (!fast) {
-        for (int i = 0; i < n; ++i) CSWIN_REQUIRE(d[i].io_bf16 == 0, CSWIN_ERR_ALIGN, "linear_bwd_weight_batch: bf16 storage needs N, K multiples of 4 and 16-B alignment");
-        for (int i = 0; i < n; ++i) {
-            int rc = cswin_linear_bwd_weight(d[i].dy, d[i].x, nullptr, 0, d[i].row_scale, d[i].rows_per_sample, d[i].dw, d[i].dbias,
-                                             d[i].workspace, d[i].ws_bytes, d[i].M, d[i].N, d[i].K, &deferred[i], precision, stream);
-            if (rc) return rc;
-        }
-        return CSWIN_OK;
-    }
-    if (w16_path) {
-        // bf16 operands: 128 x 128 tiles, ~3 workgroups per CU over the whole batch (load-bound: see wgrad16.hip)
-        // Workgroups are shared out in proportion to the work (rows x tiles), so that every workgroup of the launch walks the same
-        // number of rows: with equal shares per problem the C x C problem's workgroups finished after 10 k cycles and the C x 4C
-        // ones after 37 k (in-kernel stamps, tools/wgrad16_stamps.py), and the launch lasts as long as its slowest workgroup.
-        int splits[WGRAD_BATCH], rps[WGRAD_BATCH];
-        double work_total = 0.0;
-        for (int i = 0; i < n; ++i) work_total += (double)d[i].M * cdiv(d[i].N, 128) * cdiv(d[i].K, 128);
-        for (int i = 0; i < n; ++i) {
-            const int M = d[i].M, N = d[i].N, K = d[i].K;
-            const long slab = ((long)N * K + N) * (long)sizeof(float);
-            const int tiles = cdiv(N, 128) * cdiv(K, 128);
-            const int w16_wgs = cswin_tuning().w16_wgs, w16_even = cswin_tuning().w16_even;                // tuning aids (1 = equal share per problem)
-            int s = w16_even ? (w16_wgs / n) / tiles : (int)(w16_wgs * ((double)M * tiles / work_total) / tiles + 0.5);
-            const int cap = (int)(d[i].ws_bytes / slab);
-            if (s > cap) s = cap;
-            if (s > M / 64) s = M / 64;
-            if (s < 1) s = 1;
-            rps[i] = cdiv(cdiv(M, s), 32) * 32;
-            splits[i] = cdiv(M, rps[i]);
-            const long nk = (long)N * K;
-            deferred[i] = cswin_reduce_job{(const float*)d[i].workspace, d[i].dw, d[i].dbias, nk, nk + (d[i].dbias ? N : 0), nk + N, splits[i], 0};
-        }
-        CSWIN_REQUIRE(cswin_wgrad16_batch(d, n, splits, rps, jobs_ride16 ? extra->jobs : nullptr, jobs_ride16 ? extra->njobs : 0, stream, g_stamps) == 0,
-                      CSWIN_ERR_SHAPE, "linear_bwd_weight_batch: bad pending reduction");
-        CSWIN_LAUNCH_CHECK();
-        return CSWIN_OK;
-    }
-    WgradBatch b = {};
-    int blocks = 0;
-    for (int i = 0; i < n; ++i) {
-        const int M = d[i].M, N = d[i].N, K = d[i].K;
-        int splits, rps;
-        // 1024 workgroups per launch, i.e. exactly 4 per CU, shared by the problems (measured with four problems: 192 / 256 /
-        // 320 per problem -> 13.80 / 13.55 / 14.09 ms per step); a quarter of the slab traffic of four stand-alone launches
-        const int batch_env = cswin_tuning().gemm_batch_wgs;                                                      // tuning aid
-        // Equal shares per problem (the C x C problem then has 294-row workgroups beside the 1176-row ones of the C x 4C problems).
-        // Shares in proportion to the work (CSWIN_GEMM_BATCH_EVEN=0), which pays for the load-bound bf16 kernel above, measured
-        // SLOWER here: 13.70 against 13.28 ms/step -- this kernel is matrix-pipe bound and the extra slabs cost more than the tail.
-        const int batch_even = cswin_tuning().gemm_batch_even;                                                      // tuning aid
-        const int total_wgs = batch_env > 0 ? (batch_env < 1024 ? batch_env : 1024) * n : 1024;
-        int batch_target = total_wgs / n;                                                            // the workspace query covers <= 1024
-        if (!batch_even) {
-            double work = 0.0;
-            for (int j = 0; j < n; ++j) work += (double)d[j].M * cdiv(d[j].N, 64) * cdiv(d[j].K, 64);
-            batch_target = (int)(total_wgs * ((double)M * cdiv(N, 64) * cdiv(K, 64) / work) + 0.5);
-            if (batch_target > 1024) batch_target = 1024;
-            if (batch_target < 1) batch_target = 1;
-        }
-        choose_split(M, N, K, &splits, &rps, batch_target);
-        CSWIN_REQUIRE((size_t)splits * ((size_t)N * K + N) * sizeof(float) <= d[i].ws_bytes, CSWIN_ERR_WORKSPACE,
-                      "linear_bwd_weight_batch: %d slabs do not fit problem %d's workspace", splits, i);
-        float* slab = (float*)d[i].workspace;
-        const long slab_stride = (long)N * K + N;
-        Epilogue e = plain_epilogue(slab, K);
-        e.split_stride = slab_stride;
-        e.colsum = d[i].dbias ? slab + (long)N * K : nullptr;
-        e.colsum_stride = (int)slab_stride;
-        e.vec_store = epilogue_vec_ok(e, K);
-        b.A[i] = PlainSrc{d[i].dy, N, M, N, d[i].row_scale, d[i].row_scale ? d[i].rows_per_sample : 1};   // S(i = m (reduction), j = n)
-        b.B[i] = PlainSrc{d[i].x, K, M, K, nullptr, 1};
-        b.e[i] = e;
-        b.M[i] = N; b.N[i] = K; b.R[i] = M; b.rps[i] = rps;
-        b.tm[i] = cdiv(N, 64); b.tn[i] = cdiv(K, 64);
-        b.first[i] = blocks;
-        blocks += b.tm[i] * b.tn[i] * splits;
-        const long nk = (long)N * K;
-        deferred[i] = cswin_reduce_job{slab, d[i].dw, d[i].dbias, nk, nk + (d[i].dbias ? N : 0), slab_stride, splits, 0};
-    }
-    b.first[n] = blocks;
-    b.n = n;
-    if (ride) {
-        BlockTail t = {};
-        if (has_dgrad) {
-            Epilogue e = plain_epilogue(extra->dx, extra->K);
-            e.vec_store = epilogue_vec_ok(e, extra->K);
-            t.dA = PlainSrc{extra->dy, extra->N, extra->M, extra->N, nullptr, 1, 0};
-            t.dB = PlainSrc{extra->w, extra->K, extra->N, extra->K, nullptr, 1, 0};      // S(i = n (reduction), j = k)
-            t.de = e;
-            t.dM = extra->M; t.dN = extra->K; t.dR = extra->N; t.drps = cdiv(extra->N, BKMAX) * BKMAX;
-            t.dtm = cdiv(extra->M, 64); t.dtn = cdiv(extra->K, 64);
-            t.nd = t.dtm * t.dtn;
-        }
-        t.w = b;
-        int rblocks = 0;
-        if (extra->njobs > 0) {
-            rblocks = fill_reduce_table(extra->jobs, extra->njobs, t.r.j, t.r.first_block);
-            CSWIN_REQUIRE(rblocks >= 0, CSWIN_ERR_SHAPE, "linear_bwd_tail: bad pending reduction");
-            t.r.njobs = extra->njobs;
-        }
-        static_assert(sizeof(BlockTail) <= 4096, "kernel argument block");
-        hipLaunchKernelGGL(gemm_block_tail_kernel, dim3(blocks + t.nd + rblocks), dim3(512), 0, (hipStream_t)stream, t);
-    } else if (precision == 1) {
-        hipLaunchKernelGGL(gemm_wgrad_batch_kernel<1>, dim3(blocks), dim3(512), 0, (hipStream_t)stream, b);
-    } else {
-        hipLaunchKernelGGL(gemm_wgrad_batch_kernel<0>, dim3(blocks), dim3(512), 0, (hipStream_t)stream, b);
-    }
-    CSWIN_LAUNCH_CHECK();
-    return CSWIN_OK;
-}
-}  // namespace
-extern "C" {
 
 // -------- convolutions on the (B, H*W, C) token layout (NHWC), implicit GEMM -----------------------------------
 // w_perm: [Cout][ks*ks][Cin]  (made by cswin_conv_weight_permute from the nn.Conv2d [Cout][Cin][ks][ks] parameter)
@@ -1089,7 +1132,7 @@ int cswin_conv_tok_fwd(const float* x, const float* w_perm, const float* bias, f
     PlainSrc Bm = {w_perm, R, Cout, R, nullptr, 1};
     Epilogue e = plain_epilogue(y, Cout);
     e.bias = bias;
-    launch_gemm<true, true, 4, EPI_PLAIN, false>(A, Bm, e, M, Cout, R, 1, cdiv(R, BKMAX) * BKMAX, precision, (hipStream_t)stream);
+    launch_gemm<true, true, 4, EPI_PLAIN, false>(A, Bm, e, M, Cout, R, 1, one_split(R), precision, (hipStream_t)stream);
     CSWIN_LAUNCH_CHECK();
     return CSWIN_OK;
 }
@@ -1105,7 +1148,7 @@ int cswin_conv_tok_bwd_data(const float* dy, const float* w_permT, float* dx, in
         // four parity classes, each a dense GEMM over only the taps that reach it (Merge_Block.conv, cswin_unet.py:208),
         // launched together (gemm_conv_s2_dgrad_batch_kernel)
         GemmBatch<ConvTS2Src, TapRowsSrc> b = {};
-        int blocks = 0, n = 0, rmax = 0;
+        int rmax = 0;
         for (int py = 0; py < 2; ++py)
             for (int px = 0; px < 2; ++px) {
                 const int H2 = (H - py + 1) / 2, W2 = (W - px + 1) / 2;
@@ -1119,34 +1162,20 @@ int cswin_conv_tok_bwd_data(const float* dy, const float* w_permT, float* dx, in
                         ++nt;
                     }
                 const int Mc = B * H2 * W2, Rc = nt * Cout;
-                b.A[n] = ConvTS2Src{dy, B, H, W, Cout, OH, OW, py, px, H2, W2, kys, kxs, Mc, Rc};
-                b.B[n] = TapRowsSrc{w_permT, Cout, Cin, taps, Rc, Cin};
                 Epilogue e = plain_epilogue(dx, Cin);
                 e.rm_on = 1; e.rm_H = H; e.rm_W = W; e.rm_H2 = H2; e.rm_W2 = W2; e.rm_py = py; e.rm_px = px;
-                e.vec_store = epilogue_vec_ok(e, Cin);
-                b.e[n] = e;
-                b.M[n] = Mc; b.N[n] = Cin; b.R[n] = Rc; b.rps[n] = cdiv(Rc, BKMAX) * BKMAX;
-                b.tm[n] = cdiv(Mc, 64); b.tn[n] = cdiv(Cin, 64);
-                b.first[n] = blocks;
-                blocks += b.tm[n] * b.tn[n];
+                push(b, ConvTS2Src{dy, B, H, W, Cout, OH, OW, py, px, H2, W2, kys, kxs, Mc, Rc}, TapRowsSrc{w_permT, Cout, Cin, taps, Rc, Cin},
+                     e, Mc, Cin, Rc, one_split(Rc), 1);
                 rmax = Rc > rmax ? Rc : rmax;
-                ++n;
             }
-        if (n > 0) {
-            b.first[n] = blocks;
-            b.n = n;
+        if (b.n > 0) {
+            const int blocks = b.first[b.n];
             hipStream_t st = (hipStream_t)stream;
-            // few workgroups and a long reduction: split each k-tile over wave groups (same rule as launch_gemm)
-            const int kw = (blocks < 320 && rmax >= 512) ? 4 : ((blocks < 640 && rmax >= 256) ? 2 : 1);
-            if (precision == 1) {
-                hipLaunchKernelGGL((gemm_conv_s2_dgrad_batch_kernel<2, 1>), dim3(blocks), dim3(512), 0, st, b);
-            } else if (kw == 4) {
-                hipLaunchKernelGGL((gemm_conv_s2_dgrad_batch_kernel<4, 0>), dim3(blocks), dim3(1024), 0, st, b);
-            } else if (kw == 2) {
-                hipLaunchKernelGGL((gemm_conv_s2_dgrad_batch_kernel<2, 0>), dim3(blocks), dim3(512), 0, st, b);
-            } else {
-                hipLaunchKernelGGL((gemm_conv_s2_dgrad_batch_kernel<1, 0>), dim3(blocks), dim3(256), 0, st, b);
-            }
+            const int kw = k_groups(blocks, rmax);
+            if (precision == 1) hipLaunchKernelGGL((gemm_conv_s2_dgrad_batch_kernel<2, 1>), dim3(blocks), dim3(512), 0, st, b);
+            else if (kw == 4) hipLaunchKernelGGL((gemm_conv_s2_dgrad_batch_kernel<4, 0>), dim3(blocks), dim3(1024), 0, st, b);
+            else if (kw == 2) hipLaunchKernelGGL((gemm_conv_s2_dgrad_batch_kernel<2, 0>), dim3(blocks), dim3(512), 0, st, b);
+            else hipLaunchKernelGGL((gemm_conv_s2_dgrad_batch_kernel<1, 0>), dim3(blocks), dim3(256), 0, st, b);
         }
         CSWIN_LAUNCH_CHECK();
         return CSWIN_OK;
@@ -1155,58 +1184,14 @@ int cswin_conv_tok_bwd_data(const float* dy, const float* w_permT, float* dx, in
     ConvTSrc A = {dy, B, H, W, Cout, OH, OW, ks, stride, pad, M, R};
     PlainSrc Bm = {w_permT, Cin, R, Cin, nullptr, 1};          // S(i = (tap, co), j = ci)
     Epilogue e = plain_epilogue(dx, Cin);
-    launch_gemm<true, false, 4, EPI_PLAIN, false>(A, Bm, e, M, Cin, R, 1, cdiv(R, BKMAX) * BKMAX, precision, (hipStream_t)stream);
+    launch_gemm<true, false, 4, EPI_PLAIN, false>(A, Bm, e, M, Cin, R, 1, one_split(R), precision, (hipStream_t)stream);
     CSWIN_LAUNCH_CHECK();
     return CSWIN_OK;
 }
 
 size_t cswin_conv_tok_bwd_weight_workspace(int B, int H, int W, int Cin, int Cout, int ks, int stride, int pad) {
     int OH = (H + 2 * pad - ks) / stride + 1, OW = (W + 2 * pad - ks) / stride + 1;
-    return cswin_linear_bwd_weight_workspace(B * OH * OW, Cout, ks * ks * Cin);
-}
-
-// dw_perm: [Cout][ks*ks][Cin], or the nn.Conv2d parameter layout [Cout][Cin][ks][ks] when torch_layout != 0; dbias: [Cout]
-static int conv_wgrad_impl(const float* dy, const float* x, float* dw_perm, float* dbias, void* workspace,
-                           size_t ws_bytes, int B, int H, int W, int Cin, int Cout, int ks, int stride, int pad,
-                           int torch_layout, int Cin_param, cswin_reduce_job* deferred, int precision, void* stream) {
-    CSWIN_CHECK_PRECISION(precision, "conv_tok_bwd_weight");
-    CSWIN_REQUIRE(dy && x && dw_perm, CSWIN_ERR_SHAPE, "conv_tok_bwd_weight: null pointer");
-    CSWIN_REQUIRE(Cin % 4 == 0 && Cout % 4 == 0 && aligned16(dy) && aligned16(x), CSWIN_ERR_ALIGN, "conv_tok_bwd_weight: channels %% 4 and 16-B alignment required");
-    CSWIN_REQUIRE(!torch_layout || Cin < 65536, CSWIN_ERR_UNSUPPORTED, "conv_tok_bwd_weight: torch_layout needs Cin < 65536");
-    int OH = (H + 2 * pad - ks) / stride + 1, OW = (W + 2 * pad - ks) / stride + 1;
-    int M = B * OH * OW, K = ks * ks * Cin;
-    size_t need = cswin_linear_bwd_weight_workspace(M, Cout, K);
-    CSWIN_REQUIRE(workspace && ws_bytes >= need, CSWIN_ERR_WORKSPACE, "conv_tok_bwd_weight: workspace %zu < %zu", ws_bytes, need);
-    hipStream_t st = (hipStream_t)stream;
-    int splits, rps;
-    choose_split(M, Cout, K, &splits, &rps);
-    float* slab = (float*)workspace;
-    const long slab_stride = (long)Cout * K + Cout;
-    Epilogue e = plain_epilogue(slab, K);
-    e.split_stride = slab_stride;
-    e.colsum = dbias ? slab + (long)Cout * K : nullptr;
-    e.colsum_stride = (int)slab_stride;
-    PlainSrc A = {dy, Cout, M, Cout, nullptr, 1};
-    ConvSrc Bm = {x, B, H, W, Cin, OH, OW, ks, stride, pad, M, K};   // S(i = pixel m (reduction), j = (tap, ci))
-    launch_gemm<false, false, 4, EPI_PLAIN, false>(A, Bm, e, Cout, K, M, splits, rps, precision, st);
-    CSWIN_LAUNCH_CHECK();
-    long n = (long)Cout * K;
-    cswin_reduce_job job = {slab, dw_perm, dbias, n, n + (dbias ? Cout : 0), slab_stride, splits, 0, torch_layout ? ks * ks : 0,
-                            torch_layout ? (Cin | (Cin_param != Cin ? Cin_param << 16 : 0)) : 0};
-    if (deferred) {
-        *deferred = job;
-        return CSWIN_OK;
-    }
-    if (torch_layout) {
-        const int few = reduce_job_few_ok(job);                  // a channel-padded job only: it reduces as a plain one does
-        job.reserved = reduce_job_vec_ok(job) | (few ? 2 : 0);
-        const long cols = few ? RS_FEW_COLS : RS_COLS;
-        hipLaunchKernelGGL(rows_sum_kernel, dim3((unsigned)((job.n + cols - 1) / cols)), dim3(256), 0, st, job);
-    } else {
-        launch_rows_sum(slab, dw_perm, dbias, n, n + (dbias ? Cout : 0), splits, slab_stride, st);
-    }
-    CSWIN_LAUNCH_CHECK();
-    return CSWIN_OK;
+    return WgradSlabs::bytes(B * OH * OW, Cout, ks * ks * Cin);
 }
 
 int cswin_conv_tok_bwd_weight(const float* dy, const float* x, float* dw_perm, float* dbias, void* workspace,
@@ -1227,16 +1212,6 @@ int cswin_conv_tok_bwd_weight_cpad(const float* dy, const float* x, float* dw, f
                            stream);
 }
 
-// jobs: HOST array of njobs (<= CSWIN_MAX_REDUCE_JOBS = 48) reductions left pending by *_bwd_weight / layernorm_bwd calls with `deferred` set
-int cswin_rows_sum_multi(const cswin_reduce_job* jobs, int njobs, void* stream) {
-    CSWIN_REQUIRE(jobs && njobs > 0 && njobs <= CSWIN_MAX_REDUCE_JOBS, CSWIN_ERR_SHAPE, "rows_sum_multi: 1..%d jobs", CSWIN_MAX_REDUCE_JOBS);
-    ReduceJobs J = {};
-    const int blocks = fill_reduce_table(jobs, njobs, J.j, J.first_block);
-    CSWIN_REQUIRE(blocks >= 0, CSWIN_ERR_SHAPE, "rows_sum_multi: bad job (part / out / n / rows, or conv_kk without conv_cin)");
-    J.njobs = njobs;
-    hipLaunchKernelGGL(rows_sum_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, J);
-    CSWIN_LAUNCH_CHECK();
-    return CSWIN_OK;
-}
+int cswin_rows_sum_multi(const cswin_reduce_job* jobs, int njobs, void* stream) { return rows_sum_multi(jobs, njobs, stream); }
 
 }  // extern "C"

@@ -172,7 +172,7 @@ int cswin_loss_sums(const float* logits, const long long* labels, float* sums, v
         NC_SWITCH(ncls, hipLaunchKernelGGL((loss_sums_kernel<NC, false>), dim3(nblk), dim3(256), 0, st, logits, labels, (float*)workspace, B, HW));
     }
     CSWIN_LAUNCH_CHECK();
-    launch_rows_sum((const float*)workspace, sums, nullptr, 0, 1 + 3 * ncls, nblk, 1 + 3 * ncls, st);
+    launch_reduce_job(cswin_reduce_job{(const float*)workspace, sums, nullptr, 0, 1 + 3 * ncls, 1 + 3 * ncls, nblk, 0, 0, 0}, st);
     CSWIN_LAUNCH_CHECK();
     return CSWIN_OK;
 }
