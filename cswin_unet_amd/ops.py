@@ -61,8 +61,11 @@ class engine_backward:
         return False
 
     def grad(self, param_key, shape, device):
-        """The tensor a parameter gradient is written to: the parameter's slot of the flat gradient buffer if `param_key` (what
-        _param_keys() recorded in forward) is a leaf parameter of this pass's optimiser, a fresh tensor otherwise."""
+        """The tensor a parameter gradient is written to: None for an absent parameter (`param_key` is what _param_keys()
+        recorded in forward), the parameter's slot of the flat gradient buffer if it is a leaf parameter of this pass's
+        optimiser, a fresh tensor otherwise."""
+        if param_key is None:
+            return None
         n = math.prod(shape)
         o, numel = self._slots.get(param_key, (0, -1)) if param_key else (0, -1)
         if numel != n:
@@ -87,8 +90,7 @@ class engine_backward:
             elif j.part:
                 now.append(j)
         if now:
-            arr = (ReduceJob * len(now))(*now)
-            call("cswin_rows_sum_multi", _job_ptr(arr), len(now), stream())
+            _rows_sum((ReduceJob * len(now))(*now))
 
     def queued_outputs(self):
         """Every address a waiting reduction will write."""
@@ -104,18 +106,17 @@ class engine_backward:
 
     def flush(self):
         while self._queue:
-            jobs, n, _owner = self.take_pending(MAX_REDUCE_JOBS)
-            call("cswin_rows_sum_multi", jobs, n, stream())
+            _rows_sum(self.take_pending(MAX_REDUCE_JOBS)[2][0])
 
 
 _pass = engine_backward()
 
 
 def _param_keys(*ts):
-    """Per parameter, what engine_backward.grad() finds its slot by: the address of a leaf of the autograd graph (a module
-    parameter passed as it is), 0 for anything else -- a view or a function of a parameter shares or lacks its address, but its
-    gradient is somebody's input, not final."""
-    return tuple(t.data_ptr() if t is not None and t.is_leaf else 0 for t in ts)
+    """Per parameter, what engine_backward.grad() places its gradient by: None for an absent one (no gradient), the address of
+    a leaf of the autograd graph (a module parameter passed as it is), 0 for anything else -- a view or a function of a
+    parameter shares or lacks its address, but its gradient is somebody's input, not final."""
+    return tuple(None if t is None else t.data_ptr() if t.is_leaf else 0 for t in ts)
 
 
 def _job_ptr(jobs, i=0):
@@ -123,15 +124,21 @@ def _job_ptr(jobs, i=0):
     return ctypes.c_void_p(ctypes.addressof(jobs) + i * ctypes.sizeof(ReduceJob))
 
 
-def _fill_wgrad(d, dy, x, row_scale, dw, dbias, workspace, ws_bytes, rows_per_sample, M, N, K, io_bf16=0):
-    """One WgradDesc of cswin_linear_bwd_weight_batch / _tail.  workspace: device address."""
-    d.dy, d.x, d.row_scale, d.dw, d.dbias = (t.data_ptr() if t is not None else None for t in (dy, x, row_scale, dw, dbias))
-    d.workspace, d.ws_bytes, d.rows_per_sample, d.M, d.N, d.K = workspace, ws_bytes, rows_per_sample, M, N, K
-    d.precision, d.io_bf16 = precision(), io_bf16
+def _rows_sum(jobs):
+    """One reduction launch for a ctypes array of ReduceJob."""
+    call("cswin_rows_sum_multi", _job_ptr(jobs), len(jobs), stream())
 
 
 def _ws(nbytes, device):
     return torch.empty(max(int(nbytes), 16) // 4 + 4, dtype=torch.float32, device=device)
+
+
+def _reduced(nbytes, device, launch, njobs=1):
+    """A launch that leaves partial slabs: launch(workspace pointer, its bytes, pointer to `njobs` job slots) with a workspace
+    of its own, then the pass reduces (or queues) what it left."""
+    ws, jobs = _ws(nbytes, device), (ReduceJob * njobs)()
+    launch(ptr(ws), nbytes, _job_ptr(jobs))
+    _pass.reduce(jobs, (ws,))
 
 
 def _int_array(vals):
@@ -142,19 +149,48 @@ def _ptr_array(tensors):
     return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
+def _stored16(*ts):
+    """Storage bits (io_bf16 / y_bf16 of include/cswin_hip.h) read off the tensors: bit i = the i-th is stored as bf16."""
+    return sum(1 << i for i, t in enumerate(ts) if t is not None and t.dtype == torch.bfloat16)
+
+
+def _rows_per_sample(t):
+    """Rows of the (M, C) matrix `t` per entry of a per-sample row_scale (the entry points read it only beside one)."""
+    return t.numel() // (t.shape[0] * t.shape[-1])
+
+
 # ------------------------------------------------------------------------------------------------
 # LayerNorm
 # ------------------------------------------------------------------------------------------------
+def _layernorm_fwd(x, gamma, beta, eps, dtype=torch.float32):
+    """(y stored as `dtype`, mean, rstd) of LayerNorm over the last dimension."""
+    C = x.shape[-1]
+    M = x.numel() // C
+    y = torch.empty_like(x, dtype=dtype)
+    mean = torch.empty(M, dtype=torch.float32, device=x.device)
+    rstd = torch.empty_like(mean)
+    call("cswin_layernorm_fwd", ptr(x), ptr(gamma), ptr(beta), ptr(y), ptr(mean), ptr(rstd), M, C, eps, _stored16(y), stream())
+    return y, mean, rstd
+
+
+def _layernorm_bwd(dy, x, mean, rstd, gamma, dx, dg, db, slab=None, *, dres=None, dx16=None):
+    """dx = dres + LayerNorm backward of dy; dx16: bf16 tensor that receives the rounded twin of dx.  slab: (workspace pointer,
+    bytes, job slot) of a caller that reduces later; by default the launch has its own and is reduced at once."""
+    C = x.shape[-1]
+    M = x.numel() // C
+    if slab is None:
+        return _reduced(lib().cswin_layernorm_bwd_workspace(M, C), x.device,
+                        lambda *s: _layernorm_bwd(dy, x, mean, rstd, gamma, dx, dg, db, s, dres=dres, dx16=dx16))
+    ws, nbytes, job = slab
+    call("cswin_layernorm_bwd", ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(dres), ptr(dx), ptr(dg), ptr(db), ws, nbytes,
+         M, C, job, ptr(dx16), stream())
+
+
 class _LayerNorm(Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, eps):
         x, gamma, beta = dev_f32(x, "layer_norm input"), dev_f32(gamma), dev_f32(beta)
-        C = x.shape[-1]
-        M = x.numel() // C
-        y = torch.empty_like(x)
-        mean = torch.empty(M, dtype=torch.float32, device=x.device)
-        rstd = torch.empty_like(mean)
-        call("cswin_layernorm_fwd", ptr(x), ptr(gamma), ptr(beta), ptr(y), ptr(mean), ptr(rstd), M, C, eps, 0, stream())
+        y, mean, rstd = _layernorm_fwd(x, gamma, beta, eps)
         ctx.save_for_backward(x, gamma, mean, rstd)
         ctx.keys = _param_keys(gamma, beta)
         return y
@@ -163,17 +199,9 @@ class _LayerNorm(Function):
     @once_differentiable
     def backward(ctx, dy):
         x, gamma, mean, rstd = ctx.saved_tensors
-        dy = dev_f32(dy)
-        C = x.shape[-1]
-        M = x.numel() // C
         dx = torch.empty_like(x)
         dg, db = (_pass.grad(k, gamma.shape, gamma.device) for k in ctx.keys)
-        nbytes = lib().cswin_layernorm_bwd_workspace(M, C)
-        ws = _ws(nbytes, x.device)
-        job = (ReduceJob * 1)()
-        call("cswin_layernorm_bwd", ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), None, ptr(dx), ptr(dg), ptr(db),
-             ptr(ws), nbytes, M, C, _job_ptr(job), None, stream())
-        _pass.reduce(job, (ws,))
+        _layernorm_bwd(dev_f32(dy), x, mean, rstd, gamma, dx, dg, db)
         return dx, dg, db, None
 
 
@@ -184,10 +212,6 @@ def layer_norm(x, gamma, beta, eps=1e-5):
 # ------------------------------------------------------------------------------------------------
 # Linear (+ fused skip-concat input, residual / DropPath epilogue)
 # ------------------------------------------------------------------------------------------------
-def _rows_per_sample(x):
-    return x.numel() // (x.shape[0] * x.shape[-1])
-
-
 # bf16 TWINS of fp32 residual-stream gradients (bf16 mode): a block's backward hands the gradient of its input to the next
 # backward as fp32 (the residual path needs it) and leaves a rounded copy here for that block's GEMMs.  An entry is consumed
 # once and only by the very tensor it was made for (same TensorImpl: the entry keeps the tensor alive, so its address cannot be
@@ -211,7 +235,7 @@ def clear_twins():
 def _wsrc(w):
     """(pointer, io_bf16 bits) of a Linear weight for cswin_linear_fwd / _bwd_data: in the bf16 mode with bf16 storage, the bf16
     shadow the optimiser keeps of it (bit 2) when there is one -- same values as the GEMM's own rounding, half the bytes --,
-    else the fp32 tensor."""
+    else the fp32 tensor.  The Linear helpers below take a weight as this pair or as a plain fp32 tensor."""
     if act_bf16() and w.shape[0] % 4 == 0 and w.shape[1] % 4 == 0:
         sp = shadow_ptr(w)
         if sp is not None:
@@ -219,23 +243,63 @@ def _wsrc(w):
     return ptr(w), 0
 
 
+def _linear_fwd(x, w, b, N, *, dtype=torch.float32, gelu=False, x2=None, residual=None, row_scale=None):
+    """y (..., N) = [x | x2] @ w^T + b as `dtype`;  residual: y = residual + row_scale[sample] * (...);  gelu: (y, GELU(y))."""
+    pw, w16 = w if isinstance(w, tuple) else (ptr(w), 0)
+    K1 = x.shape[-1]
+    K = K1 + (x2.shape[-1] if x2 is not None else 0)
+    y = torch.empty(x.shape[:-1] + (N,), dtype=dtype, device=x.device)
+    y_act = torch.empty_like(y) if gelu else None
+    call("cswin_linear_fwd", ptr(x), ptr(x2), K1 if x2 is not None else 0, pw, ptr(b), ptr(y), ptr(y_act), ptr(residual), ptr(row_scale),
+         _rows_per_sample(x), x.numel() // K1, N, K, precision(), _stored16(x, y) | w16, stream())
+    return (y, y_act) if gelu else y
+
+
+def _linear_bwd_data(dy, w, dx, *, dx2=None, gelu_pre=None, row_scale=None, add=None):
+    """[dx | dx2] = add + row_scale[sample] * ((dy @ w) * gelu'(gelu_pre)); also plain c = a @ b for row-major b."""
+    pw, w16 = w if isinstance(w, tuple) else (ptr(w), 0)
+    N, K1 = dy.shape[-1], dx.shape[-1]
+    K = K1 + (dx2.shape[-1] if dx2 is not None else 0)
+    call("cswin_linear_bwd_data", ptr(dy), pw, ptr(dx), ptr(dx2), K1 if dx2 is not None else 0, ptr(gelu_pre), ptr(row_scale),
+         _rows_per_sample(dy), ptr(add), dy.numel() // N, N, K, precision(), _stored16(dy, dx, None, gelu_pre) | w16, stream())
+
+
+def _linear_bwd_weight(dy, x, dw, db, slab=None, *, x2=None, row_scale=None):
+    """dw = (row_scale * dy)^T @ [x | x2], db = column sums of dy (or None).  slab as for _layernorm_bwd."""
+    N, K1 = dy.shape[-1], x.shape[-1]
+    K = K1 + (x2.shape[-1] if x2 is not None else 0)
+    M = dy.numel() // N
+    if slab is None:
+        return _reduced(lib().cswin_linear_bwd_weight_workspace(M, N, K), dy.device,
+                        lambda *s: _linear_bwd_weight(dy, x, dw, db, s, x2=x2, row_scale=row_scale))
+    ws, nbytes, job = slab
+    call("cswin_linear_bwd_weight", ptr(dy), ptr(x), ptr(x2), K1 if x2 is not None else 0, ptr(row_scale), _rows_per_sample(dy),
+         ptr(dw), ptr(db), ws, nbytes, M, N, K, job, precision(), stream())
+
+
+def _fill_wgrad(d, dy, x, row_scale, dw, dbias, workspace, ws_bytes):
+    """One WgradDesc of cswin_linear_bwd_weight_batch / _tail.  workspace: device pointer."""
+    d.dy, d.x, d.row_scale, d.dw, d.dbias = (t.data_ptr() if t is not None else None for t in (dy, x, row_scale, dw, dbias))
+    d.workspace, d.ws_bytes, d.rows_per_sample = workspace, ws_bytes, _rows_per_sample(dy)
+    d.N, d.K = dy.shape[-1], x.shape[-1]
+    d.M, d.precision, d.io_bf16 = dy.numel() // d.N, precision(), _stored16(dy, x)
+
+
+def _linear_bwd_weight_batch(wg, jobs, pending=(None, 0)):
+    """A WgradDesc array in one launch; jobs receives their reductions, pending = (pointer, count) earlier ones ride along."""
+    call("cswin_linear_bwd_weight_batch", ctypes.cast(wg, ctypes.c_void_p), len(wg), _job_ptr(jobs), *pending, stream())
+
+
 class _Linear(Function):
     @staticmethod
     def forward(ctx, x, w, b, x2, residual, row_scale):
         x, w = dev_f32(x, "linear input"), dev_f32(w, "linear weight")
         b, x2, residual, row_scale = dev_f32(b), dev_f32(x2), dev_f32(residual), dev_f32(row_scale)
-        K1 = x.shape[-1]
-        K = K1 + (x2.shape[-1] if x2 is not None else 0)
-        N = w.shape[0]
+        K = x.shape[-1] + (x2.shape[-1] if x2 is not None else 0)
         assert w.shape[1] == K, f"linear: weight {tuple(w.shape)} vs input features {K}"
-        M = x.numel() // K1
-        y = torch.empty(x.shape[:-1] + (N,), dtype=torch.float32, device=x.device)
-        rps = _rows_per_sample(x) if row_scale is not None else 1
-        pw, fw = _wsrc(w)
-        call("cswin_linear_fwd", ptr(x), ptr(x2), K1 if x2 is not None else 0, pw, ptr(b), ptr(y), None, ptr(residual),
-             ptr(row_scale), rps, M, N, K, precision(), fw, stream())
+        y = _linear_fwd(x, _wsrc(w), b, w.shape[0], x2=x2, residual=residual, row_scale=row_scale)
         ctx.save_for_backward(x, w, x2, row_scale)
-        ctx.has_bias, ctx.has_res, ctx.rps, ctx.keys = b is not None, residual is not None, rps, _param_keys(w, b)
+        ctx.has_res, ctx.keys = residual is not None, _param_keys(w, b)
         return y
 
     @staticmethod
@@ -243,28 +307,17 @@ class _Linear(Function):
     def backward(ctx, dy):
         x, w, x2, row_scale = ctx.saved_tensors
         dy = dev_f32(dy)
-        K1 = x.shape[-1]
-        N, K = w.shape
-        M = x.numel() // K1
         need = ctx.needs_input_grad
         dx = dx2 = dw = db = None
         if need[0] or (x2 is not None and need[3]):
             dx = torch.empty_like(x)
             dx2 = torch.empty_like(x2) if x2 is not None else None
-            pw, fw = _wsrc(w)
-            call("cswin_linear_bwd_data", ptr(dy), pw, ptr(dx), ptr(dx2), K1 if x2 is not None else 0, None,
-                 ptr(row_scale), ctx.rps, None, M, N, K, precision(), fw, stream())
+            _linear_bwd_data(dy, _wsrc(w), dx, dx2=dx2, row_scale=row_scale)
         if need[1]:
             dw = _pass.grad(ctx.keys[0], w.shape, w.device)
-            db = _pass.grad(ctx.keys[1], (N,), w.device) if ctx.has_bias else None
-            nbytes = lib().cswin_linear_bwd_weight_workspace(M, N, K)
-            ws = _ws(nbytes, w.device)
-            job = (ReduceJob * 1)()
-            call("cswin_linear_bwd_weight", ptr(dy), ptr(x), ptr(x2), K1 if x2 is not None else 0, ptr(row_scale), ctx.rps,
-                 ptr(dw), ptr(db), ptr(ws), nbytes, M, N, K, _job_ptr(job), precision(), stream())
-            _pass.reduce(job, (ws,))
-        dres = dy if ctx.has_res else None
-        return dx, dw, db, dx2, dres, None
+            db = _pass.grad(ctx.keys[1], w.shape[:1], w.device)
+            _linear_bwd_weight(dy, x, dw, db, x2=x2, row_scale=row_scale)
+        return dx, dw, db, dx2, (dy if ctx.has_res else None), None
 
 
 def linear(x, w, b=None, x2=None, residual=None, row_scale=None):
@@ -280,18 +333,10 @@ class _LinearPair(Function):
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2):
         x, w1, b1, w2, b2 = (dev_f32(t) for t in (x, w1, b1, w2, b2))
-        K = x.shape[-1]
-        M = x.numel() // K
-        ys = []
-        for w, b in ((w1, b1), (w2, b2)):
-            assert w.shape[1] == K
-            y = torch.empty(x.shape[:-1] + (w.shape[0],), dtype=torch.float32, device=x.device)
-            call("cswin_linear_fwd", ptr(x), None, 0, ptr(w), ptr(b), ptr(y), None, None, None, 1, M, w.shape[0], K, precision(), 0, stream())
-            ys.append(y)
+        assert w1.shape[1] == w2.shape[1] == x.shape[-1]
         ctx.save_for_backward(x, w1, w2)
-        ctx.has_b = (b1 is not None, b2 is not None)
         ctx.keys = _param_keys(w1, b1, w2, b2)
-        return tuple(ys)
+        return tuple(_linear_fwd(x, w, b, w.shape[0]) for w, b in ((w1, b1), (w2, b2)))
 
     @staticmethod
     @once_differentiable
@@ -300,24 +345,21 @@ class _LinearPair(Function):
         dy1, dy2 = dev_f32(dy1), dev_f32(dy2)
         K = x.shape[-1]
         M = x.numel() // K
-        st = stream()
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
-            call("cswin_linear_bwd_data", ptr(dy1), ptr(w1), ptr(dx), None, 0, None, None, 1, None, M, w1.shape[0], K, precision(), 0, st)
-            call("cswin_linear_bwd_data", ptr(dy2), ptr(w2), ptr(dx), None, 0, None, None, 1, ptr(dx), M, w2.shape[0], K, precision(), 0, st)
+            _linear_bwd_data(dy1, w1, dx)
+            _linear_bwd_data(dy2, w2, dx, add=dx)
         grads, keep = [], []
         wg, jobs = (WgradDesc * 2)(), (ReduceJob * 2)()
-        for i, (dy, w, has_b) in enumerate(((dy1, w1, ctx.has_b[0]), (dy2, w2, ctx.has_b[1]))):
-            N = w.shape[0]
+        for i, (dy, w) in enumerate(((dy1, w1), (dy2, w2))):
             dw = _pass.grad(ctx.keys[2 * i], w.shape, w.device)
-            db = _pass.grad(ctx.keys[2 * i + 1], (N,), w.device) if has_b else None
-            nbytes = lib().cswin_linear_bwd_weight_workspace(M, N, K)
-            ws = _ws(nbytes, w.device)
-            keep.append(ws)
-            _fill_wgrad(wg[i], dy, x, None, dw, db, ws.data_ptr(), nbytes, 1, M, N, K)
+            db = _pass.grad(ctx.keys[2 * i + 1], w.shape[:1], w.device)
+            nbytes = lib().cswin_linear_bwd_weight_workspace(M, w.shape[0], K)
+            keep.append(_ws(nbytes, w.device))
+            _fill_wgrad(wg[i], dy, x, None, dw, db, ptr(keep[-1]), nbytes)
             grads += [dw, db]
-        call("cswin_linear_bwd_weight_batch", ctypes.cast(wg, ctypes.c_void_p), 2, _job_ptr(jobs), None, 0, st)
+        _linear_bwd_weight_batch(wg, jobs)
         _pass.reduce(jobs, keep)
         return (dx,) + tuple(grads)
 
@@ -325,80 +367,6 @@ class _LinearPair(Function):
 def linear_pair(x, w1, b1, w2, b2):
     """(x @ w1^T + b1, x @ w2^T + b2) with one fused input gradient."""
     return _LinearPair.apply(x, w1, b1, w2, b2)
-
-
-class _Mlp(Function):
-    """fc1 -> GELU(erf) -> drop -> fc2 -> drop (cswin_unet.py:22-28) with the optional residual/DropPath epilogue of :179.
-    drop_p = 0 (every reference config): two GEMMs with fused epilogues.  drop_p > 0: the two nn.Dropouts are separate
-    launches of cswin_dropout (masks regenerated from their seeds in backward; they commute with the GELU' factor)."""
-
-    @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, residual, row_scale, drop_p, seeds):
-        x, w1, b1, w2, b2 = (dev_f32(t) for t in (x, w1, b1, w2, b2))
-        residual, row_scale = dev_f32(residual), dev_f32(row_scale)
-        K = x.shape[-1]
-        Hd, N = w1.shape[0], w2.shape[0]
-        M = x.numel() // K
-        pre = torch.empty(x.shape[:-1] + (Hd,), dtype=torch.float32, device=x.device)
-        act = torch.empty_like(pre)
-        (p1, f1), (p2, f2) = _wsrc(w1), _wsrc(w2)
-        call("cswin_linear_fwd", ptr(x), None, 0, p1, ptr(b1), ptr(pre), ptr(act), None, None, 1, M, Hd, K, precision(), f1, stream())
-        y = torch.empty(x.shape[:-1] + (N,), dtype=torch.float32, device=x.device)
-        rps = _rows_per_sample(x) if row_scale is not None else 1
-        if drop_p > 0:
-            call("cswin_dropout", ptr(act), None, None, ptr(act), act.numel(), act.numel() // act.shape[0], drop_p, seeds[0], ptr(dropout_epoch(act.device)), stream())
-            call("cswin_linear_fwd", ptr(act), None, 0, p2, ptr(b2), ptr(y), None, None, None, 1, M, N, Hd, precision(), f2, stream())
-            call("cswin_dropout", ptr(y), ptr(residual), ptr(row_scale), ptr(y), y.numel(), y.numel() // y.shape[0], drop_p, seeds[1], ptr(dropout_epoch(y.device)), stream())
-        else:
-            call("cswin_linear_fwd", ptr(act), None, 0, p2, ptr(b2), ptr(y), None, ptr(residual), ptr(row_scale), rps,
-                 M, N, Hd, precision(), f2, stream())
-        ctx.save_for_backward(x, w1, w2, pre, act, row_scale)
-        ctx.has_res, ctx.rps, ctx.has_b1, ctx.has_b2 = residual is not None, rps, b1 is not None, b2 is not None
-        ctx.keys = _param_keys(w1, b1, w2, b2)
-        ctx.drop = (float(drop_p), seeds)
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dy):
-        x, w1, w2, pre, act, row_scale = ctx.saved_tensors
-        dy = dev_f32(dy)
-        K = x.shape[-1]
-        Hd, N = w1.shape[0], w2.shape[0]
-        M = x.numel() // K
-        dev = x.device
-        st = stream()
-        drop_p, seeds = ctx.drop
-        dyl, rs_gemm = dy, row_scale                 # gradient of fc2's output, and the row factor still to be applied by the GEMMs
-        if drop_p > 0:
-            dyl = torch.empty_like(dy)
-            call("cswin_dropout", ptr(dy), None, ptr(row_scale), ptr(dyl), dy.numel(), dy.numel() // dy.shape[0], drop_p, seeds[1], ptr(dropout_epoch(dy.device)), st)
-            rs_gemm = None
-        # d pre = (row_scale * dy @ w2) * gelu'(pre)   (GELU backward fused into the data-gradient epilogue)
-        dpre = torch.empty_like(pre)
-        call("cswin_linear_bwd_data", ptr(dyl), ptr(w2), ptr(dpre), None, 0, ptr(pre), ptr(rs_gemm), ctx.rps, None, M, N,
-             Hd, precision(), 0, st)
-        if drop_p > 0:
-            call("cswin_dropout", ptr(dpre), None, None, ptr(dpre), dpre.numel(), dpre.numel() // dpre.shape[0], drop_p, seeds[0], ptr(dropout_epoch(dpre.device)), st)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x)
-            call("cswin_linear_bwd_data", ptr(dpre), ptr(w1), ptr(dx), None, 0, None, None, 1, None, M, Hd, K, precision(), 0, st)
-        # both weight gradients
-        k1, kb1, k2, kb2 = ctx.keys
-        dw2 = _pass.grad(k2, w2.shape, dev)
-        db2 = _pass.grad(kb2, (N,), dev) if ctx.has_b2 else None
-        nbytes = max(lib().cswin_linear_bwd_weight_workspace(M, N, Hd), lib().cswin_linear_bwd_weight_workspace(M, Hd, K))
-        ws, ws1 = _ws(nbytes, dev), _ws(nbytes, dev)
-        jobs = (ReduceJob * 2)()
-        call("cswin_linear_bwd_weight", ptr(dyl), ptr(act), None, 0, ptr(rs_gemm), ctx.rps, ptr(dw2), ptr(db2), ptr(ws),
-             nbytes, M, N, Hd, _job_ptr(jobs, 0), precision(), stream())
-        dw1 = _pass.grad(k1, w1.shape, dev)
-        db1 = _pass.grad(kb1, (Hd,), dev) if ctx.has_b1 else None
-        call("cswin_linear_bwd_weight", ptr(dpre), ptr(x), None, 0, None, 1, ptr(dw1), ptr(db1), ptr(ws1), nbytes, M, Hd, K,
-             _job_ptr(jobs, 1), precision(), stream())
-        _pass.reduce(jobs, (ws, ws1))
-        return dx, dw1, db1, dw2, db2, (dy if ctx.has_res else None), None, None, None
 
 
 # Device-resident dropout epoch: every dropout launch adds its value to the seed it was given.  The seed itself comes from the host
@@ -423,6 +391,71 @@ def _draw_seeds(n):
     return tuple(int(v) for v in torch.randint(0, 2 ** 62, (n,)).tolist())      # host RNG: torch.manual_seed controls it
 
 
+def _dropout(x, y, p, seed, *, residual=None, row_scale=None):
+    """y (may be x) = residual + row_scale[sample] * dropout_p(x), mask of (seed + epoch); the backward: the same on dy."""
+    call("cswin_dropout", ptr(x), ptr(residual), ptr(row_scale), ptr(y), x.numel(), x.numel() // x.shape[0], float(p), int(seed),
+         ptr(dropout_epoch(x.device)), stream())
+
+
+class _Mlp(Function):
+    """fc1 -> GELU(erf) -> drop -> fc2 -> drop (cswin_unet.py:22-28) with the optional residual/DropPath epilogue of :179.
+    drop_p = 0 (every reference config): two GEMMs with fused epilogues.  drop_p > 0: the two nn.Dropouts are separate
+    launches of cswin_dropout (masks regenerated from their seeds in backward; they commute with the GELU' factor)."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, residual, row_scale, drop_p, seeds):
+        x, w1, b1, w2, b2 = (dev_f32(t) for t in (x, w1, b1, w2, b2))
+        residual, row_scale = dev_f32(residual), dev_f32(row_scale)
+        s1, s2 = _wsrc(w1), _wsrc(w2)
+        pre, act = _linear_fwd(x, s1, b1, w1.shape[0], gelu=True)
+        if drop_p > 0:
+            _dropout(act, act, drop_p, seeds[0])
+            y = _linear_fwd(act, s2, b2, w2.shape[0])
+            _dropout(y, y, drop_p, seeds[1], residual=residual, row_scale=row_scale)
+        else:
+            y = _linear_fwd(act, s2, b2, w2.shape[0], residual=residual, row_scale=row_scale)
+        ctx.save_for_backward(x, w1, w2, pre, act, row_scale)
+        ctx.has_res, ctx.keys = residual is not None, _param_keys(w1, b1, w2, b2)
+        ctx.drop = (float(drop_p), seeds)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, w1, w2, pre, act, row_scale = ctx.saved_tensors
+        dy = dev_f32(dy)
+        K = x.shape[-1]
+        Hd, N = w1.shape[0], w2.shape[0]
+        M = x.numel() // K
+        dev = x.device
+        drop_p, seeds = ctx.drop
+        dyl, rs_gemm = dy, row_scale                 # gradient of fc2's output, and the row factor still to be applied by the GEMMs
+        if drop_p > 0:
+            dyl = torch.empty_like(dy)
+            _dropout(dy, dyl, drop_p, seeds[1], row_scale=row_scale)
+            rs_gemm = None
+        # d pre = (row_scale * dy @ w2) * gelu'(pre)   (GELU backward fused into the data-gradient epilogue)
+        dpre = torch.empty_like(pre)
+        _linear_bwd_data(dyl, w2, dpre, gelu_pre=pre, row_scale=rs_gemm)
+        if drop_p > 0:
+            _dropout(dpre, dpre, drop_p, seeds[0])
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            _linear_bwd_data(dpre, w1, dx)
+        # both weight gradients
+        k1, kb1, k2, kb2 = ctx.keys
+        dw2, db2 = _pass.grad(k2, w2.shape, dev), _pass.grad(kb2, (N,), dev)
+        nbytes = max(lib().cswin_linear_bwd_weight_workspace(M, N, Hd), lib().cswin_linear_bwd_weight_workspace(M, Hd, K))
+        ws, ws1 = _ws(nbytes, dev), _ws(nbytes, dev)
+        jobs = (ReduceJob * 2)()
+        _linear_bwd_weight(dyl, act, dw2, db2, (ptr(ws), nbytes, _job_ptr(jobs, 0)), row_scale=rs_gemm)
+        dw1, db1 = _pass.grad(k1, w1.shape, dev), _pass.grad(kb1, (Hd,), dev)
+        _linear_bwd_weight(dpre, x, dw1, db1, (ptr(ws1), nbytes, _job_ptr(jobs, 1)))
+        _pass.reduce(jobs, (ws, ws1))
+        return dx, dw1, db1, dw2, db2, (dy if ctx.has_res else None), None, None, None
+
+
 def mlp(x, w1, b1, w2, b2, residual=None, row_scale=None, drop_p=0.0):
     return _Mlp.apply(x, w1, b1, w2, b2, residual, row_scale, float(drop_p), _draw_seeds(2) if drop_p > 0 else (0, 0))
 
@@ -433,10 +466,8 @@ class _MatmulNN(Function):
     @staticmethod
     def forward(ctx, a, b):
         a, b = dev_f32(a), dev_f32(b)
-        M, N = a.shape
-        K = b.shape[1]
-        c = torch.empty(M, K, dtype=torch.float32, device=a.device)
-        call("cswin_linear_bwd_data", ptr(a), ptr(b), ptr(c), None, 0, None, None, 1, None, M, N, K, precision(), 0, stream())
+        c = torch.empty(a.shape[0], b.shape[1], dtype=torch.float32, device=a.device)
+        _linear_bwd_data(a, b, c)
         ctx.save_for_backward(a, b)
         return c
 
@@ -445,17 +476,9 @@ class _MatmulNN(Function):
     def backward(ctx, dc):
         a, b = ctx.saved_tensors
         dc = dev_f32(dc)
-        M, N = a.shape
-        K = b.shape[1]
-        da = torch.empty_like(a)        # da = dc @ b^T
-        call("cswin_linear_fwd", ptr(dc), None, 0, ptr(b), None, ptr(da), None, None, None, 1, M, N, K, precision(), 0, stream())
-        db = torch.empty_like(b)        # db (N, K) = a^T @ dc
-        nbytes = lib().cswin_linear_bwd_weight_workspace(M, N, K)
-        ws = _ws(nbytes, a.device)
-        job = (ReduceJob * 1)()
-        call("cswin_linear_bwd_weight", ptr(a), ptr(dc), None, 0, None, 1, ptr(db), None, ptr(ws), nbytes, M, N, K,
-             _job_ptr(job), precision(), stream())
-        _pass.reduce(job, (ws,))
+        da = _linear_fwd(dc, b, None, a.shape[1])       # da = dc @ b^T
+        db = torch.empty_like(b)                        # db (N, K) = a^T @ dc
+        _linear_bwd_weight(a, dc, db, None)
         return da, db
 
 
@@ -466,6 +489,39 @@ def matmul_nn(a, b):
 # ------------------------------------------------------------------------------------------------
 # fused stripe attention
 # ------------------------------------------------------------------------------------------------
+# `mode` of the attention helpers (qkv_bf16 of include/cswin_hip.h).  The first three say what is STORED as bf16 and follow from
+# the tensors' dtypes; the last also selects bf16 matrix instructions, which no dtype tells: so the caller names the mode.
+#   ATTN_FP32: every tensor fp32;  ATTN_QKV16: qkv and dqkv stored as bf16;  ATTN_IO16: and the forward outputs y, y0 (arithmetic
+#   still fp32);  ATTN_MFMA16: storage of ATTN_IO16, operands rounded to bf16 on their way into bf16 matrix instructions
+ATTN_FP32, ATTN_QKV16, ATTN_IO16, ATTN_MFMA16 = 0, 1, 3, 7
+
+
+def _attn_drop_args(drop, device):
+    """(p, seed, epoch pointer) tail of the attention entry points for one _attn_drop() draw."""
+    return drop[0], drop[1], ptr(dropout_epoch(device)) if drop[0] > 0 else None
+
+
+def _attn_fwd(qkv, lw, lb, y, y0, lse, reso, split, idx, heads, scale, drop, mode):
+    """y = both branches' softmax(scale q k^T) v + LePE(v);  y0 (or None): the same without LePE, lse: row log-sum-exp."""
+    B, _, C3 = qkv.shape
+    call("cswin_attn_fwd", ptr(qkv), _ptr_array(lw), _ptr_array(lb), ptr(y), ptr(y0), ptr(lse), B, reso, C3 // 3, len(idx),
+         _int_array(heads), _int_array(idx), split, float(scale or 0.0), *_attn_drop_args(drop, qkv.device), mode, stream())
+
+
+def _attn_bwd(qkv, lw, lb, lse, y0, dy, dqkv, dlw, dlb, reso, split, idx, heads, scale, drop, mode, slab=None):
+    """Backward of _attn_fwd.  slab as for _layernorm_bwd (one job per branch)."""
+    B, _, C3 = qkv.shape
+    ha, ia = _int_array(heads), _int_array(idx)
+    if slab is None:
+        nbytes = lib().cswin_attn_bwd_workspace(B, reso, C3 // 3, len(idx), ha, ia, split)
+        again = lambda *s: _attn_bwd(qkv, lw, lb, lse, y0, dy, dqkv, dlw, dlb, reso, split, idx, heads, scale, drop, mode, s)
+        return _reduced(nbytes, qkv.device, again, njobs=2)
+    ws, nbytes, jobs = slab
+    call("cswin_attn_bwd", ptr(qkv), _ptr_array(lw), _ptr_array(lb), ptr(lse), ptr(y0), ptr(dy), ptr(dqkv), _ptr_array(dlw),
+         _ptr_array(dlb), ws, nbytes, B, reso, C3 // 3, len(idx), ha, ia, split, float(scale or 0.0), jobs,
+         *_attn_drop_args(drop, qkv.device), mode, stream())
+
+
 class _StripeAttention(Function):
     @staticmethod
     def forward(ctx, qkv, reso, split, idx, heads, scale, drop, *wb):
@@ -476,41 +532,27 @@ class _StripeAttention(Function):
         ws_ = [dev_f32(t).view(t.shape[0], 9) for t in wb[:nb]]
         bs_ = [dev_f32(t) for t in wb[nb:]]
         B, L, C3 = qkv.shape
-        C = C3 // 3
         if L != reso * reso:
             raise ValueError("flatten img_tokens has wrong size")
-        y = torch.empty(B, L, C, dtype=torch.float32, device=qkv.device)
+        y = torch.empty(B, L, C3 // 3, dtype=torch.float32, device=qkv.device)
         y0 = torch.empty_like(y) if any(ctx.needs_input_grad) else None          # P V without LePE: the backward's delta term
         lse = torch.empty(B, sum(heads), L, dtype=torch.float32, device=qkv.device)
-        call("cswin_attn_fwd", ptr(qkv), _ptr_array(ws_), _ptr_array(bs_), ptr(y), ptr(y0), ptr(lse), B, reso, C, nb,
-             _int_array(heads), _int_array(idx), split, float(scale or 0.0), drop[0], drop[1], ptr(dropout_epoch(qkv.device)) if drop[0] > 0 else None,
-             int(q16), stream())
+        ctx.meta = (reso, split, tuple(idx), tuple(heads), scale, drop, ATTN_QKV16 if q16 else ATTN_FP32)
+        _attn_fwd(qkv, ws_, bs_, y, y0, lse, *ctx.meta)
         ctx.save_for_backward(qkv, lse, y0, *ws_, *bs_)
         ctx.keys = _param_keys(*wb)
-        ctx.meta = (reso, split, tuple(idx), tuple(heads), float(scale or 0.0), drop)
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
         qkv, lse, y0, *wb_ = ctx.saved_tensors
-        reso, split, idx, heads, scale, drop = ctx.meta
-        dy = dev_f32(dy)
-        nb = len(idx)
+        nb = len(wb_) // 2
         ws_, bs_ = wb_[:nb], wb_[nb:]
-        B, L, C3 = qkv.shape
-        C = C3 // 3
         dqkv = torch.empty_like(qkv)
         dws = [_pass.grad(k, t.shape, t.device) for k, t in zip(ctx.keys[:nb], ws_)]
         dbs = [_pass.grad(k, t.shape, t.device) for k, t in zip(ctx.keys[nb:], bs_)]
-        ha, ia = _int_array(heads), _int_array(idx)
-        nbytes = lib().cswin_attn_bwd_workspace(B, reso, C, nb, ha, ia, split)
-        ws = _ws(nbytes, qkv.device)
-        jobs = (ReduceJob * 2)()
-        call("cswin_attn_bwd", ptr(qkv), _ptr_array(ws_), _ptr_array(bs_), ptr(lse), ptr(y0), ptr(dy), ptr(dqkv), _ptr_array(dws),
-             _ptr_array(dbs), ptr(ws), nbytes, B, reso, C, nb, ha, ia, split, scale, _job_ptr(jobs), drop[0], drop[1],
-             ptr(dropout_epoch(qkv.device)) if drop[0] > 0 else None, int(qkv.dtype == torch.bfloat16), stream())
-        _pass.reduce(jobs, (ws,))
+        _attn_bwd(qkv, ws_, bs_, lse, y0, dev_f32(dy), dqkv, dws, dbs, *ctx.meta)
         return (dqkv, None, None, None, None, None, None) + tuple(d.view(d.shape[0], 1, 3, 3) for d in dws) + tuple(dbs)
 
 
@@ -533,7 +575,7 @@ def stripe_attention(qkv, reso, split, idx, heads, lepe_w, lepe_b, scale=None, a
 class _CSWinBlock(Function):
     """x -> x + dp1(proj(attn(qkv(LN1 x)))) -> ... + dp2(fc2(gelu(fc1(LN2 .))))  (cswin_unet.py:160-181).
 
-    Same kernels as the fine-grained ops; as one node the backward chains them by hand, so the two residual-fork
+    Same launch helpers as the fine-grained ops; as one node the backward chains them by hand, so the two residual-fork
     gradient sums are the `dres` input of the LayerNorm backward kernel (no aten::add), and 14 autograd nodes per
     block become one."""
 
@@ -544,41 +586,31 @@ class _CSWinBlock(Function):
         B, L, C = x.shape
         if L != reso * reso:
             raise ValueError("flatten img_tokens has wrong size")
-        M = B * L
-        dev, st = x.device, stream()
+        dev = x.device
         nb = len(idx)
         lw = [dev_f32(t).view(t.shape[0], 9) for t in lepe[:nb]]
         lb = [dev_f32(t) for t in lepe[nb:]]
         rs1, rs2 = dev_f32(rs1), dev_f32(rs2)
-        E = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
         # bf16 mode: every tensor of the block that only GEMMs and the attention kernel read -- both LayerNorm outputs, qkv, the
         # attention output, the MLP hidden pair and (backward) the gradients of qkv and the hidden layer -- is STORED as bf16, and
         # the GEMMs read the weights' bf16 shadow (_wsrc).  The residual stream (x, x1, y), its gradients, the LayerNorm / softmax
         # statistics, master weights and every accumulation stay fp32.
         s16 = act_bf16() and C % 4 == 0
-        E16 = (lambda *shape: torch.empty(*shape, dtype=torch.bfloat16, device=dev)) if s16 else E
-        (pq, fq), (pp, fp), (p1, f1), (p2, f2) = [_wsrc(w) if s16 else (ptr(w), 0) for w in (wqkv, wp, w1, w2)]
-        io_x, io_xy = (1, 3) if s16 else (0, 0)                       # input / input and output stored as bf16
-        h1, m1, r1 = E16(B, L, C), E(M), E(M)
-        call("cswin_layernorm_fwd", ptr(x), ptr(g1), ptr(b1), ptr(h1), ptr(m1), ptr(r1), M, C, eps1, int(s16), st)
-        qkv = E16(B, L, 3 * C)
-        call("cswin_linear_fwd", ptr(h1), None, 0, pq, ptr(bqkv), ptr(qkv), None, None, None, 1, M, 3 * C, C, precision(), io_xy | fq, st)
-        att, lse = E16(B, L, C), E(B, sum(heads), L)
+        t16 = torch.bfloat16 if s16 else torch.float32
+        E16 = lambda *shape: torch.empty(*shape, dtype=t16, device=dev)
+        sq, sp, s1, s2 = (_wsrc(w) if s16 else w for w in (wqkv, wp, w1, w2))
+        attn = (reso, split, tuple(idx), tuple(heads), scale, drop, ATTN_MFMA16 if s16 else ATTN_FP32)
+        h1, m1, r1 = _layernorm_fwd(x, g1, b1, eps1, t16)
+        qkv = _linear_fwd(h1, sq, bqkv, 3 * C, dtype=t16)
+        att, lse = E16(B, L, C), torch.empty(B, sum(heads), L, dtype=torch.float32, device=dev)
         att0 = E16(B, L, C) if any(ctx.needs_input_grad) else None       # P V without LePE: the attention backward's delta term
-        ha, ia = _int_array(heads), _int_array(idx)
-        call("cswin_attn_fwd", ptr(qkv), _ptr_array(lw), _ptr_array(lb), ptr(att), ptr(att0), ptr(lse), B, reso, C, nb, ha, ia, split,
-             float(scale or 0.0), drop[0], drop[1], ptr(dropout_epoch(dev)) if drop[0] > 0 else None, 7 if s16 else 0, st)
-        x1 = torch.empty_like(x)
-        call("cswin_linear_fwd", ptr(att), None, 0, pp, ptr(bp), ptr(x1), None, ptr(x), ptr(rs1), L, M, C, C, precision(), io_x | fp, st)
-        h2, m2, r2 = E16(B, L, C), E(M), E(M)
-        call("cswin_layernorm_fwd", ptr(x1), ptr(g2), ptr(b2), ptr(h2), ptr(m2), ptr(r2), M, C, eps2, int(s16), st)
-        Hd = w1.shape[0]
-        pre, act = E16(B, L, Hd), E16(B, L, Hd)
-        call("cswin_linear_fwd", ptr(h2), None, 0, p1, ptr(bb1), ptr(pre), ptr(act), None, None, 1, M, Hd, C, precision(), io_xy | f1, st)
-        y = torch.empty_like(x)
-        call("cswin_linear_fwd", ptr(act), None, 0, p2, ptr(bb2), ptr(y), None, ptr(x1), ptr(rs2), L, M, C, Hd, precision(), io_x | f2, st)
+        _attn_fwd(qkv, lw, lb, att, att0, lse, *attn)
+        x1 = _linear_fwd(att, sp, bp, C, residual=x, row_scale=rs1)
+        h2, m2, r2 = _layernorm_fwd(x1, g2, b2, eps2, t16)
+        pre, act = _linear_fwd(h2, s1, bb1, w1.shape[0], dtype=t16, gelu=True)
+        y = _linear_fwd(act, s2, bb2, C, residual=x1, row_scale=rs2)
         ctx.save_for_backward(x, m1, r1, h1, qkv, lse, att, att0, x1, m2, r2, h2, pre, act, rs1, rs2, g1, wqkv, wp, g2, w1, w2, *lw, *lb)
-        ctx.meta = (reso, split, tuple(idx), tuple(heads), float(scale or 0.0), bqkv is not None, s16, drop)
+        ctx.attn = attn
         ctx.keys = _param_keys(g1, b1, wqkv, bqkv, wp, bp, g2, b2, w1, bb1, w2, bb2, *lepe)
         return y
 
@@ -586,68 +618,55 @@ class _CSWinBlock(Function):
     @once_differentiable
     def backward(ctx, dy):
         (x, m1, r1, h1, qkv, lse, att, att0, x1, m2, r2, h2, pre, act, rs1, rs2, g1, wqkv, wp, g2, w1, w2, *lwb) = ctx.saved_tensors
-        reso, split, idx, heads, scale, has_qkv_bias, s16, drop = ctx.meta
-        lw, lb = lwb[:len(idx)], lwb[len(idx):]
+        nb = len(lwb) // 2
+        lw, lb = lwb[:nb], lwb[nb:]
         dy = dev_f32(dy)
         B, L, C = x.shape
-        M, Hd, nb = B * L, w1.shape[0], len(idx)
-        dev, st, h = x.device, stream(), lib()
-        E = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        M, Hd = B * L, w1.shape[0]
+        dev, h = x.device, lib()
+        s16 = h1.dtype == torch.bfloat16                  # the storage the forward chose
         # the slab reductions (4 split-K weight gradients, 2 LayerNorm dgamma/dbeta, 1-2 LePE conv gradients) are deferred
         # and run as ONE launch
-        sizes = [h.cswin_linear_bwd_weight_workspace(M, C, Hd), h.cswin_linear_bwd_weight_workspace(M, Hd, C),
-                 h.cswin_layernorm_bwd_workspace(M, C), h.cswin_linear_bwd_weight_workspace(M, C, C),
-                 h.cswin_linear_bwd_weight_workspace(M, 3 * C, C), h.cswin_layernorm_bwd_workspace(M, C)]
+        wq, lq = h.cswin_linear_bwd_weight_workspace, h.cswin_layernorm_bwd_workspace
+        sizes = [wq(M, C, Hd), wq(M, Hd, C), lq(M, C), wq(M, C, C), wq(M, 3 * C, C), lq(M, C)]
         sizes = [(n + 255) // 256 * 256 for n in sizes]
         ws = _ws(sum(sizes), dev)
         wsp = [ctypes.c_void_p(ws.data_ptr() + sum(sizes[:i])) for i in range(6)]
         jobs = (ReduceJob * 8)()
-        (pq, fq), (pp, fp), (p1, f1), (p2, f2) = [_wsrc(w) if s16 else (ptr(w), 0) for w in (wqkv, wp, w1, w2)]
-        E16 = lambda *shape: torch.empty(*shape, dtype=torch.bfloat16, device=dev)
+        sq, sp, s1, s2 = (_wsrc(w) if s16 else w for w in (wqkv, wp, w1, w2))
         dy16 = _twin_take(dy) if s16 else None          # rounded copy of dy left by the backward that produced it (see _twins)
+        dyg = dy16 if dy16 is not None else dy          # what the GEMMs read
         # ---- MLP branch ----
         dpre = torch.empty_like(pre)
-        call("cswin_linear_bwd_data", ptr(dy16 if dy16 is not None else dy), p2, ptr(dpre), None, 0, ptr(pre), ptr(rs2), L, None, M, C, Hd,
-             precision(), ((10 if s16 else 0) | f2) | (1 if dy16 is not None else 0), st)
+        _linear_bwd_data(dyg, s2, dpre, gelu_pre=pre, row_scale=rs2)
         # the four weight gradients are off the critical path: they run as ONE batched launch once all operands exist
         wg = (WgradDesc * 4)()
-
-        def defer_wgrad(slot, dy_, x_, rs_, dw_, db_, wsi, N_, K_, io=0):
-            _fill_wgrad(wg[slot], dy_, x_, rs_, dw_, db_, wsp[wsi].value, sizes[wsi], L, M, N_, K_, io if s16 else 0)
-
         kg1, kb1, kwqkv, kbqkv, kwp, kbp, kg2, kb2, kw1, kbb1, kw2, kbb2, *klepe = ctx.keys
         G = lambda key, *shape: _pass.grad(key, shape, dev)
         dw2, db2 = G(kw2, *w2.shape), G(kbb2, C)
-        if dy16 is not None:
-            defer_wgrad(0, dy16, act, rs2, dw2, db2, 0, C, Hd, io=3)   # dy's twin and x = act are stored as bf16
-        else:
-            defer_wgrad(0, dy, act, rs2, dw2, db2, 0, C, Hd, io=2)     # x = act is stored as bf16
+        _fill_wgrad(wg[0], dyg, act, rs2, dw2, db2, wsp[0], sizes[0])
         dw1, db1 = G(kw1, *w1.shape), G(kbb1, Hd)
-        defer_wgrad(1, dpre, h2, None, dw1, db1, 1, Hd, C, io=3)        # dy = dpre and x = h2 are stored as bf16
+        _fill_wgrad(wg[1], dpre, h2, None, dw1, db1, wsp[1], sizes[1])
         dh2 = torch.empty_like(x)                                      # fp32 (x is)
-        call("cswin_linear_bwd_data", ptr(dpre), p1, ptr(dh2), None, 0, None, None, 1, None, M, Hd, C, precision(), (1 if s16 else 0) | f1, st)
+        _linear_bwd_data(dpre, s1, dh2)
         dx1, dg2, dbt2 = torch.empty_like(x), G(kg2, C), G(kb2, C)
-        dx1_16 = E16(B, L, C) if s16 else None                         # the GEMMs below read the twin, the residual path dx1
-        call("cswin_layernorm_bwd", ptr(dh2), ptr(x1), ptr(m2), ptr(r2), ptr(g2), ptr(dy), ptr(dx1), ptr(dg2), ptr(dbt2), wsp[2],
-             sizes[2], M, C, _job_ptr(jobs, 2), ptr(dx1_16), st)
+        dx1_16 = torch.empty_like(x, dtype=torch.bfloat16) if s16 else None      # the GEMMs below read the twin, the residual path dx1
+        _layernorm_bwd(dh2, x1, m2, r2, g2, dx1, dg2, dbt2, (wsp[2], sizes[2], _job_ptr(jobs, 2)), dres=dy, dx16=dx1_16)
+        dx1g = dx1_16 if s16 else dx1
         # ---- attention branch ----
         datt = dh2                                                     # reuse
-        call("cswin_linear_bwd_data", ptr(dx1_16 if s16 else dx1), pp, ptr(datt), None, 0, None, ptr(rs1), L, None, M, C, C, precision(),
-             fp | (1 if s16 else 0), st)
+        _linear_bwd_data(dx1g, sp, datt, row_scale=rs1)
         dwp, dbp = G(kwp, *wp.shape), G(kbp, C)
-        defer_wgrad(2, dx1_16 if s16 else dx1, att, rs1, dwp, dbp, 3, C, C, io=3)      # dx1's twin and x = att are stored as bf16
+        _fill_wgrad(wg[2], dx1g, att, rs1, dwp, dbp, wsp[3], sizes[3])
         dqkv = torch.empty_like(qkv)
         dlw = [G(k, *t.shape) for k, t in zip(klepe[:nb], lw)]
         dlb = [G(k, *t.shape) for k, t in zip(klepe[nb:], lb)]
-        ha, ia = _int_array(heads), _int_array(idx)
-        naw = h.cswin_attn_bwd_workspace(B, reso, C, nb, ha, ia, split)
+        reso, split, idx, heads = ctx.attn[:4]
+        naw = h.cswin_attn_bwd_workspace(B, reso, C, nb, _int_array(heads), _int_array(idx), split)
         aws = _ws(naw, dev)
-        call("cswin_attn_bwd", ptr(qkv), _ptr_array(lw), _ptr_array(lb), ptr(lse), ptr(att0), ptr(datt), ptr(dqkv),
-             _ptr_array(dlw), _ptr_array(dlb), ptr(aws), naw, B, reso, C, nb, ha, ia, split, scale, _job_ptr(jobs, 6), drop[0], drop[1],
-             ptr(dropout_epoch(dev)) if drop[0] > 0 else None, 7 if s16 else 0, st)
-        dwqkv = G(kwqkv, *wqkv.shape)
-        dbqkv = G(kbqkv, 3 * C) if has_qkv_bias else None
-        defer_wgrad(3, dqkv, h1, None, dwqkv, dbqkv, 4, 3 * C, C, io=3)  # dy = dqkv and x = h1 are stored as bf16
+        _attn_bwd(qkv, lw, lb, lse, att0, datt, dqkv, dlw, dlb, *ctx.attn, (ptr(aws), naw, _job_ptr(jobs, 6)))
+        dwqkv, dbqkv = G(kwqkv, *wqkv.shape), G(kbqkv, 3 * C)
+        _fill_wgrad(wg[3], dqkv, h1, None, dwqkv, dbqkv, wsp[4], sizes[4])
         wjobs = (ReduceJob * 4)()
         dh1 = datt                                                     # reuse again
         # the previous blocks' slab reductions ride at the end of this grid; `riders` owns them and what they read until the
@@ -655,17 +674,16 @@ class _CSWinBlock(Function):
         pend, npend, riders = _pass.take_pending()
         if precision() == 0:
             # fp32: the qkv data gradient rides in the weight-gradient batch's launch as well (both only wait for dqkv)
-            call("cswin_linear_bwd_tail", ptr(dqkv), pq, ptr(dh1), M, 3 * C, C, ctypes.cast(wg, ctypes.c_void_p), 4,
-                 _job_ptr(wjobs), pend, npend, st)
+            call("cswin_linear_bwd_tail", ptr(dqkv), ptr(wqkv), ptr(dh1), M, 3 * C, C, ctypes.cast(wg, ctypes.c_void_p), 4,
+                 _job_ptr(wjobs), pend, npend, stream())
         else:
-            call("cswin_linear_bwd_weight_batch", ctypes.cast(wg, ctypes.c_void_p), 4, _job_ptr(wjobs), pend, npend, st)
-            call("cswin_linear_bwd_data", ptr(dqkv), pq, ptr(dh1), None, 0, None, None, 1, None, M, 3 * C, C, precision(), (1 if s16 else 0) | fq, st)
+            _linear_bwd_weight_batch(wg, wjobs, (pend, npend))
+            _linear_bwd_data(dqkv, sq, dh1)
         for slot, ji in enumerate((0, 1, 3, 4)):
             jobs[ji] = wjobs[slot]
         dx, dg1, dbt1 = torch.empty_like(x), G(kg1, C), G(kb1, C)
-        dx16 = E16(B, L, C) if s16 else None
-        call("cswin_layernorm_bwd", ptr(dh1), ptr(x), ptr(m1), ptr(r1), ptr(g1), ptr(dx1), ptr(dx), ptr(dg1), ptr(dbt1), wsp[5],
-             sizes[5], M, C, _job_ptr(jobs, 5), ptr(dx16), st)
+        dx16 = torch.empty_like(x, dtype=torch.bfloat16) if s16 else None
+        _layernorm_bwd(dh1, x, m1, r1, g1, dx, dg1, dbt1, (wsp[5], sizes[5], _job_ptr(jobs, 5)), dres=dx1, dx16=dx16)
         if s16:
             _twin_put(dx, dx16)
         _pass.reduce(jobs, (ws, aws))
@@ -749,6 +767,12 @@ def _permute_w(w, cpad, want_t):
     return wp, wpt
 
 
+def _conv_tok_fwd(x, w_img, b, y, H, W, ks, stride, pad):
+    """y (B, OH*OW, Cout) = convolution of the tokens x (B, H*W, Cin) with the implicit-GEMM weight image w_img, + b."""
+    call("cswin_conv_tok_fwd", ptr(x), ptr(w_img), ptr(b), ptr(y), x.shape[0], H, W, x.shape[-1], y.shape[-1], ks, stride, pad,
+         precision(), stream())
+
+
 class _ConvTokens(Function):
     @staticmethod
     def forward(ctx, x, w, b, H, W, stride, pad):
@@ -767,9 +791,9 @@ class _ConvTokens(Function):
         else:
             wp, wpt = _permute_w(w, Cin, need_dx and not same)   # both weight images in one launch; the transposed one is kept
         y = torch.empty(B, OH * OW, Cout, dtype=torch.float32, device=x.device)
-        call("cswin_conv_tok_fwd", ptr(x), ptr(wp), ptr(b), ptr(y), B, H, W, Cin, Cout, ks, stride, pad, precision(), stream())
+        _conv_tok_fwd(x, wp, b, y, H, W, ks, stride, pad)
         ctx.save_for_backward(x, w, wpt, wf if need_dx else None)
-        ctx.meta = (H, W, stride, pad, b is not None)
+        ctx.meta = (H, W, stride, pad)
         ctx.keys = _param_keys(w, b)
         return y
 
@@ -777,11 +801,10 @@ class _ConvTokens(Function):
     @once_differentiable
     def backward(ctx, dy):
         x, w, wpt, wf = ctx.saved_tensors
-        H, W, stride, pad, has_b = ctx.meta
+        H, W, stride, pad = ctx.meta
         dy = dev_f32(dy)
         B, L, Cin = x.shape
         Cout, ks = w.shape[0], w.shape[2]
-        st = stream()
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
@@ -790,20 +813,17 @@ class _ConvTokens(Function):
                 # the generic transposed gather (CARAFE4 encoder, 16 -> 144 channels at 56 x 56: 13.41 -> 13.36 ms per step)
                 if wf is None:
                     wf = torch.empty(Cin, ks * ks, Cout, dtype=torch.float32, device=x.device)
-                    call("cswin_conv_weight_flipT", ptr(w), ptr(wf), Cout, Cin, ks, st)
-                call("cswin_conv_tok_fwd", ptr(dy), ptr(wf), None, ptr(dx), B, H, W, Cout, Cin, ks, 1, pad, precision(), st)
+                    call("cswin_conv_weight_flipT", ptr(w), ptr(wf), Cout, Cin, ks, stream())
+                _conv_tok_fwd(dy, wf, None, dx, H, W, ks, 1, pad)
             else:
                 if wpt is None:
                     _, wpt = _permute_w(w, Cin, True)
-                call("cswin_conv_tok_bwd_data", ptr(dy), ptr(wpt), ptr(dx), B, H, W, Cin, Cout, ks, stride, pad, precision(), st)
+                call("cswin_conv_tok_bwd_data", ptr(dy), ptr(wpt), ptr(dx), B, H, W, Cin, Cout, ks, stride, pad, precision(), stream())
         dw = _pass.grad(ctx.keys[0], w.shape, x.device)      # written in the parameter layout by the slab reduction itself
-        db = _pass.grad(ctx.keys[1], (Cout,), x.device) if has_b else None
-        nbytes = lib().cswin_conv_tok_bwd_weight_workspace(B, H, W, Cin, Cout, ks, stride, pad)
-        ws = _ws(nbytes, x.device)
-        job = (ReduceJob * 1)()
-        call("cswin_conv_tok_bwd_weight", ptr(dy), ptr(x), ptr(dw), ptr(db), ptr(ws), nbytes, B, H, W, Cin, Cout, ks,
-             stride, pad, 1, _job_ptr(job), precision(), stream())
-        _pass.reduce(job, (ws,))
+        db = _pass.grad(ctx.keys[1], (Cout,), x.device)
+        _reduced(lib().cswin_conv_tok_bwd_weight_workspace(B, H, W, Cin, Cout, ks, stride, pad), x.device,
+                 lambda ws, nbytes, job: call("cswin_conv_tok_bwd_weight", ptr(dy), ptr(x), ptr(dw), ptr(db), ws, nbytes, B, H, W, Cin,
+                                              Cout, ks, stride, pad, 1, job, precision(), stream()))
         return dx, dw, db, None, None, None, None
 
 
@@ -828,9 +848,9 @@ class _PatchEmbedConv(Function):
         wp = images[0] if images is not None else _permute_w(w, cpad, False)[0]
         OH, OW = (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
         y = torch.empty(B, OH * OW, Cout, dtype=torch.float32, device=img.device)
-        call("cswin_conv_tok_fwd", ptr(x), ptr(wp), ptr(b), ptr(y), B, H, W, cpad, Cout, ks, stride, pad, precision(), st)
+        _conv_tok_fwd(x, wp, b, y, H, W, ks, stride, pad)
         ctx.save_for_backward(x, w)
-        ctx.meta = (H, W, stride, pad, cpad, b is not None)
+        ctx.meta = (H, W, stride, pad)
         ctx.keys = _param_keys(w, b)
         return y
 
@@ -838,20 +858,16 @@ class _PatchEmbedConv(Function):
     @once_differentiable
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
-        H, W, stride, pad, cpad, has_b = ctx.meta
+        H, W, stride, pad = ctx.meta
         dy = dev_f32(dy)
-        B = x.shape[0]
+        B, cpad = x.shape[0], x.shape[-1]
         Cout, Cin, ks, _ = w.shape
-        st = stream()
         dw = _pass.grad(ctx.keys[0], w.shape, x.device)
-        db = _pass.grad(ctx.keys[1], (Cout,), x.device) if has_b else None
-        nbytes = lib().cswin_conv_tok_bwd_weight_workspace(B, H, W, cpad, Cout, ks, stride, pad)
-        ws = _ws(nbytes, x.device)
-        job = (ReduceJob * 1)()
+        db = _pass.grad(ctx.keys[1], (Cout,), x.device)
         # channel-padded input (3 -> 4): the slab reduction drops the padded columns as it writes the parameter layout
-        call("cswin_conv_tok_bwd_weight_cpad", ptr(dy), ptr(x), ptr(dw), ptr(db), ptr(ws), nbytes, B, H, W, cpad, Cin, Cout, ks,
-             stride, pad, _job_ptr(job), precision(), st)
-        _pass.reduce(job, (ws,))
+        _reduced(lib().cswin_conv_tok_bwd_weight_workspace(B, H, W, cpad, Cout, ks, stride, pad), x.device,
+                 lambda ws, nbytes, job: call("cswin_conv_tok_bwd_weight_cpad", ptr(dy), ptr(x), ptr(dw), ptr(db), ws, nbytes, B, H, W,
+                                              cpad, Cin, Cout, ks, stride, pad, job, precision(), stream()))
         return None, dw, db, None, None
 
 
@@ -863,56 +879,22 @@ def patch_embed_conv(img, w, b, stride=4, pad=2):
 # CARAFE reassembly, layout adapters
 # ------------------------------------------------------------------------------------------------
 class _CarafeReassemble(Function):
-    @staticmethod
-    def forward(ctx, e, z, bias, H, W, S):
-        e, z, bias = dev_f32(e, "carafe kernel logits"), dev_f32(z, "carafe features"), dev_f32(bias)
-        B, L, Cz = z.shape
-        assert L == H * W and e.shape == (B, L, 9 * S * S)
-        out = torch.empty(B, L * S * S, Cz, dtype=torch.float32, device=z.device)
-        wt = torch.empty_like(e)
-        call("cswin_carafe_fwd", ptr(e), ptr(z), ptr(bias), ptr(out), ptr(wt), B, H, W, Cz, S, stream())
-        ctx.save_for_backward(z, wt)
-        ctx.meta = (H, W, S, bias is not None)
-        ctx.keys = _param_keys(bias)
-        return out
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dout):
-        z, wt = ctx.saved_tensors
-        H, W, S, has_b = ctx.meta
-        dout = dev_f32(dout)
-        B, L, Cz = z.shape
-        de = torch.empty_like(wt)
-        dz = torch.empty_like(z)
-        db = _pass.grad(ctx.keys[0], (Cz,), z.device) if has_b else None
-        nbytes = lib().cswin_carafe_bwd_workspace(B, H, W, Cz, S)
-        ws = _ws(nbytes, z.device)
-        job = (ReduceJob * 1)()
-        call("cswin_carafe_bwd", ptr(dout), ptr(z), ptr(wt), ptr(de), ptr(dz), ptr(db), ptr(ws), nbytes, B, H, W, Cz, S,
-             _job_ptr(job), stream())
-        _pass.reduce(job, (ws,))                             # the bias gradient's partial sums
-        return de, dz, db, None, None, None
-
-
-def carafe_reassemble(e, z, bias, H, W, S):
-    return _CarafeReassemble.apply(e, z, bias, H, W, S)
-
-
-class _CarafeReassembleNchw(Function):
-    """carafe_reassemble whose output is (B, C, S*H, S*W): the first C channels as planes, written by the reassembly kernel and
-    read by its backward -- for the segmentation head, whose C class maps travel in Cz = 16 channel tokens."""
+    """C = None: out (B, S*S*L, Cz) tokens.  C: out (B, C, S*H, S*W), the first C channels as planes, written by the reassembly
+    kernel and read by its backward -- for the segmentation head, whose C class maps travel in Cz = 16 channel tokens."""
 
     @staticmethod
     def forward(ctx, e, z, bias, H, W, S, C):
         e, z, bias = dev_f32(e, "carafe kernel logits"), dev_f32(z, "carafe features"), dev_f32(bias)
         B, L, Cz = z.shape
-        assert L == H * W and e.shape == (B, L, 9 * S * S) and 0 < C <= Cz
-        out = torch.empty(B, C, S * H, S * W, dtype=torch.float32, device=z.device)
+        assert L == H * W and e.shape == (B, L, 9 * S * S) and (C is None or 0 < C <= Cz)
+        out = torch.empty((B, L * S * S, Cz) if C is None else (B, C, S * H, S * W), dtype=torch.float32, device=z.device)
         wt = torch.empty_like(e)
-        call("cswin_carafe_fwd_nchw", ptr(e), ptr(z), ptr(bias), ptr(out), ptr(wt), B, H, W, Cz, C, S, stream())
+        if C is None:
+            call("cswin_carafe_fwd", ptr(e), ptr(z), ptr(bias), ptr(out), ptr(wt), B, H, W, Cz, S, stream())
+        else:
+            call("cswin_carafe_fwd_nchw", ptr(e), ptr(z), ptr(bias), ptr(out), ptr(wt), B, H, W, Cz, C, S, stream())
         ctx.save_for_backward(z, wt)
-        ctx.meta = (H, W, S, C, bias is not None)
+        ctx.meta = (H, W, S, C)
         ctx.keys = _param_keys(bias)
         return out
 
@@ -920,26 +902,30 @@ class _CarafeReassembleNchw(Function):
     @once_differentiable
     def backward(ctx, dout):
         z, wt = ctx.saved_tensors
-        H, W, S, C, has_b = ctx.meta
+        H, W, S, C = ctx.meta
         dout = dev_f32(dout)
         B, L, Cz = z.shape
         de = torch.empty_like(wt)
         dz = torch.empty_like(z)
-        db = _pass.grad(ctx.keys[0], (Cz,), z.device) if has_b else None
-        nbytes = lib().cswin_carafe_bwd_workspace(B, H, W, Cz, S)
-        ws = _ws(nbytes, z.device)
-        job = (ReduceJob * 1)()
-        call("cswin_carafe_bwd_nchw", ptr(dout), ptr(z), ptr(wt), ptr(de), ptr(dz), ptr(db), ptr(ws), nbytes, B, H, W, Cz, C, S,
-             _job_ptr(job), stream())
-        _pass.reduce(job, (ws,))
+        db = _pass.grad(ctx.keys[0], (Cz,), z.device)
+        io = (ptr(dout), ptr(z), ptr(wt), ptr(de), ptr(dz), ptr(db))
+        if C is None:
+            launch = lambda ws, nbytes, job: call("cswin_carafe_bwd", *io, ws, nbytes, B, H, W, Cz, S, job, stream())
+        else:
+            launch = lambda ws, nbytes, job: call("cswin_carafe_bwd_nchw", *io, ws, nbytes, B, H, W, Cz, C, S, job, stream())
+        _reduced(lib().cswin_carafe_bwd_workspace(B, H, W, Cz, S), z.device, launch)       # the bias gradient's partial sums
         return de, dz, db, None, None, None, None
+
+
+def carafe_reassemble(e, z, bias, H, W, S):
+    return _CarafeReassemble.apply(e, z, bias, H, W, S, None)
 
 
 def carafe_reassemble_nchw(e, z, bias, H, W, S, C):
     """carafe_reassemble(e, z, bias, H, W, S)[..., :C] as (B, C, S*H, S*W).  Where the NCHW backward kernel does not exist (it
     is the fused S = 4, Cz = 16 one) the token form and the layout adapter run instead: same values either way."""
     if lib().cswin_carafe_bwd_nchw_ok(H, W, z.shape[-1], S):
-        return _CarafeReassembleNchw.apply(e, z, bias, H, W, S, C)
+        return _CarafeReassemble.apply(e, z, bias, H, W, S, C)
     return tokens_to_nchw(carafe_reassemble(e, z, bias, H, W, S), C, S * H, S * W)
 
 
@@ -971,7 +957,7 @@ class _HeadCompose(Function):
         dbf = dev_f32(dbf)
         dwh = _pass.grad(ctx.keys[0], w_head.shape, dev)
         dwo = _pass.grad(ctx.keys[1], w_out.shape, dev)
-        dbo = _pass.grad(ctx.keys[2], b_out.shape, dev) if b_out is not None else None
+        dbo = _pass.grad(ctx.keys[2], (E,), dev)
         call("cswin_head_compose_bwd", ptr(w_head), ptr(w_out), ptr(b_out), ptr(dwf), ptr(dbf), ptr(dwh), ptr(dwo), ptr(dbo),
              ncls, E, C, stream())
         return dwh, dwo, dbo, None
@@ -1031,6 +1017,29 @@ def windows2img(img_splits_hw, H_sp, W_sp, H, W):
 # ------------------------------------------------------------------------------------------------
 # loss
 # ------------------------------------------------------------------------------------------------
+def loss_sums(logits, labels, sums, probs=False):
+    """sums[1 + 3*ncls] = CE / Dice partial sums of logits (B, ncls, ...) or, with probs, probabilities against int64 labels."""
+    B, ncls = logits.shape[:2]
+    HW = logits.numel() // (B * ncls)
+    nbytes = lib().cswin_loss_workspace(B, ncls, HW)
+    ws = _ws(nbytes, logits.device)
+    call("cswin_loss_sums", ptr(logits), ptr(labels), ptr(sums), ptr(ws), nbytes, B, ncls, HW, int(probs), stream())
+
+
+def loss_finalize(sums, out, coef, n_pixels, w_ce, w_dice, class_weight=None):
+    """sums -> out = [loss, ce, dice] and coef[2*ncls], the Dice gradient coefficients loss_grad takes."""
+    call("cswin_loss_finalize", ptr(sums), ptr(out), ptr(coef), float(n_pixels), coef.numel() // 2, w_ce, w_dice, ptr(class_weight), stream())
+
+
+def loss_grad(logits, labels, coef, ce_scale, dice_scale, gloss=None, probs=False):
+    """d loss / d logits, times the device scalar gloss if given."""
+    B, ncls = logits.shape[:2]
+    dlogits = torch.empty_like(logits)
+    call("cswin_loss_bwd", ptr(logits), ptr(labels), ptr(coef), ptr(gloss), ptr(dlogits), ce_scale, dice_scale, B, ncls,
+         logits.numel() // (B * ncls), int(probs), stream())
+    return dlogits
+
+
 class _CeDiceLoss(Function):
     @staticmethod
     def forward(ctx, logits, labels, w_ce, w_dice, group, probs, class_weight):
@@ -1042,11 +1051,8 @@ class _CeDiceLoss(Function):
         B, ncls = logits.shape[:2]
         HW = logits.numel() // (B * ncls)
         dev = logits.device
-        st = stream()
-        nbytes = lib().cswin_loss_workspace(B, ncls, HW)
-        ws = _ws(nbytes, dev)
         sums = torch.empty(1 + 3 * ncls, dtype=torch.float32, device=dev)
-        call("cswin_loss_sums", ptr(logits), ptr(labels), ptr(sums), ptr(ws), nbytes, B, ncls, HW, int(probs), st)
+        loss_sums(logits, labels, sums, probs)
         world = 1
         if group is not None:
             import torch.distributed as dist
@@ -1055,11 +1061,10 @@ class _CeDiceLoss(Function):
                 dist.all_reduce(sums, group=group)      # 1 + 3*ncls floats: the reference's global-batch Dice
         out = torch.empty(3, dtype=torch.float32, device=dev)
         coef = torch.empty(2 * ncls, dtype=torch.float32, device=dev)
-        call("cswin_loss_finalize", ptr(sums), ptr(out), ptr(coef), float(B * HW * world), ncls, w_ce, w_dice, ptr(class_weight),
-             stream())
+        loss_finalize(sums, out, coef, B * HW * world, w_ce, w_dice, class_weight)
         ctx.save_for_backward(logits, labels, coef)
         # gradients are averaged over ranks afterwards: local CE mean -> ce/(B*HW); global Dice -> * world
-        ctx.meta = (w_ce / float(B * HW), w_dice / ncls * world, int(probs))
+        ctx.meta = (w_ce / float(B * HW), w_dice / ncls * world, probs)
         loss = out[0].clone()
         ctx.mark_non_differentiable(out)
         return loss, out
@@ -1069,12 +1074,7 @@ class _CeDiceLoss(Function):
     def backward(ctx, gloss, _gout):
         logits, labels, coef = ctx.saved_tensors
         ce_scale, dice_scale, probs = ctx.meta
-        B, ncls = logits.shape[:2]
-        HW = logits.numel() // (B * ncls)
-        gloss = dev_f32(gloss.reshape(1))
-        dlogits = torch.empty_like(logits)
-        call("cswin_loss_bwd", ptr(logits), ptr(labels), ptr(coef), ptr(gloss), ptr(dlogits), ce_scale, dice_scale, B, ncls,
-             HW, probs, stream())
+        dlogits = loss_grad(logits, labels, coef, ce_scale, dice_scale, dev_f32(gloss.reshape(1)), probs)
         return dlogits, None, None, None, None, None, None
 
 
@@ -1124,20 +1124,19 @@ class _Dropout(Function):
     def forward(ctx, x, residual, row_scale, p, seed):
         x, residual, row_scale = dev_f32(x, "dropout input"), dev_f32(residual), dev_f32(row_scale)
         y = torch.empty_like(x)
-        eps = x.numel() // x.shape[0]
-        call("cswin_dropout", ptr(x), ptr(residual), ptr(row_scale), ptr(y), x.numel(), eps, float(p), int(seed), ptr(dropout_epoch(x.device)), stream())
+        _dropout(x, y, p, seed, residual=residual, row_scale=row_scale)
         ctx.save_for_backward(row_scale)
-        ctx.meta = (float(p), int(seed), eps, residual is not None)
+        ctx.meta = (p, seed, residual is not None)
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
         (row_scale,) = ctx.saved_tensors
-        p, seed, eps, has_res = ctx.meta
+        p, seed, has_res = ctx.meta
         dy = dev_f32(dy)
         dx = torch.empty_like(dy)
-        call("cswin_dropout", ptr(dy), None, ptr(row_scale), ptr(dx), dy.numel(), eps, p, seed, ptr(dropout_epoch(dy.device)), stream())
+        _dropout(dy, dx, p, seed, row_scale=row_scale)
         return dx, (dy if has_res else None), None, None, None
 
 

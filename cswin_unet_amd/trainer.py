@@ -26,8 +26,8 @@ import os
 import torch
 import torch.distributed as dist
 
-from ._lib import call, lib, ptr, stream
-from .ops import engine_backward
+from ._lib import call, ptr, stream
+from .ops import engine_backward, loss_finalize, loss_grad, loss_sums
 from .optim import FlatSGD
 
 
@@ -116,20 +116,12 @@ class HipEngine:
             from .ops import advance_dropout_epoch
             advance_dropout_epoch(img.device)           # inside graph A when captured: a new mask set per replayed step
         logits = self.model(img)
-        B, ncls = logits.shape[:2]
-        hw = logits.numel() // (B * ncls)
-        nbytes = lib().cswin_loss_workspace(B, ncls, hw)
-        ws = torch.empty(nbytes // 4 + 4, dtype=torch.float32, device=logits.device)
-        call("cswin_loss_sums", ptr(logits.detach()), ptr(lab), ptr(self.sums), ptr(ws), nbytes, B, ncls, hw, 0, stream())
+        loss_sums(logits.detach(), lab, self.sums)
         return logits
 
     def _loss_grad(self, logits, lab, dice_grad_scale):
-        B, ncls = logits.shape[:2]
-        hw = logits.numel() // (B * ncls)
-        dlogits = torch.empty_like(logits)
-        call("cswin_loss_bwd", ptr(logits.detach()), ptr(lab), ptr(self._coef), None, ptr(dlogits),
-             self.w_ce / float(B * hw), self.w_dice / ncls * dice_grad_scale, B, ncls, hw, 0, stream())
-        return dlogits
+        ncls = logits.shape[1]
+        return loss_grad(logits.detach(), lab, self._coef, self.w_ce / float(logits.numel() // ncls), self.w_dice / ncls * dice_grad_scale)
 
     def _backward(self, outputs, grad_outputs, lo, hi, extra_inputs=()):
         """One backward phase: the gradients of parameters lo..hi-1 end in their range of opt.flat_grad (placed there by the ops,
@@ -242,8 +234,7 @@ class HipEngine:
 
     def finalize(self, n_pixels_global):
         """sums (already all-reduced) -> stats [loss, ce, dice] and the Dice gradient coefficients."""
-        call("cswin_loss_finalize", ptr(self.sums), ptr(self.stats), ptr(self._coef), float(n_pixels_global), self.ncls,
-             self.w_ce, self.w_dice, None, stream())
+        loss_finalize(self.sums, self.stats, self._coef, n_pixels_global, self.w_ce, self.w_dice)
 
     def backward_phases(self, dice_grad_scale):
         """Generator: runs one backward phase per iteration and yields the [lo, hi) range of flat_grad it completed."""

@@ -1775,6 +1775,49 @@ def test_block_with_drop_rate_matches_composition(N, ops):
         rel_err(dict(blk.named_parameters())[n].grad, P[n].grad, "dropblk.grad." + n)
 
 
+@pytest.mark.parametrize("dim,reso,heads,split,last", [(64, 14, 2, 7, False), (128, 7, 4, 7, True)])
+def test_fused_block_equals_fine_grained_composition(N, ops, dim, reso, heads, split, last):
+    """The one-node block (ops.cswin_block) against the same block composed from the public fine-grained ops -- the form a block
+    with drop_rate > 0 takes -- with the same parameters and given per-sample DropPath factors, fp32 mode, B = 2.  Two branches at
+    M = 392; one branch at M = 98, no multiple of the 64-row tile (the weight-gradient batch's unaligned route).  Both forms issue
+    the same forward launches with the same arguments: y is bit-identical.  The fused backward takes the qkv data gradient from
+    the tail kernel's fixed tile, the composition from the GEMM heuristic (another summation order): dx and every parameter
+    gradient agree to the suite's bound."""
+    blk = N.CSWinBlock(dim, reso, heads, split, qkv_bias=True, last_stage=last).to(DEV)
+    fill_state_dict(blk)
+    a, n1, n2, fc1, fc2 = blk.attns, blk.norm1, blk.norm2, blk.mlp.fc1, blk.mlp.fc2
+    idx, hd, lw, lb = [m.idx for m in a], [m.num_heads for m in a], [m.get_v.weight for m in a], [m.get_v.bias for m in a]
+    rs1, rs2 = torch.tensor([1.25, 0.5], device=DEV), torch.tensor([0.75, 1.5], device=DEV)
+    x0 = det_normal(f"fusedcomp.{dim}.x", (2, reso * reso, dim))
+    dy = T(det_normal(f"fusedcomp.{dim}.dy", (2, reso * reso, dim)))
+
+    def fused(x):
+        return ops.cswin_block(x, reso, split, idx, hd, a[0].scale, n1, blk.qkv, blk.proj, n2, fc1, fc2, lw, lb, rs1, rs2)
+
+    def composed(x):
+        qkv = ops.linear(ops.layer_norm(x, n1.weight, n1.bias, n1.eps), blk.qkv.weight, blk.qkv.bias)
+        att = ops.stripe_attention(qkv, reso, split, idx, hd, lw, lb, a[0].scale)
+        x1 = ops.linear(att, blk.proj.weight, blk.proj.bias, residual=x, row_scale=rs1)
+        return ops.mlp(ops.layer_norm(x1, n2.weight, n2.bias, n2.eps), fc1.weight, fc1.bias, fc2.weight, fc2.bias, residual=x1, row_scale=rs2)
+
+    def run(form):
+        blk.zero_grad(set_to_none=True)
+        x = T(x0, True)
+        y = form(x)
+        y.backward(dy)
+        return y.detach(), x.grad, {n: p.grad for n, p in blk.named_parameters()}
+
+    (y, dx, g), (yc, dxc, gc) = run(fused), run(composed)
+    os.makedirs(os.path.dirname(LOG), exist_ok=True)
+    with open(LOG, "a") as f:
+        f.write(f"fusedcomp.c{dim}.y max|diff| {float((y - yc).abs().max()):.3e}\n")
+    assert torch.equal(y, yc)
+    rel_err(dx, dxc, f"fusedcomp.c{dim}.dx")
+    assert len(g) == len(gc) == len(list(blk.parameters()))
+    for n in g:
+        rel_err(g[n], gc[n], f"fusedcomp.c{dim}.grad.{n}")
+
+
 @pytest.mark.parametrize("reso,idx,split,dim,heads", [(28, 1, 2, 128, 4), (14, 0, 7, 256, 8), (7, -1, 7, 512, 16), (24, 1, 12, 64, 2)])
 def test_attention_probability_dropout(ops, reso, idx, split, dim, heads):
     """attn_drop_rate > 0 (nn.Dropout on the softmax matrix, cswin_unet.py:57,101): the mask is a counter-based hash inside the
