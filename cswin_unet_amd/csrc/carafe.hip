@@ -442,13 +442,14 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __rest
     const int lanes = min(C, 256);
     const int rgroups = 256 / lanes;
     const int c0 = threadIdx.x % lanes, rg = threadIdx.x / lanes;
-    for (int c = c0; c < C; c += lanes) {
+    for (int cb = 0; cb < C; cb += lanes) {          // the same trip count for every thread: the barriers below are uniform
+        const int c = cb + c0;
         float s = 0.f;
-        if (rg < rgroups)
+        if (rg < rgroups && c < C)
             for (long r = (long)blockIdx.x * rgroups + rg; r < rows; r += (long)gridDim.x * rgroups) s += x[r * C + c];
         red[threadIdx.x] = s;
         __syncthreads();
-        if (rg == 0) {
+        if (rg == 0 && c < C) {
             float t = 0.f;
             for (int k = 0; k < rgroups; ++k) t += red[k * lanes + c0];
             partial[(long)blockIdx.x * C + c] = t;

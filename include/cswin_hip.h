@@ -107,7 +107,8 @@ int cswin_attn_bwd(const float* qkv, const float* const* lepe_w, const float* co
 int cswin_img2windows(const float* img, float* out, int B, int C, int H, int W, int H_sp, int W_sp, void* stream);
 int cswin_windows2img(const float* win, float* out, int B, int C, int H, int W, int H_sp, int W_sp, void* stream);
 
-/* ---- nn.LayerNorm over C (cswin_unet.py:168,179,218,341,497,533); C in {32,64,128,256,512,1024} ---- */
+/* ---- nn.LayerNorm over C (cswin_unet.py:168,179,218,341,497,533); any C % 4 == 0 up to 1024 (CSWIN_ERR_UNSUPPORTED
+ *      otherwise): kernels specialised per width for C in {32,64,128,256,512,1024}, one wave per row for every other C ---- */
 int cswin_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd,
                         int M, int C, float eps, int y_bf16, void* stream);
 /* y_bf16 != 0: y is STORED as bf16 (bf16 activation storage: the input format of cswin_linear_fwd io_bf16 bit 0 and of
