@@ -15,7 +15,7 @@ from ._lib import ConvImageJob, CswinHipError, ReduceJob, WgradDesc, act_bf16, c
 
 __all__ = ["layer_norm", "linear", "linear_pair", "mlp", "stripe_attention", "cswin_block", "conv_tokens", "patch_embed_conv", "carafe_reassemble",
            "carafe_reassemble_nchw", "conv_weight_images", "head_compose", "tokens_to_nchw", "matmul_nn", "ce_dice_loss", "dropout", "img2windows", "windows2img",
-           "seg_metrics"]
+           "seg_metrics", "resize_slices", "argmax_zoom_back"]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1114,6 +1114,48 @@ def seg_metrics(pred, label, ncls, ndim=None):
     ws = torch.empty(nbytes, dtype=torch.uint8, device=pred.device)
     call("cswin_seg_metrics", ptr(pred), ptr(label), ptr(counts), ptr(hist), ptr(ws), nbytes, D, H, W, ndim, int(ncls), stream())
     return counts, hist
+
+
+# ------------------------------------------------------------------------------------------------
+# the resizes around the network in a volume evaluation
+# ------------------------------------------------------------------------------------------------
+def resize_slices(x, size):
+    """scipy.ndimage.zoom(x[d], (h / H, w / W), order=3) of every slice of x (D, H, W), a float32 or float64 HIP tensor, as a
+    float32 (D, h, w) tensor; size = (h, w).  The two 1-D operators are scipy's own (utils.zoom_operator, uploaded once per size
+    pair and device), the device forms float32(R_h x[d] R_w^T) in float64 (csrc/resize.hip).  Integer dtypes raise ValueError:
+    scipy rounds integer outputs, which stays on the host path."""
+    if not x.is_cuda:
+        raise CswinHipError(f"resize_slices input is on {x.device}: the cswin_unet_amd ops run on a HIP device only (no CPU fallback)")
+    if not x.is_floating_point():
+        raise ValueError(f"resize_slices: dtype {x.dtype}; integer volumes are resized on the host (scipy rounds integer outputs)")
+    if x.dtype not in (torch.float32, torch.float64):
+        raise CswinHipError(f"resize_slices input has dtype {x.dtype}; float32 or float64 is resized")
+    if x.dim() != 3:
+        raise CswinHipError(f"resize_slices: input {tuple(x.shape)} must be (D, H, W)")
+    from .utils import zoom_operator_device
+    x = x.contiguous()
+    (D, H, W), (h, w) = x.shape, (int(size[0]), int(size[1]))
+    wh, sh = zoom_operator_device(H, h, x.device)
+    ww, sw = zoom_operator_device(W, w, x.device)
+    y = torch.empty((D, h, w), dtype=torch.float32, device=x.device)
+    call("cswin_resize_banded", ptr(x), ptr(y), ptr(wh), ptr(sh), wh.shape[1], ptr(ww), ptr(sw), ww.shape[1], D, H, W, h, w,
+         int(x.dtype == torch.float64), stream())
+    return y
+
+
+def argmax_zoom_back(logits, size):
+    """scipy.ndimage.zoom(torch.argmax(logits, 1)[b], (H / h, W / w), order=0) of logits (B, ncls, h, w) fp32 as a uint8
+    (B, H, W) HIP tensor; size = (H, W), ncls <= 255.  The source index of every output row / column is scipy's own
+    (utils.nearest_index); with size == (h, w) it is the plain argmax."""
+    logits = dev_f32(logits, "argmax_zoom_back logits")
+    if logits.dim() != 4:
+        raise CswinHipError(f"argmax_zoom_back: logits {tuple(logits.shape)} must be (B, ncls, h, w)")
+    from .utils import nearest_index_device
+    (B, ncls, h, w), (H, W) = logits.shape, (int(size[0]), int(size[1]))
+    out = torch.empty((B, H, W), dtype=torch.uint8, device=logits.device)
+    call("cswin_argmax_zoom_back", ptr(logits), ptr(out), ptr(nearest_index_device(h, H, logits.device)),
+         ptr(nearest_index_device(w, W, logits.device)), B, ncls, h, w, H, W, stream())
+    return out
 
 
 # ------------------------------------------------------------------------------------------------

@@ -12,7 +12,10 @@ Mirrors the reference's utils.py names and call signatures:
     one launch per slice.  ``metrics="hip"`` takes Dice / HD95 of all classes from one device call (``volume_metrics``:
     ops.seg_metrics returns integer counts and an integer histogram of squared surface distances, the host finishes in
     float64) instead of the per-class scipy loop; ``evaluate_volumes`` is the aggregating loop of test.py:155-164.
+    ``resize="hip"`` keeps the volume on the device: both zooms are linear maps whose 1-D operators ``zoom_operator`` /
+    ``nearest_index`` take from scipy itself, applied by ops.resize_slices / ops.argmax_zoom_back (csrc/resize.hip).
 """
+import functools
 import logging
 
 import numpy as np
@@ -154,16 +157,111 @@ def volume_metrics(pred, label, classes, device="cuda"):
     return metrics_from_counts_hist(counts.cpu().numpy(), hist[:, :last + 1].cpu().numpy())
 
 
+@functools.lru_cache(maxsize=None)
+def zoom_operator(n_in, n_out):
+    """The 1-D operator R (n_out x n_in) of ``scipy.ndimage.zoom(x, n_out / n_in, order=3)`` along an axis of n_in samples, as a
+    band: ``(weights float64 [n_out][T], start int32 [n_out])`` with row i of R = weights[i] at columns start[i] .. start[i] + T.
+    Column k of R is scipy's own zoom of the float64 unit vector e_k, so the spline prefilter, its mirror boundary and the
+    (n_in - 1) / (n_out - 1) coordinate rule are scipy's; zoom of a 2-D slice X is R_h X R_w^T.  R decays geometrically away from
+    its diagonal: a row's window covers every entry with |r| >= 2**-64 (what lies outside is below float64 rounding of the
+    result), T is the widest window (at most n_in), windows are shifted to lie inside [0, n_in) and filled with the true entries
+    of R.  A row may be all zero: scipy rounds the last output coordinate of 512 -> 224 past the last sample and writes its
+    constant 0 there.  ValueError if scipy's output length for this pair is not n_out.  The arrays are cached: do not write to them."""
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f"zoom_operator: sizes {n_in} -> {n_out} must be positive")
+    cols = [zoom(e, n_out / n_in, order=3) for e in np.eye(n_in, dtype=np.float64)]
+    if any(c.shape != (n_out,) for c in cols):
+        raise ValueError(f"zoom_operator: scipy zooms {n_in} samples by {n_out}/{n_in} to {cols[0].shape[0]}, not {n_out}")
+    R = np.stack(cols, axis=1)
+    big = np.abs(R) >= 2.0 ** -64
+    lo = big.argmax(axis=1)                                         # a row without any such entry gets the window [0, 1)
+    hi = np.where(big.any(axis=1), n_in - 1 - big[:, ::-1].argmax(axis=1), lo)
+    T = min(n_in, int((hi - lo).max()) + 1)
+    start = np.clip(lo, 0, n_in - T).astype(np.int32)
+    weights = np.ascontiguousarray(R[np.arange(n_out)[:, None], start[:, None] + np.arange(T)[None, :]])
+    weights.setflags(write=False)
+    start.setflags(write=False)
+    return weights, start
+
+
+@functools.lru_cache(maxsize=None)
+def nearest_index(n_in, n_out):
+    """int32 [n_out]: the source index ``scipy.ndimage.zoom(x, n_out / n_in, order=0)`` picks for every output sample along an
+    axis of n_in samples, read off scipy's zoom of arange(n_in) + 1.  An output whose coordinate scipy rounds past the last
+    sample is not gathered at all: scipy writes its constant 0 there (the last output of 512 -> 224), and the entry is -1.
+    ``zoom(lab, ..., order=0)`` is ``lab[np.ix_(ih, iw)]`` where both indices are >= 0 and 0 elsewhere.  Cached."""
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f"nearest_index: sizes {n_in} -> {n_out} must be positive")
+    src = zoom(np.arange(1, n_in + 1, dtype=np.float64), n_out / n_in, order=0)
+    if src.shape != (n_out,):
+        raise ValueError(f"nearest_index: scipy zooms {n_in} samples by {n_out}/{n_in} to {src.shape[0]}, not {n_out}")
+    idx = src.astype(np.int32) - 1
+    if np.any(idx + 1 != src) or idx.min() < -1 or idx.max() >= n_in:
+        raise ValueError(f"nearest_index: scipy's order-0 zoom of 1..{n_in} is not an index vector")
+    idx.setflags(write=False)
+    return idx
+
+
+_device_tables = {}
+
+
+def zoom_operator_device(n_in, n_out, device):
+    """zoom_operator's (weights, start) as tensors on `device`, uploaded once per (size pair, device)."""
+    key = ("zoom", int(n_in), int(n_out), torch.device(device))
+    if key not in _device_tables:
+        w, s = zoom_operator(n_in, n_out)
+        _device_tables[key] = (torch.from_numpy(w.copy()).to(device), torch.from_numpy(s.copy()).to(device))
+    return _device_tables[key]
+
+
+def nearest_index_device(n_in, n_out, device):
+    """nearest_index as a tensor on `device`, uploaded once per (size pair, device)."""
+    key = ("nearest", int(n_in), int(n_out), torch.device(device))
+    if key not in _device_tables:
+        _device_tables[key] = torch.from_numpy(nearest_index(n_in, n_out).copy()).to(device)
+    return _device_tables[key]
+
+
+def _predict_volume_hip(vol, net, patch_size, batch_slices, device):
+    """predict_volume's loop with the volume resident on the device: upload once, per batch resize_slices -> net ->
+    argmax_zoom_back into a uint8 (D, H, W) device volume."""
+    D, x, y = vol.shape
+    dvol = torch.from_numpy(np.ascontiguousarray(vol)).to(device)
+    resize = x != patch_size[0] or y != patch_size[1]
+    if not resize:
+        dvol = dvol.float()
+    pred = torch.empty((D, x, y), dtype=torch.uint8, device=dvol.device)
+    for d0 in range(0, D, batch_slices):
+        sl = dvol[d0:d0 + batch_slices]
+        inp = ops.resize_slices(sl, patch_size) if resize else sl
+        pred[d0:d0 + batch_slices] = ops.argmax_zoom_back(net(inp.unsqueeze(1)), (x, y))
+    return pred
+
+
 @torch.no_grad()
-def predict_volume(image, net, patch_size=(224, 224), batch_slices=16, device="cuda"):
+def predict_volume(image, net, patch_size=(224, 224), batch_slices=16, device="cuda", resize="host", return_device=False):
     """image (D, H, W) or (H, W) numpy -> integer class map of the same shape.  Per slice: cubic zoom to patch_size if the
-    size differs, network, argmax over classes (softmax is monotonic, utils.py:75), nearest zoom back (:70-81)."""
+    size differs, network, argmax over classes (softmax is monotonic, utils.py:75), nearest zoom back (:70-81).
+    resize: "host" = scipy's zooms per slice around batched network calls; "hip" = the volume is uploaded once, both zooms and
+    the argmax run on the device (same values; float32 / float64 volumes, integer ones only when nothing is resized) and only the
+    finished volume comes back, as the uint8 array it is on the device (the host path returns int64) -- or, with
+    return_device=True, stays there as a uint8 tensor."""
+    if resize not in ("host", "hip"):
+        raise ValueError(f'predict_volume: resize must be "host" or "hip", got {resize!r}')
+    if return_device and resize != "hip":
+        raise ValueError('predict_volume: return_device needs resize="hip"')
     image = np.asarray(image)
     single = image.ndim == 2
     vol = image[None] if single else image
+    net.eval()
+    if resize == "hip":
+        pred = _predict_volume_hip(vol, net, tuple(patch_size), batch_slices, device)
+        pred = pred if return_device else pred.cpu().numpy()
+        return pred[0] if single else pred
     D, x, y = vol.shape
     resize = x != patch_size[0] or y != patch_size[1]
-    net.eval()
     pred = np.zeros((D, x, y), np.int64)
     for d0 in range(0, D, batch_slices):
         sl = vol[d0:d0 + batch_slices]
@@ -177,19 +275,27 @@ def predict_volume(image, net, patch_size=(224, 224), batch_slices=16, device="c
 
 
 def test_single_volume(image, label, net, classes, patch_size=[256, 256], test_save_path=None, case=None, z_spacing=1,
-                       batch_slices=16, device="cuda", metrics="host"):
+                       batch_slices=16, device="cuda", metrics="host", resize="host"):
     """Per-class (dice, hd95) of one volume, classes 1..classes-1 (utils.py:61-102).  image / label: (1, D, H, W) tensors
     as the DataLoader yields them.  With test_save_path the volumes are written as .npz (SimpleITK, which the reference
     uses for .nii.gz, is not installed here).  metrics: "host" = the per-class scipy loop, "hip" = one volume_metrics call on
-    the device (same values)."""
+    the device (same values).  resize: predict_volume's; with resize="hip" and metrics="hip" the prediction goes from the one to
+    the other as a device tensor and is downloaded only to be saved."""
     if metrics not in ("host", "hip"):
         raise ValueError(f'test_single_volume: metrics must be "host" or "hip", got {metrics!r}')
+    if resize not in ("host", "hip"):
+        raise ValueError(f'test_single_volume: resize must be "host" or "hip", got {resize!r}')
     image, label = image.squeeze(0).cpu().detach().numpy(), label.squeeze(0).cpu().detach().numpy()
-    prediction = predict_volume(image, net, tuple(patch_size), batch_slices, device).astype(label.dtype)
+    on_device = resize == "hip" and metrics == "hip"
+    prediction = predict_volume(image, net, tuple(patch_size), batch_slices, device, resize=resize, return_device=on_device)
+    if not on_device:
+        prediction = prediction.astype(label.dtype)
     if metrics == "hip":
         metric_list = volume_metrics(prediction, label, classes, device)
     else:
         metric_list = [calculate_metric_percase(prediction == i, label == i) for i in range(1, classes)]
+    if on_device and test_save_path is not None:
+        prediction = prediction.cpu().numpy()
     if test_save_path is not None:
         np.savez_compressed(f"{test_save_path}/{case}_pred.npz", image=image.astype(np.float32),
                             prediction=prediction.astype(np.float32), label=label.astype(np.float32),
@@ -201,7 +307,7 @@ test_single_volume.__test__ = False     # not a pytest test (the name is the ref
 
 
 def evaluate_volumes(loader, net, classes, patch_size, metrics="hip", test_save_path=None, z_spacing=1, batch_slices=16,
-                     device="cuda"):
+                     device="cuda", resize="host"):
     """The volume loop of the reference's inference() (test.py:155-164): test_single_volume per batch of `loader` (dicts with
     "image", "label" (1, D, H, W) and "case_name", batch size 1), the per-volume and final lines it logs.  Returns
     (per_volume, class_mean, mean_dice, mean_hd95): the metric list of every volume, the (classes-1, 2) table of per-class
@@ -212,7 +318,7 @@ def evaluate_volumes(loader, net, classes, patch_size, metrics="hip", test_save_
         name = name if isinstance(name, str) else name[0]
         metric_i = test_single_volume(batch["image"], batch["label"], net, classes=classes, patch_size=list(patch_size),
                                       test_save_path=test_save_path, case=name, z_spacing=z_spacing, batch_slices=batch_slices,
-                                      device=device, metrics=metrics)
+                                      device=device, metrics=metrics, resize=resize)
         per_volume.append(metric_i)
         m = np.mean(metric_i, axis=0)
         logging.info('idx %d case %s mean_dice %f mean_hd95 %f' % (i_batch, name, m[0], m[1]))

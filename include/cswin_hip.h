@@ -28,7 +28,7 @@ extern "C" {
 
 /* Bumped whenever a prototype or struct below changes (1: round 1; 2: round 2 -- stream / precision / storage arguments; 3: round 3 --
  * cswin_attn_fwd writes y0, cswin_attn_bwd reads it).  cswin_abi_version() returns the value the library was built with: a consumer
- * compiled against another header must refuse to call it.  Entry points that are only ADDED (cswin_seg_metrics*) do not bump
+ * compiled against another header must refuse to call it.  Entry points that are only ADDED (cswin_seg_metrics*, cswin_resize_banded, cswin_argmax_zoom_back) do not bump
  * it: every prototype an older consumer binds is unchanged. */
 #define CSWIN_ABI_VERSION 4
 
@@ -313,6 +313,24 @@ int    cswin_seg_metrics_nbins(int D, int H, int W);
 size_t cswin_seg_metrics_workspace(int D, int H, int W, int ndim, int ncls);
 int    cswin_seg_metrics(const unsigned char* pred, const unsigned char* label, long long* counts, unsigned int* hist,
                          void* workspace, size_t ws_bytes, int D, int H, int W, int ndim, int ncls, void* stream);
+
+/* ---- evaluation: the two resizes around the network (utils.py:70-81: scipy.ndimage.zoom(order=3) of each slice to the network's
+ *      input size, argmax and scipy.ndimage.zoom(order=0) back) ----
+ * zoom of a 2-D slice is the separable linear map R_h x R_w^T; the caller takes each 1-D operator R (n_out x n_in) from scipy
+ * itself (zoom of the unit vectors; cswin_unet_amd.utils.zoom_operator) and passes it as a band: row i of R_h is
+ * wh[i][0..Th) at columns sh[i] .. sh[i] + Th (0 <= sh[i], sh[i] + Th <= H; Th <= H), the same for ww / sw / Tw along W.
+ * x (D, H, W) float32 (x_f64 = 0) or float64 (x_f64 = 1) -> y (D, h, w) float32 = float32(R_h x[d] R_w^T): every product and sum
+ * in float64 (ascending input index), one rounding at the store.  wh (h, Th), ww (w, Tw) float64; sh (h), sw (w) int32; each of
+ * D, H, W, h, w in 1..2048.  No alignment beyond the element size and no workspace; starts are clamped into range on the device. */
+int cswin_resize_banded(const void* x, float* y, const double* wh, const int* sh, int Th, const double* ww, const int* sw, int Tw,
+                        int D, int H, int W, int h, int w, int x_f64, void* stream);
+/* logits (B, ncls, h, w) fp32 -> out (B, H, W) uint8: out[b][i][j] = argmax_c logits[b][c][src_row[i]][src_col[j]] with
+ * torch.argmax's rules (the first index wins a tie, a NaN beats every number).  src_row (H), src_col (W) int32: the source index
+ * of every output row / column, as scipy's order-0 zoom picks it (cswin_unet_amd.utils.nearest_index); 0..H-1 / 0..W-1 themselves
+ * when nothing is resized.  A negative index marks an output that scipy fills with its constant instead of gathering (the last
+ * output of 512 -> 224): out is 0 there.  Indices past the end are clamped on the device.  ncls in 1..255; each of B, h, w, H, W in 1..2048. */
+int cswin_argmax_zoom_back(const float* logits, unsigned char* out, const int* src_row, const int* src_col, int B, int ncls, int h,
+                           int w, int H, int W, void* stream);
 
 #ifdef __cplusplus
 }
