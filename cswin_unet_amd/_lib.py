@@ -71,6 +71,8 @@ SIGNATURES = {
     "cswin_seg_metrics": (I, [P, P, P, P, P, SZ, I, I, I, I, I, P]),
     "cswin_resize_banded": (I, [P, P, P, P, I, P, P, I, I, I, I, I, I, I, P]),
     "cswin_argmax_zoom_back": (I, [P, P, P, P, I, I, I, I, I, I, P]),
+    "cswin_augment_gather": (I, [P, P, P, I, I, I, I, I, I, P]),
+    "cswin_augment_labels": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
 }
 
 
@@ -93,6 +95,11 @@ class ConvImageJob(ctypes.Structure):
     """Mirror of cswin_conv_image_job (include/cswin_hip.h)."""
     _fields_ = [("w", c_void_p), ("w_perm", c_void_p), ("w_permT", c_void_p), ("w_flipT", c_void_p), ("Cout", c_int),
                 ("Cin", c_int), ("ks", c_int), ("Cpad", c_int)]
+
+
+class AugmentDesc(ctypes.Structure):
+    """Mirror of cswin_augment_desc (include/cswin_hip.h)."""
+    _fields_ = [("kind", c_int), ("k", c_int), ("axis", c_int), ("src", c_int), ("map", c_void_p)]
 
 
 _lib = None

@@ -69,6 +69,48 @@ class RandomGenerator(object):
         return {'image': image_t, 'label': label_t}
 
 
+# `kind` of RawSliceParams' parameters: the one Python definition (ops.augment_batch imports it); csrc/augment.hip mirrors it
+AUG_NONE, AUG_ROT90_FLIP, AUG_ROTATE = 0, 1, 2
+
+
+class RawSliceParams(object):
+    """RandomGenerator's random draws without its arithmetic, for `augment="hip"`: {'image': (H, W) float32, 'label': (H, W)} ->
+    {'image': float32 (H, W) as it is, 'label': uint8 (H, W), 'params': int32 (4,) = (kind, k, axis, angle)}; ops.augment_batch
+    applies the transforms and the zooms to `output_size` to the collated batch on the device.  Both RNG streams are consumed in
+    RandomGenerator's order and counts (one or two `random.random()`, then k and axis or the angle from `np.random.randint`), so a
+    seeded run draws the transforms RandomGenerator would apply.  ValueError for what the device path does not take: an image
+    that is not float32 (scipy computes in the image's own dtype) or labels that are not integral values in 0..255."""
+
+    def __init__(self, output_size):
+        self.output_size = output_size
+
+    def __call__(self, sample):
+        image, label = np.asarray(sample['image']), np.asarray(sample['label'])
+        kind, k, axis, angle = AUG_NONE, 0, 0, 0
+        if random.random() > 0.5:
+            kind, k = AUG_ROT90_FLIP, np.random.randint(0, 4)
+            axis = np.random.randint(0, 2)
+        elif random.random() > 0.5:
+            kind, angle = AUG_ROTATE, np.random.randint(-20, 20)
+        if image.dtype != np.float32 or image.ndim != 2 or image.shape != label.shape:
+            raise ValueError(f"RawSliceParams: image {image.dtype} {image.shape} / label {label.shape}: the device augmentation takes "
+                             f"float32 (H, W) slices with labels of the same shape; use augment=\"host\" for this dataset")
+        if label.dtype.kind not in "biuf" or label.min() < 0 or label.max() > 255 or (label.dtype.kind == "f" and
+                                                                                      np.any(label != np.rint(label))):
+            raise ValueError("RawSliceParams: labels are not integral class ids in 0..255; use augment=\"host\" for this dataset")
+        return {'image': torch.from_numpy(np.ascontiguousarray(image)), 'label': torch.from_numpy(label.astype(np.uint8)),
+                'params': torch.tensor([kind, k, axis, angle], dtype=torch.int32)}
+
+
+def collate_raw_slices(samples):
+    """default_collate for RawSliceParams' samples; slices of different shapes in one batch raise a ValueError that names them."""
+    from torch.utils.data import default_collate
+    shapes = sorted({tuple(s['image'].shape) for s in samples})
+    if len(shapes) > 1:
+        raise ValueError(f"augment=\"hip\" needs one slice shape per batch, got {shapes}; use augment=\"host\" for this dataset")
+    return default_collate(samples)
+
+
 def _first_key(data, *names):
     for n in names:
         if n in data:

@@ -7,15 +7,16 @@ CswinHipError on a non-HIP tensor -- there is no CPU / eager fallback.
 import ctypes
 import math
 
+import numpy as np
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from ._lib import ConvImageJob, CswinHipError, ReduceJob, WgradDesc, act_bf16, call, dev_f32, lib, precision, ptr, shadow_ptr, stream
+from ._lib import AugmentDesc, ConvImageJob, CswinHipError, ReduceJob, WgradDesc, act_bf16, call, dev_f32, lib, precision, ptr, shadow_ptr, stream
 
 __all__ = ["layer_norm", "linear", "linear_pair", "mlp", "stripe_attention", "cswin_block", "conv_tokens", "patch_embed_conv", "carafe_reassemble",
            "carafe_reassemble_nchw", "conv_weight_images", "head_compose", "tokens_to_nchw", "matmul_nn", "ce_dice_loss", "dropout", "img2windows", "windows2img",
-           "seg_metrics", "resize_slices", "argmax_zoom_back"]
+           "seg_metrics", "resize_slices", "argmax_zoom_back", "augment_batch"]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1156,6 +1157,86 @@ def argmax_zoom_back(logits, size):
     call("cswin_argmax_zoom_back", ptr(logits), ptr(out), ptr(nearest_index_device(h, H, logits.device)),
          ptr(nearest_index_device(w, W, logits.device)), B, ncls, h, w, H, W, stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# training augmentation of a batch of raw slices
+# ------------------------------------------------------------------------------------------------
+def _augment_table(descs, device):
+    """Device copy of a list of (kind, k, axis, src, map tensor or None) as cswin_augment_desc records."""
+    table = (AugmentDesc * len(descs))()
+    for d, (kind, k, axis, src, amap) in zip(table, descs):
+        d.kind, d.k, d.axis, d.src, d.map = kind, k, axis, src, None if amap is None else amap.data_ptr()
+    return _upload(np.frombuffer(table, dtype=np.int64), device)           # 24-byte records; int64 keeps the 8-B alignment
+
+
+def _upload(values, device):
+    """int64 host values -> device through pinned memory: an asynchronous copy on the current stream (the caching host allocator
+    hands the pinned block out again only after that copy has run)."""
+    values = np.asarray(values, dtype=np.int64)
+    host = torch.empty(values.shape, dtype=torch.int64, pin_memory=True)
+    host.numpy()[...] = values
+    return host.to(device, non_blocking=True)
+
+
+def augment_batch(images, labels, params, size):
+    """datasets.RandomGenerator's arithmetic for a whole batch of raw slices, on the device (csrc/augment.hip, csrc/resize.hip).
+    images: float32 HIP tensor (B, H, W); labels: uint8 HIP tensor (B, H, W); params: integer HOST tensor (B, 4) of
+    (kind, k, axis, angle) per sample as datasets.RawSliceParams draws them (kind 0: nothing, 1: np.flip(np.rot90(x, k), axis),
+    2: ndimage.rotate(x, angle, order=0, reshape=False)); size = (h, w).  Returns (image float32 (B, 1, h, w), label int64
+    (B, h, w)): the transformed image through scipy's cubic zoom (resize_slices; skipped when the transformed shape is `size`
+    already), the transformed label through its order-0 zoom.  Square slices take one gather, one resize and one label launch;
+    for non-square ones the samples that keep the shape and those a quarter turn transposes are gathered and resized as two
+    groups.  Runs on the current stream and does not synchronise it in the steady state: the parameters are read on the host,
+    which is where they are, and the per-batch tables go up through pinned memory.  The FIRST use of a table is the exception:
+    each (H, W, angle) rotation map is one scipy.ndimage.rotate on the host (~10 ms at 512 x 512) and a blocking upload from
+    pageable memory, up to 40 times per shape over a run, and the nearest / zoom tables of a size pair likewise, once.  They
+    are uploaded blocking on purpose: the copies are cached per device and later read from whichever stream calls, so a
+    copy that were still in flight on the first caller's stream would race with a second stream's kernels."""
+    for t, what, dtype, why in ((images, "augment_batch images", torch.float32, "raw slices are float32 (other dtypes: augment=\"host\")"),
+                                (labels, "augment_batch labels", torch.uint8, "class ids are passed as uint8")):
+        if not t.is_cuda:
+            raise CswinHipError(f"{what} is on {t.device}: the cswin_unet_amd ops run on a HIP device only (no CPU fallback)")
+        if t.dtype != dtype:
+            raise CswinHipError(f"{what} has dtype {t.dtype}; {why}")
+    if images.dim() != 3 or images.shape != labels.shape:
+        raise CswinHipError(f"augment_batch: images {tuple(images.shape)} and labels {tuple(labels.shape)} must be equal (B, H, W) shapes")
+    if params.is_cuda or params.is_floating_point() or tuple(params.shape) != (images.shape[0], 4):
+        raise CswinHipError(f"augment_batch: params must be an integer host tensor ({images.shape[0]}, 4), got {params.dtype} "
+                            f"{tuple(params.shape)} on {params.device}")
+    from .datasets.dataset_synapse import AUG_NONE, AUG_ROT90_FLIP, AUG_ROTATE
+    from .utils import nearest_index_device, rotation_index_device
+    images, labels, dev = images.contiguous(), labels.contiguous(), images.device
+    (B, H, W), (h, w) = images.shape, (int(size[0]), int(size[1]))
+    descs, swapped = [], []
+    for b, (kind, k, axis, angle) in enumerate(params.tolist()):
+        if kind not in (AUG_NONE, AUG_ROT90_FLIP, AUG_ROTATE) or not (0 <= k <= 3 and 0 <= axis <= 1):
+            raise ValueError(f"augment_batch: sample {b} has parameters (kind, k, axis, angle) = {(kind, k, axis, angle)}")
+        descs.append((kind, k, axis, b, rotation_index_device(H, W, angle, dev) if kind == AUG_ROTATE else None))
+        swapped.append(kind == AUG_ROT90_FLIP and k % 2 == 1 and H != W)
+    groups = [([b for b in range(B) if not swapped[b]], (H, W)), ([b for b in range(B) if swapped[b]], (W, H))]
+    groups = [g for g in groups if g[0]]
+    # one table: the B samples in order (the label launch, and the only image group of square slices), then the image groups
+    rows = descs + ([descs[b] for idx, _ in groups for b in idx] if len(groups) > 1 else [])
+    table = _augment_table(rows, dev)
+    image, first = None, B if len(groups) > 1 else 0
+    for idx, (Ho, Wo) in groups:
+        y = torch.empty((len(idx), Ho, Wo), dtype=torch.float32, device=dev)
+        call("cswin_augment_gather", ptr(images), ptr(y), ptr(table[3 * first:]), len(idx), B, H, W, Ho, Wo, stream())
+        if (Ho, Wo) != (h, w):
+            y = resize_slices(y, (h, w))
+        if len(groups) == 1:
+            image = y
+        else:                                                           # the group's results go to its samples' rows
+            image = torch.empty((B, h, w), dtype=torch.float32, device=dev) if image is None else image
+            image.index_copy_(0, _upload(idx, dev), y)
+        first += len(idx)
+    label = torch.empty((B, h, w), dtype=torch.int64, device=dev)
+    keep = (nearest_index_device(H, h, dev), nearest_index_device(W, w, dev))
+    swap = (nearest_index_device(W, h, dev), nearest_index_device(H, w, dev)) if any(swapped) else keep
+    call("cswin_augment_labels", ptr(labels), ptr(label), ptr(table), ptr(keep[0]), ptr(keep[1]), ptr(swap[0]), ptr(swap[1]), B, B, H, W,
+         h, w, stream())
+    return image.unsqueeze(1), label
 
 
 # ------------------------------------------------------------------------------------------------

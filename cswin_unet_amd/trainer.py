@@ -27,7 +27,7 @@ import torch
 import torch.distributed as dist
 
 from ._lib import call, ptr, stream
-from .ops import engine_backward, loss_finalize, loss_grad, loss_sums
+from .ops import augment_batch, engine_backward, loss_finalize, loss_grad, loss_sums
 from .optim import FlatSGD
 
 
@@ -389,10 +389,17 @@ class DataParallelTrainer:
 
 
 class _Prefetcher:
-    """Pinned host batches -> device on a side stream, one batch ahead of the step that consumes them."""
+    """Pinned host batches -> device on a side stream, one batch ahead of the step that consumes them.
+    augment="hip": the loader yields RawSliceParams' raw batches (image, uint8 label, params); they are uploaded and finished by
+    ops.augment_batch(..., output_size) on the same side stream, so the augmentation too overlaps the previous step, and the
+    (image, label) pair handed out is the one the host path yields."""
 
-    def __init__(self, loader, device):
-        self.it, self.device = iter(loader), device
+    def __init__(self, loader, device, augment="host", output_size=None):
+        if augment not in ("host", "hip"):
+            raise ValueError(f'_Prefetcher: augment must be "host" or "hip", got {augment!r}')
+        if augment == "hip" and (output_size is None or len(output_size) != 2):
+            raise ValueError(f'_Prefetcher: augment="hip" needs output_size = (h, w), got {output_size!r}')
+        self.it, self.device, self.augment, self.output_size = iter(loader), device, augment, output_size
         self.stream = torch.cuda.Stream(device)
         self._next()
 
@@ -403,7 +410,12 @@ class _Prefetcher:
             self.batch = None
             return
         with torch.cuda.stream(self.stream):
-            self.batch = (batch['image'].to(self.device, non_blocking=True), batch['label'].to(self.device, non_blocking=True))
+            img, lab = batch['image'].to(self.device, non_blocking=True), batch['label'].to(self.device, non_blocking=True)
+            if self.augment == "hip":
+                # the raw uploads and augment_batch's temporaries are allocated, written and read on the side stream only: they
+                # never cross to the consumer's stream, only the two results do (recorded in __next__ like the host path's)
+                img, lab = augment_batch(img, lab, batch['params'], self.output_size)
+            self.batch = (img, lab)
 
     def __iter__(self):
         return self
@@ -422,7 +434,9 @@ class _Prefetcher:
 def trainer_synapse(args, model, snapshot_path, group=None, log_every=1):
     """Counterpart of the reference's ``trainer_synapse(args, model, snapshot_path)`` (trainer.py:20-95) on the HIP engine.
 
-    args: root_path, list_dir, img_size, num_classes, batch_size (per GPU), base_lr, max_epochs, optionally num_workers.
+    args: root_path, list_dir, img_size, num_classes, batch_size (per GPU), base_lr, max_epochs, optionally num_workers and
+    augment: "host" (default) = RandomGenerator in the workers; "hip" = the workers only draw the random parameters
+    (RawSliceParams) and the prefetcher applies them on the device (ops.augment_batch: float32 slices of one shape per batch).
     Same dataset / augmentation / loss / optimiser / LR schedule / checkpoint schedule (``epoch_N.pth`` every third epoch
     of the second half and at the end, :79-90).  Differences, all execution-side: one process per GPU (pass the process
     group; each rank reads its own shard through a DistributedSampler) instead of nn.DataParallel; batches are prefetched
@@ -436,8 +450,11 @@ def trainer_synapse(args, model, snapshot_path, group=None, log_every=1):
     from torch.utils.data.distributed import DistributedSampler
 
     from .checkpoint import save_checkpoint
-    from .datasets import RandomGenerator, Synapse_dataset
+    from .datasets import RandomGenerator, RawSliceParams, Synapse_dataset, collate_raw_slices
 
+    augment = getattr(args, "augment", "host")
+    if augment not in ("host", "hip"):
+        raise ValueError(f'trainer_synapse: augment must be "host" or "hip", got {augment!r}')
     os.makedirs(snapshot_path, exist_ok=True)
     logging.basicConfig(filename=os.path.join(snapshot_path, "log.txt"), level=logging.INFO,
                         format='[%(asctime)s.%(msecs)03d] %(message)s', datefmt='%H:%M:%S')
@@ -448,7 +465,7 @@ def trainer_synapse(args, model, snapshot_path, group=None, log_every=1):
     world = dist.get_world_size(group) if group is not None else 1
     device = next(model.parameters()).device
     db_train = Synapse_dataset(base_dir=args.root_path, list_dir=args.list_dir, split="train",
-                               transform=RandomGenerator(output_size=[args.img_size, args.img_size]))
+                               transform=(RawSliceParams if augment == "hip" else RandomGenerator)(output_size=[args.img_size, args.img_size]))
     print("The length of train set is: {}".format(len(db_train)))
     seed = getattr(args, "seed", 1234)
 
@@ -462,6 +479,7 @@ def trainer_synapse(args, model, snapshot_path, group=None, log_every=1):
     sampler = DistributedSampler(db_train, num_replicas=world, rank=rank, shuffle=True, seed=seed) if world > 1 else None
     loader = DataLoader(db_train, batch_size=args.batch_size, shuffle=sampler is None, sampler=sampler,
                         num_workers=n_workers, pin_memory=True, drop_last=True, worker_init_fn=worker_init_fn,
+                        collate_fn=collate_raw_slices if augment == "hip" else None,
                         persistent_workers=False)    # like the reference: workers are re-created and re-seeded every epoch
     max_epoch = args.max_epochs
     max_iterations = max_epoch * len(loader)
@@ -475,7 +493,7 @@ def trainer_synapse(args, model, snapshot_path, group=None, log_every=1):
     for epoch_num in range(max_epoch):
         if sampler is not None:
             sampler.set_epoch(epoch_num)
-        for image_batch, label_batch in _Prefetcher(loader, device):
+        for image_batch, label_batch in _Prefetcher(loader, device, augment, (args.img_size, args.img_size)):
             stats = trainer.train_step(image_batch, label_batch)
             iter_num += 1
             if log_every and iter_num % log_every == 0 and rank == 0:

@@ -21,7 +21,7 @@ import logging
 import numpy as np
 import torch
 import torch.nn as nn
-from scipy.ndimage import binary_erosion, distance_transform_edt, generate_binary_structure, zoom
+from scipy.ndimage import binary_erosion, distance_transform_edt, generate_binary_structure, rotate, zoom
 
 from . import ops
 
@@ -204,6 +204,27 @@ def nearest_index(n_in, n_out):
     return idx
 
 
+@functools.lru_cache(maxsize=None)
+def rotation_index(H, W, angle):
+    """int32 [H, W] map m: the flat source index ``scipy.ndimage.rotate(x, angle, order=0, reshape=False)`` reads for every
+    output pixel of an (H, W) slice, -1 where scipy writes its constant 0.  It is read off scipy's rotation of the float64 image
+    arange(1, H * W + 1): order 0 copies values exactly, so that rotation of x is
+    ``np.where(m >= 0, x.ravel()[np.maximum(m, 0)], 0)`` for every dtype.  angle: an integer number of degrees (the augmentation
+    draws -20..19: at most 40 maps per shape, 1 MiB each at 512 x 512, filled as they are asked for).  ValueError for sizes
+    outside 1..2048 and if scipy's result is not an index map.  Cached: do not write to it."""
+    H, W = int(H), int(W)
+    if not (1 <= H <= 2048 and 1 <= W <= 2048):
+        raise ValueError(f"rotation_index: slice ({H}, {W}) outside 1..2048 per dimension")
+    if int(angle) != angle:
+        raise ValueError(f"rotation_index: angle {angle!r} is not an integer number of degrees")
+    src = rotate(np.arange(1, H * W + 1, dtype=np.float64).reshape(H, W), int(angle), order=0, reshape=False)
+    idx = src.astype(np.int32) - 1
+    if src.shape != (H, W) or np.any(idx + 1 != src) or idx.min() < -1 or idx.max() >= H * W:
+        raise ValueError(f"rotation_index: scipy's order-0 rotation of 1..{H * W} by {angle} degrees is not an index map")
+    idx.setflags(write=False)
+    return idx
+
+
 _device_tables = {}
 
 
@@ -221,6 +242,14 @@ def nearest_index_device(n_in, n_out, device):
     key = ("nearest", int(n_in), int(n_out), torch.device(device))
     if key not in _device_tables:
         _device_tables[key] = torch.from_numpy(nearest_index(n_in, n_out).copy()).to(device)
+    return _device_tables[key]
+
+
+def rotation_index_device(H, W, angle, device):
+    """rotation_index as a tensor on `device`, uploaded once per (H, W, angle, device)."""
+    key = ("rotation", int(H), int(W), int(angle), torch.device(device))
+    if key not in _device_tables:
+        _device_tables[key] = torch.from_numpy(rotation_index(H, W, angle).copy()).to(device)
     return _device_tables[key]
 
 

@@ -28,7 +28,7 @@ extern "C" {
 
 /* Bumped whenever a prototype or struct below changes (1: round 1; 2: round 2 -- stream / precision / storage arguments; 3: round 3 --
  * cswin_attn_fwd writes y0, cswin_attn_bwd reads it).  cswin_abi_version() returns the value the library was built with: a consumer
- * compiled against another header must refuse to call it.  Entry points that are only ADDED (cswin_seg_metrics*, cswin_resize_banded, cswin_argmax_zoom_back) do not bump
+ * compiled against another header must refuse to call it.  Entry points that are only ADDED (cswin_seg_metrics*, cswin_resize_banded, cswin_argmax_zoom_back, cswin_augment_*) do not bump
  * it: every prototype an older consumer binds is unchanged. */
 #define CSWIN_ABI_VERSION 4
 
@@ -331,6 +331,31 @@ int cswin_resize_banded(const void* x, float* y, const double* wh, const int* sh
  * output of 512 -> 224): out is 0 there.  Indices past the end are clamped on the device.  ncls in 1..255; each of B, h, w, H, W in 1..2048. */
 int cswin_argmax_zoom_back(const float* logits, unsigned char* out, const int* src_row, const int* src_col, int B, int ncls, int h,
                            int w, int H, int W, void* stream);
+
+/* ---- training augmentation of a batch of raw slices (datasets/dataset_synapse.py:12-47: np.rot90 + np.flip, or
+ *      scipy.ndimage.rotate(order=0, reshape=False), then the zooms to the network's size) ----
+ * One descriptor per sample, in a device table (24-byte records, 8-B aligned), as cswin_multi_copy takes its table.  The transform T
+ * of a sample maps a pixel (i, j) of the transformed slice to a source pixel of slice `src`, or to none:
+ *   kind 0: the identity.
+ *   kind 1: np.flip(np.rot90(x, k), axis), k in 0..3, axis in 0..1; for odd k the transformed slice is (W, H).
+ *   kind 2: map (H * W int32, device): the flat source index scipy.ndimage.rotate reads for every output pixel, negative where it
+ *           writes its constant 0 (cswin_unet_amd.utils.rotation_index).  A NULL map gives all zeros.
+ * src, the map's entries and every derived index are clamped into range on the device. */
+typedef struct cswin_augment_desc {
+    int kind, k, axis;
+    int src;                 /* index of the source slice in the batch */
+    const int* map;          /* kind 2 only */
+} cswin_augment_desc;
+/* x (B, H, W) float32 -> y (n, Ho, Wo) float32, y[s] = T_s(x[table[s].src]) with 0 where T_s has no source.  (Ho, Wo) is (H, W)
+ * or (W, H): the caller lists in one call the samples whose transformed shape that is.  Values are copied, never computed with.
+ * Each of n, B, H, W in 1..2048; no alignment beyond the element size, no workspace. */
+int cswin_augment_gather(const float* x, float* y, const void* table, int n, int B, int H, int W, int Ho, int Wo, void* stream);
+/* lab (B, H, W) uint8 -> out (n, h, w) int64: out[s][i][j] = lab[src_s][T_s(row[i], col[j])], the order-0 zoom of the transformed
+ * label without ever forming it.  (row, col) = (src_row (h), src_col (w)): scipy's source indices (utils.nearest_index) from the
+ * transformed shape (H, W); for a sample that kind 1 with odd k transposes, (src_row_t (h), src_col_t (w)): those from (W, H).
+ * out is 0 where a row or column index is negative or T_s has no source.  Each of n, B, H, W, h, w in 1..2048. */
+int cswin_augment_labels(const unsigned char* lab, long long* out, const void* table, const int* src_row, const int* src_col,
+                         const int* src_row_t, const int* src_col_t, int n, int B, int H, int W, int h, int w, void* stream);
 
 #ifdef __cplusplus
 }
