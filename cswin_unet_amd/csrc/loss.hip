@@ -8,6 +8,12 @@
 
 namespace {
 
+// class of a pixel, or -1 for a label outside [0, NC): the 64-bit value is compared, so 2^32 + 1 is no class 1
+template <int NC>
+__device__ __forceinline__ int label_class(long long label) {
+    return (unsigned long long)label < (unsigned long long)NC ? (int)label : -1;
+}
+
 // sums layout: [0] = sum over pixels of -log p[label];  [1 + c] = intersect_c;  [1 + ncls + c] = y_sum_c;  [1 + 2 ncls + c] = z_sum_c
 // PROBS: the input already holds class probabilities (DiceLoss(..., softmax=False), utils.py:32-34): no softmax here
 template <int NC, bool PROBS>
@@ -29,22 +35,26 @@ __global__ __launch_bounds__(256) void loss_sums_kernel(const float* __restrict_
             v[c] = lp[c * HW];
             mx = fmaxf(mx, v[c]);
         }
+        const int lab = label_class<NC>(labels[i]);
+        float vl = 0.f;                                                 // the label's input, before it becomes exp(v - mx)
         float sum = 0.f;
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
+            if (c == lab) vl = v[c];
             if (!PROBS) v[c] = __expf(v[c] - mx);
             sum += v[c];
         }
         const float inv = PROBS ? 1.0f : 1.0f / sum;
-        const int lab = (int)labels[i];
         // nn.CrossEntropyLoss raises on a target outside [0, ncls) (trainer.py:40,55); without a host sync the device-side
         // equivalent is to poison the CE sum: the step's loss reads NaN instead of a silently biased value
-        if ((unsigned)lab >= (unsigned)NC) acc[0] = __builtin_nanf("");
+        if (lab < 0) acc[0] = __builtin_nanf("");
+        // -log softmax(v)[label] = (mx - v[label]) + log sum_j exp(v_j - mx), as log_softmax forms it: exact however far the
+        // label's logit lies below the row maximum (-log of the normalised probability sticks once __expf underflows)
+        else acc[0] += PROBS ? -__logf(vl) : (mx - vl) + __logf(sum);
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             const float pc = v[c] * inv;
             const float oh = (c == lab) ? 1.f : 0.f;
-            acc[0] -= oh * __logf(fmaxf(pc, 1e-37f));
             acc[1 + c] += pc * oh;
             acc[1 + NC + c] += oh;
             acc[1 + 2 * NC + c] += pc * pc;
@@ -115,7 +125,7 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__
             sum += v[c];
         }
         const float inv = PROBS ? 1.0f : 1.0f / sum;
-        const int lab = (int)labels[i];
+        const int lab = label_class<NC>(labels[i]);
         float G[NC], dot = 0.f;
 #pragma unroll
         for (int c = 0; c < NC; ++c) {

@@ -260,7 +260,13 @@ size_t cswin_loss_workspace(int B, int ncls, long HW);
 /* inputs_are_probs != 0: `logits` already holds class probabilities (DiceLoss(..., softmax=False), utils.py:32-34): no softmax
  * is applied, the gradient is d/d(probabilities) and only the Dice term is meaningful (call with w_ce = 0).
  * class_weight: ncls device floats or NULL (= all 1): utils.py:44 `loss += dice * weight[i]`.
- * A label outside [0, ncls) makes sums[0] (hence the loss) NaN: the device-side counterpart of CrossEntropyLoss raising. */
+ * A label outside [0, ncls) -- judged on the whole int64 value, so 2^32 + 1 is outside -- makes sums[0] (hence the loss) NaN:
+ * the device-side counterpart of CrossEntropyLoss raising; to the Dice sums and to the gradient such a pixel has no class.
+ * sums[0] adds (max_j logit_j - logit_label) + log sum_j exp(logit_j - max) per pixel, nn.CrossEntropyLoss's log-softmax form:
+ * it does not saturate when the label's logit lies far below the row maximum (100 for logits [100, 0] and label 1).
+ * With inputs_are_probs the term is -log p[label] as given, again without a clamp: a label probability of exactly 0 makes sums[0]
+ * and out3[1] +inf (its true value); the loss is unaffected, because that mode is called with w_ce = 0 and finalize then leaves
+ * the CE term out. */
 int cswin_loss_sums(const float* logits, const long long* labels, float* sums, void* workspace, size_t ws_bytes, int B,
                     int ncls, long HW, int inputs_are_probs, void* stream);
 int cswin_loss_finalize(const float* sums, float* out3, float* coef, double n_pixels, int ncls, float w_ce,
