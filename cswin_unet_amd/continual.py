@@ -1,0 +1,113 @@
+"""Host side of the continual-learning workflow (the reference's universal_train.py): a trained model is extended to the organ
+classes of a new dataset without forgetting the old ones.  The objective itself is ops.continual_loss (csrc/cl_loss.hip); here
+are the four small pieces around it:
+
+    old = expand_classes(model, new_classes)            # widen `output`; BEFORE any HipEngine / FlatSGD is built on the model
+    teacher = freeze_teacher(model_before_expansion)    # the frozen old model whose logits are distilled
+    table = new_label_map(old, new_classes, device)     # new-dataset label k >= 1 -> old + k - 1
+    weights = extreme_class_weights(counts, active)     # the focal loss's class weights
+
+Nothing here launches a kernel."""
+import copy
+import math
+from dataclasses import dataclass
+from typing import Optional
+
+import torch
+from torch import nn
+
+__all__ = ["expand_classes", "new_label_map", "extreme_class_weights", "freeze_teacher", "Distill"]
+
+
+def _core(model):
+    return model.cswin_unet if hasattr(model, "cswin_unet") else model
+
+
+def expand_classes(model, new_classes):
+    """Widen the final 1x1 convolution `output` (no bias) from `old` to old + new_classes - 1 classes -- the new dataset's
+    background is the old one (universal_train.py:269) -- and return `old`.  The old rows are copied bit for bit, the new rows
+    drawn by kaiming_normal_ (:302-323); `num_classes` follows on the core and on the CSwinUnet wrapper.
+
+    The convolution is REPLACED: call this before a HipEngine, a DataParallelTrainer or a FlatSGD is built on the model (they
+    alias the parameters that exist then into flat buffers), and take freeze_teacher()'s copy before it."""
+    if new_classes < 1:
+        raise ValueError(f"expand_classes: new_classes={new_classes} (it counts the new dataset's background: >= 1)")
+    core = _core(model)
+    old_conv = core.output
+    if not isinstance(old_conv, nn.Conv2d) or old_conv.bias is not None:
+        raise TypeError("expand_classes: `output` must be the bias-free nn.Conv2d of CSWinTransformer")
+    old = old_conv.out_channels
+    total = old + new_classes - 1
+    w_old = old_conv.weight
+    new_conv = nn.Conv2d(old_conv.in_channels, total, kernel_size=old_conv.kernel_size, stride=old_conv.stride,
+                         padding=old_conv.padding, bias=False).to(device=w_old.device, dtype=w_old.dtype)
+    with torch.no_grad():
+        new_conv.weight[:old] = w_old
+        if total > old:
+            nn.init.kaiming_normal_(new_conv.weight[old:])
+    new_conv.weight.requires_grad_(w_old.requires_grad)
+    new_conv.train(old_conv.training)
+    core.output = new_conv
+    core.num_classes = total
+    if core is not model and hasattr(model, "num_classes"):
+        model.num_classes = total
+    return old
+
+
+def new_label_map(old_classes, new_classes, device=None):
+    """int32 table of map_new_dataset_labels (universal_train.py:243-258): 0 -> 0, k >= 1 -> old_classes + k - 1.  It has
+    new_classes entries; ops.continual_loss treats a label outside it as out of range."""
+    table = torch.arange(new_classes, dtype=torch.int32) + (old_classes - 1)
+    table[0] = 0
+    return table.to(device) if device is not None else table
+
+
+def extreme_class_weights(counts, active_classes):
+    """Class weights of universal_train.py:1019-1030 from per-class pixel counts: 1/sqrt(count + 1e-6) on the active classes that
+    occur (0 for a count of 0), normalised so that the active weights sum to the number of active classes, background capped at
+    0.5, 0 on every other class.  Returns a float32 CPU tensor of len(counts)."""
+    counts = torch.as_tensor(counts, dtype=torch.float64)
+    active = sorted(set(int(c) for c in active_classes))
+    w = torch.zeros(counts.numel(), dtype=torch.float64)
+    for c in active:
+        if counts[c] > 0:
+            w[c] = 1.0 / math.sqrt(float(counts[c]) + 1e-6)
+    s = float(w[active].sum()) if active else 0.0
+    if s > 0:
+        w[active] = w[active] / s * len(active)
+    w[0] = min(float(w[0]), 0.5)
+    return w.float()
+
+
+def freeze_teacher(model):
+    """A deep copy of `model` in eval() whose parameters take no gradient: the old model of the distillation term."""
+    # activations a forward pass left on the modules (the U-Net's boundary tensors) belong to an autograd graph and cannot be
+    # deep-copied: the copy gets None in their place.  The model itself is not touched, and every other attribute is copied.
+    memo = {}
+    for m in model.modules():
+        for v in vars(m).values():
+            for t in (v if isinstance(v, (list, tuple)) else (v,)):
+                if isinstance(t, torch.Tensor) and t.grad_fn is not None:
+                    memo[id(t)] = None
+    teacher = copy.deepcopy(model, memo)
+    teacher.eval()
+    teacher.requires_grad_(False)
+    return teacher
+
+
+@dataclass
+class Distill:
+    """The `distill` option of HipEngine / DataParallelTrainer: the frozen teacher and the parameters of ops.continual_loss."""
+    teacher: nn.Module
+    w_focal: float = 0.2
+    w_dice: float = 0.8
+    kd_weight: float = 0.5
+    temperature: float = 3.0
+    focal_gamma: float = 4.0
+    focal_alpha: float = 1.0
+    class_weight: Optional[torch.Tensor] = None
+    label_map: Optional[torch.Tensor] = None
+
+    @classmethod
+    def of(cls, spec):
+        return spec if isinstance(spec, cls) or spec is None else cls(**dict(spec))

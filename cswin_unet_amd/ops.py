@@ -15,7 +15,7 @@ from torch.autograd.function import once_differentiable
 from ._lib import AugmentDesc, ConvImageJob, CswinHipError, ReduceJob, WgradDesc, act_bf16, call, dev_f32, lib, precision, ptr, shadow_ptr, stream
 
 __all__ = ["layer_norm", "linear", "linear_pair", "mlp", "stripe_attention", "cswin_block", "conv_tokens", "patch_embed_conv", "carafe_reassemble",
-           "carafe_reassemble_nchw", "conv_weight_images", "head_compose", "tokens_to_nchw", "matmul_nn", "ce_dice_loss", "dropout", "img2windows", "windows2img",
+           "carafe_reassemble_nchw", "conv_weight_images", "head_compose", "tokens_to_nchw", "matmul_nn", "ce_dice_loss", "continual_loss", "dropout", "img2windows", "windows2img",
            "seg_metrics", "resize_slices", "argmax_zoom_back", "augment_batch"]
 
 
@@ -1086,6 +1086,101 @@ def ce_dice_loss(logits, labels, w_ce=0.4, w_dice=0.6, group=None, inputs_are_pr
     if inputs_are_probs and w_ce != 0.0:
         raise ValueError("ce_dice_loss: cross entropy needs logits; with inputs_are_probs pass w_ce=0")
     return _CeDiceLoss.apply(logits, labels, float(w_ce), float(w_dice), group, bool(inputs_are_probs), class_weight)
+
+
+# ------------------------------------------------------------------------------------------------
+# continual-learning objective: focal CE + Dice + distillation towards a frozen teacher (universal_train.py:904-932)
+# ------------------------------------------------------------------------------------------------
+def _int32_map(label_map):
+    if label_map is not None and (label_map.dtype != torch.int32 or not label_map.is_cuda or not label_map.is_contiguous()):
+        raise CswinHipError(f"label_map must be a contiguous int32 tensor on the HIP device (continual.new_label_map), got {label_map.dtype} on {label_map.device}")
+    return label_map
+
+
+def cl_loss_sums(logits, labels, teacher, sums, temperature, focal_alpha, focal_gamma, class_weight=None, label_map=None):
+    """sums[3 + 3*ncls] = loss_sums' 1 + 3*ncls sums, then the focal sum and the distillation sum over teacher.shape[1] channels."""
+    B, ncls = logits.shape[:2]
+    HW = logits.numel() // (B * ncls)
+    nbytes = lib().cswin_cl_loss_workspace(B, ncls, HW)
+    ws = _ws(nbytes, logits.device)
+    call("cswin_cl_loss_sums", ptr(logits), ptr(labels), ptr(label_map), 0 if label_map is None else label_map.numel(), ptr(teacher),
+         ptr(class_weight), ptr(sums), ptr(ws), nbytes, B, ncls, 0 if teacher is None else teacher.shape[1], HW, temperature, focal_alpha,
+         focal_gamma, stream())
+
+
+def cl_loss_finalize(sums, out, coef, n_pixels, batch, w_focal, w_dice, kd_weight, temperature):
+    """sums -> out = [loss, focal, dice, kd, ce] and coef[2*ncls]; n_pixels and batch (images) are what the sums cover."""
+    call("cswin_cl_loss_finalize", ptr(sums), ptr(out), ptr(coef), float(n_pixels), float(batch), coef.numel() // 2, w_focal, w_dice, kd_weight,
+         temperature, stream())
+
+
+def cl_loss_grad(logits, labels, teacher, coef, focal_scale, dice_scale, kd_scale, temperature, focal_alpha, focal_gamma, class_weight=None,
+                 label_map=None, gloss=None):
+    """d loss / d logits, times the device scalar gloss if given."""
+    B, ncls = logits.shape[:2]
+    dlogits = torch.empty_like(logits)
+    call("cswin_cl_loss_bwd", ptr(logits), ptr(labels), ptr(label_map), 0 if label_map is None else label_map.numel(), ptr(teacher),
+         ptr(class_weight), ptr(coef), ptr(gloss), ptr(dlogits), focal_scale, dice_scale, kd_scale, B, ncls,
+         0 if teacher is None else teacher.shape[1], logits.numel() // (B * ncls), temperature, focal_alpha, focal_gamma, stream())
+    return dlogits
+
+
+class _ContinualLoss(Function):
+    @staticmethod
+    def forward(ctx, logits, labels, teacher, w_focal, w_dice, kd_weight, temperature, gamma, alpha, class_weight, label_map, group):
+        logits, teacher, class_weight = dev_f32(logits, "logits"), dev_f32(teacher.detach(), "teacher_logits"), dev_f32(class_weight)
+        label_map = _int32_map(label_map)
+        labels = labels.contiguous()
+        if labels.dtype != torch.int64:
+            labels = labels.long()
+        B, ncls = logits.shape[:2]
+        HW = logits.numel() // (B * ncls)
+        if teacher.shape[0] != B or teacher.numel() != B * teacher.shape[1] * HW:
+            raise ValueError(f"continual_loss: teacher logits {tuple(teacher.shape)} do not match logits {tuple(logits.shape)}")
+        # the kernels index these by pixel and by class: a mismatch would be an out-of-bounds device read
+        if not labels.is_cuda or labels.numel() != B * HW:
+            raise ValueError(f"continual_loss: labels {tuple(labels.shape)} on {labels.device} do not match logits {tuple(logits.shape)} on {logits.device}")
+        if class_weight is not None and class_weight.numel() != ncls:
+            raise ValueError(f"continual_loss: class_weight has {class_weight.numel()} entries for {ncls} classes")
+        dev = logits.device
+        sums = torch.empty(3 + 3 * ncls, dtype=torch.float32, device=dev)
+        cl_loss_sums(logits, labels, teacher, sums, temperature, alpha, gamma, class_weight, label_map)
+        world = 1
+        if group is not None:
+            import torch.distributed as dist
+            world = dist.get_world_size(group)
+            if world > 1:
+                dist.all_reduce(sums, group=group)      # 3 + 3*ncls floats: global-batch Dice, focal mean and batchmean KD
+        out = torch.empty(5, dtype=torch.float32, device=dev)
+        coef = torch.empty(2 * ncls, dtype=torch.float32, device=dev)
+        cl_loss_finalize(sums, out, coef, B * HW * world, B * world, w_focal, w_dice, kd_weight, temperature)
+        ctx.save_for_backward(logits, labels, teacher, coef, class_weight, label_map)
+        # gradients are averaged over ranks afterwards: local means for focal and KD, global Dice -> * world
+        ctx.meta = ((1.0 - kd_weight) * w_focal / float(B * HW), (1.0 - kd_weight) * w_dice / ncls * world, kd_weight * temperature / B,
+                    temperature, alpha, gamma)
+        loss = out[0].clone()
+        ctx.mark_non_differentiable(out)
+        return loss, out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gloss, _gout):
+        logits, labels, teacher, coef, class_weight, label_map = ctx.saved_tensors
+        focal_scale, dice_scale, kd_scale, temperature, alpha, gamma = ctx.meta
+        dlogits = cl_loss_grad(logits, labels, teacher, coef, focal_scale, dice_scale, kd_scale, temperature, alpha, gamma, class_weight,
+                               label_map, dev_f32(gloss.reshape(1)))
+        return (dlogits,) + (None,) * 11
+
+
+def continual_loss(logits, labels, teacher_logits, *, w_focal=0.2, w_dice=0.8, kd_weight=0.5, temperature=3.0, focal_gamma=4.0,
+                   focal_alpha=1.0, class_weight=None, label_map=None, group=None):
+    """(1 - kd_weight) * (w_focal * Focal + w_dice * Dice) + kd_weight * KD (universal_train.py:904-932) in one fused pass each way.
+    Returns (loss, stats) with stats = [loss, focal, dice, kd, ce] (no host sync).  logits (B, ncls, ...), teacher_logits
+    (B, old_classes, ...) of the frozen old model on the same images (no gradient), labels int64; label_map: int32 device table
+    applied to the labels first (continual.new_label_map); class_weight: (ncls,) device tensor, the focal loss's `weight`.
+    With a process group the 3 + 3*ncls sums are all-reduced: Dice, the focal mean and the per-image KD are the global batch's."""
+    return _ContinualLoss.apply(logits, labels, teacher_logits, float(w_focal), float(w_dice), float(kd_weight), float(temperature),
+                                float(focal_gamma), float(focal_alpha), class_weight, label_map, group)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -27,7 +27,8 @@ import torch
 import torch.distributed as dist
 
 from ._lib import call, ptr, stream
-from .ops import augment_batch, engine_backward, loss_finalize, loss_grad, loss_sums
+from .continual import Distill
+from .ops import augment_batch, cl_loss_finalize, cl_loss_grad, cl_loss_sums, engine_backward, loss_finalize, loss_grad, loss_sums
 from .optim import FlatSGD
 
 
@@ -74,10 +75,15 @@ class HipEngine:
 
     Backward runs in two phases -- decoder half, then encoder half (the U-Net's boundary tensors are the bottleneck and
     the three skips) -- each ending with the multi-tensor packing of its gradients, so that the data-parallel protocol
-    can put the decoder bucket on the wire (RCCL, own stream) while the encoder half is still computing."""
+    can put the decoder bucket on the wire (RCCL, own stream) while the encoder half is still computing.
 
-    def __init__(self, model, num_classes, lr, momentum, weight_decay, w_ce, w_dice, use_graph=True):
+    distill (continual.Distill, or a dict of its fields): the objective becomes the continual-learning one of ops.continual_loss --
+    the frozen teacher runs on the same image inside the forward part of the step, `sums` has 3 + 3*ncls entries and `stats` is
+    [loss, focal, dice, kd, ce]; w_ce / w_dice are not used then.  The teacher is no part of the optimiser's flat buffers."""
+
+    def __init__(self, model, num_classes, lr, momentum, weight_decay, w_ce, w_dice, use_graph=True, distill=None):
         self.model, self.ncls, self.w_ce, self.w_dice = model, num_classes, w_ce, w_dice
+        self.distill = Distill.of(distill)
         self.core = model.cswin_unet if hasattr(model, "cswin_unet") else model
         names = [n for n, p in model.named_parameters() if p.requires_grad]
         self.opt = FlatSGD(model.parameters(), lr=lr, momentum=momentum, weight_decay=weight_decay)
@@ -88,8 +94,9 @@ class HipEngine:
         # second cut inside the encoder, in front of merge2: parameters [n_mid, n_enc) = merge2, stage3, merge3, stage4, norm
         self.n_mid = next(i for i, n in enumerate(names) if "merge2" in n.split(".")[:2]) if self.split_backward else 0
         dev = self.opt.flat_param.device
-        self.sums = torch.zeros(1 + 3 * num_classes, dtype=torch.float32, device=dev)
-        self.stats = torch.zeros(3, dtype=torch.float32, device=dev)          # [loss, ce, dice] of the last step
+        self.sums = torch.zeros((3 if self.distill else 1) + 3 * num_classes, dtype=torch.float32, device=dev)
+        self.stats = torch.zeros(5 if self.distill else 3, dtype=torch.float32, device=dev)   # [loss, ce, dice] of the last step; distill: [loss, focal, dice, kd, ce]
+        self._teacher_logits, self._batch_pixels = None, None
         self._coef = torch.zeros(2 * num_classes, dtype=torch.float32, device=dev)
         # nn.Dropout with p > 0 (no reference config has one): the dropout kernels take their seeds from the HOST generator when the op
         # is called -- once, at capture, for a replayed graph -- and add the device-resident epoch counter (ops.dropout_epoch) to
@@ -116,11 +123,24 @@ class HipEngine:
             from .ops import advance_dropout_epoch
             advance_dropout_epoch(img.device)           # inside graph A when captured: a new mask set per replayed step
         logits = self.model(img)
-        loss_sums(logits.detach(), lab, self.sums)
+        d = self.distill
+        if d is None:
+            loss_sums(logits.detach(), lab, self.sums)
+            return logits
+        with torch.no_grad():                           # inside graph A when captured; the buffer is kept for the backward graph
+            self._teacher_logits = d.teacher(img).contiguous()
+        self._batch_pixels = lab.numel() // lab.shape[0]
+        cl_loss_sums(logits.detach(), lab, self._teacher_logits, self.sums, d.temperature, d.focal_alpha, d.focal_gamma, d.class_weight, d.label_map)
         return logits
 
     def _loss_grad(self, logits, lab, dice_grad_scale):
         ncls = logits.shape[1]
+        d = self.distill
+        if d is not None:
+            keep = 1.0 - d.kd_weight
+            return cl_loss_grad(logits.detach(), lab, self._teacher_logits, self._coef, keep * d.w_focal / float(logits.numel() // ncls),
+                                keep * d.w_dice / ncls * dice_grad_scale, d.kd_weight * d.temperature / logits.shape[0], d.temperature,
+                                d.focal_alpha, d.focal_gamma, d.class_weight, d.label_map)
         return loss_grad(logits.detach(), lab, self._coef, self.w_ce / float(logits.numel() // ncls), self.w_dice / ncls * dice_grad_scale)
 
     def _backward(self, outputs, grad_outputs, lo, hi, extra_inputs=()):
@@ -234,6 +254,12 @@ class HipEngine:
 
     def finalize(self, n_pixels_global):
         """sums (already all-reduced) -> stats [loss, ce, dice] and the Dice gradient coefficients."""
+        d = self.distill
+        if d is not None:
+            # 'batchmean' divides by images: the global image count follows from the pixels per image forward_sums saw
+            cl_loss_finalize(self.sums, self.stats, self._coef, n_pixels_global, n_pixels_global // self._batch_pixels, d.w_focal, d.w_dice,
+                             d.kd_weight, d.temperature)
+            return
         loss_finalize(self.sums, self.stats, self._coef, n_pixels_global, self.w_ce, self.w_dice)
 
     def backward_phases(self, dice_grad_scale):
@@ -275,12 +301,12 @@ class DataParallelTrainer:
 
     def __init__(self, model=None, num_classes=9, base_lr=0.05, max_iterations=1000, momentum=0.9, weight_decay=1e-4,
                  group=None, use_graph=True, buckets=2, w_ce=0.4, w_dice=0.6, engine=None, force_collectives=False,
-                 allreduce_dtype=None):
+                 allreduce_dtype=None, distill=None):
         self.group = group
         self.world = dist.get_world_size(group) if group is not None else 1
         self.base_lr, self.max_iterations, self.iter_num = base_lr, max_iterations, 0
         self.engine = engine if engine is not None else HipEngine(model, num_classes, base_lr, momentum, weight_decay,
-                                                                 w_ce, w_dice, use_graph)
+                                                                 w_ce, w_dice, use_graph, distill)
         self.model = model
         self.nbuckets = max(1, buckets)
         # torch.bfloat16: gradients travel as bf16 (47 MB instead of 94 MB per step, BASELINE configs[2]); the sum is formed

@@ -275,6 +275,35 @@ int cswin_loss_bwd(const float* logits, const long long* labels, const float* co
                    float* dlogits, float ce_scale, float dice_scale, int B, int ncls, long HW, int inputs_are_probs,
                    void* stream);
 
+/* ---- objective of the continual-learning workflow (universal_train.py:904-932): focal CE (:141-174) + soft Dice on the widened
+ *      logits, temperature-T distillation (:618-623) of their first `nold` channels towards a frozen teacher ----
+ * logits (B, ncls, HW) fp32, labels (B, HW) int64, teacher (B, nold, HW) fp32 (NULL only with nold == 0: no KD term),
+ * label_map: n_map device int32 or NULL; a label l becomes label_map[l] for 0 <= l < n_map and no class otherwise (:243-258),
+ * class_weight: ncls device floats or NULL (= all 1), the `weight` of F.cross_entropy inside the focal term.
+ * sums[3 + 3*ncls]: the first 1 + 3*ncls are cswin_loss_sums' {sum -log p[label], intersect_c, y_sum_c, z_sum_c};
+ * [1 + 3*ncls] = sum of alpha * (1 - pt)^gamma * ce with ce = w[label] * -log p[label], pt = exp(-ce);
+ * [2 + 3*ncls] = sum over pixels of sum_{c < nold} q_c (log q_c - log pT_c), q / pT = softmax of the teacher's / the student's first
+ * nold logits over T.  All are plain sums over the local pixels: all-reduce them across data-parallel ranks.
+ * A label that is no class after the map makes sums[0] and the focal sum NaN (cswin_loss_sums' convention; the reference's focal
+ * loss clamps it), has no class in the Dice sums and no focal gradient.  ncls 2..16, 0 <= nold <= ncls, temperature > 0 and
+ * focal_gamma 0 or >= 1, otherwise CSWIN_ERR_UNSUPPORTED / CSWIN_ERR_SHAPE before any launch. */
+size_t cswin_cl_loss_workspace(int B, int ncls, long HW);
+int cswin_cl_loss_sums(const float* logits, const long long* labels, const int* label_map, int n_map, const float* teacher,
+                       const float* class_weight, float* sums, void* workspace, size_t ws_bytes, int B, int ncls, int nold,
+                       long HW, float temperature, float focal_alpha, float focal_gamma, void* stream);
+/* out5 = {loss, focal, dice, kd, ce}: focal = S_focal / n_pixels, ce = S_0 / n_pixels, dice and coef[2*ncls] as cswin_loss_finalize
+ * forms them without class weights, kd = S_kd * T^2 / batch (F.kl_div's 'batchmean': per IMAGE the sums cover, not per pixel),
+ * loss = (1 - kd_weight) * (w_focal * focal + w_dice * dice) + kd_weight * kd; a term whose weight is 0 is left out, NaN or not. */
+int cswin_cl_loss_finalize(const float* sums, float* out5, float* coef, double n_pixels, double batch, int ncls, float w_focal,
+                           float w_dice, float kd_weight, float temperature, void* stream);
+/* dlogits = grad_out (NULL = 1) * [focal_scale * d focal-sum + dice_scale * d sum_c dice_c + kd_scale * (pT - q) on the first nold
+ * channels]; focal_scale = (1 - kd_weight) * w_focal / n_pixels, dice_scale = (1 - kd_weight) * w_dice / ncls (times the world
+ * size under gradient averaging), kd_scale = kd_weight * T / B.  Every channel of dlogits is written once. */
+int cswin_cl_loss_bwd(const float* logits, const long long* labels, const int* label_map, int n_map, const float* teacher,
+                      const float* class_weight, const float* coef, const float* grad_out, float* dlogits, float focal_scale,
+                      float dice_scale, float kd_scale, int B, int ncls, int nold, long HW, float temperature, float focal_alpha,
+                      float focal_gamma, void* stream);
+
 /* ---- optimiser: torch.optim.SGD(momentum, weight_decay) (trainer.py:42,60) on one flat buffer ---- */
 int cswin_sgd_flat(float* p, const float* g, float* m, long n, const float* lr_dev, float momentum,
                    float weight_decay, float grad_scale, void* shadow_bf16, void* stream);
