@@ -67,6 +67,9 @@ SIGNATURES = {
     "cswin_dropout": (I, [P, P, P, P, L, L, F, ctypes.c_ulonglong, P, P]),
     "cswin_sgd_flat": (I, [P, P, P, L, P, F, F, F, P, P]),
     "cswin_multi_copy": (I, [P, I, P]),
+    "cswin_chunk_sumsq": (I, [P, P, P, I, P, P]),
+    "cswin_norm_finalize": (I, [P, P, I, F, F, P, P, P]),
+    "cswin_adamw_flat": (I, [P, P, P, P, P, I, P, P, P, D, D, D, F, F, D, D, P, P]),
     "cswin_pack_bf16": (I, [P, P, L, P]),
     "cswin_pack_bf16_scaled": (I, [P, P, L, F, P]),
     "cswin_unpack_bf16": (I, [P, P, L, P]),

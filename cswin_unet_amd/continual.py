@@ -7,7 +7,12 @@ are the four small pieces around it:
     table = new_label_map(old, new_classes, device)     # new-dataset label k >= 1 -> old + k - 1
     weights = extreme_class_weights(counts, active)     # the focal loss's class weights
 
-Nothing here launches a kernel."""
+and the "surgical" mode's learning rate per parameter tensor (universal_train.py:626-690, 871-896):
+
+    w = surgical_lr_weights(model, engine.opt, batches, distill)    # relative gradient norms of a few batches, largest = 1
+    engine.set_lr_weights(w)                                        # FlatAdamW's per-tensor multipliers; unnamed tensors get 0
+
+Only surgical_lr_weights runs the model; nothing else here launches a kernel."""
 import copy
 import math
 from dataclasses import dataclass
@@ -16,7 +21,7 @@ from typing import Optional
 import torch
 from torch import nn
 
-__all__ = ["expand_classes", "new_label_map", "extreme_class_weights", "freeze_teacher", "Distill"]
+__all__ = ["expand_classes", "new_label_map", "extreme_class_weights", "freeze_teacher", "Distill", "rgn_weights", "surgical_lr_weights"]
 
 
 def _core(model):
@@ -111,3 +116,55 @@ class Distill:
     @classmethod
     def of(cls, spec):
         return spec if isinstance(spec, cls) or spec is None else cls(**dict(spec))
+
+
+def rgn_weights(names, norms_per_batch):
+    """The RGN learning-rate weights of universal_train.py:626-690 and :876-881 from per-tensor norms.  names: the parameter names,
+    aligned with the rows of every entry of norms_per_batch, each a (T, 2) array of (||g||, ||p||).  Names containing "bn" or
+    "norm" (any case) are dropped; per batch a tensor's ratio is ||g|| / ||p|| when ||p|| > 1e-8, else 0; the ratios are averaged
+    over the batches and divided by their maximum (a maximum <= 0 gives all zeros).  Returns {name: weight}."""
+    names = list(names)
+    keep = [i for i, n in enumerate(names) if "bn" not in n.lower() and "norm" not in n.lower()]
+    ratios = []
+    for norms in norms_per_batch:
+        norms = [[float(a), float(b)] for a, b in norms]
+        if len(norms) != len(names):
+            raise ValueError(f"rgn_weights: {len(norms)} rows of norms for {len(names)} names")
+        ratios.append([norms[i][0] / norms[i][1] if norms[i][1] > 1e-8 else 0.0 for i in keep])
+    if not ratios:
+        return {}
+    mean = [sum(r[k] for r in ratios) / len(ratios) for k in range(len(keep))]
+    top = max(mean) if mean else 0.0
+    return {names[i]: (mean[k] / top if top > 0 else 0.0) for k, i in enumerate(keep)}
+
+
+def surgical_lr_weights(model, opt, batches, distill):
+    """rgn_weights of the focal criterion's gradients on `batches` (an iterable of (image, label) device tensors), measured by the
+    flat optimiser `opt` (optim.FlatAdamW built on `model`): per batch one forward in eval() mode, ops.continual_loss with the
+    focal term alone (w_focal = 1, w_dice = 0, kd_weight = 0 and the distill's gamma, alpha, class weights and label map; the
+    teacher's logits are passed, their term has weight 0), backward, opt.gather_grads() and opt.tensor_norms().  The norms stay
+    on the device until one host read at the end; the model's training mode is restored and every .grad is None afterwards."""
+    from . import ops
+    d = Distill.of(distill)
+    names = dict((p.data_ptr(), n) for n, p in model.named_parameters())
+    names = [names[p.data_ptr()] for p in opt.params]
+    was_training = model.training
+    model.eval()
+    norms = []
+    try:
+        for img, lab in batches:
+            logits = model(img)
+            with torch.no_grad():
+                teacher_logits = d.teacher(img).contiguous()
+            loss, _ = ops.continual_loss(logits, lab, teacher_logits, w_focal=1.0, w_dice=0.0, kd_weight=0.0, temperature=d.temperature,
+                                         focal_gamma=d.focal_gamma, focal_alpha=d.focal_alpha, class_weight=d.class_weight,
+                                         label_map=d.label_map)
+            opt.zero_grad()
+            loss.backward()
+            opt.gather_grads()
+            norms.append(opt.tensor_norms())
+            opt.zero_grad()
+    finally:
+        model.train(was_training)
+    host = torch.stack(norms).cpu().tolist() if norms else []          # the one host read
+    return rgn_weights(names, host)

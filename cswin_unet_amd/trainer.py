@@ -21,6 +21,7 @@ The protocol (which collectives, which scalings) lives in ``DataParallelTrainer`
 lives in an *engine*.  ``HipEngine`` is the product (C ABI kernels, hipGraphs).  tests/test_dp_gloo.py drives the same
 protocol with a CPU engine over gloo to check 2-rank == 1-rank-global-batch semantics without a GPU.
 """
+import math
 import os
 
 import torch
@@ -29,7 +30,7 @@ import torch.distributed as dist
 from ._lib import call, ptr, stream
 from .continual import Distill
 from .ops import augment_batch, cl_loss_finalize, cl_loss_grad, cl_loss_sums, engine_backward, loss_finalize, loss_grad, loss_sums
-from .optim import FlatSGD
+from .optim import FlatAdamW, FlatSGD
 
 
 def init_distributed():
@@ -62,6 +63,12 @@ def poly_lr(base_lr, iter_num, max_iterations):
     return base_lr * (1.0 - iter_num / max_iterations) ** 0.9
 
 
+def cosine_lr(base_lr, epoch, t_max):
+    """torch.optim.lr_scheduler.CosineAnnealingLR(T_max=t_max, eta_min=0) in closed form (universal_train.py:894): the rate of
+    epoch `epoch`, for a loop that runs lr_schedule="constant" and sets the rate once per epoch."""
+    return base_lr * (1.0 + math.cos(math.pi * epoch / t_max)) / 2.0
+
+
 def scale_lr_for_batch(base_lr, batch_size):
     """train.py:104-105: base_lr *= batch_size / 24 only when batch_size != 24 and batch_size % 6 == 0 (per-GPU batch)."""
     return base_lr * batch_size / 24 if (batch_size != 24 and batch_size % 6 == 0) else base_lr
@@ -79,14 +86,27 @@ class HipEngine:
 
     distill (continual.Distill, or a dict of its fields): the objective becomes the continual-learning one of ops.continual_loss --
     the frozen teacher runs on the same image inside the forward part of the step, `sums` has 3 + 3*ncls entries and `stats` is
-    [loss, focal, dice, kd, ce]; w_ce / w_dice are not used then.  The teacher is no part of the optimiser's flat buffers."""
+    [loss, focal, dice, kd, ce]; w_ce / w_dice are not used then.  The teacher is no part of the optimiser's flat buffers.
 
-    def __init__(self, model, num_classes, lr, momentum, weight_decay, w_ce, w_dice, use_graph=True, distill=None):
+    optimizer: "sgd" (FlatSGD, the reference's trainer.py) or "adamw" (FlatAdamW, its universal_train.py: `momentum` is ignored,
+    `weight_decay` is AdamW's decoupled decay, max_grad_norm clips the global gradient norm first).  Under data parallelism the
+    update runs after the all-reduce, so the norm is the averaged gradient's and every rank forms the same coefficient."""
+
+    def __init__(self, model, num_classes, lr, momentum, weight_decay, w_ce, w_dice, use_graph=True, distill=None, optimizer="sgd",
+                 max_grad_norm=None, betas=(0.9, 0.999), eps=1e-8):
+        if optimizer not in ("sgd", "adamw"):
+            raise ValueError(f'HipEngine: optimizer must be "sgd" or "adamw", got {optimizer!r}')
+        if optimizer == "sgd" and max_grad_norm is not None:
+            raise ValueError('HipEngine: max_grad_norm needs optimizer="adamw" (FlatSGD does not clip)')
         self.model, self.ncls, self.w_ce, self.w_dice = model, num_classes, w_ce, w_dice
         self.distill = Distill.of(distill)
         self.core = model.cswin_unet if hasattr(model, "cswin_unet") else model
         names = [n for n, p in model.named_parameters() if p.requires_grad]
-        self.opt = FlatSGD(model.parameters(), lr=lr, momentum=momentum, weight_decay=weight_decay)
+        self.param_names = names                        # aligned with self.opt.params
+        if optimizer == "adamw":
+            self.opt = FlatAdamW(model.parameters(), lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+        else:
+            self.opt = FlatSGD(model.parameters(), lr=lr, momentum=momentum, weight_decay=weight_decay)
         is_dec = [any(seg.startswith(DECODER_PREFIXES) for seg in n.split(".")[:2]) for n in names]
         self.n_enc = is_dec.index(True) if True in is_dec else len(names)
         self.split_backward = 0 < self.n_enc < len(names) and all(is_dec[self.n_enc:]) and hasattr(self.core, "forward_features")
@@ -116,6 +136,19 @@ class HipEngine:
 
     def set_lr(self, lr):
         self.opt.set_lr(lr)
+
+    def set_lr_weights(self, weights, default=0.0):
+        """Per-tensor learning-rate multipliers by parameter name (continual.surgical_lr_weights' result); a tensor that is not
+        named gets `default` -- 0, as the reference's create_surgical_optimizer has it.  None: all 1.  optimizer="adamw" only."""
+        if not hasattr(self.opt, "set_lr_weights"):
+            raise ValueError('HipEngine.set_lr_weights needs optimizer="adamw"')
+        if weights is None:
+            self.opt.set_lr_weights(None)
+            return
+        unknown = set(weights) - set(self.param_names)
+        if unknown:
+            raise KeyError(f"HipEngine.set_lr_weights: no trainable parameter named {sorted(unknown)[:4]}")
+        self.opt.set_lr_weights([float(weights.get(n, default)) for n in self.param_names])
 
     # ---- eager pieces -------------------------------------------------------------------------------------------
     def _forward_sums(self, img, lab):
@@ -301,12 +334,15 @@ class DataParallelTrainer:
 
     def __init__(self, model=None, num_classes=9, base_lr=0.05, max_iterations=1000, momentum=0.9, weight_decay=1e-4,
                  group=None, use_graph=True, buckets=2, w_ce=0.4, w_dice=0.6, engine=None, force_collectives=False,
-                 allreduce_dtype=None, distill=None):
+                 allreduce_dtype=None, distill=None, optimizer="sgd", max_grad_norm=None, lr_schedule="poly"):
+        if lr_schedule not in ("poly", "constant"):
+            raise ValueError(f'DataParallelTrainer: lr_schedule must be "poly" or "constant", got {lr_schedule!r}')
+        self.lr_schedule = lr_schedule                  # "constant": the step leaves the rate alone (an outer loop sets it, cosine_lr)
         self.group = group
         self.world = dist.get_world_size(group) if group is not None else 1
         self.base_lr, self.max_iterations, self.iter_num = base_lr, max_iterations, 0
         self.engine = engine if engine is not None else HipEngine(model, num_classes, base_lr, momentum, weight_decay,
-                                                                 w_ce, w_dice, use_graph, distill)
+                                                                 w_ce, w_dice, use_graph, distill, optimizer, max_grad_norm)
         self.model = model
         self.nbuckets = max(1, buckets)
         # torch.bfloat16: gradients travel as bf16 (47 MB instead of 94 MB per step, BASELINE configs[2]); the sum is formed
@@ -406,7 +442,8 @@ class DataParallelTrainer:
         if tm is not None:
             tm["ev"][-1].append(self._mark())
         self.iter_num += 1
-        eng.set_lr(poly_lr(self.base_lr, self.iter_num - 1, self.max_iterations))   # trainer.py:61-63
+        if self.lr_schedule == "poly":
+            eng.set_lr(poly_lr(self.base_lr, self.iter_num - 1, self.max_iterations))   # trainer.py:61-63
         return eng.stats
 
     def state_dict(self):

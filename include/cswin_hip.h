@@ -28,8 +28,8 @@ extern "C" {
 
 /* Bumped whenever a prototype or struct below changes (1: round 1; 2: round 2 -- stream / precision / storage arguments; 3: round 3 --
  * cswin_attn_fwd writes y0, cswin_attn_bwd reads it).  cswin_abi_version() returns the value the library was built with: a consumer
- * compiled against another header must refuse to call it.  Entry points that are only ADDED (cswin_seg_metrics*, cswin_resize_banded, cswin_argmax_zoom_back, cswin_augment_*) do not bump
- * it: every prototype an older consumer binds is unchanged. */
+ * compiled against another header must refuse to call it.  Entry points that are only ADDED (cswin_seg_metrics*, cswin_resize_banded, cswin_argmax_zoom_back, cswin_augment_*,
+ * cswin_chunk_sumsq, cswin_norm_finalize, cswin_adamw_flat) do not bump it: every prototype an older consumer binds is unchanged. */
 #define CSWIN_ABI_VERSION 4
 
 #define CSWIN_OK 0
@@ -311,6 +311,33 @@ int cswin_sgd_flat(float* p, const float* g, float* m, long n, const float* lr_d
  * the fp32 master weights, read by the Linears' io_bf16 bit 2). */
 /* table: device array of {const float* src; float* dst; long long n;} (24-byte records), one workgroup each */
 int cswin_multi_copy(const void* table, int nchunks, void* stream);
+
+/* ---- optimiser: clip_grad_norm_(parameters, max_norm) + torch.optim.AdamW (universal_train.py:693-725, 934-939), with a learning
+ * rate per parameter tensor (the "surgical" mode, :635-690, 871-896), on the flat buffers ----
+ * chunks: device table of nchunks 16-byte records {long long off; int n; int tensor;}, 8-B aligned, one 256-thread workgroup each:
+ * elements [off, off + n) of the flat buffers belong to tensor `tensor`, n <= 16384, off % 4 == 0, no chunk crosses a tensor or
+ * covers a pad word, chunks of one tensor are consecutive; first_chunk[ntensors + 1] indexes them per tensor.  The table is the
+ * caller's (optim.chunk_table builds it): the library cannot read it, so its bounds are the caller's responsibility.
+ * No float atomics: every sum has a fixed order and two runs on the same input give the same bits.
+ *
+ * partial[c] = (sum g^2, sum p^2) over chunk c (2 * nchunks floats); p == NULL: the second entries are not written. */
+int cswin_chunk_sumsq(const float* g, const float* p, const void* chunks, int nchunks, float* partial, void* stream);
+/* One workgroup: tensor_sumsq[t] = (sum g^2, sum p^2) of tensor t, its chunk partials added in chunk order (the second column is
+ * whatever partial's holds); scalars = [total_norm, clip_coef] with total_norm = grad_scale * sqrt(sum_t sum g^2), the tensors
+ * added in tensor order, and clip_coef = min(1, max_norm / (total_norm + 1e-6)), clip_grad_norm_'s rule.  Any ntensors >= 1. */
+int cswin_norm_finalize(const float* partial, const int* first_chunk, int ntensors, float grad_scale, float max_norm,
+                        float* tensor_sumsq, float* scalars, void* stream);
+/* Per element of tensor t, in torch.optim.AdamW's order:
+ *   g' = g * grad_scale * clip_coef (scalars[1]; 1 when scalars == NULL);  m = b1 m + (1 - b1) g';  v = b2 v + (1 - b2) g'^2;
+ *   lr_t = lr_dev[0] * (lr_mult ? lr_mult[t] : 1);  p = p (1 - lr_t wd) - (lr_t / bc1) m / (sqrt(v) / sqrt(bc2) + eps);
+ *   shadow = bf16_rne(p) when given (as cswin_sgd_flat's).
+ * bc1 = 1 - beta1^t, bc2 = 1 - beta2^t come from the host (the step count never enters the device).  A tensor with lr_mult[t] == 0
+ * exactly keeps p and its shadow bit for bit (the stores are skipped); its m and v move, as torch's do in an lr = 0 group.
+ * Non-finite gradients are reported, not repaired: one +inf makes the norm inf and clip_coef 0, that element's g' NaN and every
+ * other g' 0, as in torch.  p, g, m, v 16-B aligned, the shadow 8-B. */
+int cswin_adamw_flat(float* p, const float* g, float* m, float* v, const void* chunks, int nchunks, const float* lr_dev,
+                     const float* lr_mult, const float* scalars, double beta1, double beta2, double eps, float weight_decay,
+                     float grad_scale, double bc1, double bc2, void* shadow_bf16, void* stream);
 
 /* ---- nn.Dropout(p) of the reference (cswin_unet.py:20,25,27 Mlp.drop; :135 proj_drop; :346 pos_drop), fused with the residual
  * add + DropPath row factor that follows it where there is one (:178-179):
