@@ -42,7 +42,7 @@ struct AttnBranch {
     int head0;       // global index of its first head (for the lse layout)
     int H_sp, W_sp, nW, nWin;
     int wg_begin;    // first workgroup of this branch
-    unsigned m_heads, m_nWin, m_nW, m_Wsp;   // ceil(2^32 / d) of the four divisors of the index arithmetic (fdiv below)
+    unsigned m_heads, m_nWin, m_nW, m_Wsp;   // ceil(2^32 / d) of the four divisors of the index arithmetic (fdiv, common.h)
     const float* lepe_w;   // [Cb][9]
     const float* lepe_b;   // [Cb]
     float* dw_part;        // backward: partial slabs [b * nWin + win][Cb * 9 (channel-major, tap minor) | Cb] of the
@@ -107,11 +107,8 @@ struct WgInfo {
     int bi, b, win, g, N, ih, iw;
 };
 
-// n / d for 0 <= n < 2^20 and 0 < d < 2^12 by one multiply-high with m = ceil(2^32 / d) (the integer division the compiler
-// emits is ~35 VALU instructions; the index arithmetic of a unit has eight of them and these kernels are issue-bound outside
-// their MFMA loops)
-__device__ __forceinline__ int fdiv(int n, unsigned m) { return (int)__umulhi((unsigned)n, m); }
-static inline unsigned fdiv_magic(int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); }
+// n / d of the index arithmetic by fdiv (common.h): 0 <= n < 2^20 and 0 < d < 2^12 here, inside its exactness bound (the index
+// arithmetic of a unit has eight divisions and these kernels are issue-bound outside their MFMA loops)
 
 // nn.Dropout on the attention probabilities (cswin_unet.py:101, attn_drop_rate > 0; no reference config uses it): the keep factor
 // (0 or 1 / (1 - p)) of probability (query tq, key tk) of (batch, head, window) unit `uid` is a counter-based hash of

@@ -45,6 +45,16 @@ void cswin_set_error(const char* fmt, ...);
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// n / d by one multiply-high, for a divisor d that is uniform over a launch: m = fdiv_magic(d) = ceil(2^32 / d) is made on the
+// host.  With 2^32 + e = m d, 0 <= e < d:  n m / 2^32 = n / d + n e / (d 2^32), and the floor stays that of n / d as long as
+// n e < 2^32; fdiv_exact(nmax, d) is that bound as the host checks it, n d < 2^32 for every dividend 0 <= n <= nmax.  (The
+// division the compiler expands for a run-time divisor is ~35 VALU instructions.)  d = 1 has no 32-bit magic: fdiv_magic gives
+// 0 and the caller skips the division (fdiv1 does it for a divisor that may be 1).
+__device__ __forceinline__ int fdiv(int n, unsigned m) { return (int)__umulhi((unsigned)n, m); }
+__device__ __forceinline__ int fdiv1(int n, unsigned m) { return m ? fdiv(n, m) : n; }
+static inline unsigned fdiv_magic(int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); }
+static inline bool fdiv_exact(long nmax, long d) { return d >= 1 && nmax >= 0 && (d == 1 || nmax * d < (1L << 32)); }
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

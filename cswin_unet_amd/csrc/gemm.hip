@@ -49,7 +49,10 @@ struct PlainSrc {
     const float* p; long ld; int rows, cols;
     const float* row_scale; int rows_per_sample;     // optional per-row multiplier (DropPath backward)
     int bf16;                                        // the matrix is stored as bf16 (p is then only an element-indexed handle)
+    static constexpr bool fast_div = false;          // no divisions by multiply-high in this source (see ConvSrcT)
     struct Row { const float* base; float s; };
+    typedef int Col;                                 // a column of a plain matrix is its index (the gather sources split theirs)
+    __device__ Col col(int j) const { return j; }
     __device__ Row row(int i) const {
         Row r;
         r.base = (i < rows) ? p + (long)i * ld : nullptr;
@@ -72,7 +75,10 @@ __device__ __forceinline__ u32x2 src_load4_bf16(const PlainSrc& s, const float* 
 // cat([p0 (c0 cols), p1 (cols - c0)], dim=-1) without materialising it (skip-concat, cswin_unet.py:509-510)
 struct ConcatSrc {
     const float* p0; const float* p1; long ld0, ld1; int rows, cols, c0;
+    static constexpr bool fast_div = false;
     struct Row { const float* b0; const float* b1; float s; };
+    typedef int Col;
+    __device__ Col col(int j) const { return j; }
     __device__ Row row(int i) const {
         Row r;
         r.b0 = (i < rows) ? p0 + (long)i * ld0 : nullptr;
@@ -86,99 +92,149 @@ struct ConcatSrc {
     }
 };
 
+// The gather sources below split a row index into (b, y, x) and a column index into (tap, channel), the tap into (ky, kx): integer
+// divisions by run-time divisors, per 16-byte chunk and per reduction tile.  FAST: every one of them is a multiply-high by a
+// reciprocal made on the host (fdiv, common.h), which is exact only inside fdiv's bound; the entry points check that bound for
+// every (largest dividend, divisor) pair of a launch and otherwise instantiate FAST = false, the same code with the compiler's
+// divisions.  Either way the loads issued are the same, so the results do not depend on the choice.
+template <bool FAST> __device__ __forceinline__ int qdiv(int n, int d, unsigned m) {
+    if constexpr (FAST) return fdiv1(n, m);
+    else return n / d;
+}
+// the divisors' reciprocals, made beside the bound checks (conv_magics below); unused fields stay 0
+struct ConvMagics { unsigned img, w, c, ks, stride; };
+
 // implicit im2col of NHWC tokens: i = output pixel (b, oy, ox), j = tap * C + ci
-struct ConvSrc {
+template <bool FAST>
+struct ConvSrcT {
     const float* x; int B, H, W, C, OH, OW, ks, stride, pad; int rows, cols;
+    static constexpr bool fast_div = FAST;
+    ConvMagics m;                                    // img: OH * OW, w: OW, c: C, ks: ks
     struct Row { int b, iy0, ix0; float s; };
+    struct Col { int ky, kx, ci; };                  // ci < 0: past the last column
     __device__ Row row(int i) const {
         Row r;
         r.s = 1.0f;
         if (i >= rows) { r.b = -1; r.iy0 = r.ix0 = 0; return r; }
         int ohw = OH * OW;
-        r.b = i / ohw;
+        r.b = qdiv<FAST>(i, ohw, m.img);
         int rem = i - r.b * ohw;
-        int oy = rem / OW;
+        int oy = qdiv<FAST>(rem, OW, m.w);
         r.iy0 = oy * stride - pad;
         r.ix0 = (rem - oy * OW) * stride - pad;
         return r;
     }
-    __device__ const float* ptr(const Row& r, int j) const {
-        if (r.b < 0 || j >= cols) return nullptr;
-        int tap = j / C, ci = j - tap * C;
-        int ky = tap / ks, kx = tap - ky * ks;
-        int iy = r.iy0 + ky, ix = r.ix0 + kx;
+    __device__ Col col(int j) const {
+        Col c;
+        if (j >= cols) { c.ky = c.kx = 0; c.ci = -1; return c; }
+        int tap = qdiv<FAST>(j, C, m.c);
+        c.ci = j - tap * C;
+        c.ky = qdiv<FAST>(tap, ks, m.ks);
+        c.kx = tap - c.ky * ks;
+        return c;
+    }
+    __device__ const float* ptr(const Row& r, const Col& c) const {
+        if (r.b < 0 || c.ci < 0) return nullptr;
+        int iy = r.iy0 + c.ky, ix = r.ix0 + c.kx;
         if ((unsigned)iy >= (unsigned)H || (unsigned)ix >= (unsigned)W) return nullptr;
-        return x + ((long)(r.b * H + iy) * W + ix) * C + ci;
+        return x + ((long)(r.b * H + iy) * W + ix) * C + c.ci;
     }
 };
 
 // transposed gather for the conv data-gradient: i = input pixel (b, iy, ix), j = tap * C + co over dy (NHWC, OHxOW)
-struct ConvTSrc {
+template <bool FAST>
+struct ConvTSrcT {
     const float* dy; int B, H, W, C, OH, OW, ks, stride, pad; int rows, cols;   // C = Cout here
+    static constexpr bool fast_div = FAST;
+    ConvMagics m;                                    // img: H * W, w: W, c: C, ks: ks, stride: stride
     struct Row { int b, iy, ix; float s; };
+    struct Col { int ky, kx, co; };                  // co < 0: past the last column
     __device__ Row row(int i) const {
         Row r;
         r.s = 1.0f;
         if (i >= rows) { r.b = -1; r.iy = r.ix = 0; return r; }
         int hw = H * W;
-        r.b = i / hw;
+        r.b = qdiv<FAST>(i, hw, m.img);
         int rem = i - r.b * hw;
-        r.iy = rem / W;
+        r.iy = qdiv<FAST>(rem, W, m.w);
         r.ix = rem - r.iy * W;
         return r;
     }
-    __device__ const float* ptr(const Row& r, int j) const {
-        if (r.b < 0 || j >= cols) return nullptr;
-        int tap = j / C, co = j - tap * C;
-        int ky = tap / ks, kx = tap - ky * ks;
-        int ty = r.iy + pad - ky, tx = r.ix + pad - kx;
+    __device__ Col col(int j) const {
+        Col c;
+        if (j >= cols) { c.ky = c.kx = 0; c.co = -1; return c; }
+        int tap = qdiv<FAST>(j, C, m.c);
+        c.co = j - tap * C;
+        c.ky = qdiv<FAST>(tap, ks, m.ks);
+        c.kx = tap - c.ky * ks;
+        return c;
+    }
+    __device__ const float* ptr(const Row& r, const Col& c) const {
+        if (r.b < 0 || c.co < 0) return nullptr;
+        int ty = r.iy + pad - c.ky, tx = r.ix + pad - c.kx;
         if (ty < 0 || tx < 0) return nullptr;
-        int oy = ty / stride, ox = tx / stride;
+        int oy = qdiv<FAST>(ty, stride, m.stride), ox = qdiv<FAST>(tx, stride, m.stride);
         if (oy * stride != ty || ox * stride != tx || oy >= OH || ox >= OW) return nullptr;
-        return dy + ((long)(r.b * OH + oy) * OW + ox) * C + co;
+        return dy + ((long)(r.b * OH + oy) * OW + ox) * C + c.co;
     }
 };
 
 // Stride-2 3x3 pad-1 data gradient, one input-pixel parity class (py, px) at a time: an input pixel only ever meets the
 // taps with ky = (iy + 1) mod 2 (+2), kx likewise, i.e. 1, 2, 2 or 4 of the 9 taps depending on its class.  Gathering
-// over all 9 taps (ConvTSrc) feeds 75 % structural zeros to the MFMAs; per class there are none.
+// over all 9 taps (ConvTSrcT) feeds 75 % structural zeros to the MFMAs; per class there are none.
 // i = class-local pixel (b, jy, jx) <-> (iy, ix) = (2 jy + py, 2 jx + px);  j = tap_local * C + co.
-struct ConvTS2Src {
+template <bool FAST>
+struct ConvTS2SrcT {
     const float* dy; int B, H, W, C, OH, OW, py, px, H2, W2, kys, kxs; int rows, cols;   // kys/kxs: 2 bits per local tap
+    static constexpr bool fast_div = FAST;
+    ConvMagics m;                                    // img: H2 * W2, w: W2, c: C
     struct Row { int b, iy, ix; float s; };
+    struct Col { int ky, kx, co; };                  // co < 0: past the last column
     __device__ Row row(int i) const {
         Row r;
         r.s = 1.0f;
         if (i >= rows) { r.b = -1; r.iy = r.ix = 0; return r; }
         const int hw = H2 * W2;
-        r.b = i / hw;
+        r.b = qdiv<FAST>(i, hw, m.img);
         const int rem = i - r.b * hw;
-        const int jy = rem / W2;
+        const int jy = qdiv<FAST>(rem, W2, m.w);
         r.iy = 2 * jy + py;
         r.ix = 2 * (rem - jy * W2) + px;
         return r;
     }
-    __device__ const float* ptr(const Row& r, int j) const {
-        if (r.b < 0 || j >= cols) return nullptr;
-        const int t = j / C, co = j - t * C;
-        const int oy = (r.iy + 1 - ((kys >> (2 * t)) & 3)) >> 1, ox = (r.ix + 1 - ((kxs >> (2 * t)) & 3)) >> 1;
+    __device__ Col col(int j) const {
+        Col c;
+        if (j >= cols) { c.ky = c.kx = 0; c.co = -1; return c; }
+        const int t = qdiv<FAST>(j, C, m.c);
+        c.co = j - t * C;
+        c.ky = (kys >> (2 * t)) & 3;
+        c.kx = (kxs >> (2 * t)) & 3;
+        return c;
+    }
+    __device__ const float* ptr(const Row& r, const Col& c) const {
+        if (r.b < 0 || c.co < 0) return nullptr;
+        const int oy = (r.iy + 1 - c.ky) >> 1, ox = (r.ix + 1 - c.kx) >> 1;
         if (oy >= OH || ox >= OW) return nullptr;
-        return dy + ((long)(r.b * OH + oy) * OW + ox) * C + co;
+        return dy + ((long)(r.b * OH + oy) * OW + ox) * C + c.co;
     }
 };
 
 // rows (tap_local, co) of the [9][Cout][Cin] weight image that belong to one parity class
-struct TapRowsSrc {
+template <bool FAST>
+struct TapRowsSrcT {
     const float* w; int Cout, Cin, taps; int rows, cols;      // taps: 4 bits per local tap (index into the 9 taps)
+    unsigned m_cout;
     struct Row { const float* base; float s; };
+    typedef int Col;
     __device__ Row row(int i) const {
         Row r;
         r.s = 1.0f;
         if (i >= rows) { r.base = nullptr; return r; }
-        const int t = i / Cout, co = i - t * Cout;
+        const int t = qdiv<FAST>(i, Cout, m_cout), co = i - t * Cout;
         r.base = w + ((long)((taps >> (4 * t)) & 15) * Cout + co) * Cin;
         return r;
     }
+    __device__ Col col(int j) const { return j; }
     __device__ const float* ptr(const Row& r, int j) const { return (r.base && j < cols) ? r.base + j : nullptr; }
 };
 
@@ -262,6 +318,11 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
         for (int q = 0; q < QB; ++q) brow[q] = B.row(n0 + b_r + q * B_RPP);
     }
 
+    // An operand that is not r-contiguous keeps its column (the output index m0 / n0 + 4 * chunk) through the whole reduction: a
+    // gather source splits it into (tap, channel) once, here, not per tile (16-B loaders; the scalar ones serve plain matrices only)
+    const typename ASrc::Col acol = A.col(m0 + 4 * a_c);
+    const typename BSrc::Col bcol = B.col(n0 + 4 * b_c);
+
     // register prefetch of the next tile: raw loads only -- nothing may consume pa/pb before stash(), or the
     // compiler waits for the loads in front of the MFMA section
     f32x4 pa[QA], pb[QB];
@@ -284,7 +345,7 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
             }
             if (SCALE_A) pas[q] = rr.s;
             if (VEC == 4) {
-                const float* p = (!A_RC || j < r_end) ? A.ptr(rr, j) : nullptr;
+                const float* p = A_RC ? (j < r_end ? A.ptr(rr, A.col(j)) : nullptr) : A.ptr(rr, acol);
                 if constexpr (decltype(a16)::value) {
                     pa16[q] = u32x2{0u, 0u};
                     if (p) pa16[q] = src_load4_bf16(A, p);
@@ -295,7 +356,7 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
             } else {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float* p = (!A_RC || j + e < r_end) ? A.ptr(rr, j + e) : nullptr;
+                    const float* p = (!A_RC || j + e < r_end) ? A.ptr(rr, A.col(j + e)) : nullptr;
                     pa[q][e] = p ? *p : 0.f;
                 }
             }
@@ -313,7 +374,7 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
                 j = n0 + 4 * b_c;
             }
             if (VEC == 4) {
-                const float* p = (!B_RC || j < r_end) ? B.ptr(rr, j) : nullptr;
+                const float* p = B_RC ? (j < r_end ? B.ptr(rr, B.col(j)) : nullptr) : B.ptr(rr, bcol);
                 if constexpr (decltype(b16)::value) {
                     pb16[q] = u32x2{0u, 0u};
                     if (p) pb16[q] = src_load4_bf16(B, p);
@@ -324,7 +385,7 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
             } else {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float* p = (!B_RC || j + e < r_end) ? B.ptr(rr, j + e) : nullptr;
+                    const float* p = (!B_RC || j + e < r_end) ? B.ptr(rr, B.col(j + e)) : nullptr;
                     pb[q][e] = p ? *p : 0.f;
                 }
             }
@@ -542,7 +603,11 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
         if (e.pre_bf16) run_epilogue<EPI, FM, FN, true>(e, acc, M, N, m0 + wm0, n0 + wn0, lane, lds + wave * EP_WAVE_FLOATS, e.vec_store != 0);
         else run_epilogue<EPI, FM, FN, false>(e, acc, M, N, m0 + wm0, n0 + wn0, lane, lds + wave * EP_WAVE_FLOATS, e.vec_store != 0);
     } else {
-        run_epilogue<EPI, FM, FN>(e, acc, M, N, m0 + wm0, n0 + wn0, lane, lds + wave * EP_WAVE_FLOATS, e.vec_store != 0);
+        // a FAST gather source brings the reciprocals of its own row split, which is the epilogue's (rm_on: the parity classes)
+        if constexpr (ASrc::fast_div)
+            run_epilogue<EPI, FM, FN, false, true>(e, acc, M, N, m0 + wm0, n0 + wn0, lane, lds + wave * EP_WAVE_FLOATS, e.vec_store != 0, A.m.img, A.m.w);
+        else
+            run_epilogue<EPI, FM, FN>(e, acc, M, N, m0 + wm0, n0 + wn0, lane, lds + wave * EP_WAVE_FLOATS, e.vec_store != 0);
     }
     if (epi.stamps && tid == 0) { epi.stamps[8L * stamp_row + 3] = __builtin_amdgcn_s_memtime(); epi.stamps[8L * stamp_row + 6] = __builtin_amdgcn_s_memrealtime(); }
     if (do_colsum && m0 + tid < M) epi.colsum[(long)split * epi.colsum_stride + m0 + tid] = csum;
@@ -620,14 +685,14 @@ __global__ __launch_bounds__(512) void gemm_block_tail_kernel(BlockTail t) {
         b.first[p + 1] - b.first[p], (int)blockIdx.x);
 }
 
-// The four parity classes of a stride-2 3x3 convolution's data gradient (ConvTS2Src) are independent GEMMs over a quarter of
+// The four parity classes of a stride-2 3x3 convolution's data gradient (ConvTS2SrcT) are independent GEMMs over a quarter of
 // the pixels each: alone they fill 1.1 - 1.2 workgroups per CU (the launch ends with the CUs that got two); together 4.6.
-template <int KW, int PREC>
-__global__ __launch_bounds__(256 * KW) void gemm_conv_s2_dgrad_batch_kernel(GemmBatch<ConvTS2Src, TapRowsSrc> b) {
+template <int KW, int PREC, bool FAST>
+__global__ __launch_bounds__(256 * KW) void gemm_conv_s2_dgrad_batch_kernel(GemmBatch<ConvTS2SrcT<FAST>, TapRowsSrcT<FAST>> b) {
     int p = 0;
     while (p + 1 < b.n && (int)blockIdx.x >= b.first[p + 1]) ++p;
     __shared__ __attribute__((aligned(16))) float lds[gemm_lds_floats<64, 64, (KW == 1 ? 32 : 64), KW, true, false>()];
-    gemm_body<64, 64, (KW == 1 ? 32 : 64), KW, true, false, 4, EPI_PLAIN, false, PREC, ConvTS2Src, TapRowsSrc>(
+    gemm_body<64, 64, (KW == 1 ? 32 : 64), KW, true, false, 4, EPI_PLAIN, false, PREC, ConvTS2SrcT<FAST>, TapRowsSrcT<FAST>>(
         lds, b.A[p], b.B[p], b.e[p], b.M[p], b.N[p], b.R[p], b.rps[p], b.tm[p], b.tn[p], (int)blockIdx.x - b.first[p],
         b.first[p + 1] - b.first[p], (int)blockIdx.x);
 }
@@ -952,6 +1017,21 @@ int wgrad_batch_impl(const cswin_wgrad_desc* d, int n, cswin_reduce_job* deferre
     return CSWIN_OK;
 }
 
+// The reciprocals of a gather source's divisors, and whether every division of the launch stays inside fdiv's bound: row indices
+// < nrows are split by img (pixels per image) and what remains (< img) by w; column indices < ncols by c; taps < ks * ks by ks;
+// pixel coordinates <= cmax by stride (0: the source has no such division).  The row bound is taken 64 rows past the last one: the
+// epilogue of a FAST kernel splits the rows of its last tile before it tests them.  false: the launch takes the FAST = false form.
+bool conv_magics(ConvMagics* m, long nrows, int img, int w, long ncols, int c, int ks, int cmax, int stride) {
+    *m = ConvMagics{fdiv_magic(img), fdiv_magic(w), fdiv_magic(c), fdiv_magic(ks), fdiv_magic(stride)};
+    return fdiv_exact(nrows + 63, img) && fdiv_exact(img - 1, w) && fdiv_exact(ncols - 1, c) && fdiv_exact((long)ks * ks - 1, ks) &&
+           (stride == 0 || fdiv_exact(cmax, stride));
+}
+// f(std::true_type) when the bound holds, f(std::false_type) otherwise: the two forms of a gather launch
+template <class F> void with_fast_div(bool fast, F f) {
+    if (fast) f(std::true_type{});
+    else f(std::false_type{});
+}
+
 // dw_perm: [Cout][ks*ks][Cin], or the nn.Conv2d parameter layout [Cout][Cin_param][ks][ks] when torch_layout != 0; dbias: [Cout]
 int conv_wgrad_impl(const float* dy, const float* x, float* dw_perm, float* dbias, void* workspace, size_t ws_bytes, int B, int H,
                     int W, int Cin, int Cout, int ks, int stride, int pad, int torch_layout, int Cin_param,
@@ -969,8 +1049,11 @@ int conv_wgrad_impl(const float* dy, const float* x, float* dw_perm, float* dbia
     choose_split(M, Cout, K, &splits, &rps);
     const WgradSlabs slabs(workspace, Cout, K);
     PlainSrc A = {dy, Cout, M, Cout, nullptr, 1};
-    ConvSrc Bm = {x, B, H, W, Cin, OH, OW, ks, stride, pad, M, K};   // S(i = pixel m (reduction), j = (tap, ci))
-    launch_gemm<false, false, 4, EPI_PLAIN, false>(A, Bm, slabs.epilogue(dbias != nullptr), Cout, K, M, splits, rps, precision, st);
+    ConvMagics mg;
+    with_fast_div(conv_magics(&mg, M, OH * OW, OW, K, Cin, ks, 0, 0), [&](auto fast) {
+        ConvSrcT<decltype(fast)::value> Bm = {x, B, H, W, Cin, OH, OW, ks, stride, pad, M, K, mg};   // S(i = pixel m (reduction), j = (tap, ci))
+        launch_gemm<false, false, 4, EPI_PLAIN, false>(A, Bm, slabs.epilogue(dbias != nullptr), Cout, K, M, splits, rps, precision, st);
+    });
     CSWIN_LAUNCH_CHECK();
     reduce_now_or_defer(slabs.job(dw_perm, dbias, splits, torch_layout ? ks * ks : 0,
                                   torch_layout ? (Cin | (Cin_param != Cin ? Cin_param << 16 : 0)) : 0), deferred, st);
@@ -1128,11 +1211,14 @@ int cswin_conv_tok_fwd(const float* x, const float* w_perm, const float* bias, f
     CSWIN_REQUIRE(Cin % 4 == 0 && aligned16(x) && aligned16(w_perm), CSWIN_ERR_ALIGN, "conv_tok_fwd: Cin %% 4 and 16-B alignment required");
     int OH = (H + 2 * pad - ks) / stride + 1, OW = (W + 2 * pad - ks) / stride + 1;
     int M = B * OH * OW, R = ks * ks * Cin;
-    ConvSrc A = {x, B, H, W, Cin, OH, OW, ks, stride, pad, M, R};
     PlainSrc Bm = {w_perm, R, Cout, R, nullptr, 1};
     Epilogue e = plain_epilogue(y, Cout);
     e.bias = bias;
-    launch_gemm<true, true, 4, EPI_PLAIN, false>(A, Bm, e, M, Cout, R, 1, one_split(R), precision, (hipStream_t)stream);
+    ConvMagics mg;
+    with_fast_div(conv_magics(&mg, M, OH * OW, OW, R, Cin, ks, 0, 0), [&](auto fast) {
+        ConvSrcT<decltype(fast)::value> A = {x, B, H, W, Cin, OH, OW, ks, stride, pad, M, R, mg};
+        launch_gemm<true, true, 4, EPI_PLAIN, false>(A, Bm, e, M, Cout, R, 1, one_split(R), precision, (hipStream_t)stream);
+    });
     CSWIN_LAUNCH_CHECK();
     return CSWIN_OK;
 }
@@ -1147,44 +1233,60 @@ int cswin_conv_tok_bwd_data(const float* dy, const float* w_permT, float* dx, in
     if (ks == 3 && stride == 2 && pad == 1) {
         // four parity classes, each a dense GEMM over only the taps that reach it (Merge_Block.conv, cswin_unet.py:208),
         // launched together (gemm_conv_s2_dgrad_batch_kernel)
-        GemmBatch<ConvTS2Src, TapRowsSrc> b = {};
-        int rmax = 0;
+        // every class's divisions inside fdiv's bound (the largest class is (0, 0)), or the launch keeps the compiler's divisions
+        bool fast_ok = true;
         for (int py = 0; py < 2; ++py)
             for (int px = 0; px < 2; ++px) {
                 const int H2 = (H - py + 1) / 2, W2 = (W - px + 1) / 2;
-                if (H2 <= 0 || W2 <= 0) continue;
-                int kys = 0, kxs = 0, taps = 0, nt = 0;
-                for (int ky = (py ? 0 : 1); ky < 3; ky += 2)
-                    for (int kx = (px ? 0 : 1); kx < 3; kx += 2) {
-                        kys |= ky << (2 * nt);
-                        kxs |= kx << (2 * nt);
-                        taps |= (ky * 3 + kx) << (4 * nt);
-                        ++nt;
-                    }
-                const int Mc = B * H2 * W2, Rc = nt * Cout;
-                Epilogue e = plain_epilogue(dx, Cin);
-                e.rm_on = 1; e.rm_H = H; e.rm_W = W; e.rm_H2 = H2; e.rm_W2 = W2; e.rm_py = py; e.rm_px = px;
-                push(b, ConvTS2Src{dy, B, H, W, Cout, OH, OW, py, px, H2, W2, kys, kxs, Mc, Rc}, TapRowsSrc{w_permT, Cout, Cin, taps, Rc, Cin},
-                     e, Mc, Cin, Rc, one_split(Rc), 1);
-                rmax = Rc > rmax ? Rc : rmax;
+                ConvMagics mg;
+                if (H2 > 0 && W2 > 0) fast_ok = fast_ok && conv_magics(&mg, (long)B * H2 * W2, H2 * W2, W2, 4L * Cout, Cout, 1, 0, 0);
             }
-        if (b.n > 0) {
-            const int blocks = b.first[b.n];
-            hipStream_t st = (hipStream_t)stream;
-            const int kw = k_groups(blocks, rmax);
-            if (precision == 1) hipLaunchKernelGGL((gemm_conv_s2_dgrad_batch_kernel<2, 1>), dim3(blocks), dim3(512), 0, st, b);
-            else if (kw == 4) hipLaunchKernelGGL((gemm_conv_s2_dgrad_batch_kernel<4, 0>), dim3(blocks), dim3(1024), 0, st, b);
-            else if (kw == 2) hipLaunchKernelGGL((gemm_conv_s2_dgrad_batch_kernel<2, 0>), dim3(blocks), dim3(512), 0, st, b);
-            else hipLaunchKernelGGL((gemm_conv_s2_dgrad_batch_kernel<1, 0>), dim3(blocks), dim3(256), 0, st, b);
-        }
+        with_fast_div(fast_ok, [&](auto fast) {
+            constexpr bool FAST = decltype(fast)::value;
+            GemmBatch<ConvTS2SrcT<FAST>, TapRowsSrcT<FAST>> b = {};
+            int rmax = 0;
+            for (int py = 0; py < 2; ++py)
+                for (int px = 0; px < 2; ++px) {
+                    const int H2 = (H - py + 1) / 2, W2 = (W - px + 1) / 2;
+                    if (H2 <= 0 || W2 <= 0) continue;
+                    int kys = 0, kxs = 0, taps = 0, nt = 0;
+                    for (int ky = (py ? 0 : 1); ky < 3; ky += 2)
+                        for (int kx = (px ? 0 : 1); kx < 3; kx += 2) {
+                            kys |= ky << (2 * nt);
+                            kxs |= kx << (2 * nt);
+                            taps |= (ky * 3 + kx) << (4 * nt);
+                            ++nt;
+                        }
+                    const int Mc = B * H2 * W2, Rc = nt * Cout;
+                    Epilogue e = plain_epilogue(dx, Cin);
+                    e.rm_on = 1; e.rm_H = H; e.rm_W = W; e.rm_H2 = H2; e.rm_W2 = W2; e.rm_py = py; e.rm_px = px;
+                    ConvMagics mg;
+                    conv_magics(&mg, Mc, H2 * W2, W2, Rc, Cout, 1, 0, 0);
+                    push(b, ConvTS2SrcT<FAST>{dy, B, H, W, Cout, OH, OW, py, px, H2, W2, kys, kxs, Mc, Rc, mg},
+                         TapRowsSrcT<FAST>{w_permT, Cout, Cin, taps, Rc, Cin, mg.c}, e, Mc, Cin, Rc, one_split(Rc), 1);
+                    rmax = Rc > rmax ? Rc : rmax;
+                }
+            if (b.n > 0) {
+                const int blocks = b.first[b.n];
+                hipStream_t st = (hipStream_t)stream;
+                const int kw = k_groups(blocks, rmax);
+                if (precision == 1) hipLaunchKernelGGL((gemm_conv_s2_dgrad_batch_kernel<2, 1, FAST>), dim3(blocks), dim3(512), 0, st, b);
+                else if (kw == 4) hipLaunchKernelGGL((gemm_conv_s2_dgrad_batch_kernel<4, 0, FAST>), dim3(blocks), dim3(1024), 0, st, b);
+                else if (kw == 2) hipLaunchKernelGGL((gemm_conv_s2_dgrad_batch_kernel<2, 0, FAST>), dim3(blocks), dim3(512), 0, st, b);
+                else hipLaunchKernelGGL((gemm_conv_s2_dgrad_batch_kernel<1, 0, FAST>), dim3(blocks), dim3(256), 0, st, b);
+            }
+        });
         CSWIN_LAUNCH_CHECK();
         return CSWIN_OK;
     }
     int M = B * H * W, R = ks * ks * Cout;
-    ConvTSrc A = {dy, B, H, W, Cout, OH, OW, ks, stride, pad, M, R};
     PlainSrc Bm = {w_permT, Cin, R, Cin, nullptr, 1};          // S(i = (tap, co), j = ci)
     Epilogue e = plain_epilogue(dx, Cin);
-    launch_gemm<true, false, 4, EPI_PLAIN, false>(A, Bm, e, M, Cin, R, 1, one_split(R), precision, (hipStream_t)stream);
+    ConvMagics mg;
+    with_fast_div(conv_magics(&mg, M, H * W, W, R, Cout, ks, (H > W ? H : W) + pad, stride), [&](auto fast) {
+        ConvTSrcT<decltype(fast)::value> A = {dy, B, H, W, Cout, OH, OW, ks, stride, pad, M, R, mg};
+        launch_gemm<true, false, 4, EPI_PLAIN, false>(A, Bm, e, M, Cin, R, 1, one_split(R), precision, (hipStream_t)stream);
+    });
     CSWIN_LAUNCH_CHECK();
     return CSWIN_OK;
 }

@@ -48,16 +48,23 @@ constexpr int EP_WAVE_FLOATS = 32 * EP_LD;
 
 // PRE16: gelu_pre is stored as bf16 (EPI_GELUBWD) -- compile-time, so that the four auxiliary loads of a fragment stay in one
 // basic block and are issued back to back.
-template <int EPI, int FM, int FN, bool PRE16 = false>
+// FDIV: the row split of rm_on by multiply-high with the reciprocals m_hw, m_w2 of rm_H2 * rm_W2 and rm_W2 (fdiv, common.h; the
+// kernels of the FAST gather sources, which carry them: the launch's host side has checked fdiv's bound for M + 63 rows).
+// Compile-time, and off for the dense kernels, whose epilogue and Epilogue struct are exactly what they were: hoisting their row
+// divisions cost the residual-epilogue kernels registers and a step of occupancy (profiles/conv_gather_notes.md).
+template <int EPI, int FM, int FN, bool PRE16 = false, bool FDIV = false>
 __device__ __forceinline__ void run_epilogue(const Epilogue& e, f32x16 (&acc)[FM][FN], int M, int N, int mb, int nb,
-                                             int lane, float* wbuf, bool vec) {
+                                             int lane, float* wbuf, bool vec, unsigned m_hw = 0, unsigned m_w2 = 0) {
     const int li = lane & 31, lh = lane >> 5;
     const int rrow = lane >> 3, rcol = (lane & 7) * 4;
     const bool has_rs = e.row_scale != nullptr;
     auto out_row = [&](int m) -> long {           // class-local pixel -> row of the full (B, H*W, C) token matrix
         if (!e.rm_on) return m;
         const int hw = e.rm_H2 * e.rm_W2;
-        const int b = m / hw, rem = m - b * hw, jy = rem / e.rm_W2;
+        int b, jy;
+        if constexpr (FDIV) { b = fdiv1(m, m_hw); jy = fdiv1(m - b * hw, m_w2); }
+        else { b = m / hw; jy = (m - b * hw) / e.rm_W2; }
+        const int rem = m - b * hw;
         return ((long)b * e.rm_H + 2 * jy + e.rm_py) * e.rm_W + 2 * (rem - jy * e.rm_W2) + e.rm_px;
     };
 #pragma unroll
