@@ -70,6 +70,9 @@ SIGNATURES = {
     "cswin_chunk_sumsq": (I, [P, P, P, I, P, P]),
     "cswin_norm_finalize": (I, [P, P, I, F, F, P, P, P]),
     "cswin_adamw_flat": (I, [P, P, P, P, P, I, P, P, P, D, D, D, F, F, D, D, P, P]),
+    "cswin_tpgm_chunk_stats": (I, [P, P, P, P, I, I, P, P]),
+    "cswin_tpgm_finalize": (I, [P, P, I, I, P, P, P, P, D, D, D, D, I, P, P, P, P]),
+    "cswin_tpgm_project": (I, [P, P, P, P, P, I, P, P]),
     "cswin_pack_bf16": (I, [P, P, L, P]),
     "cswin_pack_bf16_scaled": (I, [P, P, L, F, P]),
     "cswin_unpack_bf16": (I, [P, P, L, P]),

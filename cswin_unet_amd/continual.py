@@ -12,7 +12,13 @@ and the "surgical" mode's learning rate per parameter tensor (universal_train.py
     w = surgical_lr_weights(model, engine.opt, batches, distill)    # relative gradient norms of a few batches, largest = 1
     engine.set_lr_weights(w)                                        # FlatAdamW's per-tensor multipliers; unnamed tensors get 0
 
-Only surgical_lr_weights runs the model; nothing else here launches a kernel."""
+and TPGM, the trainable projection toward the pretrained weights (universal_train.py:391-615, 898-902, 972-974):
+
+    tpgm = TPGM(trainer)                                            # BEFORE fine-tuning: the anchor is the weights as they are now
+    if tpgm_due(epoch, start_epoch, frequency): tpgm.iterate(held_out_batches, max_iters)     # learns the radii; the weights are restored
+    tpgm.apply()                                                    # once, after training: the weights are projected
+
+Only surgical_lr_weights and TPGM run the model; nothing else here launches a kernel."""
 import copy
 import math
 from dataclasses import dataclass
@@ -21,7 +27,7 @@ from typing import Optional
 import torch
 from torch import nn
 
-__all__ = ["expand_classes", "new_label_map", "extreme_class_weights", "freeze_teacher", "Distill", "rgn_weights", "surgical_lr_weights"]
+__all__ = ["expand_classes", "new_label_map", "extreme_class_weights", "freeze_teacher", "Distill", "rgn_weights", "surgical_lr_weights", "TPGM", "tpgm_due"]
 
 
 def _core(model):
@@ -168,3 +174,76 @@ def surgical_lr_weights(model, opt, batches, distill):
         model.train(was_training)
     host = torch.stack(norms).cpu().tolist() if norms else []          # the one host read
     return rgn_weights(names, host)
+
+
+def tpgm_due(epoch, start_epoch, frequency):
+    """Whether the projection update runs before epoch `epoch` (universal_train.py:898-900)."""
+    return epoch >= start_epoch and (epoch - start_epoch + 1) % frequency == 0
+
+
+class TPGM:
+    """The TPGM of universal_train.py:391-615 on a DataParallelTrainer whose engine is a HipEngine: optim.FlatTPGM on the engine's
+    flat buffers, driven through the engine's own step hooks, so the captured hipGraphs are replayed as they are (they read the
+    projected weights from the flat parameter buffer).  The anchor is the weights at construction.
+
+    Two deliberate differences from universal_train.py ("TPGM"): the radii receive the gradient tpgm.py:47-56 gives
+    them (the reference's temporary_parameter_replace cuts the autograd graph, so its own update loop changes nothing), and the
+    iterations minimise the objective the engine was built with, through the engine's own forward.  With no iteration run,
+    apply() is the reference's projection.
+
+    names in `exclude` are never projected.  Nothing is printed or logged; ratio_stats() is the reference's get_ratio_stats."""
+
+    def __init__(self, trainer, norm_mode="l2", proj_lr=0.01, exclude=()):
+        from .optim import FlatTPGM
+        eng = trainer.engine
+        if not hasattr(eng, "opt") or not hasattr(eng, "param_names"):
+            raise TypeError("continual.TPGM needs a trainer whose engine owns flat buffers (HipEngine)")
+        self.trainer = trainer
+        self.flat = FlatTPGM(eng.opt, eng.param_names, norm_mode=norm_mode, proj_lr=proj_lr, exclude=exclude)
+
+    def iterate(self, batches, max_iters):
+        """max_iters projection-update iterations (tpgm_iters(apply=False), :579-603) on `batches`, a re-iterable of (image, label)
+        device tensors that is cycled when exhausted: forward and backward under the projected weights, all-reduce of the
+        gradient under data parallelism, Adam on the radii, re-projection.  The weights (and the bf16 shadow) are restored
+        afterwards, also when a batch raises; the optimiser's state is never touched."""
+        import torch.distributed as dist
+        tr, flat = self.trainer, self.flat
+        eng, world = tr.engine, tr.world
+        it = iter(batches)
+        flat.begin()
+        try:
+            for _ in range(int(max_iters)):
+                try:
+                    img, lab = next(it)
+                except StopIteration:
+                    it = iter(batches)
+                    img, lab = next(it)
+                lab = (lab if lab.dtype == torch.int64 else lab.long()).contiguous()
+                eng.forward_sums(img, lab, dice_grad_scale=float(world))
+                if tr.collectives:
+                    dist.all_reduce(eng.sums, group=tr.group)
+                eng.finalize(lab.numel() * world)
+                for _range in eng.backward_phases(dice_grad_scale=float(world)):
+                    pass
+                if tr.collectives:
+                    dist.all_reduce(eng.flat_grad, group=tr.group)
+                flat.update(1.0 / world)
+                flat.reproject()
+        finally:
+            flat.end()
+
+    def apply(self):
+        """The final projection (tpgm_iters(apply=True), :613-615): the weights are moved into their balls, once."""
+        self.flat.apply()
+
+    def ratio_stats(self):
+        return self.flat.ratio_stats()
+
+    def set_constraints(self, gamma):
+        self.flat.set_constraints(gamma)
+
+    def state_dict(self):
+        return self.flat.state_dict()
+
+    def load_state_dict(self, sd):
+        self.flat.load_state_dict(sd)

@@ -1,11 +1,14 @@
 """The optimisers of the training loops on flat buffers: SGD(momentum, weight_decay) of the reference's trainer.py:42,60-63
-(FlatSGD) and clip_grad_norm_ + AdamW with a learning rate per tensor of its universal_train.py:693-725, 934-939 (FlatAdamW).
+(FlatSGD), clip_grad_norm_ + AdamW with a learning rate per tensor of its universal_train.py:693-725, 934-939 (FlatAdamW), and
+the trainable projection toward the pretrained weights of its :391-615 (FlatTPGM, over either of the two).
 
 All parameters are re-pointed into ONE flat fp32 buffer (32-B aligned slots), the optimiser state and the gradients live in
 more of the same layout.  A step is a multi-tensor gather of the per-parameter .grad tensors into the flat gradient buffer (the
 buffer RCCL all-reduces, in buckets, under data parallelism) and one fused update kernel -- for AdamW with clipping, two norm
 kernels in front of it.  The learning rate lives in device memory so that a captured hipGraph can be replayed under a schedule.
 """
+from typing import NamedTuple
+
 import numpy as np
 import torch
 
@@ -239,3 +242,193 @@ class FlatAdamW(_FlatBuffers):
         self.step_count = int(sd["step"])
         self.set_lr(sd["lr"])
         self.set_lr_weights(sd["lr_weights"])
+
+
+TPGM_BETAS, TPGM_EPS = (0.9, 0.999), 1e-8       # torch.optim.Adam's defaults, which universal_train.py:552 takes; csrc/tpgm.hip holds the same constants
+TPGM_HEAD_WORDS = ("head", "final", "classifier", "output", "segmentation_head")
+TPGM_EXCLUDED, TPGM_HEAD = 1, 2                  # the bits of cswin_tpgm_finalize's per-tensor flags
+
+
+def tpgm_is_head(name):
+    """The "final / classification layer" rule of universal_train.py:418 and :471: a wider initial radius and a wider clamp."""
+    return any(w in name.lower() for w in TPGM_HEAD_WORDS)
+
+
+def tpgm_init_gamma(name, param_norm):
+    """The initial projection radius of universal_train.py:415-421 from the tensor's own L2 norm."""
+    return max(10.0, param_norm * 5.0) if tpgm_is_head(name) else max(3.0, param_norm * 2.0)
+
+
+class RatioStats(NamedTuple):
+    """(min, max, mean) of the projection ratios, the order of the reference's get_ratio_stats (universal_train.py:507-515)."""
+    min: float
+    max: float
+    mean: float
+
+
+class FlatTPGM:
+    """TPGM (universal_train.py:391-615) over the flat buffers of a FlatSGD / FlatAdamW `opt`: every tensor of opt.params is kept
+    inside a ball of learned radius gamma_t around its value when this object was built (the anchor).  names: the parameter names,
+    aligned with opt.params (they decide the head tensors and match `exclude`).  csrc/tpgm.hip's three kernels do all the work;
+    nothing here synchronises with the host except the one read that forms the initial radii and ratio_stats().
+
+        begin()                  save theta, put the projected theta~ into opt.flat_param (and the bf16 shadow)
+        update(grad_scale)       opt.flat_grad holds dL/dtheta~: clip_grad_norm_(gamma, 1) + one Adam step on gamma
+        reproject()              theta~ of the new gamma, from the saved theta
+        end()                    theta and the shadow back, bit for bit
+        apply()                  theta <- theta~ (the final projection), in place
+
+    Memory: two more flat buffers (anchor, saved) and a few floats per tensor."""
+
+    def __init__(self, opt, names, norm_mode="l2", proj_lr=0.01, exclude=()):
+        names = list(names)
+        if len(names) != len(opt.params):
+            raise ValueError(f"FlatTPGM: {len(names)} names for {len(opt.params)} parameter tensors")
+        unknown = set(exclude) - set(names)
+        if unknown:
+            raise KeyError(f"FlatTPGM: no trainable parameter named {sorted(unknown)[:4]}")
+        self.opt, self.names, self.norm_mode, self.proj_lr = opt, names, str(norm_mode), float(proj_lr)
+        self.l1 = 0 if "l2" in self.norm_mode else 1                                     # universal_train.py:463
+        dev, T = opt.flat_param.device, len(names)
+        if hasattr(opt, "_chunks"):
+            self._chunks, self._first_chunk, self.nchunks = opt._chunks, opt._first_chunk, opt.nchunks
+        else:
+            rows, first = chunk_table([p.numel() for p in opt.params], opt.offsets)
+            self.nchunks = len(rows)
+            self._chunks = torch.from_numpy(rows.view(np.int64).reshape(-1, 2)).to(dev)
+            self._first_chunk = torch.from_numpy(first).to(dev)
+        self._partial = torch.zeros(self.nchunks, 2, dtype=torch.float32, device=dev)
+        excl = set(exclude)
+        self.flags_host = [(TPGM_EXCLUDED if n in excl else 0) | (TPGM_HEAD if tpgm_is_head(n) else 0) for n in names]
+        self._flags = torch.tensor(self.flags_host, dtype=torch.int32, device=dev)
+        self.flat_anchor = opt.flat_param.clone()
+        self.flat_saved = torch.zeros_like(opt.flat_param)
+        self.gamma = torch.zeros(T, dtype=torch.float32, device=dev)
+        self.ratio = torch.ones(T, dtype=torch.float32, device=dev)
+        self.norm = torch.zeros(T, dtype=torch.float32, device=dev)                      # ||theta - anchor|| of the last launch
+        self.gamma_m = torch.zeros(T, dtype=torch.float32, device=dev)
+        self.gamma_v = torch.zeros(T, dtype=torch.float32, device=dev)
+        self.scalars = torch.tensor([0.0, 1.0], dtype=torch.float32, device=dev)         # [norm of dL/dgamma, clip coefficient] of the last update
+        self.step_count = 0
+        self._active, self._ratio_current = False, False
+        # the initial radii: ||theta_t|| is the distance to an anchor of zeros, which flat_saved still is
+        self._ratios(opt.flat_param, self.flat_saved, l1=0)
+        pn = self.norm.cpu().tolist()                                                    # the one host read
+        self.gamma.copy_(torch.tensor([tpgm_init_gamma(n, v) for n, v in zip(names, pn)], dtype=torch.float32))
+        self.norm.zero_()
+        self.ratio.fill_(1.0)
+
+    # -- launches -------------------------------------------------------------------------------------------
+    def _stats(self, p, anchor, g, l1=None):
+        call("cswin_tpgm_chunk_stats", ptr(p), ptr(anchor), ptr(g), ptr(self._chunks), self.nchunks, self.l1 if l1 is None else l1,
+             ptr(self._partial), stream())
+
+    def _finalize(self, mode, grad_scale=1.0, bc1=1.0, bc2=1.0, l1=None):
+        call("cswin_tpgm_finalize", ptr(self._partial), ptr(self._first_chunk), len(self.names), self.l1 if l1 is None else l1, ptr(self._flags),
+             ptr(self.gamma), ptr(self.gamma_m), ptr(self.gamma_v), float(grad_scale), self.proj_lr, bc1, bc2, mode, ptr(self.ratio),
+             ptr(self.norm), ptr(self.scalars), stream())
+
+    def _ratios(self, p, anchor, l1=None):
+        self._stats(p, anchor, None, l1)
+        self._finalize(0, l1=l1)
+
+    def _project(self, src):
+        opt = self.opt
+        call("cswin_tpgm_project", ptr(src), ptr(self.flat_anchor), ptr(opt.flat_param), ptr(self.ratio), ptr(self._chunks), self.nchunks,
+             ptr(opt.flat_param16) if precision() == 1 else None, stream())
+
+    # -- the projection update ------------------------------------------------------------------------------
+    def begin(self):
+        """Save theta once, then theta~ -> opt.flat_param (+ the shadow in the bf16 mode)."""
+        if self._active:
+            raise RuntimeError("FlatTPGM.begin(): already begun (end() restores the parameters)")
+        self.flat_saved.copy_(self.opt.flat_param)
+        self._active = True
+        self._ratio_current = False
+        self.reproject()
+
+    def reproject(self):
+        """theta~ of the current gamma, from the saved theta (one launch right after update(), three otherwise)."""
+        if not self._active:
+            raise RuntimeError("FlatTPGM.reproject() outside begin() ... end()")
+        if not self._ratio_current:
+            self._ratios(self.flat_saved, self.flat_anchor)
+            self._ratio_current = True
+        self._project(self.flat_saved)
+
+    def update(self, grad_scale=1.0):
+        """opt.flat_grad * grad_scale is dL/dtheta~: gamma <- Adam(clip_grad_norm_(dL/dgamma, 1)), against the SAVED theta (two
+        launches); self.ratio holds the ratios of the new gamma afterwards."""
+        if not self._active:
+            raise RuntimeError("FlatTPGM.update() outside begin() ... end()")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FlatTPGM.update() inside a stream capture: the host's step count, and with it the bias corrections, "
+                               "would be frozen into the graph")
+        self.step_count += 1
+        b1, b2 = TPGM_BETAS
+        self._stats(self.flat_saved, self.flat_anchor, self.opt.flat_grad)
+        self._finalize(1, grad_scale, 1.0 - b1 ** self.step_count, 1.0 - b2 ** self.step_count)
+        self._ratio_current = True
+
+    def end(self):
+        """theta and its shadow back, bit for bit."""
+        if not self._active:
+            return
+        self.opt.flat_param.copy_(self.flat_saved)
+        if precision() == 1:
+            self.opt.refresh_shadow()
+        self._active = False
+
+    # -- the projection -------------------------------------------------------------------------------------
+    def apply(self):
+        """theta <- anchor + ratio (theta - anchor) in place (universal_train.py:613-615); a tensor inside its ball is not stored."""
+        if self._active:
+            raise RuntimeError("FlatTPGM.apply() between begin() and end(): the parameters hold theta~")
+        self._ratios(self.opt.flat_param, self.flat_anchor)
+        self._project(self.opt.flat_param)
+
+    def tensor_norms(self):
+        """(T,) device tensor of ||theta - anchor|| per tensor (sum |.| in the l1 mode), of opt.flat_param as it is -- of the saved
+        theta between begin() and end().  No sync; self.ratio holds the ratios of the current gamma afterwards."""
+        self._ratios(self.flat_saved if self._active else self.opt.flat_param, self.flat_anchor)
+        self._ratio_current = self._active
+        return self.norm.clone()
+
+    def ratio_stats(self):
+        """RatioStats (min, max, mean) of the last launch's ratios over the tensors that are not excluded, (0, 0, 0) when there is
+        none: get_ratio_stats of universal_train.py:507-515.  One host read."""
+        r = [v for v, f in zip(self.ratio.cpu().tolist(), self.flags_host) if not f & TPGM_EXCLUDED]
+        return RatioStats(min(r), max(r), sum(r) / len(r)) if r else RatioStats(0.0, 0.0, 0.0)
+
+    def set_constraints(self, gamma):
+        """The radii, aligned with names (a sequence or tensor of T floats) or {name: value} for some of them."""
+        if isinstance(gamma, dict):
+            unknown = set(gamma) - set(self.names)
+            if unknown:
+                raise KeyError(f"FlatTPGM.set_constraints: no trainable parameter named {sorted(unknown)[:4]}")
+            cur = self.gamma.cpu()
+            for i, n in enumerate(self.names):
+                if n in gamma:
+                    cur[i] = float(gamma[n])
+            gamma = cur
+        gamma = torch.as_tensor(gamma, dtype=torch.float32).reshape(-1)
+        if gamma.numel() != len(self.names):
+            raise ValueError(f"FlatTPGM.set_constraints: {gamma.numel()} radii for {len(self.names)} parameter tensors")
+        self.gamma.copy_(gamma)
+        self._ratio_current = False
+
+    def state_dict(self):
+        return {"gamma": self.gamma.clone(), "m": self.gamma_m.clone(), "v": self.gamma_v.clone(), "step": self.step_count,
+                "anchor": self.flat_anchor.clone(), "norm_mode": self.norm_mode, "proj_lr": self.proj_lr}
+
+    def load_state_dict(self, sd):
+        if self._active:
+            raise RuntimeError("FlatTPGM.load_state_dict() between begin() and end()")
+        self.gamma.copy_(sd["gamma"])
+        self.gamma_m.copy_(sd["m"])
+        self.gamma_v.copy_(sd["v"])
+        self.flat_anchor.copy_(sd["anchor"])
+        self.step_count = int(sd["step"])
+        self.norm_mode, self.proj_lr = str(sd["norm_mode"]), float(sd["proj_lr"])
+        self.l1 = 0 if "l2" in self.norm_mode else 1
+        self._ratio_current = False

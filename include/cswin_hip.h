@@ -29,7 +29,7 @@ extern "C" {
 /* Bumped whenever a prototype or struct below changes (1: round 1; 2: round 2 -- stream / precision / storage arguments; 3: round 3 --
  * cswin_attn_fwd writes y0, cswin_attn_bwd reads it).  cswin_abi_version() returns the value the library was built with: a consumer
  * compiled against another header must refuse to call it.  Entry points that are only ADDED (cswin_seg_metrics*, cswin_resize_banded, cswin_argmax_zoom_back, cswin_augment_*,
- * cswin_chunk_sumsq, cswin_norm_finalize, cswin_adamw_flat) do not bump it: every prototype an older consumer binds is unchanged. */
+ * cswin_chunk_sumsq, cswin_norm_finalize, cswin_adamw_flat, cswin_tpgm_*) do not bump it: every prototype an older consumer binds is unchanged. */
 #define CSWIN_ABI_VERSION 4
 
 #define CSWIN_OK 0
@@ -338,6 +338,32 @@ int cswin_norm_finalize(const float* partial, const int* first_chunk, int ntenso
 int cswin_adamw_flat(float* p, const float* g, float* m, float* v, const void* chunks, int nchunks, const float* lr_dev,
                      const float* lr_mult, const float* scalars, double beta1, double beta2, double eps, float weight_decay,
                      float grad_scale, double bc1, double bc2, void* shadow_bf16, void* stream);
+
+/* ---- TPGM, the trainable projection of the continual-learning loop (universal_train.py:391-615; the gradient of the radii is
+ * tpgm.py:47-56's), on the flat buffers and the chunk table above.  Per tensor t, with d = p - anchor:
+ *   norm_t = sqrt(sum d^2) (l1 == 0) or sum |d| (l1 != 0);  cmax_t = max(8 norm_t, 80), head tensors max(10 norm_t, 100);
+ *   ratio_t = hardtanh(clamp(gamma_t, 1e-2, cmax_t) / (norm_t + 1e-8), 0, 1);  projected = anchor + ratio_t d.
+ * No float atomics, fixed summation order, no host synchronisation.
+ *
+ * partial[c] = (sum d^2 or sum |d|, sum g d) over chunk c (2 * nchunks floats); g == NULL: the second entries are not written.
+ * p, anchor, g 16-B aligned. */
+int cswin_tpgm_chunk_stats(const float* p, const float* anchor, const float* g, const void* chunks, int nchunks, int l1,
+                           float* partial, void* stream);
+/* One workgroup.  flags[t]: bit 0 = excluded (ratio exactly 1, gamma never moves), bit 1 = head tensor.  norm[t] is written in
+ * both modes.
+ * mode 0 (ratios): ratio[t] from the current gamma; gm, gv, scalars and the four doubles are not used.
+ * mode 1 (update): dgamma_t = grad_scale * (sum g d) / (norm_t + 1e-8) where 1e-2 <= gamma_t <= cmax_t and the unclamped ratio lies
+ *   strictly inside (0, 1), else 0; clip = min(1, 1 / (sqrt(sum_t dgamma_t^2) + 1e-6)), the tensors added in tensor order; one
+ *   torch.optim.Adam step (betas 0.9 / 0.999, eps 1e-8, no decay, lr = proj_lr, bc1 = 1 - 0.9^step and bc2 = 1 - 0.999^step from the
+ *   host) on every gamma that is not excluded, a zero gradient included; ratio[t] from the new gamma; scalars = [norm of dgamma, clip]. */
+int cswin_tpgm_finalize(const float* partial, const int* first_chunk, int ntensors, int l1, const int* flags, float* gamma,
+                        float* gm, float* gv, double grad_scale, double proj_lr, double bc1, double bc2, int mode, float* ratio,
+                        float* norm, float* scalars, void* stream);
+/* dst = anchor + ratio[t] (src - anchor) and shadow = bf16_rne(dst) when given.  A tensor whose ratio is exactly 1 comes out with
+ * src's bits: copied when src != dst, not stored at all (nor its shadow) when src == dst.  src, anchor, dst 16-B aligned, the
+ * shadow 8-B; src == dst is the only overlap allowed. */
+int cswin_tpgm_project(const float* src, const float* anchor, float* dst, const float* ratio, const void* chunks, int nchunks,
+                       void* shadow_bf16, void* stream);
 
 /* ---- nn.Dropout(p) of the reference (cswin_unet.py:20,25,27 Mlp.drop; :135 proj_drop; :346 pos_drop), fused with the residual
  * add + DropPath row factor that follows it where there is one (:178-179):

@@ -334,6 +334,43 @@ def g9_augment(ref):
         d[f"lab{i}"] = out["label"].numpy().astype(np.uint8)
     save("g9_augment", d)
 
+def g10_tpgm(ref):
+    """The reference's tpgm.py (TPGM.forward, apply=False: the graph from the projected parameters to the constraints is kept) on
+    the toy model of tests/test_tpgm_host.py: l2 mode, init=False, the constraints preset inside (0, norm).  Stored: the inputs, the
+    projected parameters and the constraints' gradients after one backward."""
+    import importlib.util
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_tpgm_host import TOY_NAMES, toy_loss, toy_model
+    spec = importlib.util.spec_from_file_location("ref_tpgm", os.path.join(REF, "tpgm.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    pre = toy_model("golden.anchor", torch.float32)
+    new = toy_model("golden.new", torch.float32, delta_of=pre)
+    d = {}
+    for n, p in new.named_parameters():
+        d["new." + n] = p.detach().numpy().copy()
+    for n, p in pre.named_parameters():
+        d["anchor." + n] = p.detach().numpy().copy()
+    assert tuple(n for n, _ in new.named_parameters()) == TOY_NAMES
+    tp = mod.TPGM(new, norm_mode="l2_norm")
+    tp.init = False
+    norms = [float(torch.norm(a.detach() - b.detach())) for a, b in zip(new.parameters(), pre.parameters())]
+    gamma = np.array([f * n for f, n in zip((0.5, 0.25, 0.75), norms)], np.float32)
+    with torch.no_grad():
+        for c, g in zip(tp.constraints, gamma):
+            c.fill_(float(g))
+    d["gamma"] = gamma
+    d["x"], d["dy"] = det_normal("tpgm.golden.x", (5, 4)), det_normal("tpgm.golden.dy", (5, 2))
+    out = tp(new, pre, x=T(d["x"]))
+    toy_loss(out, T(d["dy"])).backward()
+    d["out"] = out.detach().numpy().copy()
+    for n, p in new.named_parameters():
+        d["projected." + n] = p.detach().numpy().copy()
+    d["gamma_grad"] = np.array([float(c.grad) for c in tp.constraints], np.float32)
+    assert all(np.array_equal(d["gamma"][i], tp.constraints[i].detach().numpy()[0]) for i in range(3))      # _clip left them alone
+    save("g10_tpgm", d)
+
+
 def main():
     torch.manual_seed(0)
     torch.set_num_threads(8)
@@ -342,7 +379,7 @@ def main():
     import networks.cswin_unet as ref
     which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g8", "g9"]
     fns = {"g1": g1_index_maps, "g2": g2_attention, "g3": g3_blocks, "g4": g4_convs, "g5": g5_model,
-           "g8": g8_checkpoint, "g9": g9_augment}
+           "g8": g8_checkpoint, "g9": g9_augment, "g10": g10_tpgm}
     cwd = os.getcwd()
     os.chdir("/tmp")
     try:
