@@ -71,6 +71,17 @@ template <class S> __device__ __forceinline__ u32x2 src_load4_bf16(const S&, con
 __device__ __forceinline__ u32x2 src_load4_bf16(const PlainSrc& s, const float* p) {
     return *reinterpret_cast<const u32x2*>(reinterpret_cast<const __bf16*>(s.p) + (p - s.p));
 }
+// a sample-masked reduction (RowMask below) maps its own rows: row < 0 = past the end, s = the row's DropPath factor.  Only plain
+// matrices are masked; the generic forms exist so that every source compiles.
+template <class S> __device__ __forceinline__ typename S::Row src_mapped_row(const S&, int, float) { return typename S::Row{}; }
+__device__ __forceinline__ PlainSrc::Row src_mapped_row(const PlainSrc& s, int row, float f) {
+    PlainSrc::Row r;
+    r.base = row >= 0 ? s.p + (long)row * s.ld : nullptr;
+    r.s = f;
+    return r;
+}
+template <class S> __device__ __forceinline__ const float* src_row_scale(const S&) { return nullptr; }
+__device__ __forceinline__ const float* src_row_scale(const PlainSrc& s) { return s.row_scale; }
 
 // cat([p0 (c0 cols), p1 (cols - c0)], dim=-1) without materialising it (skip-concat, cswin_unet.py:509-510)
 struct ConcatSrc {
@@ -258,9 +269,22 @@ constexpr int gemm_lds_floats() {
     return (A_ELEMS + B_ELEMS) > NW * EP_WAVE_FLOATS ? (A_ELEMS + B_ELEMS) : NW * EP_WAVE_FLOATS;
 }
 
-template <int BM, int BN, int BK, int KW, bool A_RC, bool B_RC, int VEC, int EPI, bool SCALE_A, int PREC, class ASrc, class BSrc>
+// A weight gradient's sample mask (DropPath: a dropped sample's rows of row_scale . dy are exact zeros).  skip: nsamples per-sample
+// floats, 0 = the sample adds nothing; its rows_per_sample rows of BOTH operands are then not read.  The workgroup reduces over the
+// compacted index c in [0, nk * rows_per_sample) of the nk kept samples, shared out over the host's `splits` slabs:
+//   j = c / rows_per_sample (magic: fdiv, bound checked by the host),  row = kept[j] * rows_per_sample + (c - j * rows_per_sample)
+struct RowMask { const float* skip; int nsamples, rows_per_sample, splits; unsigned magic; };
+constexpr int MASK_MAX_SAMPLES = 256;
+// the ascending list of kept samples and their DropPath factors (1 without row_scale), in LDS beside the operand images
+struct KeptList { int n; int idx[MASK_MAX_SAMPLES]; float scale[MASK_MAX_SAMPLES]; };
+
+// MASKED (weight gradients of plain matrices only): the reduction runs over the kept samples' rows (RowMask); a compile-time
+// variant, the unmasked form is untouched by it
+template <int BM, int BN, int BK, int KW, bool A_RC, bool B_RC, int VEC, int EPI, bool SCALE_A, int PREC, class ASrc, class BSrc,
+          bool MASKED = false>
 __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc& B, const Epilogue& epi, int M, int N, int R,
-                                          int r_per_split, int tiles_m, int tiles_n, int bid, int nblk, int stamp_row) {
+                                          int r_per_split, int tiles_m, int tiles_n, int bid, int nblk, int stamp_row,
+                                          const RowMask* mk = nullptr, KeptList* kept = nullptr) {
     // waves of one k-group: 2 x 2 for 64 x 64 (and larger) tiles, 2 x 1 for 64 x 32: the narrow tile
     // exists for launches whose 64 x 64 tile count is a poor multiple of the 256 CUs (every workgroup is resident at once,
     // so the kernel ends with the most loaded CU)
@@ -294,6 +318,32 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
     const int split = lb / tiles;
     const int tile = lb - split * tiles;
     const int m0 = (tile / tiles_n) * BM, n0 = (tile % tiles_n) * BN;
+    if constexpr (MASKED) {
+        static_assert(!A_RC && !B_RC && VEC == 4 && BM == BN && std::is_same<ASrc, PlainSrc>::value && std::is_same<BSrc, PlainSrc>::value,
+                      "the sample mask serves weight gradients of plain matrices (one row mapping for both operands)");
+        // One wave lists the kept samples in ascending order (ballot + popcount, 64 samples a pass).  Every workgroup of the problem
+        // builds the same list, and from its length the same split ranges: with S slabs, 8 * ceil(ceil(nk rps / S) / 8) rows each.
+        // With every sample kept that is the host's own r_per_split (choose_split makes rps from a count s >= S = ceil(M / rps): M / S
+        // <= rps, and rps - 8 < M / s <= M / S leaves no smaller multiple of 8), so the launch then sums exactly what the unmasked does.
+        if (tid < 64) {
+            int n = 0;
+            for (int s0 = 0; s0 < mk->nsamples; s0 += 64) {
+                const int s = s0 + lane;
+                const bool keep = s < mk->nsamples && mk->skip[s] != 0.0f;
+                const unsigned long long bal = __ballot(keep);
+                if (keep) {
+                    const int at = n + __popcll(bal & ((1ull << lane) - 1ull));
+                    kept->idx[at] = s;
+                    kept->scale[at] = src_row_scale(A) ? src_row_scale(A)[s] : 1.0f;
+                }
+                n += __popcll(bal);
+            }
+            if (tid == 0) kept->n = n;
+        }
+        __syncthreads();
+        R = __builtin_amdgcn_readfirstlane(kept->n) * mk->rows_per_sample;
+        r_per_split = ((R + mk->splits - 1) / mk->splits + 7) / 8 * 8;
+    }
     const int r_begin = split * r_per_split;
     const int r_end = min(R, r_begin + r_per_split);
     const int wm0 = (wave / WGN) * WM, wn0 = (wave % WGN) * WN;
@@ -331,6 +381,21 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
     // a16 (std::true_type / false_type): A is STORED as bf16.  A compile-time copy of the main loop per storage type: a run-time
     // choice between the 8-B and the 16-B load inside fetch() splits it into basic blocks and the loads end up waiting for one another.
     auto fetch = [&](int r0, auto a16, auto b16) {
+        int mrow[QA];                                    // MASKED: the rows of this thread's chunks (both operands'), < 0 past the end
+        float msc[QA];
+        if constexpr (MASKED) {
+#pragma unroll
+            for (int q = 0; q < QA; ++q) {
+                const int c = r0 + a_r + q * A_RPP;
+                mrow[q] = -1;
+                msc[q] = 1.0f;
+                if (c < r_end) {
+                    const int j = fdiv1(c, mk->magic);
+                    mrow[q] = kept->idx[j] * mk->rows_per_sample + (c - j * mk->rows_per_sample);
+                    msc[q] = kept->scale[j];
+                }
+            }
+        }
 #pragma unroll
         for (int q = 0; q < QA; ++q) {
             typename ASrc::Row rr;
@@ -340,7 +405,8 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
                 j = r0 + 4 * a_c;
             } else {
                 const int r = r0 + a_r + q * A_RPP;
-                rr = A.row(r < r_end ? r : 0x7fffffff);
+                if constexpr (MASKED) rr = src_mapped_row(A, mrow[q], msc[q]);
+                else rr = A.row(r < r_end ? r : 0x7fffffff);
                 j = m0 + 4 * a_c;
             }
             if (SCALE_A) pas[q] = rr.s;
@@ -370,7 +436,8 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
                 j = r0 + 4 * b_c;
             } else {
                 const int r = r0 + b_r + q * B_RPP;
-                rr = B.row(r < r_end ? r : 0x7fffffff);
+                if constexpr (MASKED) rr = src_mapped_row(B, mrow[q], 1.0f);
+                else rr = B.row(r < r_end ? r : 0x7fffffff);
                 j = n0 + 4 * b_c;
             }
             if (VEC == 4) {
@@ -636,8 +703,23 @@ struct GemmBatch {
     int M[WGRAD_BATCH], N[WGRAD_BATCH], R[WGRAD_BATCH], rps[WGRAD_BATCH], tm[WGRAD_BATCH], tn[WGRAD_BATCH];
     int first[WGRAD_BATCH + 1];
     int n;
+    RowMask mask[WGRAD_BATCH];   // weight-gradient batches only, read by the *_masked kernels only (skip == NULL: problem without a mask)
 };
 typedef GemmBatch<PlainSrc, PlainSrc> WgradBatch;
+
+// workgroup bid of problem p of a weight-gradient batch (fp32) that has a problem with a sample mask: that problem takes the masked
+// form of the body, the others the same form as in an unmasked launch
+__device__ __forceinline__ void wgrad_masked_batch_body(float* lds, KeptList* kept, const WgradBatch& b, int p, int bid) {
+    if (b.mask[p].skip) {
+        gemm_body<64, 64, 64, 2, false, false, 4, EPI_PLAIN, true, 0, PlainSrc, PlainSrc, true>(
+            lds, b.A[p], b.B[p], b.e[p], b.M[p], b.N[p], b.R[p], b.rps[p], b.tm[p], b.tn[p], bid - b.first[p],
+            b.first[p + 1] - b.first[p], bid, &b.mask[p], kept);
+        return;
+    }
+    gemm_body<64, 64, 64, 2, false, false, 4, EPI_PLAIN, true, 0, PlainSrc, PlainSrc>(
+        lds, b.A[p], b.B[p], b.e[p], b.M[p], b.N[p], b.R[p], b.rps[p], b.tm[p], b.tn[p], bid - b.first[p],
+        b.first[p + 1] - b.first[p], bid);
+}
 
 template <int PREC>
 __global__ __launch_bounds__(512) void gemm_wgrad_batch_kernel(WgradBatch b) {
@@ -647,6 +729,13 @@ __global__ __launch_bounds__(512) void gemm_wgrad_batch_kernel(WgradBatch b) {
     gemm_body<64, 64, 64, 2, false, false, 4, EPI_PLAIN, true, PREC, PlainSrc, PlainSrc>(
         lds, b.A[p], b.B[p], b.e[p], b.M[p], b.N[p], b.R[p], b.rps[p], b.tm[p], b.tn[p], (int)blockIdx.x - b.first[p],
         b.first[p + 1] - b.first[p], (int)blockIdx.x);
+}
+__global__ __launch_bounds__(512) void gemm_wgrad_batch_masked_kernel(WgradBatch b) {
+    int p = 0;
+    while (p + 1 < b.n && (int)blockIdx.x >= b.first[p + 1]) ++p;
+    __shared__ __attribute__((aligned(16))) float lds[gemm_lds_floats<64, 64, 64, 2, false, false>()];
+    __shared__ KeptList kept;
+    wgrad_masked_batch_body(lds, &kept, b, p, (int)blockIdx.x);
 }
 
 // The tail of a CSWinBlock's backward in ONE launch: the data gradient of the qkv Linear (dqkv . Wqkv, the last Linear whose input
@@ -661,9 +750,10 @@ struct BlockTail {
     WgradBatch w;
     ReduceRiders r;          // pending slab reductions of EARLIER launches (the previous block's): the grid's last workgroups
 };
-__global__ __launch_bounds__(512) void gemm_block_tail_kernel(BlockTail t) {
-    constexpr int L0 = gemm_lds_floats<64, 64, 64, 2, true, false>(), L1 = gemm_lds_floats<64, 64, 64, 2, false, false>();
-    __shared__ __attribute__((aligned(16))) float lds[L0 > L1 ? L0 : L1];
+constexpr int BLOCK_TAIL_LDS = gemm_lds_floats<64, 64, 64, 2, true, false>() > gemm_lds_floats<64, 64, 64, 2, false, false>()
+                                   ? gemm_lds_floats<64, 64, 64, 2, true, false>() : gemm_lds_floats<64, 64, 64, 2, false, false>();
+template <bool MASKED>
+__device__ __forceinline__ void block_tail_body(float (&lds)[BLOCK_TAIL_LDS], KeptList* kept, const BlockTail& t) {
     const WgradBatch& b = t.w;
     const int nw = b.first[b.n];
     if ((int)blockIdx.x >= nw + t.nd) {    // riders: 256-thread reduction workgroups (the upper four waves leave)
@@ -680,9 +770,23 @@ __global__ __launch_bounds__(512) void gemm_block_tail_kernel(BlockTail t) {
     const int bid = (int)blockIdx.x;
     int p = 0;
     while (p + 1 < b.n && bid >= b.first[p + 1]) ++p;
-    gemm_body<64, 64, 64, 2, false, false, 4, EPI_PLAIN, true, 0, PlainSrc, PlainSrc>(
-        lds, b.A[p], b.B[p], b.e[p], b.M[p], b.N[p], b.R[p], b.rps[p], b.tm[p], b.tn[p], bid - b.first[p],
-        b.first[p + 1] - b.first[p], (int)blockIdx.x);
+    if constexpr (MASKED) {
+        wgrad_masked_batch_body(lds, kept, b, p, bid);
+    } else {
+        gemm_body<64, 64, 64, 2, false, false, 4, EPI_PLAIN, true, 0, PlainSrc, PlainSrc>(
+            lds, b.A[p], b.B[p], b.e[p], b.M[p], b.N[p], b.R[p], b.rps[p], b.tm[p], b.tn[p], bid - b.first[p],
+            b.first[p + 1] - b.first[p], (int)blockIdx.x);
+    }
+}
+__global__ __launch_bounds__(512) void gemm_block_tail_kernel(BlockTail t) {
+    __shared__ __attribute__((aligned(16))) float lds[BLOCK_TAIL_LDS];
+    block_tail_body<false>(lds, nullptr, t);
+}
+// the same launch with a sample mask on at least one of its weight gradients
+__global__ __launch_bounds__(512) void gemm_block_tail_masked_kernel(BlockTail t) {
+    __shared__ __attribute__((aligned(16))) float lds[BLOCK_TAIL_LDS];
+    __shared__ KeptList kept;
+    block_tail_body<true>(lds, &kept, t);
 }
 
 // The four parity classes of a stride-2 3x3 convolution's data gradient (ConvTS2SrcT) are independent GEMMs over a quarter of
@@ -882,13 +986,17 @@ bool wgrad_aligned(const cswin_wgrad_desc& p) {
 
 // what may ride at the end of the weight-gradient batch's grid: a plain fp32 data gradient dx[M,K] = dy[M,N] @ w[N,K] (dy == NULL:
 // none; cswin_linear_bwd_tail) and reductions left pending by earlier launches.  who: the entry point, for its error text.
-struct TailExtras { const char* who; const float* dy; const float* w; float* dx; int M, N, K; const cswin_reduce_job* jobs; int njobs; };
+struct TailExtras {
+    const char* who; const float* dy; const float* w; float* dx; int M, N, K; const cswin_reduce_job* jobs; int njobs;
+    // sample masks of the weight gradients (NULL: none): skip[i] (NULL: problem i has none) holds nsamples[i] floats, see RowMask
+    const float* const* skip; const int* nsamples;
+};
 
 int wgrad_batch_impl(const cswin_wgrad_desc* d, int n, cswin_reduce_job* deferred, const TailExtras& x, void* stream) {
     CSWIN_REQUIRE(x.njobs >= 0 && x.njobs <= CSWIN_TAIL_RIDER_JOBS && (x.njobs == 0 || x.jobs), CSWIN_ERR_SHAPE,
                   "%s: 0..%d pending reductions", x.who, CSWIN_TAIL_RIDER_JOBS);
     CSWIN_REQUIRE(d && deferred && n >= 1 && n <= WGRAD_BATCH, CSWIN_ERR_SHAPE, "linear_bwd_weight_batch: 1..%d problems and their deferred slots", WGRAD_BATCH);
-    bool fast = true, any_bf16 = false;
+    bool fast = true, any_bf16 = false, any_mask = false;
     const int precision = d[0].precision;
     CSWIN_CHECK_PRECISION(precision, "linear_bwd_weight_batch");
     for (int i = 0; i < n; ++i) {
@@ -900,7 +1008,19 @@ int wgrad_batch_impl(const cswin_wgrad_desc* d, int n, cswin_reduce_job* deferre
         CSWIN_REQUIRE(d[i].workspace && d[i].ws_bytes >= need, CSWIN_ERR_WORKSPACE, "linear_bwd_weight_batch: workspace %zu < %zu", d[i].ws_bytes, need);
         fast = fast && wgrad_aligned(d[i]);
         any_bf16 = any_bf16 || d[i].io_bf16;
+        if (x.skip && x.skip[i]) {
+            // the contract of a mask is that a dropped sample's rows are NOT READ: what cannot keep it is refused, not run unmasked
+            any_mask = true;
+            CSWIN_REQUIRE(precision == 0, CSWIN_ERR_UNSUPPORTED, "%s: a sample mask needs precision 0", x.who);
+            CSWIN_REQUIRE(x.nsamples && x.nsamples[i] >= 1 && x.nsamples[i] <= MASK_MAX_SAMPLES, CSWIN_ERR_SHAPE,
+                          "%s: problem %d's mask must have 1..%d samples", x.who, i, MASK_MAX_SAMPLES);
+            CSWIN_REQUIRE(d[i].rows_per_sample > 0 && (long)x.nsamples[i] * d[i].rows_per_sample == d[i].M, CSWIN_ERR_SHAPE,
+                          "%s: problem %d's mask: nsamples * rows_per_sample != M", x.who, i);
+            CSWIN_REQUIRE(fdiv_exact(d[i].M, d[i].rows_per_sample), CSWIN_ERR_UNSUPPORTED,
+                          "%s: problem %d's mask: M * rows_per_sample must stay below 2^32", x.who, i);
+        }
     }
+    CSWIN_REQUIRE(!any_mask || fast, CSWIN_ERR_ALIGN, "%s: a sample mask needs N, K multiples of 4 and 16-B aligned operands", x.who);
     const bool has_dgrad = x.dy != nullptr, extra = has_dgrad || x.njobs > 0;
     // the data gradient as a GEMM problem (as cswin_linear_bwd_data poses it): M x K outputs, reduction N in one split
     const PlainSrc gA = {x.dy, x.N, x.M, x.N, nullptr, 1, 0}, gB = {x.w, x.K, x.N, x.K, nullptr, 1, 0};      // gB: S(i = n (reduction), j = k)
@@ -987,6 +1107,7 @@ int wgrad_batch_impl(const cswin_wgrad_desc* d, int n, cswin_reduce_job* deferre
         push(b, PlainSrc{d[i].dy, N, M, N, d[i].row_scale, d[i].row_scale ? d[i].rows_per_sample : 1},   // S(i = m (reduction), j = n)
              PlainSrc{d[i].x, K, M, K, nullptr, 1}, slabs.epilogue(d[i].dbias != nullptr), N, K, M, rps, splits);
         deferred[i] = slabs.job(d[i].dw, d[i].dbias, splits);
+        if (x.skip && x.skip[i]) b.mask[i] = RowMask{x.skip[i], x.nsamples[i], d[i].rows_per_sample, splits, fdiv_magic(d[i].rows_per_sample)};
     }
     const int blocks = b.first[n];
     if (ride) {
@@ -1007,7 +1128,10 @@ int wgrad_batch_impl(const cswin_wgrad_desc* d, int n, cswin_reduce_job* deferre
             t.r.njobs = x.njobs;
         }
         static_assert(sizeof(BlockTail) <= 4096, "kernel argument block");
-        hipLaunchKernelGGL(gemm_block_tail_kernel, dim3(blocks + t.nd + rblocks), dim3(512), 0, (hipStream_t)stream, t);
+        if (any_mask) hipLaunchKernelGGL(gemm_block_tail_masked_kernel, dim3(blocks + t.nd + rblocks), dim3(512), 0, (hipStream_t)stream, t);
+        else hipLaunchKernelGGL(gemm_block_tail_kernel, dim3(blocks + t.nd + rblocks), dim3(512), 0, (hipStream_t)stream, t);
+    } else if (any_mask) {
+        hipLaunchKernelGGL(gemm_wgrad_batch_masked_kernel, dim3(blocks), dim3(512), 0, (hipStream_t)stream, b);
     } else if (precision == 1) {
         hipLaunchKernelGGL(gemm_wgrad_batch_kernel<1>, dim3(blocks), dim3(512), 0, (hipStream_t)stream, b);
     } else {
@@ -1072,6 +1196,13 @@ extern "C" {
 // slots 0-3 s_memtime at start / first tile staged / main loop done / epilogue done, 4 the hardware id register, 5-6 s_memrealtime
 // at start / end (7 unused)
 void cswin_debug_set_stamps(void* p) { g_stamps = (long long*)p; }
+
+// the unmasked batch entry points are the masked ones without masks (defined below, beside them)
+int cswin_linear_bwd_weight_batch_masked(const cswin_wgrad_desc* d, int n, cswin_reduce_job* deferred, const cswin_reduce_job* pending,
+                                         int npending, const float* const* skip, const int* nsamples, void* stream);
+int cswin_linear_bwd_tail_masked(const float* dy, const float* w, float* dx, int M, int N, int K, const cswin_wgrad_desc* d, int n,
+                                 cswin_reduce_job* deferred, const cswin_reduce_job* pending, int npending, const float* const* skip,
+                                 const int* nsamples, void* stream);
 
 int cswin_linear_fwd(const float* x, const float* x2, int k_split, const float* w, const float* bias, float* y,
                      float* y_act, const float* residual, const float* row_scale, int rows_per_sample, int M, int N,
@@ -1190,7 +1321,15 @@ int cswin_linear_bwd_weight(const float* dy, const float* x, const float* x2, in
 // aligned / a multiple of 4 in N and K.
 int cswin_linear_bwd_weight_batch(const cswin_wgrad_desc* d, int n, cswin_reduce_job* deferred, const cswin_reduce_job* pending, int npending,
                                   void* stream) {
-    return wgrad_batch_impl(d, n, deferred, TailExtras{"linear_bwd_weight_batch", nullptr, nullptr, nullptr, 0, 0, 0, pending, npending}, stream);
+    return cswin_linear_bwd_weight_batch_masked(d, n, deferred, pending, npending, nullptr, nullptr, stream);
+}
+
+// The same with sample masks: skip[i] (or NULL) = nsamples[i] per-sample floats of problem i, M = nsamples[i] * rows_per_sample; a
+// sample whose float is 0 adds nothing to dw / dbias and its rows of dy and x are not read (fp32, aligned problems only)
+int cswin_linear_bwd_weight_batch_masked(const cswin_wgrad_desc* d, int n, cswin_reduce_job* deferred, const cswin_reduce_job* pending,
+                                         int npending, const float* const* skip, const int* nsamples, void* stream) {
+    return wgrad_batch_impl(d, n, deferred,
+                            TailExtras{"linear_bwd_weight_batch", nullptr, nullptr, nullptr, 0, 0, 0, pending, npending, skip, nsamples}, stream);
 }
 
 // The tail of a CSWinBlock's backward: dx[M,K] = dy[M,N] @ w[N,K] (the qkv Linear's data gradient, plain fp32, no epilogue extras)
@@ -1198,8 +1337,15 @@ int cswin_linear_bwd_weight_batch(const cswin_wgrad_desc* d, int n, cswin_reduce
 // launch (gemm_block_tail_kernel); otherwise the data gradient is launched first and the batch follows -- same results either way.
 int cswin_linear_bwd_tail(const float* dy, const float* w, float* dx, int M, int N, int K, const cswin_wgrad_desc* d, int n,
                           cswin_reduce_job* deferred, const cswin_reduce_job* pending, int npending, void* stream) {
+    return cswin_linear_bwd_tail_masked(dy, w, dx, M, N, K, d, n, deferred, pending, npending, nullptr, nullptr, stream);
+}
+
+// skip / nsamples: masks of the weight gradients as for cswin_linear_bwd_weight_batch_masked; the data gradient has none
+int cswin_linear_bwd_tail_masked(const float* dy, const float* w, float* dx, int M, int N, int K, const cswin_wgrad_desc* d, int n,
+                                 cswin_reduce_job* deferred, const cswin_reduce_job* pending, int npending, const float* const* skip,
+                                 const int* nsamples, void* stream) {
     CSWIN_REQUIRE(dy && w && dx && M > 0 && N > 0 && K > 0, CSWIN_ERR_SHAPE, "linear_bwd_tail: bad data-gradient arguments");
-    return wgrad_batch_impl(d, n, deferred, TailExtras{"linear_bwd_tail", dy, w, dx, M, N, K, pending, npending}, stream);
+    return wgrad_batch_impl(d, n, deferred, TailExtras{"linear_bwd_tail", dy, w, dx, M, N, K, pending, npending, skip, nsamples}, stream);
 }
 
 // -------- convolutions on the (B, H*W, C) token layout (NHWC), implicit GEMM -----------------------------------

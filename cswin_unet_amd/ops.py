@@ -278,6 +278,9 @@ def _linear_bwd_weight(dy, x, dw, db, slab=None, *, x2=None, row_scale=None):
          ptr(dw), ptr(db), ws, nbytes, M, N, K, job, precision(), stream())
 
 
+MAX_MASK_SAMPLES = 256     # nsamples bound of the *_masked weight-gradient entry points (include/cswin_hip.h)
+
+
 def _fill_wgrad(d, dy, x, row_scale, dw, dbias, workspace, ws_bytes):
     """One WgradDesc of cswin_linear_bwd_weight_batch / _tail.  workspace: device pointer."""
     d.dy, d.x, d.row_scale, d.dw, d.dbias = (t.data_ptr() if t is not None else None for t in (dy, x, row_scale, dw, dbias))
@@ -675,8 +678,15 @@ class _CSWinBlock(Function):
         pend, npend, riders = _pass.take_pending()
         if precision() == 0:
             # fp32: the qkv data gradient rides in the weight-gradient batch's launch as well (both only wait for dqkv)
-            call("cswin_linear_bwd_tail", ptr(dqkv), ptr(wqkv), ptr(dh1), M, 3 * C, C, ctypes.cast(wg, ctypes.c_void_p), 4,
-                 _job_ptr(wjobs), pend, npend, stream())
+            tail = (ptr(dqkv), ptr(wqkv), ptr(dh1), M, 3 * C, C, ctypes.cast(wg, ctypes.c_void_p), 4, _job_ptr(wjobs), pend, npend)
+            masks = (rs2, rs2, rs1, rs1) if B <= MAX_MASK_SAMPLES else (None,) * 4
+            if any(m is not None for m in masks):
+                # DropPath: a sample with rs2 == 0 has zero rows in rs2 . dy and in dpre, one with rs1 == 0 in rs1 . dx1 and in dqkv
+                # (the attention backward of datt = 0), so the factors are the sample masks of the weight gradients those feed
+                skip = (ctypes.c_void_p * 4)(*[m.data_ptr() if m is not None else None for m in masks])
+                call("cswin_linear_bwd_tail_masked", *tail, skip, _int_array([B] * 4), stream())
+            else:
+                call("cswin_linear_bwd_tail", *tail, stream())
         else:
             _linear_bwd_weight_batch(wg, wjobs, (pend, npend))
             _linear_bwd_data(dqkv, sq, dh1)

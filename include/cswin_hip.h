@@ -173,6 +173,20 @@ int cswin_linear_bwd_weight_batch(const cswin_wgrad_desc* problems, int n, cswin
  * pending / npending as for cswin_linear_bwd_weight_batch. */
 int cswin_linear_bwd_tail(const float* dy, const float* w, float* dx, int M, int N, int K, const cswin_wgrad_desc* problems, int n,
                           cswin_reduce_job* deferred, const cswin_reduce_job* pending, int npending, void* stream);
+/* The two calls above with SAMPLE MASKS on the weight gradients (DropPath: the dy rows of a dropped sample are exact zeros, so they
+ * add nothing to dw / dbias).  skip: host array of n device pointers (an entry, or skip itself, may be NULL: no mask); skip[i] holds
+ * nsamples[i] floats, one per sample of rows_per_sample consecutive rows, M == nsamples[i] * rows_per_sample.  A sample whose float is
+ * 0 is left out of the reduction and its rows of dy and x are NOT READ (they may hold anything); the kept samples' rows are shared
+ * out evenly over the launch's workgroups, so the launch gets shorter by the dropped share.  row_scale keeps its meaning.  With every
+ * sample kept the results equal the unmasked call's bit for bit; otherwise the summation is regrouped (last-bit differences).
+ * Masks need precision 0, nsamples <= 256, N and K multiples of 4 and 16-B aligned operands: anything else is an error return,
+ * never an unmasked run.  The unmasked calls are these with skip == NULL. */
+int cswin_linear_bwd_weight_batch_masked(const cswin_wgrad_desc* problems, int n, cswin_reduce_job* deferred,
+                                         const cswin_reduce_job* pending, int npending, const float* const* skip, const int* nsamples,
+                                         void* stream);
+int cswin_linear_bwd_tail_masked(const float* dy, const float* w, float* dx, int M, int N, int K, const cswin_wgrad_desc* problems, int n,
+                                 cswin_reduce_job* deferred, const cswin_reduce_job* pending, int npending, const float* const* skip,
+                                 const int* nsamples, void* stream);
 /* jobs: host array of 1..48 pending reductions (the workspaces they point into must still be alive) */
 int cswin_rows_sum_multi(const cswin_reduce_job* jobs, int njobs, void* stream);
 
