@@ -77,7 +77,6 @@ struct AttnParams {
 
 // q / k / v and their gradients may be stored as bf16.  Addresses are computed in ELEMENTS on fp32-typed pointers (a plain
 // fp32 access when qkv_bf16 == 0); for bf16 storage the element offset is re-applied to the bf16 base.
-typedef __bf16 attn_bf16x4 __attribute__((ext_vector_type(4)));
 // Storage is a COMPILE-TIME parameter of every kernel that touches q / k / v (Q16): a run-time choice between 8-B and 16-B loads
 // splits the load sequences into basic blocks whose loads then wait for one another.  Loads come in two halves: ldq_raw issues
 // the load (4 fp32, or 4 bf16 as two raw dwords) and qcv widens it where the value is consumed.  The raw bf16 pair is an
@@ -99,7 +98,7 @@ template <bool Y16> __device__ __forceinline__ typename QRaw<Y16>::type ldy_raw(
 }
 template <bool Q16> __device__ __forceinline__ f32x4 ldq(const AttnParams& p, const float* elem_ptr) { return qcv(ldq_raw<Q16>(p, elem_ptr)); }
 template <bool Q16> __device__ __forceinline__ void stdq(const AttnParams& p, float* elem_ptr, f32x4 v) {
-    if constexpr (Q16) *reinterpret_cast<attn_bf16x4*>(reinterpret_cast<__bf16*>(p.dqkv) + (elem_ptr - p.dqkv)) = __builtin_convertvector(v, attn_bf16x4);
+    if constexpr (Q16) *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(p.dqkv) + (elem_ptr - p.dqkv)) = __builtin_convertvector(v, bf16x4);
     else *reinterpret_cast<f32x4*>(elem_ptr) = v;
 }
 
@@ -194,9 +193,9 @@ __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
 //           accumulator tile: P / dS tiles are B operands as they stand).
 typedef short attn_s16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 attn_bf16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ attn_s16x4 pk4(f32x4 v) { return __builtin_bit_cast(attn_s16x4, __builtin_convertvector(v, attn_bf16x4)); }
+__device__ __forceinline__ attn_s16x4 pk4(f32x4 v) { return __builtin_bit_cast(attn_s16x4, __builtin_convertvector(v, bf16x4)); }
 __device__ __forceinline__ attn_bf16x8 pk8(f32x4 lo, f32x4 hi) {
-    return __builtin_shufflevector(__builtin_convertvector(lo, attn_bf16x4), __builtin_convertvector(hi, attn_bf16x4), 0, 1, 2, 3, 4, 5, 6, 7);
+    return __builtin_shufflevector(__builtin_convertvector(lo, bf16x4), __builtin_convertvector(hi, bf16x4), 0, 1, 2, 3, 4, 5, 6, 7);
 }
 __device__ __forceinline__ f32x4 mfma16(attn_s16x4 a, attn_s16x4 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ f32x4 mfma32(attn_bf16x8 a, attn_bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
@@ -429,10 +428,10 @@ __global__ __launch_bounds__(64 * (QS == 2 ? (NT + 1) / 2 : (NT < 8 ? NT : 8))) 
                 const f32x4 out0 = o[df] * inv, out = out0 + acc;
                 if (d0 < p.hd) {
                     const long yi = ((long)w.b * L + lq) * p.C + ch0 + d0;
-                    if constexpr (Y16) *reinterpret_cast<attn_bf16x4*>(reinterpret_cast<__bf16*>(p.y) + yi) = __builtin_convertvector(out, attn_bf16x4);
+                    if constexpr (Y16) *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(p.y) + yi) = __builtin_convertvector(out, bf16x4);
                     else *reinterpret_cast<f32x4*>(p.y + yi) = out;
                     if (p.y0) {
-                        if constexpr (Y16) *reinterpret_cast<attn_bf16x4*>(reinterpret_cast<__bf16*>(p.y0) + yi) = __builtin_convertvector(out0, attn_bf16x4);
+                        if constexpr (Y16) *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(p.y0) + yi) = __builtin_convertvector(out0, bf16x4);
                         else *reinterpret_cast<f32x4*>(p.y0 + yi) = out0;
                     }
                 }
@@ -651,10 +650,10 @@ __global__ __launch_bounds__(64 * (QS == 2 ? (NT + 1) / 2 : NT), 4) void attn_fw
                     const f32x4 out0 = o[df] * inv, out = out0 + acc;
                     if (d0 < p.hd) {
                         const long yi = ((long)w.b * L + lq) * p.C + ch0 + d0;
-                        if constexpr (Y16) *reinterpret_cast<attn_bf16x4*>(reinterpret_cast<__bf16*>(p.y) + yi) = __builtin_convertvector(out, attn_bf16x4);
+                        if constexpr (Y16) *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(p.y) + yi) = __builtin_convertvector(out, bf16x4);
                         else *reinterpret_cast<f32x4*>(p.y + yi) = out;
                         if (p.y0) {
-                            if constexpr (Y16) *reinterpret_cast<attn_bf16x4*>(reinterpret_cast<__bf16*>(p.y0) + yi) = __builtin_convertvector(out0, attn_bf16x4);
+                            if constexpr (Y16) *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(p.y0) + yi) = __builtin_convertvector(out0, bf16x4);
                             else *reinterpret_cast<f32x4*>(p.y0 + yi) = out0;
                         }
                     }

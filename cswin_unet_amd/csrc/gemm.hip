@@ -35,7 +35,6 @@ namespace {
 constexpr int BKMAX = 64;     // largest reduction tile (split sizes are multiples of it)
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 // matmul precision is an ARGUMENT of every entry point (no library state): 0 = exact fp32 MFMA (the parity path);
 // 1 = operands rounded to bf16 while they are staged into LDS, v_mfma_f32_32x32x16_bf16, fp32 accumulation and fp32

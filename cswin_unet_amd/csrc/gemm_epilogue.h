@@ -4,7 +4,6 @@
 
 namespace {
 
-typedef __bf16 epi_bf16x4 __attribute__((ext_vector_type(4)));
 // widen 4 bf16 held as two raw dwords.  Raw bf16 bits travel in INTEGER vectors: hipcc 7.2 miscompiles bit casts of the
 // elements of a 2-float vector (element 1 reads element 0).
 __device__ __forceinline__ f32x4 widen_bf16x4(u32x2 raw) {
@@ -12,7 +11,7 @@ __device__ __forceinline__ f32x4 widen_bf16x4(u32x2 raw) {
                  __builtin_bit_cast(float, raw[1] << 16), __builtin_bit_cast(float, raw[1] & 0xffff0000u)};
 }
 __device__ __forceinline__ void epi_store4(float* base, long idx, f32x4 v, int bf16) {
-    if (bf16) *reinterpret_cast<epi_bf16x4*>(reinterpret_cast<__bf16*>(base) + idx) = __builtin_convertvector(v, epi_bf16x4);
+    if (bf16) *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(base) + idx) = __builtin_convertvector(v, bf16x4);
     else *reinterpret_cast<f32x4*>(base + idx) = v;
 }
 

@@ -7,9 +7,8 @@
 namespace {
 
 // y may be STORED as bf16 (bf16 activation storage: the output feeds only GEMMs, which round it to bf16 anyway)
-typedef __bf16 ln_bf16x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void ln_store4(float* y, long idx, f32x4 v, int y_bf16) {
-    if (y_bf16) *reinterpret_cast<ln_bf16x4*>(reinterpret_cast<__bf16*>(y) + idx) = __builtin_convertvector(v, ln_bf16x4);
+    if (y_bf16) *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(y) + idx) = __builtin_convertvector(v, bf16x4);
     else *reinterpret_cast<f32x4*>(y + idx) = v;
 }
 
@@ -116,7 +115,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ d
             for (int e = 0; e < 4; ++e) o4[e] = rs * (gy[v][e] - s1 - xh[v][e] * s2);
             if (dres) o4 += *reinterpret_cast<const f32x4*>(dres + off);
             *reinterpret_cast<f32x4*>(dx + off) = o4;
-            if (dx16) *reinterpret_cast<ln_bf16x4*>(dx16 + off) = __builtin_convertvector(o4, ln_bf16x4);      // bf16 twin for the GEMMs
+            if (dx16) *reinterpret_cast<bf16x4*>(dx16 + off) = __builtin_convertvector(o4, bf16x4);      // bf16 twin for the GEMMs
         }
     }
     // reduce the RPB row-groups of this block, then write one partial slab
@@ -226,7 +225,7 @@ __global__ __launch_bounds__(256) void ln_bwd_generic_kernel(const float* __rest
                 for (int e = 0; e < 4; ++e) o4[e] = rs * (gy[v][e] - s1 - xh[v][e] * s2);
                 if (dres) o4 += *reinterpret_cast<const f32x4*>(dres + row * C + 4 * ch);
                 *reinterpret_cast<f32x4*>(dx + row * C + 4 * ch) = o4;
-                if (dx16) *reinterpret_cast<ln_bf16x4*>(dx16 + row * C + 4 * ch) = __builtin_convertvector(o4, ln_bf16x4);
+                if (dx16) *reinterpret_cast<bf16x4*>(dx16 + row * C + 4 * ch) = __builtin_convertvector(o4, bf16x4);
             }
         }
     }

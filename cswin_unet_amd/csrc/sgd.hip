@@ -3,14 +3,19 @@
 // gradients into the flat gradient buffer that RCCL all-reduces.  One launch each instead of 463.
 //   g' = g * grad_scale + wd * p ;  m = mu * m + g' ;  p -= lr * m      (m starts at 0, so step 1 gives m = g')
 // lr is read from DEVICE memory so a captured hipGraph can be replayed under the poly schedule.
-#include "common.h"
+#include "flat_chunks.h"
 
 namespace {
+
+// workgroups of a grid-stride launch over n floats, 16 B per thread and trip
+static inline int flat_grid(long n) {
+    const long b = (n / 4 + 255) / 256;
+    return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
+}
 
 __global__ __launch_bounds__(256) void sgd_flat_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                         float* __restrict__ m, long n, const float* __restrict__ lr_dev,
                                                         float momentum, float wd, float grad_scale, __bf16* __restrict__ shadow) {
-    typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
     const float lr = lr_dev[0];
     const long n4 = n / 4;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
@@ -49,19 +54,17 @@ __global__ __launch_bounds__(256) void multi_copy_kernel(const CopyChunk* __rest
 
 // bf16 gradient wire (BASELINE configs[2]: "RCCL all-reduce bf16"): the fp32 flat gradient bucket is rounded to bf16 (RNE,
 // v_cvt_pk_bf16_f32: NaN stays NaN) into a wire buffer that the collective sums, then widened back in place of the bucket.
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-
 __global__ __launch_bounds__(256) void pack_bf16_kernel(const float* __restrict__ src, __bf16* __restrict__ dst, long n, float scale) {
     const long n4 = n / 4;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256)
-        reinterpret_cast<bf16x4_t*>(dst)[i] = __builtin_convertvector(reinterpret_cast<const f32x4*>(src)[i] * scale, bf16x4_t);
+        reinterpret_cast<bf16x4*>(dst)[i] = __builtin_convertvector(reinterpret_cast<const f32x4*>(src)[i] * scale, bf16x4);
     for (long i = n4 * 4 + (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) dst[i] = (__bf16)(src[i] * scale);
 }
 
 __global__ __launch_bounds__(256) void unpack_bf16_kernel(const __bf16* __restrict__ src, float* __restrict__ dst, long n) {
     const long n4 = n / 4;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256)
-        reinterpret_cast<f32x4*>(dst)[i] = __builtin_convertvector(reinterpret_cast<const bf16x4_t*>(src)[i], f32x4);
+        reinterpret_cast<f32x4*>(dst)[i] = __builtin_convertvector(reinterpret_cast<const bf16x4*>(src)[i], f32x4);
     for (long i = n4 * 4 + (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) dst[i] = (float)src[i];
 }
 
@@ -73,8 +76,7 @@ extern "C" {
 int cswin_pack_bf16_scaled(const float* src, void* dst, long n, float scale, void* stream) {
     CSWIN_REQUIRE(src && dst && n > 0, CSWIN_ERR_SHAPE, "pack_bf16: bad arguments");
     CSWIN_REQUIRE((((uintptr_t)src) & 15) == 0 && (((uintptr_t)dst) & 7) == 0, CSWIN_ERR_ALIGN, "pack_bf16: src 16-B / dst 8-B alignment required");
-    long b = (n / 4 + 255) / 256;
-    hipLaunchKernelGGL(pack_bf16_kernel, dim3((int)(b < 1 ? 1 : (b > 4096 ? 4096 : b))), dim3(256), 0, (hipStream_t)stream, src, (__bf16*)dst, n, scale);
+    hipLaunchKernelGGL(pack_bf16_kernel, dim3(flat_grid(n)), dim3(256), 0, (hipStream_t)stream, src, (__bf16*)dst, n, scale);
     CSWIN_LAUNCH_CHECK();
     return CSWIN_OK;
 }
@@ -84,8 +86,7 @@ int cswin_pack_bf16(const float* src, void* dst, long n, void* stream) { return 
 int cswin_unpack_bf16(const void* src, float* dst, long n, void* stream) {
     CSWIN_REQUIRE(src && dst && n > 0, CSWIN_ERR_SHAPE, "unpack_bf16: bad arguments");
     CSWIN_REQUIRE((((uintptr_t)dst) & 15) == 0 && (((uintptr_t)src) & 7) == 0, CSWIN_ERR_ALIGN, "unpack_bf16: dst 16-B / src 8-B alignment required");
-    long b = (n / 4 + 255) / 256;
-    hipLaunchKernelGGL(unpack_bf16_kernel, dim3((int)(b < 1 ? 1 : (b > 4096 ? 4096 : b))), dim3(256), 0, (hipStream_t)stream, (const __bf16*)src, dst, n);
+    hipLaunchKernelGGL(unpack_bf16_kernel, dim3(flat_grid(n)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)src, dst, n);
     CSWIN_LAUNCH_CHECK();
     return CSWIN_OK;
 }
@@ -93,11 +94,8 @@ int cswin_unpack_bf16(const void* src, float* dst, long n, void* stream) {
 int cswin_sgd_flat(float* p, const float* g, float* m, long n, const float* lr_dev, float momentum, float weight_decay,
                    float grad_scale, void* shadow_bf16, void* stream) {
     CSWIN_REQUIRE(p && g && m && lr_dev && n > 0, CSWIN_ERR_SHAPE, "sgd_flat: bad arguments");
-    CSWIN_REQUIRE(((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m)) & 15) == 0, CSWIN_ERR_ALIGN, "sgd_flat: buffers must be 16-B aligned");
-    CSWIN_REQUIRE(!shadow_bf16 || (((uintptr_t)shadow_bf16) & 7) == 0, CSWIN_ERR_ALIGN, "sgd_flat: the bf16 shadow must be 8-B aligned");
-    long b = (n / 4 + 255) / 256;
-    int grid = (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
-    hipLaunchKernelGGL(sgd_flat_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, n, lr_dev, momentum, weight_decay, grad_scale, (__bf16*)shadow_bf16);
+    if (int e = flat_align_check("sgd_flat", (uintptr_t)p | (uintptr_t)g | (uintptr_t)m, nullptr, shadow_bf16)) return e;      // no chunk table: the whole buffer, pad words included
+    hipLaunchKernelGGL(sgd_flat_kernel, dim3(flat_grid(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, n, lr_dev, momentum, weight_decay, grad_scale, (__bf16*)shadow_bf16);
     CSWIN_LAUNCH_CHECK();
     return CSWIN_OK;
 }

@@ -8,8 +8,8 @@
 //   dL/dgamma_t = (sum gtilde d) / (norm_t + 1e-8)    where 1e-2 <= gamma_t <= cmax_t and 0 < c_t / (norm_t + 1e-8) < 1, else 0
 //                                                     (torch's clamp passes its bounds, its hardtanh does not)
 //
-// Three launches walk the STATIC chunk table of adamw.hip (records {element offset, n <= 16384, tensor}, one 256-thread workgroup
-// each, an f32x4 body and a scalar tail of at most three elements, no pad word read or written):
+// Three launches walk the static chunk table of flat_chunks.h (one 256-thread workgroup per chunk, an f32x4 body and a scalar tail
+// of at most three elements, no pad word read or written):
 //
 //   cswin_tpgm_chunk_stats  partial[c] = (sum d^2 or sum |d|, sum g d) over chunk c
 //   cswin_tpgm_finalize     one workgroup, thread k owns tensors k, k + 256, ...: the chunk partials added in chunk order, then
@@ -18,64 +18,39 @@
 //   cswin_tpgm_project      dst = anchor + ratio_t (src - anchor), and its bf16 shadow; a tensor whose ratio is exactly 1 keeps
 //                           src's bits (anchor + 1 (src - anchor) is not src in fp32, and a tensor inside its ball must not drift)
 //
-// There is no float atomic and no host synchronisation: every sum has a fixed order (a thread's trips, the xor butterfly of a
-// wave, the four waves as (w0 + w1) + (w2 + w3), chunks in chunk order, tensors in tensor order), so two runs give the same bits.
+// There is no float atomic and no host synchronisation: every sum has flat_chunks.h's fixed order, so two runs give the same bits.
 // A non-finite gradient is reported, not repaired: it makes the gamma-gradient norm, the clip coefficient and every gamma NaN.
-#include "common.h"
+#include "flat_chunks.h"
 
 namespace {
 
-struct AdamChunk { long long off; int n; int tensor; };      // adamw.hip's record (optim.chunk_table builds it)
-static_assert(sizeof(AdamChunk) == 16, "the chunk record is 16 bytes");
-
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
 constexpr int FLAG_EXCLUDED = 1, FLAG_HEAD = 2;
 constexpr float GAMMA_MIN = 1e-2f, NORM_EPS = 1e-8f;
-constexpr float ADAM_B1 = 0.9f, ADAM_OMB1 = (float)(1.0 - 0.9), ADAM_B2 = 0.999f, ADAM_OMB2 = (float)(1.0 - 0.999), ADAM_EPS = 1e-8f;
-
-// as adamw.hip's: the same value in every thread; red: 4 floats of LDS per reduced value
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 template <bool L1>
 __global__ __launch_bounds__(256) void tpgm_chunk_stats_kernel(const float* __restrict__ p, const float* __restrict__ anchor,
-                                                                const float* __restrict__ g, const AdamChunk* __restrict__ chunks,
+                                                                const float* __restrict__ g, const FlatChunk* __restrict__ chunks,
                                                                 float* __restrict__ partial) {
-    __shared__ float red[8];
-    const AdamChunk c = chunks[blockIdx.x];
+    const FlatChunk c = chunks[blockIdx.x];
     const float* pp = p + c.off;
     const float* ap = anchor + c.off;
     const float* gp = g ? g + c.off : nullptr;
-    const int n4 = c.n >> 2;
-    f32x4 an = {0.f, 0.f, 0.f, 0.f}, ad = an;
-    for (int i = threadIdx.x; i < n4; i += 256) {
-        const f32x4 d = reinterpret_cast<const f32x4*>(pp)[i] - reinterpret_cast<const f32x4*>(ap)[i];
-        if (L1) {
+    chunk_sums(c.n, gp != nullptr, partial,
+        [&](int i, f32x4& an, f32x4& ad) {
+            const f32x4 d = reinterpret_cast<const f32x4*>(pp)[i] - reinterpret_cast<const f32x4*>(ap)[i];
+            if (L1) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) an[e] += fabsf(d[e]);
-        } else {
-            an += d * d;
-        }
-        if (gp) ad += reinterpret_cast<const f32x4*>(gp)[i] * d;
-    }
-    float sn = (an[0] + an[1]) + (an[2] + an[3]), sd = (ad[0] + ad[1]) + (ad[2] + ad[3]);
-    const int it = n4 * 4 + threadIdx.x;
-    if (it < c.n) {
-        const float d = pp[it] - ap[it];
-        sn += L1 ? fabsf(d) : d * d;
-        if (gp) sd += gp[it] * d;
-    }
-    sn = block_sum(sn, red);
-    if (gp) sd = block_sum(sd, red + 4);
-    if (threadIdx.x == 0) {
-        partial[2 * (long)blockIdx.x] = sn;
-        if (gp) partial[2 * (long)blockIdx.x + 1] = sd;
-    }
+                for (int e = 0; e < 4; ++e) an[e] += fabsf(d[e]);
+            } else {
+                an += d * d;
+            }
+            if (gp) ad += reinterpret_cast<const f32x4*>(gp)[i] * d;
+        },
+        [&](int it, float& sn, float& sd) {
+            const float d = pp[it] - ap[it];
+            sn += L1 ? fabsf(d) : d * d;
+            if (gp) sd += gp[it] * d;
+        });
 }
 
 __device__ __forceinline__ float tpgm_cmax(float norm, int flags) {
@@ -93,24 +68,19 @@ __device__ __forceinline__ float tpgm_ratio(float gamma, float norm, int flags, 
 
 struct FinalizeArgs { float grad_scale, step, inv_sqrt_bc2; int l1, update; };
 
-// one workgroup; thread k owns tensors k, k + 256, ... in both passes, so what it leaves in ratio[] / norm[] for itself needs no fence
+// thread k owns tensors k, k + 256, ... in both passes, so what it leaves in ratio[] / norm[] for itself needs no fence
 __global__ __launch_bounds__(256) void tpgm_finalize_kernel(const float* __restrict__ partial, const int* __restrict__ first_chunk, int ntensors,
                                                              const int* __restrict__ flags, float* __restrict__ gamma, float* __restrict__ gm,
                                                              float* __restrict__ gv, FinalizeArgs a, float* __restrict__ ratio,
                                                              float* __restrict__ norm, float* __restrict__ scalars) {
-    __shared__ float slot[256];
     __shared__ float coef_s;
     float total = 0.f;
     for (int base = 0; base < ntensors; base += 256) {
         const int t = base + threadIdx.x;
         float dg = 0.f;
         if (t < ntensors) {
-            const int c1 = first_chunk[t + 1];
-            float sn = 0.f, sd = 0.f;
-            for (int c = first_chunk[t]; c < c1; ++c) {
-                sn += partial[2 * (long)c];
-                if (a.update) sd += partial[2 * (long)c + 1];
-            }
+            float sn, sd;
+            tensor_sums(partial, first_chunk, t, a.update, sn, sd);
             const float nt = a.l1 ? sn : sqrtf(sn);
             norm[t] = nt;
             const int f = flags[t];
@@ -124,24 +94,18 @@ __global__ __launch_bounds__(256) void tpgm_finalize_kernel(const float* __restr
             }
         }
         if (!a.update) continue;                             // uniform over the workgroup
-        slot[threadIdx.x] = dg * dg;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const int cnt = ntensors - base < 256 ? ntensors - base : 256;
-            for (int k = 0; k < cnt; ++k) total += slot[k];
-        }
-        __syncthreads();
+        tensor_order_add(total, dg * dg, base, ntensors);
     }
     if (!a.update) return;
     if (threadIdx.x == 0) {
         const float gnorm = sqrtf(total);
-        const float c = 1.f / (gnorm + 1e-6f);               // clip_grad_norm_(gamma, 1.0)
-        coef_s = c > 1.f ? 1.f : c;                          // a NaN norm stays a NaN coefficient
+        coef_s = clip_coef(1.f, gnorm);                      // clip_grad_norm_(gamma, 1.0)
         scalars[0] = gnorm;
         scalars[1] = coef_s;
     }
     __syncthreads();
     const float coef = coef_s;
+    constexpr AdamBetas ADAM = {0.9f, (float)(1.0 - 0.9), 0.999f, (float)(1.0 - 0.999), 1e-8f};      // torch.optim.Adam's defaults
     for (int t = threadIdx.x; t < ntensors; t += 256) {
         const int f = flags[t];
         if (f & FLAG_EXCLUDED) {
@@ -149,10 +113,8 @@ __global__ __launch_bounds__(256) void tpgm_finalize_kernel(const float* __restr
             continue;
         }
         const float gg = ratio[t] * coef;                    // a zero gradient is still a gradient: gamma moves by its momentum
-        const float m = fmaf(ADAM_B1, gm[t], ADAM_OMB1 * gg);
-        const float v = fmaf(ADAM_B2, gv[t], ADAM_OMB2 * (gg * gg));
-        const float denom = fmaf(sqrtf(v), a.inv_sqrt_bc2, ADAM_EPS);
-        const float gn = gamma[t] - a.step * (m / denom);
+        float m = gm[t], v = gv[t];
+        const float gn = gamma[t] - a.step * adam_quotient(m, v, gg, ADAM, a.inv_sqrt_bc2);
         gm[t] = m, gv[t] = v, gamma[t] = gn;
         bool live;
         ratio[t] = tpgm_ratio(gn, norm[t], f, live);
@@ -161,9 +123,9 @@ __global__ __launch_bounds__(256) void tpgm_finalize_kernel(const float* __restr
 
 // src and dst may be the same buffer (the in-place projection): every element is read and written by one thread
 __global__ __launch_bounds__(256) void tpgm_project_kernel(const float* src, const float* __restrict__ anchor, float* dst,
-                                                            const float* __restrict__ ratio, const AdamChunk* __restrict__ chunks,
+                                                            const float* __restrict__ ratio, const FlatChunk* __restrict__ chunks,
                                                             __bf16* __restrict__ shadow) {
-    const AdamChunk c = chunks[blockIdx.x];
+    const FlatChunk c = chunks[blockIdx.x];
     const float r = ratio[c.tensor];
     const bool keep = r == 1.f;                              // src's bits: copied, or (in place) nothing stored
     if (keep && src == dst) return;
@@ -171,8 +133,7 @@ __global__ __launch_bounds__(256) void tpgm_project_kernel(const float* src, con
     const float* ap = anchor + c.off;
     float* dp = dst + c.off;
     __bf16* hp = shadow ? shadow + c.off : nullptr;
-    const int n4 = c.n >> 2;
-    for (int i = threadIdx.x; i < n4; i += 256) {
+    const int it = chunk_walk(c.n, [&](int i) {
         f32x4 s = reinterpret_cast<const f32x4*>(sp)[i];
         if (!keep) {
             const f32x4 av = reinterpret_cast<const f32x4*>(ap)[i];
@@ -181,8 +142,7 @@ __global__ __launch_bounds__(256) void tpgm_project_kernel(const float* src, con
         }
         reinterpret_cast<f32x4*>(dp)[i] = s;
         if (hp) reinterpret_cast<bf16x4*>(hp)[i] = __builtin_convertvector(s, bf16x4);
-    }
-    const int it = n4 * 4 + threadIdx.x;
+    });
     if (it < c.n) {
         float s = sp[it];
         if (!keep) s = fmaf(r, s - ap[it], ap[it]);
@@ -198,12 +158,11 @@ extern "C" {
 int cswin_tpgm_chunk_stats(const float* p, const float* anchor, const float* g, const void* chunks, int nchunks, int l1, float* partial,
                            void* stream) {
     CSWIN_REQUIRE(p && anchor && chunks && partial && nchunks > 0, CSWIN_ERR_SHAPE, "tpgm_chunk_stats: bad arguments");
-    CSWIN_REQUIRE(((((uintptr_t)p) | ((uintptr_t)anchor) | ((uintptr_t)g)) & 15) == 0, CSWIN_ERR_ALIGN, "tpgm_chunk_stats: buffers must be 16-B aligned");
-    CSWIN_REQUIRE((((uintptr_t)chunks) & 7) == 0, CSWIN_ERR_ALIGN, "tpgm_chunk_stats: the chunk table must be 8-B aligned");
+    if (int e = flat_align_check("tpgm_chunk_stats", (uintptr_t)p | (uintptr_t)anchor | (uintptr_t)g, chunks, nullptr)) return e;
     if (l1)
-        hipLaunchKernelGGL(tpgm_chunk_stats_kernel<true>, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, p, anchor, g, (const AdamChunk*)chunks, partial);
+        hipLaunchKernelGGL(tpgm_chunk_stats_kernel<true>, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, p, anchor, g, (const FlatChunk*)chunks, partial);
     else
-        hipLaunchKernelGGL(tpgm_chunk_stats_kernel<false>, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, p, anchor, g, (const AdamChunk*)chunks, partial);
+        hipLaunchKernelGGL(tpgm_chunk_stats_kernel<false>, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, p, anchor, g, (const FlatChunk*)chunks, partial);
     CSWIN_LAUNCH_CHECK();
     return CSWIN_OK;
 }
@@ -229,10 +188,8 @@ int cswin_tpgm_finalize(const float* partial, const int* first_chunk, int ntenso
 int cswin_tpgm_project(const float* src, const float* anchor, float* dst, const float* ratio, const void* chunks, int nchunks,
                        void* shadow_bf16, void* stream) {
     CSWIN_REQUIRE(src && anchor && dst && ratio && chunks && nchunks > 0, CSWIN_ERR_SHAPE, "tpgm_project: bad arguments");
-    CSWIN_REQUIRE(((((uintptr_t)src) | ((uintptr_t)anchor) | ((uintptr_t)dst)) & 15) == 0, CSWIN_ERR_ALIGN, "tpgm_project: buffers must be 16-B aligned");
-    CSWIN_REQUIRE((((uintptr_t)chunks) & 7) == 0, CSWIN_ERR_ALIGN, "tpgm_project: the chunk table must be 8-B aligned");
-    CSWIN_REQUIRE(!shadow_bf16 || (((uintptr_t)shadow_bf16) & 7) == 0, CSWIN_ERR_ALIGN, "tpgm_project: the bf16 shadow must be 8-B aligned");
-    hipLaunchKernelGGL(tpgm_project_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, src, anchor, dst, ratio, (const AdamChunk*)chunks,
+    if (int e = flat_align_check("tpgm_project", (uintptr_t)src | (uintptr_t)anchor | (uintptr_t)dst, chunks, shadow_bf16)) return e;
+    hipLaunchKernelGGL(tpgm_project_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, src, anchor, dst, ratio, (const FlatChunk*)chunks,
                        (__bf16*)shadow_bf16);
     CSWIN_LAUNCH_CHECK();
     return CSWIN_OK;

@@ -20,7 +20,6 @@ namespace {
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
@@ -146,9 +145,9 @@ __device__ __forceinline__ void wgrad16_tile(const W16Problem& P, const int lb, 
             d *= grs[j];
             bsum += d;
             const int off = img_off(r, lc >> 1) + 8 * (lc & 1);
-            *reinterpret_cast<bf16x4v*>(dimg + off) = __builtin_convertvector(d, bf16x4v);
+            *reinterpret_cast<bf16x4*>(dimg + off) = __builtin_convertvector(d, bf16x4);
             if constexpr (X16) *reinterpret_cast<u32x2*>(ximg + off) = gxh[j];
-            else *reinterpret_cast<bf16x4v*>(ximg + off) = __builtin_convertvector(gx[j], bf16x4v);
+            else *reinterpret_cast<bf16x4*>(ximg + off) = __builtin_convertvector(gx[j], bf16x4);
         }
     };
 
@@ -345,7 +344,7 @@ __device__ __forceinline__ void wgrad16_dma_tile(const W16Problem& P, const int 
                                 __builtin_bit_cast(float, raw[1] << 16), __builtin_bit_cast(float, raw[1] & 0xffff0000u)};
                     f32x4 hi = {__builtin_bit_cast(float, raw[2] << 16), __builtin_bit_cast(float, raw[2] & 0xffff0000u),
                                 __builtin_bit_cast(float, raw[3] << 16), __builtin_bit_cast(float, raw[3] & 0xffff0000u)};
-                    af[a] = __builtin_shufflevector(__builtin_convertvector(lo * s0, bf16x4v), __builtin_convertvector(hi * s1, bf16x4v), 0, 1, 2, 3, 4, 5, 6, 7);
+                    af[a] = __builtin_shufflevector(__builtin_convertvector(lo * s0, bf16x4), __builtin_convertvector(hi * s1, bf16x4), 0, 1, 2, 3, 4, 5, 6, 7);
                 }
             }
 #pragma unroll

@@ -17,8 +17,17 @@ from ._lib import call, precision, ptr, register_shadow, stream
 _CHUNK = 16384      # floats per gather / update workgroup
 
 
+def _next_bias_corrections(obj, what, betas):
+    """obj.step_count moved on by one and (1 - beta1^t, 1 - beta2^t) of the new count, in Python floats as torch forms them.
+    Refused inside a stream capture, the count untouched."""
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(f"{what} inside a stream capture: the host's step count, and with it the bias corrections, would be frozen into the graph")
+    obj.step_count += 1
+    return 1.0 - betas[0] ** obj.step_count, 1.0 - betas[1] ** obj.step_count
+
+
 class _FlatBuffers:
-    """The slot layout, the gradient gather and the bf16 shadow that the flat optimisers share."""
+    """The slot layout, the chunk table, the gradient gather and the bf16 shadow that the flat optimisers share."""
 
     def __init__(self, params, lr):
         name = type(self).__name__
@@ -33,6 +42,10 @@ class _FlatBuffers:
             self.offsets.append(off)
             off += (p.numel() + 7) // 8 * 8          # 32-B slots: the bf16 shadow of every parameter is 16-B aligned as well
         self.numel = off
+        rows, first = chunk_table([p.numel() for p in self.params], self.offsets)
+        self.nchunks = len(rows)
+        self.chunks = torch.from_numpy(rows.view(np.int64).reshape(-1, 2)).to(dev)        # built and uploaded once, for FlatTPGM as well
+        self.first_chunk = torch.from_numpy(first).to(dev)
         self.flat_param = torch.zeros(off, dtype=torch.float32, device=dev)
         self.flat_grad = torch.zeros(off, dtype=torch.float32, device=dev)
         self._alloc_state(off, dev)
@@ -144,7 +157,7 @@ class FlatSGD(_FlatBuffers):
 
 
 def chunk_table(numels, offsets):
-    """The static table the AdamW kernels walk: (records, first_chunk).  records: one {'off': int64 element offset into the flat
+    """The static table the chunked kernels walk (csrc/flat_chunks.h): (records, first_chunk).  records: one {'off': int64 element offset into the flat
     buffers, 'n': int32 <= 16384, 'tensor': int32} per chunk (16 bytes, the library's record), tensors in order and each tensor's
     chunks in order; chunks tile [offset, offset + numel) of every tensor exactly, so none crosses a slot or covers a pad word,
     and every offset is a multiple of 4 (slots start at multiples of 8, 16384 is one of 4).  first_chunk: int32 (T + 1,), the
@@ -172,10 +185,6 @@ class FlatAdamW(_FlatBuffers):
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         super().__init__(params, lr)
         dev, T = self.flat_param.device, len(self.params)
-        rows, first = chunk_table([p.numel() for p in self.params], self.offsets)
-        self.nchunks = len(rows)
-        self._chunks = torch.from_numpy(rows.view(np.int64).reshape(-1, 2)).to(dev)       # built and uploaded once
-        self._first_chunk = torch.from_numpy(first).to(dev)
         self._partial = torch.zeros(self.nchunks, 2, dtype=torch.float32, device=dev)
         self.tensor_sumsq = torch.zeros(T, 2, dtype=torch.float32, device=dev)            # (sum g^2, sum p^2) per tensor
         self.scalars = torch.tensor([0.0, 1.0], dtype=torch.float32, device=dev)          # [total_norm, clip_coef] of the last apply
@@ -206,24 +215,20 @@ class FlatAdamW(_FlatBuffers):
         self._use_mult = True
 
     def _sumsq(self, with_params, tensor_sumsq, scalars, grad_scale, max_norm):
-        call("cswin_chunk_sumsq", ptr(self.flat_grad), ptr(self.flat_param) if with_params else None, ptr(self._chunks), self.nchunks,
+        call("cswin_chunk_sumsq", ptr(self.flat_grad), ptr(self.flat_param) if with_params else None, ptr(self.chunks), self.nchunks,
              ptr(self._partial), stream())
-        call("cswin_norm_finalize", ptr(self._partial), ptr(self._first_chunk), len(self.params), float(grad_scale), float(max_norm),
+        call("cswin_norm_finalize", ptr(self._partial), ptr(self.first_chunk), len(self.params), float(grad_scale), float(max_norm),
              ptr(tensor_sumsq), ptr(scalars), stream())
 
     def apply(self, grad_scale=1.0):
         """p, m, v <- AdamW(clip(flat_grad * grad_scale))."""
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("FlatAdamW.apply() inside a stream capture: the host's step count, and with it the bias corrections, "
-                               "would be frozen into the graph")
-        self.step_count += 1
-        b1, b2 = self.betas
+        bc1, bc2 = _next_bias_corrections(self, "FlatAdamW.apply()", self.betas)
         clip = self.max_grad_norm is not None
         if clip:
             self._sumsq(False, self.tensor_sumsq, self.scalars, grad_scale, self.max_grad_norm)
-        call("cswin_adamw_flat", ptr(self.flat_param), ptr(self.flat_grad), ptr(self.flat_m), ptr(self.flat_v), ptr(self._chunks), self.nchunks,
-             ptr(self.lr_dev), ptr(self._lr_mult) if self._use_mult else None, ptr(self.scalars) if clip else None, b1, b2, self.eps,
-             self.weight_decay, float(grad_scale), 1.0 - b1 ** self.step_count, 1.0 - b2 ** self.step_count,
+        call("cswin_adamw_flat", ptr(self.flat_param), ptr(self.flat_grad), ptr(self.flat_m), ptr(self.flat_v), ptr(self.chunks), self.nchunks,
+             ptr(self.lr_dev), ptr(self._lr_mult) if self._use_mult else None, ptr(self.scalars) if clip else None, *self.betas, self.eps,
+             self.weight_decay, float(grad_scale), bc1, bc2,
              ptr(self.flat_param16) if precision() == 1 else None, stream())
 
     def tensor_norms(self):
@@ -290,13 +295,7 @@ class FlatTPGM:
         self.opt, self.names, self.norm_mode, self.proj_lr = opt, names, str(norm_mode), float(proj_lr)
         self.l1 = 0 if "l2" in self.norm_mode else 1                                     # universal_train.py:463
         dev, T = opt.flat_param.device, len(names)
-        if hasattr(opt, "_chunks"):
-            self._chunks, self._first_chunk, self.nchunks = opt._chunks, opt._first_chunk, opt.nchunks
-        else:
-            rows, first = chunk_table([p.numel() for p in opt.params], opt.offsets)
-            self.nchunks = len(rows)
-            self._chunks = torch.from_numpy(rows.view(np.int64).reshape(-1, 2)).to(dev)
-            self._first_chunk = torch.from_numpy(first).to(dev)
+        self.chunks, self.first_chunk, self.nchunks = opt.chunks, opt.first_chunk, opt.nchunks     # the optimiser's own table
         self._partial = torch.zeros(self.nchunks, 2, dtype=torch.float32, device=dev)
         excl = set(exclude)
         self.flags_host = [(TPGM_EXCLUDED if n in excl else 0) | (TPGM_HEAD if tpgm_is_head(n) else 0) for n in names]
@@ -320,11 +319,11 @@ class FlatTPGM:
 
     # -- launches -------------------------------------------------------------------------------------------
     def _stats(self, p, anchor, g, l1=None):
-        call("cswin_tpgm_chunk_stats", ptr(p), ptr(anchor), ptr(g), ptr(self._chunks), self.nchunks, self.l1 if l1 is None else l1,
+        call("cswin_tpgm_chunk_stats", ptr(p), ptr(anchor), ptr(g), ptr(self.chunks), self.nchunks, self.l1 if l1 is None else l1,
              ptr(self._partial), stream())
 
     def _finalize(self, mode, grad_scale=1.0, bc1=1.0, bc2=1.0, l1=None):
-        call("cswin_tpgm_finalize", ptr(self._partial), ptr(self._first_chunk), len(self.names), self.l1 if l1 is None else l1, ptr(self._flags),
+        call("cswin_tpgm_finalize", ptr(self._partial), ptr(self.first_chunk), len(self.names), self.l1 if l1 is None else l1, ptr(self._flags),
              ptr(self.gamma), ptr(self.gamma_m), ptr(self.gamma_v), float(grad_scale), self.proj_lr, bc1, bc2, mode, ptr(self.ratio),
              ptr(self.norm), ptr(self.scalars), stream())
 
@@ -334,7 +333,7 @@ class FlatTPGM:
 
     def _project(self, src):
         opt = self.opt
-        call("cswin_tpgm_project", ptr(src), ptr(self.flat_anchor), ptr(opt.flat_param), ptr(self.ratio), ptr(self._chunks), self.nchunks,
+        call("cswin_tpgm_project", ptr(src), ptr(self.flat_anchor), ptr(opt.flat_param), ptr(self.ratio), ptr(self.chunks), self.nchunks,
              ptr(opt.flat_param16) if precision() == 1 else None, stream())
 
     # -- the projection update ------------------------------------------------------------------------------
@@ -361,13 +360,9 @@ class FlatTPGM:
         launches); self.ratio holds the ratios of the new gamma afterwards."""
         if not self._active:
             raise RuntimeError("FlatTPGM.update() outside begin() ... end()")
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("FlatTPGM.update() inside a stream capture: the host's step count, and with it the bias corrections, "
-                               "would be frozen into the graph")
-        self.step_count += 1
-        b1, b2 = TPGM_BETAS
+        bc1, bc2 = _next_bias_corrections(self, "FlatTPGM.update()", TPGM_BETAS)
         self._stats(self.flat_saved, self.flat_anchor, self.opt.flat_grad)
-        self._finalize(1, grad_scale, 1.0 - b1 ** self.step_count, 1.0 - b2 ** self.step_count)
+        self._finalize(1, grad_scale, bc1, bc2)
         self._ratio_current = True
 
     def end(self):

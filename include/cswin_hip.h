@@ -326,13 +326,17 @@ int cswin_sgd_flat(float* p, const float* g, float* m, long n, const float* lr_d
 /* table: device array of {const float* src; float* dst; long long n;} (24-byte records), one workgroup each */
 int cswin_multi_copy(const void* table, int nchunks, void* stream);
 
-/* ---- optimiser: clip_grad_norm_(parameters, max_norm) + torch.optim.AdamW (universal_train.py:693-725, 934-939), with a learning
- * rate per parameter tensor (the "surgical" mode, :635-690, 871-896), on the flat buffers ----
+/* ---- the chunk table of the six entry points below (the `chunks`, `nchunks` and `first_chunk` arguments of the AdamW and TPGM
+ * sections) ----
  * chunks: device table of nchunks 16-byte records {long long off; int n; int tensor;}, 8-B aligned, one 256-thread workgroup each:
  * elements [off, off + n) of the flat buffers belong to tensor `tensor`, n <= 16384, off % 4 == 0, no chunk crosses a tensor or
  * covers a pad word, chunks of one tensor are consecutive; first_chunk[ntensors + 1] indexes them per tensor.  The table is the
  * caller's (optim.chunk_table builds it): the library cannot read it, so its bounds are the caller's responsibility.
- * No float atomics: every sum has a fixed order and two runs on the same input give the same bits.
+ * No float atomics: every sum has a fixed order (within a chunk, then chunks in chunk order, then tensors in tensor order) and two
+ * runs on the same input give the same bits. */
+
+/* ---- optimiser: clip_grad_norm_(parameters, max_norm) + torch.optim.AdamW (universal_train.py:693-725, 934-939), with a learning
+ * rate per parameter tensor (the "surgical" mode, :635-690, 871-896), on the flat buffers and the chunk table above ----
  *
  * partial[c] = (sum g^2, sum p^2) over chunk c (2 * nchunks floats); p == NULL: the second entries are not written. */
 int cswin_chunk_sumsq(const float* g, const float* p, const void* chunks, int nchunks, float* partial, void* stream);
@@ -357,7 +361,7 @@ int cswin_adamw_flat(float* p, const float* g, float* m, float* v, const void* c
  * tpgm.py:47-56's), on the flat buffers and the chunk table above.  Per tensor t, with d = p - anchor:
  *   norm_t = sqrt(sum d^2) (l1 == 0) or sum |d| (l1 != 0);  cmax_t = max(8 norm_t, 80), head tensors max(10 norm_t, 100);
  *   ratio_t = hardtanh(clamp(gamma_t, 1e-2, cmax_t) / (norm_t + 1e-8), 0, 1);  projected = anchor + ratio_t d.
- * No float atomics, fixed summation order, no host synchronisation.
+ * No host synchronisation.
  *
  * partial[c] = (sum d^2 or sum |d|, sum g d) over chunk c (2 * nchunks floats); g == NULL: the second entries are not written.
  * p, anchor, g 16-B aligned. */

@@ -75,7 +75,7 @@ def adamw_bound(p, g, m, v, step, lr, beta1=BETA1, beta2=BETA2, eps=EPS, wd=0.01
 
 
 def sumsq_depth(numel, nchunks=0, ntensors=0):
-    """Additions a term of a sum of squares passes through, a transcription of the launch rule (it MUST FOLLOW csrc/adamw.hip): a
+    """Additions a term of a sum of squares passes through, a transcription of the launch rule (it MUST FOLLOW csrc/flat_chunks.h): a
     chunk is at most 16384 elements under one 256-thread workgroup, so a thread takes cdiv(n / 4, 256) trips of four elements,
     adds its four lanes in 2 levels and a tail element in 1, then the 8 levels of the workgroup tree (6 in the wave, 2 over the
     four waves); a tensor's `nchunks` partials are added in chunk order and the `ntensors` tensor sums in tensor order."""

@@ -322,7 +322,7 @@ def test_refusals_touch_nothing(hip):
 
 @pytest.mark.parametrize("kind", ["adamw", "sgd"])
 def test_flat_tpgm_over_both_optimisers(monkeypatch, kind):
-    """optim.FlatTPGM on small parameters: it shares FlatAdamW's chunk table and builds an equal one over FlatSGD; the initial radii
+    """optim.FlatTPGM on small parameters: it walks the optimiser's own chunk table, FlatAdamW's or FlatSGD's; the initial radii
     follow the init rule; begin() ... end() restores bit for bit; an excluded tensor and one inside its ball are never stored;
     update() outside begin() and inside a stream capture is refused and leaves the step count alone."""
     from cswin_unet_amd.optim import FlatAdamW, FlatSGD, FlatTPGM, chunk_table
@@ -333,10 +333,9 @@ def test_flat_tpgm_over_both_optimisers(monkeypatch, kind):
     opt = FlatAdamW(params, lr=1e-3) if kind == "adamw" else FlatSGD(params, lr=1e-3)
     tp = FlatTPGM(opt, names, proj_lr=LR, exclude=("stage1.0.qkv.bias",))
     rows, first = chunk_table(list(numels), opt.offsets)
-    if kind == "adamw":
-        assert tp._chunks is opt._chunks and tp._first_chunk is opt._first_chunk
-    assert tp.nchunks == len(rows) and np.array_equal(tp._chunks.cpu().numpy(), rows.view(np.int64).reshape(-1, 2)) and \
-        np.array_equal(tp._first_chunk.cpu().numpy(), first)
+    assert tp.chunks is opt.chunks and tp.first_chunk is opt.first_chunk
+    assert tp.nchunks == opt.nchunks == len(rows) and np.array_equal(tp.chunks.cpu().numpy(), rows.view(np.int64).reshape(-1, 2)) and \
+        np.array_equal(tp.first_chunk.cpu().numpy(), first)
     assert tp.flags_host == [0, EXCLUDED, HEAD, 0]
     pn = norms_ref(anchors, [np.zeros(n) for n in numels], False)
     want = np.array([max(3.0, 2 * pn[0]), max(3.0, 2 * pn[1]), max(10.0, 5 * pn[2]), max(3.0, 2 * pn[3])])

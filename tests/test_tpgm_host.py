@@ -90,7 +90,7 @@ def gamma_adam_ref(gamma, dgamma, m, v, step, lr, flags=None, coef=None):
 # where two roundings are counted only helps).  sqrt and the division are taken at two roundings (1 ulp), as in test_adamw_host.
 # ------------------------------------------------------------------------------------------------
 def stat_depth(numel, nchunks):
-    """Additions a term passes through up to the per-tensor sum: adamw.hip's launch rule (test_adamw_host.sumsq_depth: a thread's
+    """Additions a term passes through up to the per-tensor sum: flat_chunks.h's launch rule (test_adamw_host.sumsq_depth: a thread's
     trips, its four lanes, the tail, the 8 levels of the workgroup) and the tensor's chunks in chunk order."""
     return sumsq_depth(numel, nchunks)
 
