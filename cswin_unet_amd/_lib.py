@@ -83,6 +83,8 @@ SIGNATURES = {
     "cswin_seg_metrics": (I, [P, P, P, P, P, SZ, I, I, I, I, I, P]),
     "cswin_resize_banded": (I, [P, P, P, P, I, P, P, I, I, I, I, I, I, I, P]),
     "cswin_argmax_zoom_back": (I, [P, P, P, P, I, I, I, I, I, I, P]),
+    "cswin_argmax_zoom_back_classes": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P]),
+    "cswin_class_counts": (I, [P, I, P, I, P, I, L, I, P]),
     "cswin_augment_gather": (I, [P, P, P, I, I, I, I, I, I, P]),
     "cswin_augment_labels": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
 }

@@ -18,16 +18,31 @@ and TPGM, the trainable projection toward the pretrained weights (universal_trai
     if tpgm_due(epoch, start_epoch, frequency): tpgm.iterate(held_out_batches, max_iters)     # learns the radii; the weights are restored
     tpgm.apply()                                                    # once, after training: the weights are projected
 
-Only surgical_lr_weights and TPGM run the model; nothing else here launches a kernel."""
+and the two ends of a stage that close the loop, label statistics before it and evaluation after it:
+
+    counts = scan_labels(raw_label_slices, total_classes, table)    # (N, classes + 1) per-slice class histogram, ops.class_counts
+    weights = extreme_class_weights(counts.sum(0)[:total_classes], active)
+    sampler = PositiveSampling(dataset, scan_labels(raw_label_slices, 4)[:, :4] > 0, KITS23_RULE)
+    ...
+    results = evaluate_tasks(net, {0: synapse_volumes, 1: kits23_volumes}, REFERENCE_STAGE_CLASSES, (224, 224), resize="hip")
+
+(universal_test.py scores a model per dataset on that dataset's own output channels, task_class_indices; checkpoint_num_classes,
+strip_wrapper_prefixes and task_level read a checkpoint's task level.)
+
+surgical_lr_weights, TPGM, scan_labels and evaluate_tasks run kernels; nothing else here does."""
 import copy
 import math
+import random
 from dataclasses import dataclass
 from typing import Optional
 
+import numpy as np
 import torch
 from torch import nn
 
-__all__ = ["expand_classes", "new_label_map", "extreme_class_weights", "freeze_teacher", "Distill", "rgn_weights", "surgical_lr_weights", "TPGM", "tpgm_due"]
+__all__ = ["expand_classes", "new_label_map", "extreme_class_weights", "freeze_teacher", "Distill", "rgn_weights", "surgical_lr_weights", "TPGM", "tpgm_due",
+           "task_class_indices", "task_level", "checkpoint_num_classes", "strip_wrapper_prefixes", "evaluate_tasks", "scan_labels",
+           "PositiveSampling", "REFERENCE_TASKS", "REFERENCE_STAGE_CLASSES", "KITS23_RULE", "LITS17_RULE"]
 
 
 def _core(model):
@@ -247,3 +262,169 @@ class TPGM:
 
     def load_state_dict(self, sd):
         self.flat.load_state_dict(sd)
+
+
+# ------------------------------------------------------------------------------------------------
+# evaluation of a continual model (universal_test.py) and the label statistics of a stage
+# ------------------------------------------------------------------------------------------------
+REFERENCE_TASKS = {"synapse": 0, "kits23": 1, "lits17": 2}          # the reference's chain, in training order
+REFERENCE_STAGE_CLASSES = (9, 4, 3)                                 # each dataset's class count, its background included
+KITS23_RULE = [(0.3, 3), (0.5, 2), (None, 1)]                       # PositiveSamplingDataset.__getitem__, stage 1 (:223-230)
+LITS17_RULE = [(0.4, 2), (None, 1)]                                 # stage 2 (:234-239); None stands for positive_ratio
+
+
+def _stage_offsets(stage_classes):
+    """Total class count after every stage: n0, n0 + (n1 - 1), ... (every later dataset shares the background)."""
+    stage_classes = [int(n) for n in stage_classes]
+    if not stage_classes or any(n < 1 for n in stage_classes):
+        raise ValueError(f"stage_classes={stage_classes!r}: one class count >= 1 per dataset")
+    totals = [stage_classes[0]]
+    for n in stage_classes[1:]:
+        totals.append(totals[-1] + n - 1)
+    return stage_classes, totals
+
+
+def task_class_indices(stage_classes, task):
+    """The output channels of dataset `task` in a model trained on the chain stage_classes (per-dataset class counts in training
+    order): task 0 has range(n0); task t >= 1 has [0] + the n_t - 1 channels its stage appended.  For (9, 4, 3) these are the
+    three lists of universal_test.py:27-40: 0..8, [0, 9, 10, 11], [0, 12, 13]."""
+    stage_classes, totals = _stage_offsets(stage_classes)
+    if not 0 <= task < len(stage_classes):
+        raise ValueError(f"task_class_indices: task {task} of a chain of {len(stage_classes)}")
+    if task == 0:
+        return list(range(stage_classes[0]))
+    return [0] + list(range(totals[task - 1], totals[task]))
+
+
+def task_level(num_classes, stage_classes):
+    """How many tasks of the chain a model with num_classes outputs has learned (9 -> 1, 12 -> 2, 14 -> 3 for the reference's
+    chain, universal_test.py:171-178).  ValueError for a count that no prefix of the chain gives."""
+    _, totals = _stage_offsets(stage_classes)
+    if int(num_classes) not in totals:
+        raise ValueError(f"task_level: {num_classes} classes match no prefix of the chain {tuple(stage_classes)} (totals {totals})")
+    return totals.index(int(num_classes)) + 1
+
+
+def strip_wrapper_prefixes(state_dict):
+    """A copy of state_dict whose keys have lost every leading "module." (DataParallel) and "base_model." (the reference's
+    continual wrapper), in whichever order they were stacked (universal_test.py:206-218)."""
+    out = {}
+    for key, value in state_dict.items():
+        while key.startswith(("module.", "base_model.")):
+            key = key.split(".", 1)[1]
+        out[key] = value
+    return out
+
+
+def checkpoint_num_classes(state_dict):
+    """Class count of a checkpoint: the rows of output.weight or cswin_unet.output.weight after strip_wrapper_prefixes.  KeyError
+    if neither is there (the reference goes on to guess among all keys that contain "output"; here that is an error)."""
+    sd = strip_wrapper_prefixes(state_dict)
+    for key in ("output.weight", "cswin_unet.output.weight"):
+        if key in sd:
+            return int(sd[key].shape[0])
+    raise KeyError("checkpoint_num_classes: neither output.weight nor cswin_unet.output.weight in the state dict")
+
+
+def evaluate_tasks(net, loaders, stage_classes, patch_size, *, num_classes=None, **evaluate_volumes_kwargs):
+    """utils.evaluate_volumes per task of a continual model: loaders maps a task index of the chain stage_classes to a volume
+    loader, every task is scored on its own channels (task_class_indices) against its dataset's own label ids.  The model's class
+    count is num_classes, or else the num_classes attribute of the first module of net that has one.  A task whose channels reach
+    beyond it is refused by name before anything runs (the reference fails with an IndexError inside the first volume).
+    Returns {task: (per_volume, class_mean, mean_dice, mean_hd95)}."""
+    from .utils import evaluate_volumes
+    stage_classes = [int(n) for n in stage_classes]
+    if num_classes is None:
+        num_classes = next((m.num_classes for m in net.modules() if isinstance(getattr(m, "num_classes", None), int)), None)
+    if num_classes is None:
+        raise TypeError("evaluate_tasks: no module of the model has a num_classes attribute; pass num_classes=")
+    num_classes = int(num_classes)
+    plan = {}
+    for task in loaders:
+        idx = task_class_indices(stage_classes, task)
+        if max(idx) >= num_classes:
+            names = {v: k for k, v in REFERENCE_TASKS.items()} if tuple(stage_classes) == REFERENCE_STAGE_CLASSES else {}
+            raise ValueError(f"evaluate_tasks: task {task}{' (' + names[task] + ')' if task in names else ''} reads output channels up "
+                             f"to {max(idx)}, the model has {num_classes} classes: it has not learned that task")
+        plan[task] = idx
+    return {task: evaluate_volumes(loaders[task], net, stage_classes[task], patch_size, class_indices=idx, **evaluate_volumes_kwargs)
+            for task, idx in plan.items()}
+
+
+def _label_bytes(a, where):
+    """An (H, W) / (n, H, W) array of integer values in 0..255 (any integer or float dtype) as uint8 (n, H, W); ValueError else."""
+    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    if a.ndim not in (2, 3) or a.dtype.kind not in "biuf":
+        raise ValueError(f"scan_labels: {where} has shape {a.shape} and dtype {a.dtype}; (H, W) or (n, H, W) numbers are scanned")
+    a = a[None] if a.ndim == 2 else a
+    if a.size:
+        bad = (a != np.rint(a)) if a.dtype.kind == "f" else np.zeros(a.shape, bool)
+        bad |= ~((a >= 0) & (a <= 255))                         # a NaN fails both comparisons
+        if bad.any():
+            k = tuple(int(i) for i in np.argwhere(bad)[0])
+            raise ValueError(f"scan_labels: {where} holds {a[k]!r} at {k}: not an integer in 0..255")
+    return np.ascontiguousarray(a.astype(np.uint8))
+
+
+def scan_labels(label_slices, ncls, label_map=None, batch=256, device="cuda"):
+    """Per-slice class histogram of a dataset's raw labels: an int64 CPU tensor (N, ncls + 1) in input order, column c < ncls the
+    pixels of class c, the last column the pixels without a class (ops.class_counts).  label_slices: an iterable of (H, W) or
+    (n, H, W) numpy arrays (or CPU tensors) of any integer or float dtype holding integers in 0..255, as the .npz slices do; a
+    value that is not raises ValueError before anything is uploaded.  Runs of equal shape are uploaded as uint8 in batches of up
+    to `batch` slices, one kernel launch each.  label_map: continual.new_label_map's table (any device) or None.
+
+    `.sum(0)[:ncls]` is the `counts` argument of extreme_class_weights over the WHOLE dataset: the reference counts the first 21
+    batches of its shuffled loader only (universal_train.py:1006-1015).  `[:, :classes] > 0` is PositiveSampling's presence
+    table, taken from the raw slices and not, as the reference's constructor does, from one random augmentation of each."""
+    from . import ops
+    dmap = None if label_map is None else torch.as_tensor(label_map).to(device=device, dtype=torch.int32)
+    out, pending, held = [], [], 0
+
+    def flush():
+        nonlocal pending, held
+        if pending:
+            dev = torch.from_numpy(np.concatenate(pending)).to(device)
+            out.append(ops.class_counts(dev, ncls, dmap).cpu())
+            pending, held = [], 0
+
+    for i, a in enumerate(label_slices):
+        a = _label_bytes(a, f"entry {i}")
+        if pending and pending[0].shape[1:] != a.shape[1:]:
+            flush()
+        while len(a):
+            take = a[:int(batch) - held]
+            pending.append(take)
+            held += len(take)
+            a = a[len(take):]
+            if held >= int(batch):
+                flush()
+    flush()
+    return torch.cat(out) if out else torch.zeros((0, int(ncls) + 1), dtype=torch.int64)
+
+
+class PositiveSampling(torch.utils.data.Dataset):
+    """PositiveSamplingDataset of universal_train.py:193-241 with its draw order, on a presence table instead of a decoding pass:
+    presence is the boolean (N, classes) table `scan_labels(...)[:, :classes] > 0`, rule an ordered list of (probability or None,
+    class), None standing for positive_ratio (KITS23_RULE, LITS17_RULE).  __getitem__(idx): for every entry in turn one
+    random.random() is drawn -- always, before the class's slice list is looked at, as in `random.random() < p and
+    self.class_indices[c]` -- and on a draw below the probability with a non-empty list the item is
+    base_dataset[random.choice(list)]; if no entry fires it is base_dataset[idx % len(base_dataset)]."""
+
+    def __init__(self, base_dataset, presence, rule, positive_ratio=0.8):
+        presence = torch.as_tensor(presence)
+        if presence.dim() != 2 or presence.shape[0] != len(base_dataset):
+            raise ValueError(f"PositiveSampling: presence {tuple(presence.shape)} for a dataset of {len(base_dataset)} samples")
+        self.base_dataset, self.positive_ratio = base_dataset, positive_ratio
+        self.rule = [(positive_ratio if p is None else float(p), int(c)) for p, c in rule]
+        if any(not 0 <= c < presence.shape[1] for _, c in self.rule):
+            raise ValueError(f"PositiveSampling: the rule names a class outside the {presence.shape[1]} columns of presence")
+        self.class_indices = {c: torch.nonzero(presence[:, c] != 0).flatten().tolist() for _, c in self.rule}
+
+    def __len__(self):
+        return len(self.base_dataset)
+
+    def __getitem__(self, idx):
+        for p, c in self.rule:
+            if random.random() < p and self.class_indices[c]:
+                return self.base_dataset[random.choice(self.class_indices[c])]
+        return self.base_dataset[idx % len(self.base_dataset)]

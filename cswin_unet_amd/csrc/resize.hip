@@ -10,6 +10,9 @@
 //   cswin_argmax_zoom_back  out[b][i][j] = argmax_c logits[b][c][src_row[i]][src_col[j]]  (torch.argmax's tie and NaN rules);
 //                           0 where an index is negative: scipy rounds such an output's coordinate past the last sample and
 //                           writes its constant there (as it leaves the matching row of R all zero)
+//   cswin_argmax_zoom_back_classes  the same over a list of classes: out = the POSITION k in the list of the largest of
+//                           logits[b][classes[k]][..][..], torch.argmax(logits[:, classes], 1) before the zoom (how a continual
+//                           model is scored on one dataset's own classes, universal_test.py:50-54)
 #include "common.h"
 
 namespace {
@@ -138,9 +141,14 @@ void resize_launch(const ResizeArgs& a, int D, int vec2, int f64, hipStream_t st
 // One workgroup per output row (b, i): the argmax over the classes of source row src_row[i] once into LDS, then the gather
 // along the row.  First index wins a tie; a NaN beats every number and the first NaN wins (torch.argmax).  A negative source
 // index marks an output that scipy does not gather but fills with its constant 0.
+// SUBSET: candidate k of nsel reads channel classes[k], clamped into [0, ncls) like the index tables, and the result is k.  k is
+// the same for every lane, so the table entry is a scalar load and the channel offset scalar arithmetic; a repeated class never
+// wins at its later position (the comparison is strict).  Without SUBSET, nsel = ncls and candidate k is channel k.
+template <bool SUBSET>
 __global__ __launch_bounds__(256) void argmax_zoom_back_kernel(const float* __restrict__ logits, unsigned char* __restrict__ out,
                                                                const int* __restrict__ src_row, const int* __restrict__ src_col,
-                                                               int ncls, int h, int w, int H, int W) {
+                                                               const int* __restrict__ classes, int nsel, int ncls, int h, int w,
+                                                               int H, int W) {
     __shared__ unsigned char am[RZ_MAX_DIM];
     const int i = blockIdx.x, b = blockIdx.y;
     unsigned char* __restrict__ o = out + ((long)b * H + i) * W;
@@ -151,11 +159,15 @@ __global__ __launch_bounds__(256) void argmax_zoom_back_kernel(const float* __re
     const int r = min(src_row[i], h - 1);
     const long plane = (long)h * w;
     const float* __restrict__ src = logits + (long)b * ncls * plane + (long)r * w;
+    auto channel = [&](int k) -> long {
+        if constexpr (SUBSET) return (long)min(max(classes[k], 0), ncls - 1) * plane;
+        else return k * plane;
+    };
     for (int j = threadIdx.x; j < w; j += 256) {
-        float best = src[j];
+        float best = src[channel(0) + j];
         int arg = 0;
-        for (int c = 1; c < ncls; ++c) {
-            const float v = src[c * plane + j];
+        for (int c = 1; c < nsel; ++c) {
+            const float v = src[channel(c) + j];
             if (!(best != best) && (v > best || v != v)) {
                 best = v;
                 arg = c;
@@ -206,8 +218,24 @@ int cswin_argmax_zoom_back(const float* logits, unsigned char* out, const int* s
     CSWIN_REQUIRE(ncls >= 1 && ncls <= RZ_MAX_CLS, CSWIN_ERR_SHAPE, "argmax_zoom_back: ncls=%d outside 1..%d", ncls, RZ_MAX_CLS);
     CSWIN_REQUIRE((uintptr_t)logits % 4 == 0 && (uintptr_t)src_row % 4 == 0 && (uintptr_t)src_col % 4 == 0, CSWIN_ERR_ALIGN,
                   "argmax_zoom_back: a pointer is not aligned to its element size");
-    hipLaunchKernelGGL(argmax_zoom_back_kernel, dim3(H, B), dim3(256), 0, (hipStream_t)stream, logits, out, src_row, src_col, ncls, h,
-                       w, H, W);
+    hipLaunchKernelGGL(argmax_zoom_back_kernel<false>, dim3(H, B), dim3(256), 0, (hipStream_t)stream, logits, out, src_row, src_col,
+                       (const int*)nullptr, ncls, ncls, h, w, H, W);
+    CSWIN_LAUNCH_CHECK();
+    return CSWIN_OK;
+}
+
+int cswin_argmax_zoom_back_classes(const float* logits, unsigned char* out, const int* src_row, const int* src_col, const int* classes,
+                                   int nsel, int B, int ncls, int h, int w, int H, int W, void* stream) {
+    CSWIN_REQUIRE(logits && out && src_row && src_col && classes, CSWIN_ERR_SHAPE, "argmax_zoom_back_classes: null argument");
+    CSWIN_REQUIRE(rz_dim_ok(B) && rz_dim_ok(h) && rz_dim_ok(w) && rz_dim_ok(H) && rz_dim_ok(W), CSWIN_ERR_SHAPE,
+                  "argmax_zoom_back_classes: B=%d, (%d, %d) -> (%d, %d) outside the supported 1..%d per dimension", B, h, w, H, W,
+                  RZ_MAX_DIM);
+    CSWIN_REQUIRE(nsel >= 1 && nsel <= RZ_MAX_CLS, CSWIN_ERR_SHAPE, "argmax_zoom_back_classes: nsel=%d outside 1..%d", nsel, RZ_MAX_CLS);
+    CSWIN_REQUIRE(ncls >= 1, CSWIN_ERR_SHAPE, "argmax_zoom_back_classes: ncls=%d must be positive", ncls);
+    CSWIN_REQUIRE((uintptr_t)logits % 4 == 0 && (uintptr_t)src_row % 4 == 0 && (uintptr_t)src_col % 4 == 0 && (uintptr_t)classes % 4 == 0,
+                  CSWIN_ERR_ALIGN, "argmax_zoom_back_classes: a pointer is not aligned to its element size");
+    hipLaunchKernelGGL(argmax_zoom_back_kernel<true>, dim3(H, B), dim3(256), 0, (hipStream_t)stream, logits, out, src_row, src_col,
+                       classes, nsel, ncls, h, w, H, W);
     CSWIN_LAUNCH_CHECK();
     return CSWIN_OK;
 }

@@ -16,7 +16,7 @@ from ._lib import AugmentDesc, ConvImageJob, CswinHipError, ReduceJob, WgradDesc
 
 __all__ = ["layer_norm", "linear", "linear_pair", "mlp", "stripe_attention", "cswin_block", "conv_tokens", "patch_embed_conv", "carafe_reassemble",
            "carafe_reassemble_nchw", "conv_weight_images", "head_compose", "tokens_to_nchw", "matmul_nn", "ce_dice_loss", "continual_loss", "dropout", "img2windows", "windows2img",
-           "seg_metrics", "resize_slices", "argmax_zoom_back", "augment_batch"]
+           "seg_metrics", "resize_slices", "argmax_zoom_back", "augment_batch", "class_counts"]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1249,19 +1249,72 @@ def resize_slices(x, size):
     return y
 
 
-def argmax_zoom_back(logits, size):
+_class_tables = {}
+
+
+def _class_table(classes, ncls, device):
+    """Device int32 table of a class list, validated on the host and uploaded once per (list, device)."""
+    classes = tuple(classes)
+    if not 1 <= len(classes) <= 255:
+        raise CswinHipError(f"argmax_zoom_back: classes has {len(classes)} entries; 1..255 are supported (the result is a byte)")
+    for k, c in enumerate(classes):
+        if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= c < ncls:
+            raise CswinHipError(f"argmax_zoom_back: classes[{k}] = {c!r} is not a class index in [0, {ncls})")
+    key = (tuple(int(c) for c in classes), torch.device(device))
+    if key not in _class_tables:
+        _class_tables[key] = torch.tensor(key[0], dtype=torch.int32).to(device)
+    return _class_tables[key]
+
+
+def argmax_zoom_back(logits, size, classes=None):
     """scipy.ndimage.zoom(torch.argmax(logits, 1)[b], (H / h, W / w), order=0) of logits (B, ncls, h, w) fp32 as a uint8
     (B, H, W) HIP tensor; size = (H, W), ncls <= 255.  The source index of every output row / column is scipy's own
-    (utils.nearest_index); with size == (h, w) it is the plain argmax."""
+    (utils.nearest_index); with size == (h, w) it is the plain argmax.
+    classes: a sequence of 1..255 class indices in [0, ncls) (CswinHipError otherwise): the argmax is torch.argmax(logits[:, classes],
+    1), i.e. the result is the POSITION in the list -- how a continual model is scored on one dataset's own classes.  The list may
+    be unordered or repeat a class (the earlier position wins); ncls itself is then not limited."""
     logits = dev_f32(logits, "argmax_zoom_back logits")
     if logits.dim() != 4:
         raise CswinHipError(f"argmax_zoom_back: logits {tuple(logits.shape)} must be (B, ncls, h, w)")
     from .utils import nearest_index_device
     (B, ncls, h, w), (H, W) = logits.shape, (int(size[0]), int(size[1]))
+    table = None if classes is None else _class_table(classes, ncls, logits.device)
     out = torch.empty((B, H, W), dtype=torch.uint8, device=logits.device)
-    call("cswin_argmax_zoom_back", ptr(logits), ptr(out), ptr(nearest_index_device(h, H, logits.device)),
-         ptr(nearest_index_device(w, W, logits.device)), B, ncls, h, w, H, W, stream())
+    rows, cols = nearest_index_device(h, H, logits.device), nearest_index_device(w, W, logits.device)
+    if table is None:
+        call("cswin_argmax_zoom_back", ptr(logits), ptr(out), ptr(rows), ptr(cols), B, ncls, h, w, H, W, stream())
+    else:
+        call("cswin_argmax_zoom_back_classes", ptr(logits), ptr(out), ptr(rows), ptr(cols), ptr(table), table.numel(), B, ncls, h, w,
+             H, W, stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# label statistics of a continual-learning stage
+# ------------------------------------------------------------------------------------------------
+def class_counts(labels, ncls, label_map=None):
+    """Per-slice class histogram (csrc/label_stats.hip).  labels: uint8 or int64 HIP tensor (N, H, W) or (H, W); label_map: None
+    or an int32 HIP tensor (continual.new_label_map: raw id r < len(label_map) has class label_map[r], the convention of
+    continual_loss).  Returns the int64 device tensor (N, ncls + 1): column c < ncls counts the elements of a slice with class c,
+    the last column those without a class (outside the map, or outside [0, ncls)), so every row sums to H * W.  ncls in 1..256.
+    One launch, no host sync, the same bits on every run."""
+    if not labels.is_cuda:
+        raise CswinHipError(f"class_counts labels are on {labels.device}: the cswin_unet_amd ops run on a HIP device only (no CPU fallback)")
+    if labels.dtype not in (torch.uint8, torch.int64):
+        raise CswinHipError(f"class_counts labels have dtype {labels.dtype}; class ids are passed as uint8 or int64")
+    if labels.dim() not in (2, 3):
+        raise CswinHipError(f"class_counts: labels {tuple(labels.shape)} must be (N, H, W) or (H, W)")
+    if label_map is not None and (not label_map.is_cuda or label_map.dtype != torch.int32 or label_map.dim() != 1):
+        raise CswinHipError("class_counts: label_map must be a one-dimensional int32 tensor on the HIP device")
+    if not 1 <= int(ncls) <= 256:
+        raise CswinHipError(f"class_counts: ncls={ncls} outside 1..256")
+    labels = labels.contiguous()
+    N = labels.shape[0] if labels.dim() == 3 else 1
+    counts = torch.empty((N, int(ncls) + 1), dtype=torch.int64, device=labels.device)
+    lmap = None if label_map is None else label_map.contiguous()
+    call("cswin_class_counts", ptr(labels), labels.element_size(), ptr(lmap), 0 if lmap is None else lmap.numel(), ptr(counts), N,
+         labels.shape[-2] * labels.shape[-1], int(ncls), stream())
+    return counts
 
 
 # ------------------------------------------------------------------------------------------------

@@ -14,6 +14,8 @@ Mirrors the reference's utils.py names and call signatures:
     float64) instead of the per-class scipy loop; ``evaluate_volumes`` is the aggregating loop of test.py:155-164.
     ``resize="hip"`` keeps the volume on the device: both zooms are linear maps whose 1-D operators ``zoom_operator`` /
     ``nearest_index`` take from scipy itself, applied by ops.resize_slices / ops.argmax_zoom_back (csrc/resize.hip).
+    ``class_indices`` scores a continual model on one dataset's own output channels (universal_test.py:50-54): the argmax runs
+    over ``net(x)[:, class_indices]``, on the device through the class list of ops.argmax_zoom_back.
 """
 import functools
 import logging
@@ -253,9 +255,9 @@ def rotation_index_device(H, W, angle, device):
     return _device_tables[key]
 
 
-def _predict_volume_hip(vol, net, patch_size, batch_slices, device):
+def _predict_volume_hip(vol, net, patch_size, batch_slices, device, class_indices=None):
     """predict_volume's loop with the volume resident on the device: upload once, per batch resize_slices -> net ->
-    argmax_zoom_back into a uint8 (D, H, W) device volume."""
+    argmax_zoom_back (over class_indices, if given) into a uint8 (D, H, W) device volume."""
     D, x, y = vol.shape
     dvol = torch.from_numpy(np.ascontiguousarray(vol)).to(device)
     resize = x != patch_size[0] or y != patch_size[1]
@@ -265,18 +267,22 @@ def _predict_volume_hip(vol, net, patch_size, batch_slices, device):
     for d0 in range(0, D, batch_slices):
         sl = dvol[d0:d0 + batch_slices]
         inp = ops.resize_slices(sl, patch_size) if resize else sl
-        pred[d0:d0 + batch_slices] = ops.argmax_zoom_back(net(inp.unsqueeze(1)), (x, y))
+        pred[d0:d0 + batch_slices] = ops.argmax_zoom_back(net(inp.unsqueeze(1)), (x, y), classes=class_indices)
     return pred
 
 
 @torch.no_grad()
-def predict_volume(image, net, patch_size=(224, 224), batch_slices=16, device="cuda", resize="host", return_device=False):
+def predict_volume(image, net, patch_size=(224, 224), batch_slices=16, device="cuda", resize="host", return_device=False,
+                   class_indices=None):
     """image (D, H, W) or (H, W) numpy -> integer class map of the same shape.  Per slice: cubic zoom to patch_size if the
     size differs, network, argmax over classes (softmax is monotonic, utils.py:75), nearest zoom back (:70-81).
     resize: "host" = scipy's zooms per slice around batched network calls; "hip" = the volume is uploaded once, both zooms and
     the argmax run on the device (same values; float32 / float64 volumes, integer ones only when nothing is resized) and only the
     finished volume comes back, as the uint8 array it is on the device (the host path returns int64) -- or, with
-    return_device=True, stays there as a uint8 tensor."""
+    return_device=True, stays there as a uint8 tensor.
+    class_indices: None, or the output channels of one dataset in a continual model (continual.task_class_indices): the argmax
+    runs over net(x)[:, class_indices] and the result is the position in that list, the dataset's own class id
+    (universal_test.py:50-54); the hip path passes the list to ops.argmax_zoom_back instead of slicing the logits."""
     if resize not in ("host", "hip"):
         raise ValueError(f'predict_volume: resize must be "host" or "hip", got {resize!r}')
     if return_device and resize != "hip":
@@ -286,7 +292,7 @@ def predict_volume(image, net, patch_size=(224, 224), batch_slices=16, device="c
     vol = image[None] if single else image
     net.eval()
     if resize == "hip":
-        pred = _predict_volume_hip(vol, net, tuple(patch_size), batch_slices, device)
+        pred = _predict_volume_hip(vol, net, tuple(patch_size), batch_slices, device, class_indices)
         pred = pred if return_device else pred.cpu().numpy()
         return pred[0] if single else pred
     D, x, y = vol.shape
@@ -297,26 +303,31 @@ def predict_volume(image, net, patch_size=(224, 224), batch_slices=16, device="c
         if resize:
             sl = np.stack([zoom(s, (patch_size[0] / x, patch_size[1] / y), order=3) for s in sl])
         inp = torch.from_numpy(np.ascontiguousarray(sl)).unsqueeze(1).float().to(device)
-        out = torch.argmax(net(inp), dim=1).cpu().numpy()
+        logits = net(inp)
+        out = torch.argmax(logits if class_indices is None else logits[:, list(class_indices)], dim=1).cpu().numpy()
         for i, o in enumerate(out):
             pred[d0 + i] = zoom(o, (x / patch_size[0], y / patch_size[1]), order=0) if resize else o
     return pred[0] if single else pred
 
 
 def test_single_volume(image, label, net, classes, patch_size=[256, 256], test_save_path=None, case=None, z_spacing=1,
-                       batch_slices=16, device="cuda", metrics="host", resize="host"):
+                       batch_slices=16, device="cuda", metrics="host", resize="host", class_indices=None):
     """Per-class (dice, hd95) of one volume, classes 1..classes-1 (utils.py:61-102).  image / label: (1, D, H, W) tensors
     as the DataLoader yields them.  With test_save_path the volumes are written as .npz (SimpleITK, which the reference
     uses for .nii.gz, is not installed here).  metrics: "host" = the per-class scipy loop, "hip" = one volume_metrics call on
     the device (same values).  resize: predict_volume's; with resize="hip" and metrics="hip" the prediction goes from the one to
-    the other as a device tensor and is downloaded only to be saved."""
+    the other as a device tensor and is downloaded only to be saved.  class_indices: predict_volume's; it must name `classes`
+    channels (ValueError otherwise), the labels being that dataset's own ids 0..classes-1."""
+    if class_indices is not None and len(class_indices) != classes:
+        raise ValueError(f"test_single_volume: class_indices has {len(class_indices)} entries for classes={classes}")
     if metrics not in ("host", "hip"):
         raise ValueError(f'test_single_volume: metrics must be "host" or "hip", got {metrics!r}')
     if resize not in ("host", "hip"):
         raise ValueError(f'test_single_volume: resize must be "host" or "hip", got {resize!r}')
     image, label = image.squeeze(0).cpu().detach().numpy(), label.squeeze(0).cpu().detach().numpy()
     on_device = resize == "hip" and metrics == "hip"
-    prediction = predict_volume(image, net, tuple(patch_size), batch_slices, device, resize=resize, return_device=on_device)
+    prediction = predict_volume(image, net, tuple(patch_size), batch_slices, device, resize=resize, return_device=on_device,
+                                class_indices=class_indices)
     if not on_device:
         prediction = prediction.astype(label.dtype)
     if metrics == "hip":
@@ -336,18 +347,18 @@ test_single_volume.__test__ = False     # not a pytest test (the name is the ref
 
 
 def evaluate_volumes(loader, net, classes, patch_size, metrics="hip", test_save_path=None, z_spacing=1, batch_slices=16,
-                     device="cuda", resize="host"):
+                     device="cuda", resize="host", class_indices=None):
     """The volume loop of the reference's inference() (test.py:155-164): test_single_volume per batch of `loader` (dicts with
     "image", "label" (1, D, H, W) and "case_name", batch size 1), the per-volume and final lines it logs.  Returns
     (per_volume, class_mean, mean_dice, mean_hd95): the metric list of every volume, the (classes-1, 2) table of per-class
-    means over the volumes, and that table's column means."""
+    means over the volumes, and that table's column means.  class_indices: test_single_volume's."""
     per_volume = []
     for i_batch, batch in enumerate(loader):
         name = batch["case_name"]
         name = name if isinstance(name, str) else name[0]
         metric_i = test_single_volume(batch["image"], batch["label"], net, classes=classes, patch_size=list(patch_size),
                                       test_save_path=test_save_path, case=name, z_spacing=z_spacing, batch_slices=batch_slices,
-                                      device=device, metrics=metrics, resize=resize)
+                                      device=device, metrics=metrics, resize=resize, class_indices=class_indices)
         per_volume.append(metric_i)
         m = np.mean(metric_i, axis=0)
         logging.info('idx %d case %s mean_dice %f mean_hd95 %f' % (i_batch, name, m[0], m[1]))

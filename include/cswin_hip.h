@@ -29,7 +29,7 @@ extern "C" {
 /* Bumped whenever a prototype or struct below changes (1: round 1; 2: round 2 -- stream / precision / storage arguments; 3: round 3 --
  * cswin_attn_fwd writes y0, cswin_attn_bwd reads it).  cswin_abi_version() returns the value the library was built with: a consumer
  * compiled against another header must refuse to call it.  Entry points that are only ADDED (cswin_seg_metrics*, cswin_resize_banded, cswin_argmax_zoom_back, cswin_augment_*,
- * cswin_chunk_sumsq, cswin_norm_finalize, cswin_adamw_flat, cswin_tpgm_*) do not bump it: every prototype an older consumer binds is unchanged. */
+ * cswin_chunk_sumsq, cswin_norm_finalize, cswin_adamw_flat, cswin_tpgm_*, cswin_argmax_zoom_back_classes, cswin_class_counts) do not bump it: every prototype an older consumer binds is unchanged. */
 #define CSWIN_ABI_VERSION 4
 
 #define CSWIN_OK 0
@@ -437,6 +437,26 @@ int cswin_resize_banded(const void* x, float* y, const double* wh, const int* sh
  * output of 512 -> 224): out is 0 there.  Indices past the end are clamped on the device.  ncls in 1..255; each of B, h, w, H, W in 1..2048. */
 int cswin_argmax_zoom_back(const float* logits, unsigned char* out, const int* src_row, const int* src_col, int B, int ncls, int h,
                            int w, int H, int W, void* stream);
+/* cswin_argmax_zoom_back over a list of classes: out[b][i][j] = the POSITION k < nsel of the largest of
+ * logits[b][classes[k]][src_row[i]][src_col[j]], i.e. torch.argmax(logits[:, classes], 1) before the zoom -- how a continual model
+ * with ncls outputs is scored on one dataset's own classes (universal_test.py:50-54).  The first k in list order wins a tie, a NaN
+ * beats every number and the first NaN wins; a negative source index writes 0.  classes: device int32 [nsel], entries clamped into
+ * [0, ncls) on the device; the list may be unordered and may repeat a class (the earlier position wins).  nsel in 1..255 (the
+ * output byte), ncls >= 1; every other limit is cswin_argmax_zoom_back's. */
+int cswin_argmax_zoom_back_classes(const float* logits, unsigned char* out, const int* src_row, const int* src_col,
+                                   const int* classes, int nsel, int B, int ncls, int h, int w, int H, int W, void* stream);
+
+/* ---- label statistics of a continual-learning stage (universal_train.py:1006-1015 class pixel counts, :204-211 the slices that
+ * hold a class): per-slice class histogram in one streaming pass.
+ * labels: N slices of slice_elems class ids, uint8 (label_bytes = 1) or int64 (8), densely packed.  counts: int64 [N][ncls + 1],
+ * written in full (no memset, no workspace, no global atomics, bit-reproducible): column c < ncls = the elements of slice n with
+ * class c, column ncls = the elements without a class, so every row sums to slice_elems.  The class of a raw id r is r itself
+ * (label_map NULL, nmap 0) or label_map[r] for 0 <= r < nmap (device int32; the table of continual.new_label_map, the convention
+ * of cswin_cl_loss_sums); an id outside the map, or a class outside [0, ncls), has no class.
+ * ncls in 1..256, N >= 1, slice_elems in 1..2^31-1; another label_bytes is CSWIN_ERR_UNSUPPORTED; pointers aligned to their
+ * element size. */
+int cswin_class_counts(const void* labels, int label_bytes, const int* label_map, int nmap, long long* counts, int N,
+                       long long slice_elems, int ncls, void* stream);
 
 /* ---- training augmentation of a batch of raw slices (datasets/dataset_synapse.py:12-47: np.rot90 + np.flip, or
  *      scipy.ndimage.rotate(order=0, reshape=False), then the zooms to the network's size) ----
