@@ -87,6 +87,7 @@ SIGNATURES = {
     "cswin_class_counts": (I, [P, I, P, I, P, I, L, I, P]),
     "cswin_augment_gather": (I, [P, P, P, I, I, I, I, I, I, P]),
     "cswin_augment_labels": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
+    "cswin_gaussian_blur": (I, [P, P, P, I, I, I, I, P]),
 }
 
 

@@ -51,13 +51,20 @@ def _resize_pair(image, label, size):
 
 
 class RandomGenerator(object):
-    """{'image': (H, W), 'label': (H, W)} -> {'image': float32 (1, h, w), 'label': int64 (h, w)} (:29-47)."""
+    """{'image': (H, W), 'label': (H, W)} -> {'image': float32 (1, h, w), 'label': int64 (h, w)} (:29-47).
+    blur_sigma: None, or the sigma of the blurred copy of the dataset (apply_blur_train.py:147-150): the image, cast to float32
+    unless it is floating already, goes through ndimage.gaussian_filter before the transforms, as if the blurred slice had been
+    read from disk.  The random draws are the same either way."""
 
-    def __init__(self, output_size):
-        self.output_size = output_size
+    def __init__(self, output_size, blur_sigma=None):
+        self.output_size, self.blur_sigma = output_size, blur_sigma
 
     def __call__(self, sample):
         pair = (sample['image'], sample['label'])
+        if self.blur_sigma is not None:
+            image = np.asarray(pair[0])
+            image = image if np.issubdtype(image.dtype, np.floating) else image.astype(np.float32)
+            pair = (ndimage.gaussian_filter(image, self.blur_sigma), pair[1])
         # one uniform draw decides "rot90 + flip"; only if that fails a second draw decides "small rotation"
         if random.random() > 0.5:
             pair = random_rot_flip(*pair)

@@ -16,7 +16,7 @@ from ._lib import AugmentDesc, ConvImageJob, CswinHipError, ReduceJob, WgradDesc
 
 __all__ = ["layer_norm", "linear", "linear_pair", "mlp", "stripe_attention", "cswin_block", "conv_tokens", "patch_embed_conv", "carafe_reassemble",
            "carafe_reassemble_nchw", "conv_weight_images", "head_compose", "tokens_to_nchw", "matmul_nn", "ce_dice_loss", "continual_loss", "dropout", "img2windows", "windows2img",
-           "seg_metrics", "resize_slices", "argmax_zoom_back", "augment_batch", "class_counts"]
+           "seg_metrics", "resize_slices", "argmax_zoom_back", "augment_batch", "class_counts", "gaussian_blur"]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1249,6 +1249,29 @@ def resize_slices(x, size):
     return y
 
 
+def gaussian_blur(x, sigma, truncate=4.0):
+    """scipy.ndimage.gaussian_filter(x[d], sigma, truncate=truncate) (mode "reflect") of every slice of x (D, H, W), a float32 HIP
+    tensor, as a new float32 tensor of the same shape (csrc/blur.hip).  The taps are scipy's own (utils.gaussian_taps, uploaded
+    once per sigma and device); the device repeats scipy's float64 sums in scipy's order and rounds to float32 after each axis, as
+    scipy does.  A non-contiguous view is copied.  sigma: finite, positive, radius int(truncate * sigma + 0.5) <= 32 (ValueError
+    otherwise).  Integer dtypes raise ValueError: scipy rounds integer outputs, which stays on the host path."""
+    if not x.is_cuda:
+        raise CswinHipError(f"gaussian_blur input is on {x.device}: the cswin_unet_amd ops run on a HIP device only (no CPU fallback)")
+    if not x.is_floating_point():
+        raise ValueError(f"gaussian_blur: dtype {x.dtype}; integer slices are blurred on the host (scipy rounds integer outputs)")
+    if x.dtype != torch.float32:
+        raise CswinHipError(f"gaussian_blur input has dtype {x.dtype}; float32 is blurred")
+    if x.dim() != 3:
+        raise CswinHipError(f"gaussian_blur: input {tuple(x.shape)} must be (D, H, W)")
+    from .utils import gaussian_taps_device
+    taps, r = gaussian_taps_device(sigma, truncate, x.device)
+    x = x.contiguous()
+    D, H, W = x.shape
+    y = torch.empty_like(x)
+    call("cswin_gaussian_blur", ptr(x), ptr(y), ptr(taps), r, D, H, W, stream())
+    return y
+
+
 _class_tables = {}
 
 
@@ -1337,7 +1360,7 @@ def _upload(values, device):
     return host.to(device, non_blocking=True)
 
 
-def augment_batch(images, labels, params, size):
+def augment_batch(images, labels, params, size, blur_sigma=None):
     """datasets.RandomGenerator's arithmetic for a whole batch of raw slices, on the device (csrc/augment.hip, csrc/resize.hip).
     images: float32 HIP tensor (B, H, W); labels: uint8 HIP tensor (B, H, W); params: integer HOST tensor (B, 4) of
     (kind, k, axis, angle) per sample as datasets.RawSliceParams draws them (kind 0: nothing, 1: np.flip(np.rot90(x, k), axis),
@@ -1350,7 +1373,9 @@ def augment_batch(images, labels, params, size):
     each (H, W, angle) rotation map is one scipy.ndimage.rotate on the host (~10 ms at 512 x 512) and a blocking upload from
     pageable memory, up to 40 times per shape over a run, and the nearest / zoom tables of a size pair likewise, once.  They
     are uploaded blocking on purpose: the copies are cached per device and later read from whichever stream calls, so a
-    copy that were still in flight on the first caller's stream would race with a second stream's kernels."""
+    copy that were still in flight on the first caller's stream would race with a second stream's kernels.
+    blur_sigma: None, or the sigma of scipy.ndimage.gaussian_filter applied to the raw images first (gaussian_blur: one more
+    launch), as the reference blurs the stored slices that RandomGenerator then transforms; labels are untouched."""
     for t, what, dtype, why in ((images, "augment_batch images", torch.float32, "raw slices are float32 (other dtypes: augment=\"host\")"),
                                 (labels, "augment_batch labels", torch.uint8, "class ids are passed as uint8")):
         if not t.is_cuda:
@@ -1365,6 +1390,8 @@ def augment_batch(images, labels, params, size):
     from .datasets.dataset_synapse import AUG_NONE, AUG_ROT90_FLIP, AUG_ROTATE
     from .utils import nearest_index_device, rotation_index_device
     images, labels, dev = images.contiguous(), labels.contiguous(), images.device
+    if blur_sigma is not None:
+        images = gaussian_blur(images, blur_sigma)
     (B, H, W), (h, w) = images.shape, (int(size[0]), int(size[1]))
     descs, swapped = [], []
     for b, (kind, k, axis, angle) in enumerate(params.tolist()):

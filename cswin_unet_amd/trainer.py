@@ -455,14 +455,16 @@ class _Prefetcher:
     """Pinned host batches -> device on a side stream, one batch ahead of the step that consumes them.
     augment="hip": the loader yields RawSliceParams' raw batches (image, uint8 label, params); they are uploaded and finished by
     ops.augment_batch(..., output_size) on the same side stream, so the augmentation too overlaps the previous step, and the
-    (image, label) pair handed out is the one the host path yields."""
+    (image, label) pair handed out is the one the host path yields.  blur_sigma (augment="hip" only): augment_batch's; on the
+    host path the loader's RandomGenerator blurs."""
 
-    def __init__(self, loader, device, augment="host", output_size=None):
+    def __init__(self, loader, device, augment="host", output_size=None, blur_sigma=None):
         if augment not in ("host", "hip"):
             raise ValueError(f'_Prefetcher: augment must be "host" or "hip", got {augment!r}')
         if augment == "hip" and (output_size is None or len(output_size) != 2):
             raise ValueError(f'_Prefetcher: augment="hip" needs output_size = (h, w), got {output_size!r}')
         self.it, self.device, self.augment, self.output_size = iter(loader), device, augment, output_size
+        self.blur_sigma = blur_sigma if augment == "hip" else None
         self.stream = torch.cuda.Stream(device)
         self._next()
 
@@ -477,7 +479,7 @@ class _Prefetcher:
             if self.augment == "hip":
                 # the raw uploads and augment_batch's temporaries are allocated, written and read on the side stream only: they
                 # never cross to the consumer's stream, only the two results do (recorded in __next__ like the host path's)
-                img, lab = augment_batch(img, lab, batch['params'], self.output_size)
+                img, lab = augment_batch(img, lab, batch['params'], self.output_size, blur_sigma=self.blur_sigma)
             self.batch = (img, lab)
 
     def __iter__(self):
@@ -499,7 +501,10 @@ def trainer_synapse(args, model, snapshot_path, group=None, log_every=1):
 
     args: root_path, list_dir, img_size, num_classes, batch_size (per GPU), base_lr, max_epochs, optionally num_workers and
     augment: "host" (default) = RandomGenerator in the workers; "hip" = the workers only draw the random parameters
-    (RawSliceParams) and the prefetcher applies them on the device (ops.augment_batch: float32 slices of one shape per batch).
+    (RawSliceParams) and the prefetcher applies them on the device (ops.augment_batch: float32 slices of one shape per batch);
+    blur_sigma: None (default), or the sigma of the blurred copy of the dataset to train on (finetune.py:262-268 reads
+    Synapse_blurred, written by apply_blur_train.py with scipy.ndimage.gaussian_filter): the stored slices are blurred as they
+    are read, by RandomGenerator on the host or by ops.augment_batch on the device, whichever `augment` selects.
     Same dataset / augmentation / loss / optimiser / LR schedule / checkpoint schedule (``epoch_N.pth`` every third epoch
     of the second half and at the end, :79-90).  Differences, all execution-side: one process per GPU (pass the process
     group; each rank reads its own shard through a DistributedSampler) instead of nn.DataParallel; batches are prefetched
@@ -518,6 +523,10 @@ def trainer_synapse(args, model, snapshot_path, group=None, log_every=1):
     augment = getattr(args, "augment", "host")
     if augment not in ("host", "hip"):
         raise ValueError(f'trainer_synapse: augment must be "host" or "hip", got {augment!r}')
+    blur_sigma = getattr(args, "blur_sigma", None)
+    if blur_sigma is not None:
+        from .utils import gaussian_taps
+        gaussian_taps(blur_sigma)                                       # ValueError for a sigma neither path takes
     os.makedirs(snapshot_path, exist_ok=True)
     logging.basicConfig(filename=os.path.join(snapshot_path, "log.txt"), level=logging.INFO,
                         format='[%(asctime)s.%(msecs)03d] %(message)s', datefmt='%H:%M:%S')
@@ -528,7 +537,8 @@ def trainer_synapse(args, model, snapshot_path, group=None, log_every=1):
     world = dist.get_world_size(group) if group is not None else 1
     device = next(model.parameters()).device
     db_train = Synapse_dataset(base_dir=args.root_path, list_dir=args.list_dir, split="train",
-                               transform=(RawSliceParams if augment == "hip" else RandomGenerator)(output_size=[args.img_size, args.img_size]))
+                               transform=RawSliceParams(output_size=[args.img_size, args.img_size]) if augment == "hip" else
+                               RandomGenerator(output_size=[args.img_size, args.img_size], blur_sigma=blur_sigma))
     print("The length of train set is: {}".format(len(db_train)))
     seed = getattr(args, "seed", 1234)
 
@@ -556,7 +566,7 @@ def trainer_synapse(args, model, snapshot_path, group=None, log_every=1):
     for epoch_num in range(max_epoch):
         if sampler is not None:
             sampler.set_epoch(epoch_num)
-        for image_batch, label_batch in _Prefetcher(loader, device, augment, (args.img_size, args.img_size)):
+        for image_batch, label_batch in _Prefetcher(loader, device, augment, (args.img_size, args.img_size), blur_sigma=blur_sigma):
             stats = trainer.train_step(image_batch, label_batch)
             iter_num += 1
             if log_every and iter_num % log_every == 0 and rank == 0:

@@ -16,6 +16,8 @@ Mirrors the reference's utils.py names and call signatures:
     ``nearest_index`` take from scipy itself, applied by ops.resize_slices / ops.argmax_zoom_back (csrc/resize.hip).
     ``class_indices`` scores a continual model on one dataset's own output channels (universal_test.py:50-54): the argmax runs
     over ``net(x)[:, class_indices]``, on the device through the class list of ops.argmax_zoom_back.
+    ``blur_sigma`` scores on the blurred copy of the data (apply_blur_test.py:79-81: ``gaussian_filter`` of every slice) without
+    writing that copy: scipy per slice on the host path, ops.gaussian_blur (csrc/blur.hip, same bits) with ``resize="hip"``.
 """
 import functools
 import logging
@@ -23,7 +25,7 @@ import logging
 import numpy as np
 import torch
 import torch.nn as nn
-from scipy.ndimage import binary_erosion, distance_transform_edt, generate_binary_structure, rotate, zoom
+from scipy.ndimage import binary_erosion, distance_transform_edt, gaussian_filter, gaussian_filter1d, generate_binary_structure, rotate, zoom
 
 from . import ops
 
@@ -227,6 +229,34 @@ def rotation_index(H, W, angle):
     return idx
 
 
+@functools.lru_cache(maxsize=None)
+def _gaussian_taps(sigma, truncate):
+    r = int(truncate * sigma + 0.5)
+    if r > 32:
+        raise ValueError(f"gaussian_taps: sigma={sigma:g}, truncate={truncate:g} give radius {r}; 0..32 is supported")
+    impulse = np.zeros(4 * r + 3, np.float64)
+    impulse[2 * r + 1] = 1.0
+    w = np.ascontiguousarray(gaussian_filter1d(impulse, sigma, truncate=truncate)[r + 1:3 * r + 2])
+    if w.shape != (2 * r + 1,) or not np.array_equal(w, w[::-1]):
+        raise ValueError(f"gaussian_taps: scipy's impulse response for sigma={sigma:g} is not a symmetric kernel of {2 * r + 1} taps")
+    w.setflags(write=False)
+    return w, r
+
+
+def gaussian_taps(sigma, truncate=4.0):
+    """``(weights float64 [2r + 1], r)``: the taps of ``scipy.ndimage.gaussian_filter1d(x, sigma, truncate=truncate)`` and its
+    radius r = int(truncate * sigma + 0.5).  The weights are scipy's own: its response to a float64 unit impulse in the middle of
+    4r + 3 samples (no boundary reaches the 2r + 1 read out), so the exponential and its normalisation are not restated here.
+    ValueError for a sigma or truncate that is not finite and positive, for taps that are not exactly symmetric (the device
+    folds them, as scipy's correlate1d does) and for r > 32.  Cached: do not write to the array."""
+    sigma, truncate = float(sigma), float(truncate)
+    if not (np.isfinite(sigma) and sigma > 0):
+        raise ValueError(f"gaussian_taps: sigma={sigma!r} must be finite and positive")
+    if not (np.isfinite(truncate) and truncate > 0):
+        raise ValueError(f"gaussian_taps: truncate={truncate!r} must be finite and positive")
+    return _gaussian_taps(sigma, truncate)
+
+
 _device_tables = {}
 
 
@@ -255,10 +285,23 @@ def rotation_index_device(H, W, angle, device):
     return _device_tables[key]
 
 
-def _predict_volume_hip(vol, net, patch_size, batch_slices, device, class_indices=None):
-    """predict_volume's loop with the volume resident on the device: upload once, per batch resize_slices -> net ->
-    argmax_zoom_back (over class_indices, if given) into a uint8 (D, H, W) device volume."""
+def gaussian_taps_device(sigma, truncate, device):
+    """gaussian_taps' first half ``w[-r] .. w[0]`` (what cswin_gaussian_blur reads) as a float64 tensor on `device`, and r;
+    uploaded once per (sigma, truncate, device), blocking for the reason ops.augment_batch's docstring gives."""
+    key = ("gauss", float(sigma), float(truncate), torch.device(device))
+    if key not in _device_tables:
+        w, r = gaussian_taps(sigma, truncate)
+        _device_tables[key] = (torch.from_numpy(w[:r + 1].copy()).to(device), r)
+    return _device_tables[key]
+
+
+def _predict_volume_hip(vol, net, patch_size, batch_slices, device, class_indices=None, blur_sigma=None):
+    """predict_volume's loop with the volume resident on the device: upload once, per batch (gaussian_blur ->) resize_slices ->
+    net -> argmax_zoom_back (over class_indices, if given) into a uint8 (D, H, W) device volume."""
     D, x, y = vol.shape
+    if blur_sigma is not None and vol.dtype != np.float32:
+        raise ValueError(f'predict_volume: blur_sigma with resize="hip" takes float32 volumes, got {vol.dtype} (scipy blurs in the '
+                         f'volume\'s own dtype); use resize="host"')
     dvol = torch.from_numpy(np.ascontiguousarray(vol)).to(device)
     resize = x != patch_size[0] or y != patch_size[1]
     if not resize:
@@ -266,6 +309,8 @@ def _predict_volume_hip(vol, net, patch_size, batch_slices, device, class_indice
     pred = torch.empty((D, x, y), dtype=torch.uint8, device=dvol.device)
     for d0 in range(0, D, batch_slices):
         sl = dvol[d0:d0 + batch_slices]
+        if blur_sigma is not None:
+            sl = ops.gaussian_blur(sl, blur_sigma)
         inp = ops.resize_slices(sl, patch_size) if resize else sl
         pred[d0:d0 + batch_slices] = ops.argmax_zoom_back(net(inp.unsqueeze(1)), (x, y), classes=class_indices)
     return pred
@@ -273,7 +318,7 @@ def _predict_volume_hip(vol, net, patch_size, batch_slices, device, class_indice
 
 @torch.no_grad()
 def predict_volume(image, net, patch_size=(224, 224), batch_slices=16, device="cuda", resize="host", return_device=False,
-                   class_indices=None):
+                   class_indices=None, blur_sigma=None):
     """image (D, H, W) or (H, W) numpy -> integer class map of the same shape.  Per slice: cubic zoom to patch_size if the
     size differs, network, argmax over classes (softmax is monotonic, utils.py:75), nearest zoom back (:70-81).
     resize: "host" = scipy's zooms per slice around batched network calls; "hip" = the volume is uploaded once, both zooms and
@@ -282,17 +327,22 @@ def predict_volume(image, net, patch_size=(224, 224), batch_slices=16, device="c
     return_device=True, stays there as a uint8 tensor.
     class_indices: None, or the output channels of one dataset in a continual model (continual.task_class_indices): the argmax
     runs over net(x)[:, class_indices] and the result is the position in that list, the dataset's own class id
-    (universal_test.py:50-54); the hip path passes the list to ops.argmax_zoom_back instead of slicing the logits."""
+    (universal_test.py:50-54); the hip path passes the list to ops.argmax_zoom_back instead of slicing the logits.
+    blur_sigma: None, or the sigma of scipy.ndimage.gaussian_filter applied to every slice on its own before the cubic zoom
+    (apply_blur_test.py:79-81): scipy in the volume's own dtype on the host path, ops.gaussian_blur per batch of slices with
+    resize="hip" (also when nothing is resized), which takes float32 volumes only (ValueError otherwise)."""
     if resize not in ("host", "hip"):
         raise ValueError(f'predict_volume: resize must be "host" or "hip", got {resize!r}')
     if return_device and resize != "hip":
         raise ValueError('predict_volume: return_device needs resize="hip"')
+    if blur_sigma is not None:
+        gaussian_taps(blur_sigma)                                       # ValueError for a sigma neither path takes
     image = np.asarray(image)
     single = image.ndim == 2
     vol = image[None] if single else image
     net.eval()
     if resize == "hip":
-        pred = _predict_volume_hip(vol, net, tuple(patch_size), batch_slices, device, class_indices)
+        pred = _predict_volume_hip(vol, net, tuple(patch_size), batch_slices, device, class_indices, blur_sigma)
         pred = pred if return_device else pred.cpu().numpy()
         return pred[0] if single else pred
     D, x, y = vol.shape
@@ -300,6 +350,8 @@ def predict_volume(image, net, patch_size=(224, 224), batch_slices=16, device="c
     pred = np.zeros((D, x, y), np.int64)
     for d0 in range(0, D, batch_slices):
         sl = vol[d0:d0 + batch_slices]
+        if blur_sigma is not None:
+            sl = np.stack([gaussian_filter(s, blur_sigma) for s in sl])
         if resize:
             sl = np.stack([zoom(s, (patch_size[0] / x, patch_size[1] / y), order=3) for s in sl])
         inp = torch.from_numpy(np.ascontiguousarray(sl)).unsqueeze(1).float().to(device)
@@ -311,13 +363,14 @@ def predict_volume(image, net, patch_size=(224, 224), batch_slices=16, device="c
 
 
 def test_single_volume(image, label, net, classes, patch_size=[256, 256], test_save_path=None, case=None, z_spacing=1,
-                       batch_slices=16, device="cuda", metrics="host", resize="host", class_indices=None):
+                       batch_slices=16, device="cuda", metrics="host", resize="host", class_indices=None, blur_sigma=None):
     """Per-class (dice, hd95) of one volume, classes 1..classes-1 (utils.py:61-102).  image / label: (1, D, H, W) tensors
     as the DataLoader yields them.  With test_save_path the volumes are written as .npz (SimpleITK, which the reference
     uses for .nii.gz, is not installed here).  metrics: "host" = the per-class scipy loop, "hip" = one volume_metrics call on
     the device (same values).  resize: predict_volume's; with resize="hip" and metrics="hip" the prediction goes from the one to
     the other as a device tensor and is downloaded only to be saved.  class_indices: predict_volume's; it must name `classes`
-    channels (ValueError otherwise), the labels being that dataset's own ids 0..classes-1."""
+    channels (ValueError otherwise), the labels being that dataset's own ids 0..classes-1.  blur_sigma: predict_volume's; the
+    saved .npz keeps the image as it was passed in."""
     if class_indices is not None and len(class_indices) != classes:
         raise ValueError(f"test_single_volume: class_indices has {len(class_indices)} entries for classes={classes}")
     if metrics not in ("host", "hip"):
@@ -327,7 +380,7 @@ def test_single_volume(image, label, net, classes, patch_size=[256, 256], test_s
     image, label = image.squeeze(0).cpu().detach().numpy(), label.squeeze(0).cpu().detach().numpy()
     on_device = resize == "hip" and metrics == "hip"
     prediction = predict_volume(image, net, tuple(patch_size), batch_slices, device, resize=resize, return_device=on_device,
-                                class_indices=class_indices)
+                                class_indices=class_indices, blur_sigma=blur_sigma)
     if not on_device:
         prediction = prediction.astype(label.dtype)
     if metrics == "hip":
@@ -347,18 +400,19 @@ test_single_volume.__test__ = False     # not a pytest test (the name is the ref
 
 
 def evaluate_volumes(loader, net, classes, patch_size, metrics="hip", test_save_path=None, z_spacing=1, batch_slices=16,
-                     device="cuda", resize="host", class_indices=None):
+                     device="cuda", resize="host", class_indices=None, blur_sigma=None):
     """The volume loop of the reference's inference() (test.py:155-164): test_single_volume per batch of `loader` (dicts with
     "image", "label" (1, D, H, W) and "case_name", batch size 1), the per-volume and final lines it logs.  Returns
     (per_volume, class_mean, mean_dice, mean_hd95): the metric list of every volume, the (classes-1, 2) table of per-class
-    means over the volumes, and that table's column means.  class_indices: test_single_volume's."""
+    means over the volumes, and that table's column means.  class_indices, blur_sigma: test_single_volume's."""
     per_volume = []
     for i_batch, batch in enumerate(loader):
         name = batch["case_name"]
         name = name if isinstance(name, str) else name[0]
         metric_i = test_single_volume(batch["image"], batch["label"], net, classes=classes, patch_size=list(patch_size),
                                       test_save_path=test_save_path, case=name, z_spacing=z_spacing, batch_slices=batch_slices,
-                                      device=device, metrics=metrics, resize=resize, class_indices=class_indices)
+                                      device=device, metrics=metrics, resize=resize, class_indices=class_indices,
+                                      blur_sigma=blur_sigma)
         per_volume.append(metric_i)
         m = np.mean(metric_i, axis=0)
         logging.info('idx %d case %s mean_dice %f mean_hd95 %f' % (i_batch, name, m[0], m[1]))

@@ -29,7 +29,7 @@ extern "C" {
 /* Bumped whenever a prototype or struct below changes (1: round 1; 2: round 2 -- stream / precision / storage arguments; 3: round 3 --
  * cswin_attn_fwd writes y0, cswin_attn_bwd reads it).  cswin_abi_version() returns the value the library was built with: a consumer
  * compiled against another header must refuse to call it.  Entry points that are only ADDED (cswin_seg_metrics*, cswin_resize_banded, cswin_argmax_zoom_back, cswin_augment_*,
- * cswin_chunk_sumsq, cswin_norm_finalize, cswin_adamw_flat, cswin_tpgm_*, cswin_argmax_zoom_back_classes, cswin_class_counts) do not bump it: every prototype an older consumer binds is unchanged. */
+ * cswin_chunk_sumsq, cswin_norm_finalize, cswin_adamw_flat, cswin_tpgm_*, cswin_argmax_zoom_back_classes, cswin_class_counts, cswin_gaussian_blur) do not bump it: every prototype an older consumer binds is unchanged. */
 #define CSWIN_ABI_VERSION 4
 
 #define CSWIN_OK 0
@@ -457,6 +457,16 @@ int cswin_argmax_zoom_back_classes(const float* logits, unsigned char* out, cons
  * element size. */
 int cswin_class_counts(const void* labels, int label_bytes, const int* label_map, int nmap, long long* counts, int N,
                        long long slice_elems, int ncls, void* stream);
+
+/* ---- Gaussian blur of a batch of slices (csrc/blur.hip): scipy.ndimage.gaussian_filter(x[d], sigma), mode "reflect" ----
+ * x (D, H, W) float32 -> y (D, H, W) float32.  taps[0 .. radius] float64 = w[-radius] .. w[0], one half of scipy's symmetric
+ * kernel with the centre last (cswin_unet_amd.utils.gaussian_taps).  Axis 0 is filtered first and rounded to float32, then
+ * axis 1 and rounded again; every product and sum in float64 in correlate1d's folded order, acc = x[i] w[0], then
+ * acc += (x[i - k] + x[i + k]) w[-k] for k = radius .. 1, multiply and add rounded separately.  The reflected indices are
+ * computed on the device from H and W alone, so the radius may exceed either.  One launch, no workspace, no allocation, no
+ * synchronisation.  Each of D, H, W in 1..2048 (CSWIN_ERR_SHAPE), radius in 0..32 and x != y (CSWIN_ERR_UNSUPPORTED: the filter
+ * does not work in place); pointers aligned to their element size. */
+int cswin_gaussian_blur(const float* x, float* y, const double* taps, int radius, int D, int H, int W, void* stream);
 
 /* ---- training augmentation of a batch of raw slices (datasets/dataset_synapse.py:12-47: np.rot90 + np.flip, or
  *      scipy.ndimage.rotate(order=0, reshape=False), then the zooms to the network's size) ----
