@@ -3,15 +3,10 @@
 // teacher's (B, nold, H, W) logits -- fused like loss.hip: one pass over the logits each way, no one-hot tensor, no softmax
 // tensor, the new-dataset label map (:243-258) applied as a table lookup while the label is read.  `cswin_cl_loss_sums` leaves
 // 3 + 3*ncls plain sums over this rank's pixels in device memory; they add across data-parallel ranks.
-#include "common.h"
+// The per-pixel steps are loss_pixel.h's; this file owns the label map, the distillation block, the focal term and its derivative.
+#include "loss_pixel.h"
 
 namespace {
-
-// class of a pixel, or -1 for a label outside [0, NC): the 64-bit value is compared (as in loss.hip)
-template <int NC>
-__device__ __forceinline__ int label_class(long long label) {
-    return (unsigned long long)label < (unsigned long long)NC ? (int)label : -1;
-}
 
 // the label after the optional map (int32 table of n_map entries); an index outside the table is no class
 template <int NC>
@@ -37,7 +32,7 @@ __host__ __device__ inline int gamma_int(float gamma) {
     return (float)gi == gamma ? gi : -1;
 }
 
-// sums layout: [0] = sum -log p[label];  [1 + c] = intersect_c;  [1 + NC + c] = y_sum_c;  [1 + 2 NC + c] = z_sum_c (loss.hip's);
+// sums layout: loss_pixel.h's 1 + 3 NC, then
 // [1 + 3 NC] = sum of focal terms;  [2 + 3 NC] = sum over pixels of KL(teacher_T || student_T) over the first nold channels
 template <int NC>
 __global__ __launch_bounds__(256) void cl_loss_sums_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
@@ -54,14 +49,8 @@ __global__ __launch_bounds__(256) void cl_loss_sums_kernel(const float* __restri
     const long total = (long)B * HW;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const long b = i / HW, p = i - b * HW;
-        const float* lp = logits + b * NC * HW + p;
         float v[NC];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            v[c] = lp[c * HW];
-            mx = fmaxf(mx, v[c]);
-        }
+        const float mx = load_row<NC>(logits + b * NC * HW + p, HW, v);
         if (nold > 0) {
             // distillation: both rows are shifted by their own maximum BEFORE the division by T (an offset of 1e4 must cancel
             // exactly), and log q is formed from the shifted logits, never as log(q_c): where exp underflows, q_c is an exact
@@ -97,16 +86,15 @@ __global__ __launch_bounds__(256) void cl_loss_sums_kernel(const float* __restri
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             if (c == lab) vl = v[c];
-            v[c] = __expf(v[c] - mx);
-            sum += v[c];
+            sum += softmax_term<false>(v[c], mx);
         }
         const float inv = 1.0f / sum;
-        // an out-of-range label poisons the plain and the focal sum (loss.hip's convention; the reference's focal loss clamps)
+        // an out-of-range label poisons the plain and the focal sum (as loss.hip's CE sum; the reference's focal loss clamps)
         if (lab < 0) {
             acc[0] = __builtin_nanf("");
             acc[1 + 3 * NC] = __builtin_nanf("");
         } else {
-            const float nll = (mx - vl) + __logf(sum);
+            const float nll = row_nll(mx, vl, sum);
             acc[0] += nll;
             // F.cross_entropy(weight=, reduction='none') = w[label] * nll;  pt = exp(-ce);  1 - pt = -expm1(-ce): for a confident
             // pixel ce ~ 1e-6 and 1 - exp(-ce) has no correct digit in fp32
@@ -114,13 +102,7 @@ __global__ __launch_bounds__(256) void cl_loss_sums_kernel(const float* __restri
             acc[1 + 3 * NC] += alpha * pow_gamma(-expm1f(-ce), gamma, gi) * ce;
         }
 #pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const float pc = v[c] * inv;
-            const float oh = (c == lab) ? 1.f : 0.f;
-            acc[1 + c] += pc * oh;
-            acc[1 + NC + c] += oh;
-            acc[1 + 2 * NC + c] += pc * pc;
-        }
+        for (int c = 0; c < NC; ++c) dice_terms(v[c] * inv, c == lab, acc[1 + c], acc[1 + NC + c], acc[1 + 2 * NC + c]);
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
@@ -133,25 +115,16 @@ __global__ __launch_bounds__(256) void cl_loss_sums_kernel(const float* __restri
         partial[(long)blockIdx.x * NV + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
-// out[0..4] = loss, focal, dice, kd, ce;  coef as loss_finalize_kernel's (unweighted Dice)
+// out[0..4] = loss, focal, dice, kd, ce;  coef: dice_finalize's (unweighted Dice)
 __global__ void cl_loss_finalize_kernel(const float* __restrict__ sums, float* __restrict__ out, float* __restrict__ coef,
                                         float n_pixels, float batch, int ncls, float w_focal, float w_dice, float kd_weight,
                                         float temperature) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const float smooth = 1e-5f;
     const float ce = sums[0] / n_pixels;
     const float focal = sums[1 + 3 * ncls] / n_pixels;
     // F.kl_div(..., 'batchmean') divides by the first dimension only: per image, not per pixel (universal_train.py:622)
     const float kd = sums[2 + 3 * ncls] * (temperature * temperature) / batch;
-    float dice = 0.f;
-    for (int c = 0; c < ncls; ++c) {
-        const float I = sums[1 + c], Y = sums[1 + ncls + c], Z = sums[1 + 2 * ncls + c];
-        const float D = Z + Y + smooth;
-        dice += 1.f - (2.f * I + smooth) / D;
-        coef[c] = -2.f / D;
-        coef[ncls + c] = 2.f * (2.f * I + smooth) / (D * D);
-    }
-    dice /= ncls;
+    const float dice = dice_finalize(sums, coef, ncls, nullptr);
     // a term whose weight is 0 must not carry its NaN into the loss (loss_finalize_kernel's w_ce != 0 rule)
     const float seg = (w_focal != 0.f ? w_focal * focal : 0.f) + w_dice * dice;
     const float keep = 1.f - kd_weight;
@@ -173,24 +146,14 @@ __global__ __launch_bounds__(256) void cl_loss_bwd_kernel(const float* __restric
                                                            float kd_scale, int B, int nold, long HW, float inv_t, float alpha,
                                                            float gamma) {
     float a[NC], bb[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        a[c] = coef[c];
-        bb[c] = coef[NC + c];
-    }
+    load_coef<NC>(coef, a, bb);
     const float g = gout ? gout[0] : 1.f;
     const int gi = gamma_int(gamma);
     const long total = (long)B * HW;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const long b = i / HW, p = i - b * HW;
-        const float* lp = logits + b * NC * HW + p;
         float v[NC];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            v[c] = lp[c * HW];
-            mx = fmaxf(mx, v[c]);
-        }
+        const float mx = load_row<NC>(logits + b * NC * HW + p, HW, v);
         float kdg[NC];                                                  // kd_scale * (pT_c - q_c), 0 past nold
 #pragma unroll
         for (int c = 0; c < NC; ++c) kdg[c] = 0.f;
@@ -225,15 +188,14 @@ __global__ __launch_bounds__(256) void cl_loss_bwd_kernel(const float* __restric
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             if (c == lab) vl = v[c];
-            v[c] = __expf(v[c] - mx);
-            sum += v[c];
+            sum += softmax_term<false>(v[c], mx);
         }
         const float inv = 1.0f / sum;
         // an out-of-range label has no focal gradient (and makes no NaN): what test_out_of_range_labels pins for the base loss
         float cf = 0.f;
         if (lab >= 0) {
             const float w = class_weight ? class_weight[lab] : 1.f;
-            const float ce = w * ((mx - vl) + __logf(sum));
+            const float ce = w * row_nll(mx, vl, sum);
             const float omp = -expm1f(-ce);
             float fp = pow_gamma(omp, gamma, gi);
             // gamma == 0: the second term is 0 * (1-pt)^(-1), NaN at pt == 1; it is left out
@@ -242,11 +204,7 @@ __global__ __launch_bounds__(256) void cl_loss_bwd_kernel(const float* __restric
         }
         float G[NC], dot = 0.f;
 #pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            v[c] *= inv;
-            G[c] = (c == lab ? a[c] : 0.f) + bb[c] * v[c];
-            dot += v[c] * G[c];
-        }
+        for (int c = 0; c < NC; ++c) dot += dice_grad_term(v[c], inv, c == lab, a[c], bb[c], G[c]);
         float* dp = dlogits + b * NC * HW + p;
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
@@ -256,29 +214,12 @@ __global__ __launch_bounds__(256) void cl_loss_bwd_kernel(const float* __restric
     }
 }
 
-int cl_loss_blocks(long total) {                                        // loss.hip's clamp rule
-    long b = (total + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > 512 ? 512 : b));
-}
-
-#define CL_NC_SWITCH(NCV, CALL_)                                                                                              \
-    switch (NCV) {                                                                                                            \
-        case 2: { constexpr int NC = 2; CALL_; } break;                                                                       \
-        case 3: { constexpr int NC = 3; CALL_; } break;                                                                       \
-        case 4: { constexpr int NC = 4; CALL_; } break;                                                                       \
-        case 5: { constexpr int NC = 5; CALL_; } break;                                                                       \
-        case 6: { constexpr int NC = 6; CALL_; } break;                                                                       \
-        case 7: { constexpr int NC = 7; CALL_; } break;                                                                       \
-        case 8: { constexpr int NC = 8; CALL_; } break;                                                                       \
-        case 9: { constexpr int NC = 9; CALL_; } break;                                                                       \
-        case 10: { constexpr int NC = 10; CALL_; } break;                                                                     \
-        case 11: { constexpr int NC = 11; CALL_; } break;                                                                     \
-        case 12: { constexpr int NC = 12; CALL_; } break;                                                                     \
-        case 13: { constexpr int NC = 13; CALL_; } break;                                                                     \
-        case 14: { constexpr int NC = 14; CALL_; } break;                                                                     \
-        case 15: { constexpr int NC = 15; CALL_; } break;                                                                     \
-        case 16: { constexpr int NC = 16; CALL_; } break;                                                                     \
-        default: cswin_set_error("cl_loss: num_classes=%d unsupported (2..16)", NCV); return CSWIN_ERR_UNSUPPORTED;           \
+#define CL_NC_SWITCH(NCV, CALL)                                                                                            \
+    switch (NCV) {                                                                                                         \
+        LOSS_NC_CASE(2, CALL) LOSS_NC_CASE(3, CALL) LOSS_NC_CASE(4, CALL) LOSS_NC_CASE(5, CALL) LOSS_NC_CASE(6, CALL)      \
+        LOSS_NC_CASE(7, CALL) LOSS_NC_CASE(8, CALL) LOSS_NC_CASE(9, CALL) LOSS_NC_CASE(10, CALL) LOSS_NC_CASE(11, CALL)    \
+        LOSS_NC_CASE(12, CALL) LOSS_NC_CASE(13, CALL) LOSS_NC_CASE(14, CALL) LOSS_NC_CASE(15, CALL) LOSS_NC_CASE(16, CALL) \
+        default: cswin_set_error("cl_loss: num_classes=%d unsupported (2..16)", NCV); return CSWIN_ERR_UNSUPPORTED;        \
     }
 
 // the checks both passes share, before any launch
@@ -299,7 +240,7 @@ int cl_loss_check(const char* who, const void* logits, const void* labels, const
 
 extern "C" {
 
-size_t cswin_cl_loss_workspace(int B, int ncls, long HW) { return (size_t)cl_loss_blocks((long)B * HW) * (3 + 3 * ncls) * sizeof(float); }
+size_t cswin_cl_loss_workspace(int B, int ncls, long HW) { return (size_t)loss_blocks((long)B * HW) * (3 + 3 * ncls) * sizeof(float); }
 
 // logits (B, ncls, HW) fp32, labels (B, HW) int64, teacher (B, nold, HW) fp32 -> sums[3 + 3*ncls] (local batch)
 int cswin_cl_loss_sums(const float* logits, const long long* labels, const int* label_map, int n_map, const float* teacher,
@@ -310,7 +251,7 @@ int cswin_cl_loss_sums(const float* logits, const long long* labels, const int* 
     CSWIN_REQUIRE(sums, CSWIN_ERR_SHAPE, "cl_loss_sums: bad arguments");
     CSWIN_REQUIRE(workspace && ws_bytes >= cswin_cl_loss_workspace(B, ncls, HW), CSWIN_ERR_WORKSPACE, "cl_loss_sums: workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    const int nblk = cl_loss_blocks((long)B * HW);
+    const int nblk = loss_blocks((long)B * HW);
     CL_NC_SWITCH(ncls, hipLaunchKernelGGL((cl_loss_sums_kernel<NC>), dim3(nblk), dim3(256), 0, st, logits, labels, label_map, n_map, teacher,
                                           class_weight, (float*)workspace, B, nold, HW, 1.0f / temperature, focal_alpha, focal_gamma));
     CSWIN_LAUNCH_CHECK();
@@ -338,7 +279,7 @@ int cswin_cl_loss_bwd(const float* logits, const long long* labels, const int* l
     if (rc != CSWIN_OK) return rc;
     CSWIN_REQUIRE(coef && dlogits, CSWIN_ERR_SHAPE, "cl_loss_bwd: bad arguments");
     hipStream_t st = (hipStream_t)stream;
-    const int nblk = cl_loss_blocks((long)B * HW) * 4;
+    const int nblk = loss_blocks((long)B * HW) * 4;
     CL_NC_SWITCH(ncls, hipLaunchKernelGGL((cl_loss_bwd_kernel<NC>), dim3(nblk), dim3(256), 0, st, logits, labels, label_map, n_map, teacher,
                                           class_weight, coef, grad_out, dlogits, focal_scale, dice_scale, kd_scale, B, nold, HW,
                                           1.0f / temperature, focal_alpha, focal_gamma));

@@ -4,17 +4,12 @@
 // (intersect, y_sum, z_sum per class): `cswin_loss_sums` leaves the 1 + 3*ncls partial sums in device
 // memory so a data-parallel job can all-reduce exactly those floats before `cswin_loss_finalize`
 // (the reference's DataParallel computes the loss on the gathered global batch).
-#include "common.h"
+// The per-pixel steps are loss_pixel.h's; this file owns the probabilities mode, the CE term and the use of class weights in the Dice.
+#include "loss_pixel.h"
 
 namespace {
 
-// class of a pixel, or -1 for a label outside [0, NC): the 64-bit value is compared, so 2^32 + 1 is no class 1
-template <int NC>
-__device__ __forceinline__ int label_class(long long label) {
-    return (unsigned long long)label < (unsigned long long)NC ? (int)label : -1;
-}
-
-// sums layout: [0] = sum over pixels of -log p[label];  [1 + c] = intersect_c;  [1 + ncls + c] = y_sum_c;  [1 + 2 ncls + c] = z_sum_c
+// sums layout: loss_pixel.h's 1 + 3 NC
 // PROBS: the input already holds class probabilities (DiceLoss(..., softmax=False), utils.py:32-34): no softmax here
 template <int NC, bool PROBS>
 __global__ __launch_bounds__(256) void loss_sums_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
@@ -27,38 +22,23 @@ __global__ __launch_bounds__(256) void loss_sums_kernel(const float* __restrict_
     const long total = (long)B * HW;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const long b = i / HW, p = i - b * HW;
-        const float* lp = logits + b * NC * HW + p;
         float v[NC];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            v[c] = lp[c * HW];
-            mx = fmaxf(mx, v[c]);
-        }
+        const float mx = load_row<NC>(logits + b * NC * HW + p, HW, v);
         const int lab = label_class<NC>(labels[i]);
         float vl = 0.f;                                                 // the label's input, before it becomes exp(v - mx)
         float sum = 0.f;
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             if (c == lab) vl = v[c];
-            if (!PROBS) v[c] = __expf(v[c] - mx);
-            sum += v[c];
+            sum += softmax_term<PROBS>(v[c], mx);
         }
         const float inv = PROBS ? 1.0f : 1.0f / sum;
         // nn.CrossEntropyLoss raises on a target outside [0, ncls) (trainer.py:40,55); without a host sync the device-side
         // equivalent is to poison the CE sum: the step's loss reads NaN instead of a silently biased value
         if (lab < 0) acc[0] = __builtin_nanf("");
-        // -log softmax(v)[label] = (mx - v[label]) + log sum_j exp(v_j - mx), as log_softmax forms it: exact however far the
-        // label's logit lies below the row maximum (-log of the normalised probability sticks once __expf underflows)
-        else acc[0] += PROBS ? -__logf(vl) : (mx - vl) + __logf(sum);
+        else acc[0] += PROBS ? -__logf(vl) : row_nll(mx, vl, sum);
 #pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const float pc = v[c] * inv;
-            const float oh = (c == lab) ? 1.f : 0.f;
-            acc[1 + c] += pc * oh;
-            acc[1 + NC + c] += oh;
-            acc[1 + 2 * NC + c] += pc * pc;
-        }
+        for (int c = 0; c < NC; ++c) dice_terms(v[c] * inv, c == lab, acc[1 + c], acc[1 + NC + c], acc[1 + 2 * NC + c]);
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
@@ -71,22 +51,12 @@ __global__ __launch_bounds__(256) void loss_sums_kernel(const float* __restrict_
         partial[(long)blockIdx.x * NV + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
-// out[0..2] = loss, ce, dice;  coef[c] = a_c, coef[ncls + c] = b_c with d dice_c / d p_c(pixel) = a_c * onehot + b_c * p
+// out[0..2] = loss, ce, dice;  coef: dice_finalize's, with the class weights (utils.py:44: loss += dice * weight[i])
 __global__ void loss_finalize_kernel(const float* __restrict__ sums, float* __restrict__ out, float* __restrict__ coef,
                                      float n_pixels, int ncls, float w_ce, float w_dice, const float* __restrict__ class_weight) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const float smooth = 1e-5f;
     const float ce = sums[0] / n_pixels;
-    float dice = 0.f;
-    for (int c = 0; c < ncls; ++c) {
-        const float I = sums[1 + c], Y = sums[1 + ncls + c], Z = sums[1 + 2 * ncls + c];
-        const float D = Z + Y + smooth;
-        const float wc = class_weight ? class_weight[c] : 1.f;          // utils.py:44: loss += dice * weight[i]
-        dice += wc * (1.f - (2.f * I + smooth) / D);
-        coef[c] = wc * -2.f / D;
-        coef[ncls + c] = wc * 2.f * (2.f * I + smooth) / (D * D);
-    }
-    dice /= ncls;
+    const float dice = dice_finalize(sums, coef, ncls, class_weight);
     // an out-of-range label poisons the CE sum (NaN); utils.DiceLoss (w_ce = 0) one-hots with == and simply ignores such a label
     // (utils.py:13-19), so the CE term must not reach a loss that has none
     out[0] = (w_ce != 0.f ? w_ce * ce : 0.f) + w_dice * dice;
@@ -101,38 +71,23 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__
                                                         float* __restrict__ dlogits, float ce_scale, float dice_scale,
                                                         int B, long HW) {
     float a[NC], bb[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        a[c] = coef[c];
-        bb[c] = coef[NC + c];
-    }
+    load_coef<NC>(coef, a, bb);
     const float g = gout ? gout[0] : 1.f;
     const long total = (long)B * HW;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const long b = i / HW, p = i - b * HW;
-        const float* lp = logits + b * NC * HW + p;
         float v[NC];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            v[c] = lp[c * HW];
-            mx = fmaxf(mx, v[c]);
-        }
+        const float mx = load_row<NC>(logits + b * NC * HW + p, HW, v);
         float sum = 0.f;
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
-            if (!PROBS) v[c] = __expf(v[c] - mx);
-            sum += v[c];
+            sum += softmax_term<PROBS>(v[c], mx);
         }
         const float inv = PROBS ? 1.0f : 1.0f / sum;
         const int lab = label_class<NC>(labels[i]);
         float G[NC], dot = 0.f;
 #pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            v[c] *= inv;
-            G[c] = (c == lab ? a[c] : 0.f) + bb[c] * v[c];
-            dot += v[c] * G[c];
-        }
+        for (int c = 0; c < NC; ++c) dot += dice_grad_term(v[c], inv, c == lab, a[c], bb[c], G[c]);
         float* dp = dlogits + b * NC * HW + p;
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
@@ -143,24 +98,11 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__
     }
 }
 
-int loss_blocks(long total) {
-    long b = (total + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > 512 ? 512 : b));
-}
-
-#define NC_SWITCH(NCV, CALL)                                                                     \
-    switch (NCV) {                                                                               \
-        case 2: { constexpr int NC = 2; CALL; } break;                                           \
-        case 3: { constexpr int NC = 3; CALL; } break;                                           \
-        case 4: { constexpr int NC = 4; CALL; } break;                                           \
-        case 5: { constexpr int NC = 5; CALL; } break;                                           \
-        case 6: { constexpr int NC = 6; CALL; } break;                                           \
-        case 7: { constexpr int NC = 7; CALL; } break;                                           \
-        case 8: { constexpr int NC = 8; CALL; } break;                                           \
-        case 9: { constexpr int NC = 9; CALL; } break;                                           \
-        case 14: { constexpr int NC = 14; CALL; } break;                                         \
-        case 16: { constexpr int NC = 16; CALL; } break;                                         \
-        default: cswin_set_error("loss: num_classes=%d unsupported", NCV); return CSWIN_ERR_UNSUPPORTED; \
+#define NC_SWITCH(NCV, CALL)                                                                                             \
+    switch (NCV) {                                                                                                       \
+        LOSS_NC_CASE(2, CALL) LOSS_NC_CASE(3, CALL) LOSS_NC_CASE(4, CALL) LOSS_NC_CASE(5, CALL) LOSS_NC_CASE(6, CALL)    \
+        LOSS_NC_CASE(7, CALL) LOSS_NC_CASE(8, CALL) LOSS_NC_CASE(9, CALL) LOSS_NC_CASE(14, CALL) LOSS_NC_CASE(16, CALL)  \
+        default: cswin_set_error("loss: num_classes=%d unsupported", NCV); return CSWIN_ERR_UNSUPPORTED;                 \
     }
 
 }  // namespace

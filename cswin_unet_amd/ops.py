@@ -6,6 +6,7 @@ CswinHipError on a non-HIP tensor -- there is no CPU / eager fallback.
 """
 import ctypes
 import math
+import types
 
 import numpy as np
 import torch
@@ -1026,56 +1027,120 @@ def windows2img(img_splits_hw, H_sp, W_sp, H, W):
 
 
 # ------------------------------------------------------------------------------------------------
-# loss
+# segmentation objectives: CE + Dice (csrc/loss.hip) and focal CE + Dice + distillation (csrc/cl_loss.hip)
+#
+# An objective has n_sums(ncls), n_stats, sums() (this rank's partial sums, left in device memory: they add across ranks),
+# finalize() (the -- possibly all-reduced -- sums -> stats and the Dice gradient coefficients) and grad() (d loss / d logits).
+# _SegLoss drives either under autograd, HipEngine (trainer.py) calls the same methods inside its captured graphs.  grad_scales()
+# alone forms the gradient scales: gradients are averaged over ranks afterwards, so local means keep the local counts and the
+# global Dice gets the world size.
 # ------------------------------------------------------------------------------------------------
-def loss_sums(logits, labels, sums, probs=False):
-    """sums[1 + 3*ncls] = CE / Dice partial sums of logits (B, ncls, ...) or, with probs, probabilities against int64 labels."""
+def _pixels(logits):
     B, ncls = logits.shape[:2]
-    HW = logits.numel() // (B * ncls)
-    nbytes = lib().cswin_loss_workspace(B, ncls, HW)
-    ws = _ws(nbytes, logits.device)
-    call("cswin_loss_sums", ptr(logits), ptr(labels), ptr(sums), ptr(ws), nbytes, B, ncls, HW, int(probs), stream())
+    return B, ncls, logits.numel() // (B * ncls)
 
 
-def loss_finalize(sums, out, coef, n_pixels, w_ce, w_dice, class_weight=None):
-    """sums -> out = [loss, ce, dice] and coef[2*ncls], the Dice gradient coefficients loss_grad takes."""
-    call("cswin_loss_finalize", ptr(sums), ptr(out), ptr(coef), float(n_pixels), coef.numel() // 2, w_ce, w_dice, ptr(class_weight), stream())
+class CeDiceObjective:
+    """w_ce * CE + w_dice * Dice (trainer.py:55-57); stats = [loss, ce, dice].  probs: the input holds probabilities
+    (DiceLoss(softmax=False)); class_weight: (ncls,) device tensor or None, the Dice weights."""
+    n_stats = 3
 
+    def __init__(self, w_ce=0.4, w_dice=0.6, class_weight=None, probs=False):
+        self.w_ce, self.w_dice, self.class_weight, self.probs = w_ce, w_dice, class_weight, probs
 
-def loss_grad(logits, labels, coef, ce_scale, dice_scale, gloss=None, probs=False):
-    """d loss / d logits, times the device scalar gloss if given."""
-    B, ncls = logits.shape[:2]
-    dlogits = torch.empty_like(logits)
-    call("cswin_loss_bwd", ptr(logits), ptr(labels), ptr(coef), ptr(gloss), ptr(dlogits), ce_scale, dice_scale, B, ncls,
-         logits.numel() // (B * ncls), int(probs), stream())
-    return dlogits
-
-
-class _CeDiceLoss(Function):
     @staticmethod
-    def forward(ctx, logits, labels, w_ce, w_dice, group, probs, class_weight):
-        logits = dev_f32(logits, "logits")
-        class_weight = dev_f32(class_weight)
+    def n_sums(ncls):
+        return 1 + 3 * ncls
+
+    def sums(self, logits, labels, sums, teacher=None):
+        B, ncls, HW = _pixels(logits)
+        nbytes = lib().cswin_loss_workspace(B, ncls, HW)
+        call("cswin_loss_sums", ptr(logits), ptr(labels), ptr(sums), ptr(_ws(nbytes, logits.device)), nbytes, B, ncls, HW, int(self.probs), stream())
+
+    def finalize(self, sums, out, coef, n_pixels, batch):
+        call("cswin_loss_finalize", ptr(sums), ptr(out), ptr(coef), float(n_pixels), coef.numel() // 2, self.w_ce, self.w_dice,
+             ptr(self.class_weight), stream())
+
+    def grad_scales(self, B, HW, ncls, world):
+        """(ce_scale, dice_scale) of cswin_loss_bwd."""
+        w_ce, w_dice = self.w_ce, self.w_dice
+        return w_ce / float(B * HW), w_dice / ncls * world
+
+    def grad(self, logits, labels, coef, dice_grad_scale, teacher=None, gloss=None):
+        B, ncls, HW = _pixels(logits)
+        dlogits = torch.empty_like(logits)
+        call("cswin_loss_bwd", ptr(logits), ptr(labels), ptr(coef), ptr(gloss), ptr(dlogits), *self.grad_scales(B, HW, ncls, dice_grad_scale),
+             B, ncls, HW, int(self.probs), stream())
+        return dlogits
+
+
+class ContinualObjective:
+    """(1 - kd_weight) * (w_focal * Focal + w_dice * Dice) + kd_weight * KD (universal_train.py:904-932); stats = [loss, focal,
+    dice, kd, ce].  spec: a continual.Distill, or any object with its fields w_focal, w_dice, kd_weight, temperature, focal_gamma,
+    focal_alpha, class_weight, label_map; they are read at every call, so a field changed between eager steps takes effect."""
+    n_stats = 5
+
+    def __init__(self, spec):
+        self.spec = spec
+
+    @staticmethod
+    def n_sums(ncls):
+        return 3 + 3 * ncls
+
+    def _inputs(self, teacher):
+        """((label_map, n_map, teacher, class_weight) as the entry points take them, old_classes)"""
+        d = self.spec
+        return (ptr(d.label_map), 0 if d.label_map is None else d.label_map.numel(), ptr(teacher), ptr(d.class_weight)), 0 if teacher is None else teacher.shape[1]
+
+    def sums(self, logits, labels, sums, teacher=None):
+        d = self.spec
+        B, ncls, HW = _pixels(logits)
+        nbytes = lib().cswin_cl_loss_workspace(B, ncls, HW)
+        tensors, nold = self._inputs(teacher)
+        call("cswin_cl_loss_sums", ptr(logits), ptr(labels), *tensors, ptr(sums), ptr(_ws(nbytes, logits.device)), nbytes, B, ncls, nold, HW, d.temperature,
+             d.focal_alpha, d.focal_gamma, stream())
+
+    def finalize(self, sums, out, coef, n_pixels, batch):
+        """'batchmean' divides the distillation term by images: batch is the image count the sums cover."""
+        d = self.spec
+        call("cswin_cl_loss_finalize", ptr(sums), ptr(out), ptr(coef), float(n_pixels), float(batch), coef.numel() // 2, d.w_focal, d.w_dice,
+             d.kd_weight, d.temperature, stream())
+
+    def grad_scales(self, B, HW, ncls, world):
+        """(focal_scale, dice_scale, kd_scale) of cswin_cl_loss_bwd."""
+        d = self.spec
+        w_focal, w_dice, kd_weight, temperature = d.w_focal, d.w_dice, d.kd_weight, d.temperature
+        return (1.0 - kd_weight) * w_focal / float(B * HW), (1.0 - kd_weight) * w_dice / ncls * world, kd_weight * temperature / B
+
+    def grad(self, logits, labels, coef, dice_grad_scale, teacher=None, gloss=None):
+        d = self.spec
+        B, ncls, HW = _pixels(logits)
+        dlogits = torch.empty_like(logits)
+        tensors, nold = self._inputs(teacher)
+        call("cswin_cl_loss_bwd", ptr(logits), ptr(labels), *tensors, ptr(coef), ptr(gloss), ptr(dlogits), *self.grad_scales(B, HW, ncls, dice_grad_scale),
+             B, ncls, nold, HW, d.temperature, d.focal_alpha, d.focal_gamma, stream())
+        return dlogits
+
+
+class _SegLoss(Function):
+    @staticmethod
+    def forward(ctx, logits, labels, teacher, objective, group):
+        logits, teacher = dev_f32(logits, "logits"), dev_f32(teacher, "teacher_logits")
         labels = labels.contiguous()
         if labels.dtype != torch.int64:
             labels = labels.long()
-        B, ncls = logits.shape[:2]
-        HW = logits.numel() // (B * ncls)
-        dev = logits.device
-        sums = torch.empty(1 + 3 * ncls, dtype=torch.float32, device=dev)
-        loss_sums(logits, labels, sums, probs)
+        B, ncls, HW = _pixels(logits)
+        sums, out, coef = (torch.empty(n, dtype=torch.float32, device=logits.device) for n in (objective.n_sums(ncls), objective.n_stats, 2 * ncls))
+        objective.sums(logits, labels, sums, teacher)
         world = 1
         if group is not None:
             import torch.distributed as dist
             world = dist.get_world_size(group)
             if world > 1:
-                dist.all_reduce(sums, group=group)      # 1 + 3*ncls floats: the reference's global-batch Dice
-        out = torch.empty(3, dtype=torch.float32, device=dev)
-        coef = torch.empty(2 * ncls, dtype=torch.float32, device=dev)
-        loss_finalize(sums, out, coef, B * HW * world, w_ce, w_dice, class_weight)
-        ctx.save_for_backward(logits, labels, coef)
-        # gradients are averaged over ranks afterwards: local CE mean -> ce/(B*HW); global Dice -> * world
-        ctx.meta = (w_ce / float(B * HW), w_dice / ncls * world, probs)
+                dist.all_reduce(sums, group=group)      # a few floats: the reference's global-batch Dice, the global means
+        objective.finalize(sums, out, coef, B * HW * world, B * world)
+        ctx.save_for_backward(logits, labels, coef, teacher)
+        ctx.meta = (objective, world)
         loss = out[0].clone()
         ctx.mark_non_differentiable(out)
         return loss, out
@@ -1083,10 +1148,9 @@ class _CeDiceLoss(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gloss, _gout):
-        logits, labels, coef = ctx.saved_tensors
-        ce_scale, dice_scale, probs = ctx.meta
-        dlogits = loss_grad(logits, labels, coef, ce_scale, dice_scale, dev_f32(gloss.reshape(1)), probs)
-        return dlogits, None, None, None, None, None, None
+        logits, labels, coef, teacher = ctx.saved_tensors
+        objective, world = ctx.meta
+        return objective.grad(logits, labels, coef, world, teacher, dev_f32(gloss.reshape(1))), None, None, None, None
 
 
 def ce_dice_loss(logits, labels, w_ce=0.4, w_dice=0.6, group=None, inputs_are_probs=False, class_weight=None):
@@ -1095,91 +1159,13 @@ def ce_dice_loss(logits, labels, w_ce=0.4, w_dice=0.6, group=None, inputs_are_pr
     inputs_are_probs: the input holds probabilities (DiceLoss(softmax=False)); class_weight: (ncls,) device tensor or None."""
     if inputs_are_probs and w_ce != 0.0:
         raise ValueError("ce_dice_loss: cross entropy needs logits; with inputs_are_probs pass w_ce=0")
-    return _CeDiceLoss.apply(logits, labels, float(w_ce), float(w_dice), group, bool(inputs_are_probs), class_weight)
+    return _SegLoss.apply(logits, labels, None, CeDiceObjective(float(w_ce), float(w_dice), dev_f32(class_weight), bool(inputs_are_probs)), group)
 
 
-# ------------------------------------------------------------------------------------------------
-# continual-learning objective: focal CE + Dice + distillation towards a frozen teacher (universal_train.py:904-932)
-# ------------------------------------------------------------------------------------------------
 def _int32_map(label_map):
     if label_map is not None and (label_map.dtype != torch.int32 or not label_map.is_cuda or not label_map.is_contiguous()):
         raise CswinHipError(f"label_map must be a contiguous int32 tensor on the HIP device (continual.new_label_map), got {label_map.dtype} on {label_map.device}")
     return label_map
-
-
-def cl_loss_sums(logits, labels, teacher, sums, temperature, focal_alpha, focal_gamma, class_weight=None, label_map=None):
-    """sums[3 + 3*ncls] = loss_sums' 1 + 3*ncls sums, then the focal sum and the distillation sum over teacher.shape[1] channels."""
-    B, ncls = logits.shape[:2]
-    HW = logits.numel() // (B * ncls)
-    nbytes = lib().cswin_cl_loss_workspace(B, ncls, HW)
-    ws = _ws(nbytes, logits.device)
-    call("cswin_cl_loss_sums", ptr(logits), ptr(labels), ptr(label_map), 0 if label_map is None else label_map.numel(), ptr(teacher),
-         ptr(class_weight), ptr(sums), ptr(ws), nbytes, B, ncls, 0 if teacher is None else teacher.shape[1], HW, temperature, focal_alpha,
-         focal_gamma, stream())
-
-
-def cl_loss_finalize(sums, out, coef, n_pixels, batch, w_focal, w_dice, kd_weight, temperature):
-    """sums -> out = [loss, focal, dice, kd, ce] and coef[2*ncls]; n_pixels and batch (images) are what the sums cover."""
-    call("cswin_cl_loss_finalize", ptr(sums), ptr(out), ptr(coef), float(n_pixels), float(batch), coef.numel() // 2, w_focal, w_dice, kd_weight,
-         temperature, stream())
-
-
-def cl_loss_grad(logits, labels, teacher, coef, focal_scale, dice_scale, kd_scale, temperature, focal_alpha, focal_gamma, class_weight=None,
-                 label_map=None, gloss=None):
-    """d loss / d logits, times the device scalar gloss if given."""
-    B, ncls = logits.shape[:2]
-    dlogits = torch.empty_like(logits)
-    call("cswin_cl_loss_bwd", ptr(logits), ptr(labels), ptr(label_map), 0 if label_map is None else label_map.numel(), ptr(teacher),
-         ptr(class_weight), ptr(coef), ptr(gloss), ptr(dlogits), focal_scale, dice_scale, kd_scale, B, ncls,
-         0 if teacher is None else teacher.shape[1], logits.numel() // (B * ncls), temperature, focal_alpha, focal_gamma, stream())
-    return dlogits
-
-
-class _ContinualLoss(Function):
-    @staticmethod
-    def forward(ctx, logits, labels, teacher, w_focal, w_dice, kd_weight, temperature, gamma, alpha, class_weight, label_map, group):
-        logits, teacher, class_weight = dev_f32(logits, "logits"), dev_f32(teacher.detach(), "teacher_logits"), dev_f32(class_weight)
-        label_map = _int32_map(label_map)
-        labels = labels.contiguous()
-        if labels.dtype != torch.int64:
-            labels = labels.long()
-        B, ncls = logits.shape[:2]
-        HW = logits.numel() // (B * ncls)
-        if teacher.shape[0] != B or teacher.numel() != B * teacher.shape[1] * HW:
-            raise ValueError(f"continual_loss: teacher logits {tuple(teacher.shape)} do not match logits {tuple(logits.shape)}")
-        # the kernels index these by pixel and by class: a mismatch would be an out-of-bounds device read
-        if not labels.is_cuda or labels.numel() != B * HW:
-            raise ValueError(f"continual_loss: labels {tuple(labels.shape)} on {labels.device} do not match logits {tuple(logits.shape)} on {logits.device}")
-        if class_weight is not None and class_weight.numel() != ncls:
-            raise ValueError(f"continual_loss: class_weight has {class_weight.numel()} entries for {ncls} classes")
-        dev = logits.device
-        sums = torch.empty(3 + 3 * ncls, dtype=torch.float32, device=dev)
-        cl_loss_sums(logits, labels, teacher, sums, temperature, alpha, gamma, class_weight, label_map)
-        world = 1
-        if group is not None:
-            import torch.distributed as dist
-            world = dist.get_world_size(group)
-            if world > 1:
-                dist.all_reduce(sums, group=group)      # 3 + 3*ncls floats: global-batch Dice, focal mean and batchmean KD
-        out = torch.empty(5, dtype=torch.float32, device=dev)
-        coef = torch.empty(2 * ncls, dtype=torch.float32, device=dev)
-        cl_loss_finalize(sums, out, coef, B * HW * world, B * world, w_focal, w_dice, kd_weight, temperature)
-        ctx.save_for_backward(logits, labels, teacher, coef, class_weight, label_map)
-        # gradients are averaged over ranks afterwards: local means for focal and KD, global Dice -> * world
-        ctx.meta = ((1.0 - kd_weight) * w_focal / float(B * HW), (1.0 - kd_weight) * w_dice / ncls * world, kd_weight * temperature / B,
-                    temperature, alpha, gamma)
-        loss = out[0].clone()
-        ctx.mark_non_differentiable(out)
-        return loss, out
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gloss, _gout):
-        logits, labels, teacher, coef, class_weight, label_map = ctx.saved_tensors
-        focal_scale, dice_scale, kd_scale, temperature, alpha, gamma = ctx.meta
-        dlogits = cl_loss_grad(logits, labels, teacher, coef, focal_scale, dice_scale, kd_scale, temperature, alpha, gamma, class_weight,
-                               label_map, dev_f32(gloss.reshape(1)))
-        return (dlogits,) + (None,) * 11
 
 
 def continual_loss(logits, labels, teacher_logits, *, w_focal=0.2, w_dice=0.8, kd_weight=0.5, temperature=3.0, focal_gamma=4.0,
@@ -1189,8 +1175,19 @@ def continual_loss(logits, labels, teacher_logits, *, w_focal=0.2, w_dice=0.8, k
     (B, old_classes, ...) of the frozen old model on the same images (no gradient), labels int64; label_map: int32 device table
     applied to the labels first (continual.new_label_map); class_weight: (ncls,) device tensor, the focal loss's `weight`.
     With a process group the 3 + 3*ncls sums are all-reduced: Dice, the focal mean and the per-image KD are the global batch's."""
-    return _ContinualLoss.apply(logits, labels, teacher_logits, float(w_focal), float(w_dice), float(kd_weight), float(temperature),
-                                float(focal_gamma), float(focal_alpha), class_weight, label_map, group)
+    logits, teacher, class_weight = dev_f32(logits, "logits"), dev_f32(teacher_logits.detach(), "teacher_logits"), dev_f32(class_weight)
+    label_map = _int32_map(label_map)
+    B, ncls, HW = _pixels(logits)
+    if teacher.shape[0] != B or teacher.numel() != B * teacher.shape[1] * HW:
+        raise ValueError(f"continual_loss: teacher logits {tuple(teacher.shape)} do not match logits {tuple(logits.shape)}")
+    # the kernels index these by pixel and by class: a mismatch would be an out-of-bounds device read
+    if not labels.is_cuda or labels.numel() != B * HW:
+        raise ValueError(f"continual_loss: labels {tuple(labels.shape)} on {labels.device} do not match logits {tuple(logits.shape)} on {logits.device}")
+    if class_weight is not None and class_weight.numel() != ncls:
+        raise ValueError(f"continual_loss: class_weight has {class_weight.numel()} entries for {ncls} classes")
+    spec = types.SimpleNamespace(w_focal=float(w_focal), w_dice=float(w_dice), kd_weight=float(kd_weight), temperature=float(temperature),
+                                 focal_gamma=float(focal_gamma), focal_alpha=float(focal_alpha), class_weight=class_weight, label_map=label_map)
+    return _SegLoss.apply(logits, labels, teacher, ContinualObjective(spec), group)
 
 
 # ------------------------------------------------------------------------------------------------

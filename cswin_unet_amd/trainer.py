@@ -29,7 +29,7 @@ import torch.distributed as dist
 
 from ._lib import call, ptr, stream
 from .continual import Distill
-from .ops import augment_batch, cl_loss_finalize, cl_loss_grad, cl_loss_sums, engine_backward, loss_finalize, loss_grad, loss_sums
+from .ops import CeDiceObjective, ContinualObjective, augment_batch, engine_backward
 from .optim import FlatAdamW, FlatSGD
 
 
@@ -114,8 +114,9 @@ class HipEngine:
         # second cut inside the encoder, in front of merge2: parameters [n_mid, n_enc) = merge2, stage3, merge3, stage4, norm
         self.n_mid = next(i for i, n in enumerate(names) if "merge2" in n.split(".")[:2]) if self.split_backward else 0
         dev = self.opt.flat_param.device
-        self.sums = torch.zeros((3 if self.distill else 1) + 3 * num_classes, dtype=torch.float32, device=dev)
-        self.stats = torch.zeros(5 if self.distill else 3, dtype=torch.float32, device=dev)   # [loss, ce, dice] of the last step; distill: [loss, focal, dice, kd, ce]
+        self.objective = ContinualObjective(self.distill) if self.distill else CeDiceObjective(w_ce, w_dice)
+        self.sums = torch.zeros(self.objective.n_sums(num_classes), dtype=torch.float32, device=dev)
+        self.stats = torch.zeros(self.objective.n_stats, dtype=torch.float32, device=dev)     # [loss, ce, dice] of the last step; distill: [loss, focal, dice, kd, ce]
         self._teacher_logits, self._batch_pixels = None, None
         self._coef = torch.zeros(2 * num_classes, dtype=torch.float32, device=dev)
         # nn.Dropout with p > 0 (no reference config has one): the dropout kernels take their seeds from the HOST generator when the op
@@ -156,25 +157,12 @@ class HipEngine:
             from .ops import advance_dropout_epoch
             advance_dropout_epoch(img.device)           # inside graph A when captured: a new mask set per replayed step
         logits = self.model(img)
-        d = self.distill
-        if d is None:
-            loss_sums(logits.detach(), lab, self.sums)
-            return logits
-        with torch.no_grad():                           # inside graph A when captured; the buffer is kept for the backward graph
-            self._teacher_logits = d.teacher(img).contiguous()
+        if self.distill is not None:
+            with torch.no_grad():                       # inside graph A when captured; the buffer is kept for the backward graph
+                self._teacher_logits = self.distill.teacher(img).contiguous()
         self._batch_pixels = lab.numel() // lab.shape[0]
-        cl_loss_sums(logits.detach(), lab, self._teacher_logits, self.sums, d.temperature, d.focal_alpha, d.focal_gamma, d.class_weight, d.label_map)
+        self.objective.sums(logits.detach(), lab, self.sums, self._teacher_logits)
         return logits
-
-    def _loss_grad(self, logits, lab, dice_grad_scale):
-        ncls = logits.shape[1]
-        d = self.distill
-        if d is not None:
-            keep = 1.0 - d.kd_weight
-            return cl_loss_grad(logits.detach(), lab, self._teacher_logits, self._coef, keep * d.w_focal / float(logits.numel() // ncls),
-                                keep * d.w_dice / ncls * dice_grad_scale, d.kd_weight * d.temperature / logits.shape[0], d.temperature,
-                                d.focal_alpha, d.focal_gamma, d.class_weight, d.label_map)
-        return loss_grad(logits.detach(), lab, self._coef, self.w_ce / float(logits.numel() // ncls), self.w_dice / ncls * dice_grad_scale)
 
     def _backward(self, outputs, grad_outputs, lo, hi, extra_inputs=()):
         """One backward phase: the gradients of parameters lo..hi-1 end in their range of opt.flat_grad (placed there by the ops,
@@ -189,7 +177,7 @@ class HipEngine:
 
     def _backward_decoder(self, logits, lab, dice_grad_scale):
         """loss backward + decoder half; returns the gradients of the boundary tensors."""
-        dlogits = self._loss_grad(logits, lab, dice_grad_scale)
+        dlogits = self.objective.grad(logits.detach(), lab, self._coef, dice_grad_scale, self._teacher_logits)
         n, n_enc = len(self.opt.params), self.n_enc
         self.opt.zero_grad()
         if not self.split_backward:
@@ -286,14 +274,9 @@ class HipEngine:
             self._lab_eager = lab
 
     def finalize(self, n_pixels_global):
-        """sums (already all-reduced) -> stats [loss, ce, dice] and the Dice gradient coefficients."""
-        d = self.distill
-        if d is not None:
-            # 'batchmean' divides by images: the global image count follows from the pixels per image forward_sums saw
-            cl_loss_finalize(self.sums, self.stats, self._coef, n_pixels_global, n_pixels_global // self._batch_pixels, d.w_focal, d.w_dice,
-                             d.kd_weight, d.temperature)
-            return
-        loss_finalize(self.sums, self.stats, self._coef, n_pixels_global, self.w_ce, self.w_dice)
+        """sums (already all-reduced) -> stats and the Dice gradient coefficients.  The global image count (the distillation's
+        'batchmean' divides by images) follows from the pixels per image forward_sums saw."""
+        self.objective.finalize(self.sums, self.stats, self._coef, n_pixels_global, n_pixels_global // self._batch_pixels)
 
     def backward_phases(self, dice_grad_scale):
         """Generator: runs one backward phase per iteration and yields the [lo, hi) range of flat_grad it completed."""

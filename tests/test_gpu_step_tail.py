@@ -39,7 +39,7 @@ def cdiv(a, b):
 
 
 # ------------------------------------------------------------------------------------------------
-# launch rules (a transcription of the host code: it MUST FOLLOW csrc/loss.hip, sgd.hip, layout.hip and the end of attn.hip)
+# launch rules (a transcription of the host code: it MUST FOLLOW csrc/loss_pixel.h, loss.hip, sgd.hip, layout.hip and the end of attn.hip)
 # ------------------------------------------------------------------------------------------------
 NC_SWITCH = (2, 3, 4, 5, 6, 7, 8, 9, 14, 16)
 SUMS_CLAMP, BWD_CLAMP = 512, 2048                        # workgroups of 256 threads, one pixel per thread and trip

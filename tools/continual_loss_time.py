@@ -11,7 +11,8 @@ each (a single call of the fused op is about 0.2 ms, too short a window), divide
 are left as found.  Every call reads the same tensors (about 110 MB for the objective), so they may stay cache-resident.  A child that fails ends the run: nothing further is started and nothing is written.
 
   fused / torch: forward + backward of the objective at B 24, 224 x 224, 12 classes, 9 old ones, class weights and the label map
-  given; fused_powf is the fused op at gamma 2.5, which takes the powf path instead of repeated products.  The torch composition is universal_train.py:904-932 with one-hot Dice sums taken over all classes at once (kinder to
+  given; fused_powf is the fused op at gamma 2.5, which takes the powf path instead of repeated products.  fused_base is ops.ce_dice_loss
+  (the base objective, csrc/loss.hip) on the same labels at 9 classes, windowed the same way.  The torch composition is universal_train.py:904-932 with one-hot Dice sums taken over all classes at once (kinder to
   torch than the reference's per-class loop); the two losses must agree to 1e-4 relative or the run fails.
   step / step_distill / teacher: the configuration of tests/test_gpu_continual_step.py (depth [1, 1, 1, 1], B 2, hipGraphs):
   train_step on the 9-class model without the option, on the 12-class student with it, and the teacher's forward alone."""
@@ -26,7 +27,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 B, HW, NCLS, NOLD, TEMP, GAMMA = 24, 224, 12, 9, 3.0, 4.0
-CHILDREN = ("fused", "fused_powf", "torch", "step", "step_distill", "teacher")
+CHILDREN = ("fused", "fused_powf", "fused_base", "torch", "step", "step_distill", "teacher")
+BASE_NCLS = 9
 CALLS = 20
 
 
@@ -71,12 +73,14 @@ def child(name, repeats):
     res = {"name": name, "device": torch.cuda.get_device_name(0)}
     lmap = new_label_map(NOLD, NCLS - NOLD + 1, dev)
     cw = extreme_class_weights([9.0e5] + [0.0] * (NOLD - 1) + [4.0e4, 2.5e4, 9.0e3], [0, 9, 10, 11]).to(dev)
-    if name in ("fused", "fused_powf", "torch"):
+    if name in ("fused", "fused_powf", "fused_base", "torch"):
         g = torch.Generator().manual_seed(2025)
-        logits = (2.0 * torch.randn(B, NCLS, HW, HW, generator=g)).to(dev).requires_grad_()
+        logits = (2.0 * torch.randn(B, BASE_NCLS if name == "fused_base" else NCLS, HW, HW, generator=g)).to(dev).requires_grad_()
         teacher = (2.0 * torch.randn(B, NOLD, HW, HW, generator=g)).to(dev)
         labels = torch.randint(0, NCLS - NOLD + 1, (B, HW, HW), generator=g).to(dev)
-        if name != "torch":
+        if name == "fused_base":
+            f = lambda: ops.ce_dice_loss(logits, labels)[0]
+        elif name != "torch":
             gamma = GAMMA if name == "fused" else 2.5
             f = lambda: ops.continual_loss(logits, labels, teacher, focal_gamma=gamma, class_weight=cw, label_map=lmap)[0]
         else:
@@ -148,7 +152,8 @@ def main():
              f"forward + backward, ops.continual_loss (3 launches forward, 1 backward): {ms(fu)}, peak memory {fu['peak_MiB']:.0f} MiB",
              f"forward + backward, the same objective from torch ops (one-hot, two softmaxes, autograd): {ms(to)}, peak memory {to['peak_MiB']:.0f} MiB",
              f"forward + backward, ops.continual_loss at gamma 2.5 (powf instead of repeated products): {ms(fp)}",
-             f"torch / fused: {to['ms'][0] / fu['ms'][0]:.2f}x" + ("" if to['ms'][0] > fu['ms'][0] else "  (the fused path is NOT faster)"),
+             f"forward + backward, ops.ce_dice_loss (the base objective, csrc/loss.hip) at {BASE_NCLS} classes: {ms(got['fused_base'])}",
+             f"torch / fused: {to['ms'][0] / fu['ms'][0]:.2f}x" +("" if to['ms'][0] > fu['ms'][0] else "  (the fused path is NOT faster)"),
              "training step, depth [1, 1, 1, 1], B 2, 224 x 224, hipGraphs (the configuration of tests/test_gpu_continual_step.py):",
              f"  without distill (9 classes): {ms(st)}",
              f"  with distill (12 classes, 9-class teacher): {ms(sd)}",
