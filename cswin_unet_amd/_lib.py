@@ -75,6 +75,8 @@ SIGNATURES = {
     "cswin_tpgm_chunk_stats": (I, [P, P, P, P, I, I, P, P]),
     "cswin_tpgm_finalize": (I, [P, P, I, I, P, P, P, P, D, D, D, D, I, P, P, P, P]),
     "cswin_tpgm_project": (I, [P, P, P, P, P, I, P, P]),
+    "cswin_eb_tiles": (I, [P, P, I, P, P]),
+    "cswin_eb_finalize": (I, [P, P, P, I, P, P]),
     "cswin_pack_bf16": (I, [P, P, L, P]),
     "cswin_pack_bf16_scaled": (I, [P, P, L, F, P]),
     "cswin_unpack_bf16": (I, [P, P, L, P]),

@@ -10,6 +10,7 @@ are the four small pieces around it:
 and the "surgical" mode's learning rate per parameter tensor (universal_train.py:626-690, 871-896):
 
     w = surgical_lr_weights(model, engine.opt, batches, distill)    # relative gradient norms of a few batches, largest = 1
+    w = surgical_lr_weights(model, engine.opt, batches, distill, method="eb-criterion")     # or: 1 where mean(g^2 / (var_0(g) + 1e-8)) >= 0.95, else 0
     engine.set_lr_weights(w)                                        # FlatAdamW's per-tensor multipliers; unnamed tensors get 0
 
 and TPGM, the trainable projection toward the pretrained weights (universal_train.py:391-615, 898-902, 972-974):
@@ -40,7 +41,7 @@ import numpy as np
 import torch
 from torch import nn
 
-__all__ = ["expand_classes", "new_label_map", "extreme_class_weights", "freeze_teacher", "Distill", "rgn_weights", "surgical_lr_weights", "TPGM", "tpgm_due",
+__all__ = ["expand_classes", "new_label_map", "extreme_class_weights", "freeze_teacher", "Distill", "rgn_weights", "eb_weights", "eb_metrics", "surgical_lr_weights", "TPGM", "tpgm_due",
            "task_class_indices", "task_level", "checkpoint_num_classes", "strip_wrapper_prefixes", "evaluate_tasks", "scan_labels",
            "PositiveSampling", "REFERENCE_TASKS", "REFERENCE_STAGE_CLASSES", "KITS23_RULE", "LITS17_RULE"]
 
@@ -139,11 +140,12 @@ class Distill:
         return spec if isinstance(spec, cls) or spec is None else cls(**dict(spec))
 
 
-def rgn_weights(names, norms_per_batch):
+def rgn_weights(names, norms_per_batch, normalise=True):
     """The RGN learning-rate weights of universal_train.py:626-690 and :876-881 from per-tensor norms.  names: the parameter names,
     aligned with the rows of every entry of norms_per_batch, each a (T, 2) array of (||g||, ||p||).  Names containing "bn" or
     "norm" (any case) are dropped; per batch a tensor's ratio is ||g|| / ||p|| when ||p|| > 1e-8, else 0; the ratios are averaged
-    over the batches and divided by their maximum (a maximum <= 0 gives all zeros).  Returns {name: weight}."""
+    over the batches and divided by their maximum (a maximum <= 0 gives all zeros; normalise=False: the means as they are).
+    Returns {name: weight}."""
     names = list(names)
     keep = [i for i, n in enumerate(names) if "bn" not in n.lower() and "norm" not in n.lower()]
     ratios = []
@@ -155,23 +157,67 @@ def rgn_weights(names, norms_per_batch):
     if not ratios:
         return {}
     mean = [sum(r[k] for r in ratios) / len(ratios) for k in range(len(keep))]
+    if not normalise:
+        return {names[i]: mean[k] for k, i in enumerate(keep)}
     top = max(mean) if mean else 0.0
     return {names[i]: (mean[k] / top if top > 0 else 0.0) for k, i in enumerate(keep)}
 
 
-def surgical_lr_weights(model, opt, batches, distill):
-    """rgn_weights of the focal criterion's gradients on `batches` (an iterable of (image, label) device tensors), measured by the
-    flat optimiser `opt` (optim.FlatAdamW built on `model`): per batch one forward in eval() mode, ops.continual_loss with the
-    focal term alone (w_focal = 1, w_dice = 0, kd_weight = 0 and the distill's gamma, alpha, class weights and label map; the
-    teacher's logits are passed, their term has weight 0), backward, opt.gather_grads() and opt.tensor_norms().  The norms stay
-    on the device until one host read at the end; the model's training mode is restored and every .grad is None afterwards."""
+def eb_weights(names, evidence_per_batch, threshold=0.95):
+    """The eb-criterion learning-rate weights of universal_train.py:669-672 and :883-891 from per-tensor statistics, the counterpart
+    of rgn_weights.  names: the parameter names, aligned with the entries of every element of evidence_per_batch, each a (T,)
+    sequence of mean(g * g / (var(g, dim 0) + 1e-8)) (optim.FlatAdamW.tensor_evidence).  Names containing "bn" or "norm" (any case)
+    are dropped; the statistic is averaged over the batches as np.array(v).mean(0) does, in float64 on the values given; the weight
+    is 1.0 where the mean is >= threshold and 0.0 elsewhere, a NaN mean included (the reference's comparison is false for it).
+    Nothing is normalised.  Returns {name: weight}, {} without batches; eb_metrics gives the means themselves."""
+    return {n: (1.0 if m >= threshold else 0.0) for n, m in eb_metrics(names, evidence_per_batch).items()}
+
+
+def eb_metrics(names, evidence_per_batch):
+    """{name: batch mean of the eb-criterion statistic} for the names eb_weights keeps, in order; {} without batches."""
+    names = list(names)
+    keep = [i for i, n in enumerate(names) if "bn" not in n.lower() and "norm" not in n.lower()]
+    rows = []
+    for ev in evidence_per_batch:
+        ev = [float(v) for v in ev]
+        if len(ev) != len(names):
+            raise ValueError(f"eb_weights: {len(ev)} statistics for {len(names)} names")
+        rows.append(ev)
+    if not rows:
+        return {}
+    return {names[i]: float(np.array([r[i] for r in rows]).mean(0)) for i in keep}
+
+
+SURGICAL_METHODS = ("RGN", "eb-criterion")              # universal_train.py's --auto_tune modes
+
+
+def surgical_lr_weights(model, opt, batches, distill, method="RGN", return_metrics=False):
+    """The learning-rate weights of the surgical mode from the focal criterion's gradients on `batches` (an iterable of (image,
+    label) device tensors), measured by the flat optimiser `opt` (optim.FlatAdamW built on `model`): per batch one forward in
+    eval() mode, ops.continual_loss with the focal term alone (w_focal = 1, w_dice = 0, kd_weight = 0 and the distill's gamma,
+    alpha, class weights and label map; the teacher's logits are passed, their term has weight 0), backward, opt.gather_grads()
+    and, by `method`, "RGN": opt.tensor_norms() -> rgn_weights; "eb-criterion": opt.tensor_evidence() -> eb_weights.  The
+    statistics stay on the device until one host read at the end; the model's training mode is restored and every .grad is None
+    afterwards.  `opt` may be a HipEngine's (trainer.engine.opt): the engine's cut of the autograd graph between encoder and decoder
+    is lifted while the gradients are measured.  return_metrics=True: (weights, {name: the batch mean the weight was made from}),
+    that is the ratio ||g|| / ||p|| before the division by the maximum, or the eb statistic before the threshold (the reference
+    logs their range)."""
     from . import ops
+    if method not in SURGICAL_METHODS:
+        raise ValueError(f"surgical_lr_weights: method={method!r} (one of {SURGICAL_METHODS})")
+    eb = method == "eb-criterion"
     d = Distill.of(distill)
     names = dict((p.data_ptr(), n) for n, p in model.named_parameters())
     names = [names[p.data_ptr()] for p in opt.params]
     was_training = model.training
     model.eval()
-    norms = []
+    # a HipEngine built on the model cuts the autograd graph at the decoder's inputs for its phased backward: one loss.backward()
+    # must reach every parameter here, so the cut is lifted for the measurement
+    core = _core(model)
+    cut = bool(getattr(core, "detach_decoder_inputs", False))
+    if cut:
+        core.detach_decoder_inputs = False
+    stats = []
     try:
         for img, lab in batches:
             logits = model(img)
@@ -183,12 +229,17 @@ def surgical_lr_weights(model, opt, batches, distill):
             opt.zero_grad()
             loss.backward()
             opt.gather_grads()
-            norms.append(opt.tensor_norms())
+            stats.append(opt.tensor_evidence() if eb else opt.tensor_norms())
             opt.zero_grad()
     finally:
+        if cut:
+            core.detach_decoder_inputs = True
         model.train(was_training)
-    host = torch.stack(norms).cpu().tolist() if norms else []          # the one host read
-    return rgn_weights(names, host)
+    host = torch.stack(stats).cpu().tolist() if stats else []          # the one host read
+    weights = eb_weights(names, host) if eb else rgn_weights(names, host)
+    if not return_metrics:
+        return weights
+    return weights, (eb_metrics(names, host) if eb else rgn_weights(names, host, normalise=False))
 
 
 def tpgm_due(epoch, start_epoch, frequency):

@@ -172,6 +172,38 @@ def chunk_table(numels, offsets):
     return np.array(rows, dtype=rec), np.array(first, dtype=np.int32)
 
 
+_EB_COLS = 64       # columns of a tile of csrc/eb.hip at the most: one wave's lanes
+
+
+def column_tiles(shapes, offsets):
+    """The static table of csrc/eb.hip, which reduces along dimension 0 of every tensor: (records, first_tile).  A tensor of shape
+    (d0, ...) at element offset `off` is d0 rows of inner = numel / d0 contiguous columns (a 0-dimensional tensor counts as (1,)).
+    records: one {'off': int64, 'd0', 'inner', 'col0', 'ncols', 'tensor', 'width': int32} per tile (32 bytes, the library's record),
+    tensors in order and each tensor's tiles in column order; a tile is all d0 rows of columns col0 .. col0 + ncols - 1, tiles take
+    64 columns each until the last takes the rest, so every column is covered exactly once and no pad word is.  width is the
+    smallest power of two >= ncols: the lanes that run along the columns, 256 / width row phases share dimension 0 (1 for a bias,
+    16 for inner = 9).  first_tile: int32 (T + 1,), the tiles of tensor t are first_tile[t] .. first_tile[t + 1] - 1.  This is the
+    table's only producer, so the kernel's preconditions are checked here."""
+    rec = np.dtype([("off", "<i8"), ("d0", "<i4"), ("inner", "<i4"), ("col0", "<i4"), ("ncols", "<i4"), ("tensor", "<i4"), ("width", "<i4")])
+    rows, first = [], [0]
+    for t, (shape, o) in enumerate(zip(shapes, offsets)):
+        shape = tuple(int(s) for s in shape) or (1,)
+        numel = int(np.prod(shape, dtype=np.int64))
+        if numel <= 0 or numel >= 2 ** 31 or o % 8:
+            raise ValueError(f"column_tiles: tensor {t} has shape {shape} at offset {o} (1 to 2^31 - 1 elements, slots start at multiples of 8 floats)")
+        d0, inner = shape[0], numel // shape[0]
+        for col0 in range(0, inner, _EB_COLS):
+            ncols = min(_EB_COLS, inner - col0)
+            rows.append((o, d0, inner, col0, ncols, t, 1 << (ncols - 1).bit_length()))
+        first.append(len(rows))
+    rows = np.array(rows, dtype=rec)
+    ok = ((rows["col0"] >= 0) & (rows["ncols"] >= 1) & (rows["col0"] + rows["ncols"] <= rows["inner"]) & (rows["ncols"] <= rows["width"])
+          & (rows["width"] <= _EB_COLS) & (rows["width"] & (rows["width"] - 1) == 0))
+    if not ok.all():
+        raise ValueError(f"column_tiles: record {int(np.argmin(ok))} would read outside its tensor: {rows[int(np.argmin(ok))]}")
+    return rows, np.array(first, dtype=np.int32)
+
+
 class FlatAdamW(_FlatBuffers):
     """torch.optim.AdamW (decoupled weight decay) on the flat buffers, with torch.nn.utils.clip_grad_norm_(max_grad_norm) fused
     in front of it when max_grad_norm is given and an optional learning-rate multiplier per parameter tensor (set_lr_weights).
@@ -191,6 +223,7 @@ class FlatAdamW(_FlatBuffers):
         self._norms_scalars = torch.zeros(2, dtype=torch.float32, device=dev)             # tensor_norms() leaves `scalars` alone
         self._lr_mult = torch.ones(T, dtype=torch.float32, device=dev)
         self._use_mult = False
+        self._eb = None                                                                   # tensor_evidence()'s table and partials, on first use
         self.step_count = 0
 
     def _alloc_state(self, numel, dev):
@@ -236,6 +269,22 @@ class FlatAdamW(_FlatBuffers):
         out = torch.empty_like(self.tensor_sumsq)
         self._sumsq(True, out, self._norms_scalars, 1.0, 1.0)
         return out.sqrt_()
+
+    def tensor_evidence(self):
+        """(T,) device tensor of the eb-criterion statistic per parameter tensor, mean(g * g / (var(g, dim 0, unbiased) + 1e-8)) of
+        flat_grad as it is (universal_train.py:669-672; NaN for a tensor whose first dimension is 1, as torch.var gives): two
+        launches of csrc/eb.hip, no sync, no allocation but the result.  The tile table is built and uploaded on first use."""
+        if self._eb is None:
+            dev = self.flat_grad.device
+            rows, first = column_tiles([tuple(p.shape) for p in self.params], self.offsets)
+            self._eb = (torch.from_numpy(rows.view(np.int64).reshape(-1, 4)).to(dev), len(rows), torch.from_numpy(first).to(dev),
+                        torch.tensor([p.numel() for p in self.params], dtype=torch.int32, device=dev),
+                        torch.zeros(len(rows), dtype=torch.float32, device=dev))
+        tiles, ntiles, first_tile, numel, partial = self._eb
+        out = torch.empty(len(self.params), dtype=torch.float32, device=self.flat_grad.device)
+        call("cswin_eb_tiles", ptr(self.flat_grad), ptr(tiles), ntiles, ptr(partial), stream())
+        call("cswin_eb_finalize", ptr(partial), ptr(first_tile), ptr(numel), len(self.params), ptr(out), stream())
+        return out
 
     def state_dict(self):
         return {"m": self.flat_m.clone(), "v": self.flat_v.clone(), "step": self.step_count, "lr": self.lr,

@@ -29,7 +29,8 @@ extern "C" {
 /* Bumped whenever a prototype or struct below changes (1: round 1; 2: round 2 -- stream / precision / storage arguments; 3: round 3 --
  * cswin_attn_fwd writes y0, cswin_attn_bwd reads it).  cswin_abi_version() returns the value the library was built with: a consumer
  * compiled against another header must refuse to call it.  Entry points that are only ADDED (cswin_seg_metrics*, cswin_resize_banded, cswin_argmax_zoom_back, cswin_augment_*,
- * cswin_chunk_sumsq, cswin_norm_finalize, cswin_adamw_flat, cswin_tpgm_*, cswin_argmax_zoom_back_classes, cswin_class_counts, cswin_gaussian_blur) do not bump it: every prototype an older consumer binds is unchanged. */
+ * cswin_chunk_sumsq, cswin_norm_finalize, cswin_adamw_flat, cswin_tpgm_*, cswin_argmax_zoom_back_classes, cswin_class_counts, cswin_gaussian_blur, cswin_eb_tiles,
+ * cswin_eb_finalize) do not bump it: every prototype an older consumer binds is unchanged. */
 #define CSWIN_ABI_VERSION 4
 
 #define CSWIN_OK 0
@@ -382,6 +383,20 @@ int cswin_tpgm_finalize(const float* partial, const int* first_chunk, int ntenso
  * shadow 8-B; src == dst is the only overlap allowed. */
 int cswin_tpgm_project(const float* src, const float* anchor, float* dst, const float* ratio, const void* chunks, int nchunks,
                        void* shadow_bf16, void* stream);
+
+/* ---- the "eb-criterion" statistic of the surgical mode (universal_train.py:669-672) per parameter tensor of the flat gradient
+ * buffer: evidence[t] = mean(g * g / (var(g, dim 0, unbiased) + 1e-8)), one variance per column (an index of the dimensions after
+ * the first, flattened: inner = numel / shape[0] columns of d0 = shape[0] rows) ----
+ *
+ * tiles: ntiles 32-byte records {int64 off; int32 d0, inner, col0, ncols, tensor, width} in DEVICE memory, 8-B aligned, built and
+ * checked by optim.column_tiles (its only producer: col0 + ncols <= inner, 1 <= ncols <= width, width a power of two <= 64, the
+ * d0 * inner elements at `off` inside one tensor's slot).  One workgroup per record reads all d0 rows of its ncols columns of g
+ * (16-B aligned) and writes partial[tile] = sum_j (sum_i g_ij^2) / (var_j + 1e-8f), var_j by a shifted one-pass form (the shift is
+ * the column's first row), every sum in a fixed order.  d0 == 1 gives var = 0 / 0 = NaN, as torch.var does, and stores it. */
+int cswin_eb_tiles(const float* g, const void* tiles, int ntiles, float* partial, void* stream);
+/* One workgroup: evidence[t] = (partial[first_tile[t]] + ... + partial[first_tile[t + 1] - 1], in tile order) / numel[t].
+ * first_tile: ntensors + 1 ints, numel: ntensors ints, both in device memory.  Any ntensors >= 1. */
+int cswin_eb_finalize(const float* partial, const int* first_tile, const int* numel, int ntensors, float* evidence, void* stream);
 
 /* ---- nn.Dropout(p) of the reference (cswin_unet.py:20,25,27 Mlp.drop; :135 proj_drop; :346 pos_drop), fused with the residual
  * add + DropPath row factor that follows it where there is one (:178-179):

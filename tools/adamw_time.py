@@ -8,7 +8,14 @@ on the same device and, for scale, against FlatSGD.apply, at the layout of the f
 One process holds the three optimisers on three copies of the parameters with the same gradients.  After a warm-up every
 repetition times one device-event window of CALLS updates of each of the three, in turn, each window ended by a synchronise;
 the medians are per update; clocks are left as found.  torch.optim.AdamW runs fused if this torch offers it on the device, foreach
-otherwise, and the file says which.  The condition recorded is that ours is not slower than the torch pair."""
+otherwise, and the file says which.  The condition recorded is that ours is not slower than the torch pair.
+
+    python tools/adamw_time.py --eb [--out FILE] [--repeats 20]
+
+times, on the same layout and gradient, FlatAdamW.tensor_evidence() (csrc/eb.hip: two launches, no host read) against the
+reference's eb-criterion loop (universal_train.py:669-672: torch.var, mul, add, div, mean and .item() per tensor, over the 349
+tensors whose names hold neither "bn" nor "norm", as views of the same flat gradient) and records it in
+profiles/eb_criterion_timing.txt.  The loop is the yardstick; nothing is gated on the ratio."""
 import argparse
 import os
 import statistics
@@ -22,9 +29,12 @@ CALLS = 10
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "adamw_timing.txt"))
-    ap.add_argument("--repeats", type=int, default=50)
+    ap.add_argument("--eb", action="store_true", help="time tensor_evidence() against the reference's per-tensor loop instead")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--repeats", type=int, default=None)
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "eb_criterion_timing.txt" if a.eb else "adamw_timing.txt")
+    a.repeats = a.repeats or (20 if a.eb else 50)
     import torch
     from cswin_unet_amd import _lib
     from cswin_unet_amd.networks.cswin_unet import CSWinTransformer
@@ -48,6 +58,8 @@ def main():
             p.grad = g.to(dev)
         opt.gather_grads()
         opt.zero_grad()
+    if a.eb:
+        return eb_main(a, torch, net, adamw, nparam)
     for p, g in zip(theirs, grads):
         p.grad = g.to(dev)
     try:
@@ -93,6 +105,63 @@ def main():
     lines.append("every update of a case touches the same buffers (about 0.4 GB for ours): part of them may stay in the last-level cache between updates")
     ok = med[0] <= med[1]
     lines.append(f"condition (ours not slower than the torch pair): {'met' if ok else 'NOT MET'}: torch pair / ours = {med[1] / med[0]:.2f}x; ours / FlatSGD.apply = {med[0] / med[2]:.2f}x")
+    text = "\n".join(lines) + "\n"
+    print(text)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    open(a.out, "w").write(text)
+    return 0
+
+
+def eb_main(a, torch, net, adamw, nparam):
+    """The --eb mode: adamw.flat_grad holds the gathered N(0, 1) gradient."""
+    names = [n for n, _ in net.named_parameters()]
+    views = [adamw.flat_grad[o:o + p.numel()].view(p.shape) for n, p, o in zip(names, adamw.params, adamw.offsets)
+             if "bn" not in n.lower() and "norm" not in n.lower()]
+    assert len(views) == 349, len(views)
+
+    def ours():
+        return adamw.tensor_evidence()
+
+    def loop():
+        out = []
+        for g in views:
+            grad_var = torch.var(g, dim=0, keepdim=True)
+            tmp = (g * g) / (grad_var + 1e-8)
+            out.append(tmp.mean().item())
+        return out
+
+    cases = [("FlatAdamW.tensor_evidence() (eb_tiles + eb_finalize, all 463 tensors, no host read)", ours),
+             ("the reference's loop (torch.var, mul, add, div, mean, .item() per tensor; 349 tensors)", loop)]
+    for _, fn in cases:
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    kept = [i for i, n in enumerate(names) if "bn" not in n.lower() and "norm" not in n.lower()]
+    got, want = ours().cpu()[kept].double(), torch.tensor(loop(), dtype=torch.float64)
+    agree = float(((got - want).abs() / want.abs().clamp_min(1e-30)).max())
+    times = [[] for _ in cases]
+    for _ in range(a.repeats):
+        for t, (_, fn) in zip(times, cases):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(CALLS):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            t.append(e0.elapsed_time(e1) / CALLS)
+    med = [statistics.median(t) for t in times]
+    ntiles = adamw._eb[1]
+    lines = [f"eb-criterion timing: {len(adamw.params)} tensors, {nparam} parameters ({adamw.numel} floats with the slots' pad words, {ntiles} column tiles), "
+             f"{torch.cuda.get_device_name(0)}, torch {torch.__version__}",
+             f"one process, 3 warm-up calls each, then {a.repeats} repetitions of one device-event window of {CALLS} calls per case, the cases in turn; "
+             f"median per call (min, max); clocks as found",
+             f"both read the same flat gradient (N(0, 1)); largest relative difference of the 349 statistics: {agree:.2e}"]
+    for (what, _), t, m in zip(cases, times, med):
+        lines.append(f"  {what}: {m:.4f} ms (min {min(t):.4f}, max {max(t):.4f})")
+    gbytes = nparam * 4 / 1e9
+    lines.append(f"ours reads every gradient element once ({gbytes:.3f} GB): {gbytes / med[0]:.2f} TB/s at the median; every call reads the same buffer, "
+                 f"which may stay in the last-level cache between calls")
+    lines.append(f"the loop / ours = {med[1] / med[0]:.1f}x" + ("" if med[0] <= med[1] else "  (ours is SLOWER than the loop)"))
     text = "\n".join(lines) + "\n"
     print(text)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
