@@ -104,6 +104,7 @@ template <bool Q16> __device__ __forceinline__ void stdq(const AttnParams& p, fl
 
 struct WgInfo {
     int bi, b, win, g, N, ih, iw;
+    int blk;         // two-pass backward: this workgroup's block of 64 tokens inside the unit (0 elsewhere)
 };
 
 // n / d of the index arithmetic by fdiv (common.h): 0 <= n < 2^20 and 0 < d < 2^12 here, inside its exactness bound (the index
@@ -143,8 +144,11 @@ __device__ __forceinline__ unsigned attn_keep_bits(const AttnParams& p, long uid
     return bits;
 }
 
-__device__ __forceinline__ WgInfo decode_wg(const AttnParams& p, int wg) {
+// workgroup -> unit; nblk > 1 (two-pass backward): nblk consecutive workgroups share a unit, one per block of 64 tokens
+__device__ __forceinline__ WgInfo decode_wg(const AttnParams& p, int wg, int nblk = 1) {
     WgInfo w;
+    w.blk = wg % nblk;
+    wg /= nblk;
     w.bi = (p.nbranch > 1 && wg >= p.br[1].wg_begin) ? 1 : 0;
     const AttnBranch& br = p.br[w.bi];
     const int loc = wg - br.wg_begin;
@@ -158,10 +162,18 @@ __device__ __forceinline__ WgInfo decode_wg(const AttnParams& p, int wg) {
     return w;
 }
 
-// in-window token t -> image token l
-__device__ __forceinline__ int token_of(const AttnBranch& br, const WgInfo& w, int reso, int t) {
-    const int r = br.W_sp > 1 ? fdiv(t, br.m_Wsp) : t, c = t - r * br.W_sp;
+// in-window token t -> its (row, column) in the window -> image token l
+__device__ __forceinline__ void token_rc(const AttnBranch& br, int t, int& r, int& c) {
+    r = br.W_sp > 1 ? fdiv(t, br.m_Wsp) : t;
+    c = t - r * br.W_sp;
+}
+__device__ __forceinline__ int token_at(const AttnBranch& br, const WgInfo& w, int reso, int r, int c) {
     return (w.ih * br.H_sp + r) * reso + w.iw * br.W_sp + c;
+}
+__device__ __forceinline__ int token_of(const AttnBranch& br, const WgInfo& w, int reso, int t) {
+    int r, c;
+    token_rc(br, t, r, c);
+    return token_at(br, w, reso, r, c);
 }
 
 // partial-slab row of workgroup (b, win, head g): element i = tap * HD + d of the [10][HD] scratch (tap 9 = bias)
@@ -199,6 +211,55 @@ __device__ __forceinline__ attn_bf16x8 pk8(f32x4 lo, f32x4 hi) {
 }
 __device__ __forceinline__ f32x4 mfma16(attn_s16x4 a, attn_s16x4 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ f32x4 mfma32(attn_bf16x8 a, attn_bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+
+// ---- tile steps ---------------------------------------------------------------------------------------------------
+// A lane's 8-value register fragment (head channels 8 kq .. 8 kq + 7 of its token) from the two 16-B halves, and its bf16 pack
+// (M16 only; dead code otherwise)
+__device__ __forceinline__ void frag8(float (&f)[8], f32x4 lo, f32x4 hi) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        f[e] = lo[e];
+        f[4 + e] = hi[e];
+    }
+}
+__device__ __forceinline__ attn_bf16x8 pk8(const float (&f)[8]) { return pk8(f32x4{f[0], f[1], f[2], f[3]}, f32x4{f[4], f[5], f[6], f[7]}); }
+
+// One 16 x 16 tile over the 32 head channels: rows 16 t + li, columns 8 kq .. of an [.][LDT] LDS image times the fragment f
+// (fb: its bf16 pack).  fp32: eight 16x16x4 steps in channel order, which is the summation order; M16: one 16x16x32 step.
+template <bool M16>
+__device__ __forceinline__ f32x4 rows_x_frag(const float* img, int t, int li, int kq, const float (&f)[8], attn_bf16x8 fb) {
+    const float* rp = &img[(16 * t + li) * LDT + 8 * kq];
+    const f32x4 r0 = *reinterpret_cast<const f32x4*>(rp), r1 = *reinterpret_cast<const f32x4*>(rp + 4);
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (M16) {
+        acc = mfma32(pk8(r0, r1), fb, acc);
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc = mfma4(r0[e], f[e], acc);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc = mfma4(r1[e], f[4 + e], acc);
+    }
+    return acc;
+}
+
+// o[df] += image^T . tile: rows row0 + r (r = 0 .. 3; row0 = 16 t + 4 kq) and columns 16 df + li of an [.][LDT] LDS image times
+// the accumulator tile `b`, whose four values belong to those rows: an accumulator tile is the B operand as it stands.  fp32: r
+// ascending, which is the summation order; M16: the four strided words of a column packed, one 16x16x16 step per df.
+template <bool M16>
+__device__ __forceinline__ void acc_imgT_x_tile(f32x4 (&o)[2], const float* img, int row0, int li, f32x4 b) {
+    const float* ip = &img[row0 * LDT + li];
+    if constexpr (M16) {
+        const attn_s16x4 bb = pk4(b);
+        o[0] = mfma16(pk4(f32x4{ip[0], ip[LDT], ip[2 * LDT], ip[3 * LDT]}), bb, o[0]);
+        o[1] = mfma16(pk4(f32x4{ip[16], ip[LDT + 16], ip[2 * LDT + 16], ip[3 * LDT + 16]}), bb, o[1]);
+    } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            o[0] = mfma4(ip[r * LDT], b[r], o[0]);
+            o[1] = mfma4(ip[r * LDT + 16], b[r], o[1]);
+        }
+    }
+}
 
 // ---- LePE taps ------------------------------------------------------------------------------------------------
 // The 3x3 depthwise conv is zero padded at the WINDOW border.  Reads use a clamped address and a select instead of a
@@ -263,9 +324,62 @@ __device__ __forceinline__ void lepe_wgrad_taps(const AttnBranch& br, const floa
     }
 }
 
+// LePE taps + bias of a head's channels -> the [10][HD] LDS patch, two values per thread of a T-thread workgroup: lepe_fetch2
+// issues the loads with the other loads of the unit, lepe_store2 writes the patch when the images are staged
+template <int T>
+__device__ __forceinline__ void lepe_fetch2(const AttnParams& p, const AttnBranch& br, int ch0, int tid, float& wl0, float& wl1) {
+    static_assert(10 * HD <= 2 * T, "LePE taps: at most two per thread");
+    auto value = [&](int i) {
+        const int tap = i / HD, ch = i - tap * HD, cb = ch0 - br.c0 + ch;
+        return (i >= 10 * HD || ch >= p.hd) ? 0.f : (tap < 9 ? br.lepe_w[cb * 9 + tap] : br.lepe_b[cb]);
+    };
+    wl0 = value(tid);
+    wl1 = value(tid + T);
+}
+template <int T>
+__device__ __forceinline__ void lepe_store2(float* Wl, int tid, float wl0, float wl1) {
+    if (tid < 10 * HD) Wl[tid] = wl0;
+    if (tid + T < 10 * HD) Wl[tid + T] = wl1;
+}
+
 // =====================================================================================
 // forward
 // =====================================================================================
+// The phase both forward kernels run on one query tile per wave: the S^T tiles s[kt] (rows = keys 16 kt + 4 kq + reg, col = query
+// li) of the K image times the scaled q fragment, keys >= N masked; then s <- exp(s - mx).  mx and sum are the row's maximum and
+// sum over all keys: per-lane reductions over the registers + two cross-group shuffles each.  They are the statistics of the
+// undropped P.  (The epilogue stays written out in both kernels: as a helper it cost attn_fwd_kernel<18, ., 7> two more spilled
+// VGPRs -- profiles/attn_helpers_notes.md.)
+template <int NT, bool M16>
+__device__ __forceinline__ void softmax_tiles(f32x4 (&s)[NT], const float* Ks, int N, int li, int kq, const float (&qr)[8], float& mx,
+                                              float& sum) {
+    const attn_bf16x8 qb = pk8(qr);     // M16 only
+    mx = -INFINITY;
+#pragma unroll
+    for (int kt = 0; kt < NT; ++kt) {
+        f32x4 acc = rows_x_frag<M16>(Ks, kt, li, kq, qr, qb);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            if (16 * kt + 4 * kq + r >= N) acc[r] = -INFINITY;
+            mx = fmaxf(mx, acc[r]);
+        }
+        s[kt] = acc;
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    sum = 0.f;
+#pragma unroll
+    for (int kt = 0; kt < NT; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float e = __expf(s[kt][r] - mx);
+            s[kt][r] = e;
+            sum += e;
+        }
+    sum += __shfl_xor(sum, 16, 64);
+    sum += __shfl_xor(sum, 32, 64);
+}
+
 // QS = 2: the query tiles of a (window, head) are split over two workgroups (each stages the whole K / V stripe): with
 // 384 units on 256 CUs half the CUs would otherwise carry two whole units and set the kernel time; 768 half-units are
 // three per CU.  The two halves are `units` apart in the grid, i.e. on the same XCD / L2 when units % 8 == 0.
@@ -343,51 +457,11 @@ __global__ __launch_bounds__(64 * (QS == 2 ? (NT + 1) / 2 : (NT < 8 ? NT : 8))) 
                     q1r = ldq_raw<Q16>(p, src + 4);
                 }
             }
-            const f32x4 q0 = qcv(q0r), q1 = qcv(q1r);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                qr[e] = q0[e] * p.scale;
-                qr[4 + e] = q1[e] * p.scale;
-            }
+            frag8(qr, qcv(q0r) * p.scale, qcv(q1r) * p.scale);
         }
-        // S^T tiles: rows = keys (16 kt + 4 kq + reg), col = query li
-        const attn_bf16x8 qb = pk8(f32x4{qr[0], qr[1], qr[2], qr[3]}, f32x4{qr[4], qr[5], qr[6], qr[7]});     // M16 only
         f32x4 s[NT];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int kt = 0; kt < NT; ++kt) {
-            const float* kp = &Ks[(16 * kt + li) * LDT + 8 * kq];
-            const f32x4 k0 = *reinterpret_cast<const f32x4*>(kp);
-            const f32x4 k1 = *reinterpret_cast<const f32x4*>(kp + 4);
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            if constexpr (M16) {
-                acc = mfma32(pk8(k0, k1), qb, acc);
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc = mfma4(k0[e], qr[e], acc);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc = mfma4(k1[e], qr[4 + e], acc);
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (16 * kt + 4 * kq + r >= N) acc[r] = -INFINITY;
-                mx = fmaxf(mx, acc[r]);
-            }
-            s[kt] = acc;
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        float sum = 0.f;
-#pragma unroll
-        for (int kt = 0; kt < NT; ++kt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float e = __expf(s[kt][r] - mx);
-                s[kt][r] = e;
-                sum += e;
-            }
-        sum += __shfl_xor(sum, 16, 64);
-        sum += __shfl_xor(sum, 32, 64);
+        float mx, sum;
+        softmax_tiles<NT, M16>(s, Ks, N, li, kq, qr, mx, sum);
         const float inv = 1.0f / sum;
         if (p.drop_p > 0.f) {                      // attention dropout: P o M goes into P V, the statistics stay those of P
             const long uid = attn_unit_id(p, br, w.b, w.g, w.win);
@@ -401,21 +475,7 @@ __global__ __launch_bounds__(64 * (QS == 2 ? (NT + 1) / 2 : (NT < 8 ? NT : 8))) 
         // O^T[d][q] = sum_key V[key][d] * P^T[key][q]; the P accumulator tile is the B operand as it stands
         f32x4 o[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
-        for (int kt = 0; kt < NT; ++kt) {
-            if constexpr (M16) {
-                const float* vp = &Vs[(16 * kt + 4 * kq) * LDT + li];
-                const attn_s16x4 pb = pk4(s[kt]);
-                o[0] = mfma16(pk4(f32x4{vp[0], vp[LDT], vp[2 * LDT], vp[3 * LDT]}), pb, o[0]);
-                o[1] = mfma16(pk4(f32x4{vp[16], vp[LDT + 16], vp[2 * LDT + 16], vp[3 * LDT + 16]}), pb, o[1]);
-            } else {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float* vp = &Vs[(16 * kt + 4 * kq + r) * LDT + li];
-                    o[0] = mfma4(vp[0], s[kt][r], o[0]);
-                    o[1] = mfma4(vp[16], s[kt][r], o[1]);
-                }
-            }
-        }
+        for (int kt = 0; kt < NT; ++kt) acc_imgT_x_tile<M16>(o, Vs, 16 * kt + 4 * kq, li, s[kt]);
         // lane now holds O^T[d = 16 df + 4 kq + e][q = li]
         if (qt == qt0) ATTN_STAMP(3);
         if (qvalid) {
@@ -462,7 +522,6 @@ __global__ __launch_bounds__(64 * (QS == 2 ? (NT + 1) / 2 : NT), 4) void attn_fw
     constexpr int NW = QS == 2 ? (NT + 1) / 2 : NT;
     constexpr int T = 64 * NW;
     constexpr int NLD = (NP * 8 + T - 1) / T;          // 16-B row chunks of K (and of V) staged per thread
-    static_assert(10 * HD <= 2 * T, "LePE taps: at most two per thread");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Ks = smem;                  // [NP][LDT]
     float* Vs = Ks + NP * LDT;         // [NP][LDT]
@@ -504,12 +563,7 @@ __global__ __launch_bounds__(64 * (QS == 2 ? (NT + 1) / 2 : NT), 4) void attn_fw
             if (idx < NP * 8 && row < N && 4 * c4 < p.hd)
                 kraw[i] = ldq_raw<Q16>(p, qkv_b + (long)token_of(br, w, p.reso, row) * C3 + ch0 + 4 * c4 + p.C);
         }
-        {
-            const int tap = tid / HD, ch = tid - tap * HD, cb = ch0 - br.c0 + ch;
-            wl0 = (tid >= 10 * HD || ch >= p.hd) ? 0.f : (tap < 9 ? br.lepe_w[cb * 9 + tap] : br.lepe_b[cb]);
-            const int i2 = tid + T, tap2 = i2 / HD, ch2 = i2 - tap2 * HD, cb2 = ch0 - br.c0 + ch2;
-            wl1 = (i2 >= 10 * HD || ch2 >= p.hd) ? 0.f : (tap2 < 9 ? br.lepe_w[cb2 * 9 + tap2] : br.lepe_b[cb2]);
-        }
+        lepe_fetch2<T>(p, br, ch0, tid, wl0, wl1);
     };
     auto issue_v = [&](int item) {
         int half;
@@ -547,58 +601,17 @@ __global__ __launch_bounds__(64 * (QS == 2 ? (NT + 1) / 2 : NT), 4) void attn_fw
             const int idx = tid + i * T, row = idx >> 3, c4 = idx & 7;
             if (idx < NP * 8) *reinterpret_cast<f32x4*>(&Ks[row * LDT + 4 * c4]) = qcv(kraw[i]);
         }
-        if (tid < 10 * HD) Wl[tid] = wl0;
-        if (tid + T < 10 * HD) Wl[tid + T] = wl1;
+        lepe_store2<T>(Wl, tid, wl0, wl1);
         float qr[8];
-        {
-            const f32x4 q0 = qcv(q0r), q1 = qcv(q1r);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                qr[e] = q0[e] * p.scale;
-                qr[4 + e] = q1[e] * p.scale;
-            }
-        }
+        frag8(qr, qcv(q0r) * p.scale, qcv(q1r) * p.scale);
         lds_barrier();
         ATTN_STAMP(1);
 
-        // ---- S^T tiles: rows = keys (16 kt + 4 kq + reg), col = query li; softmax over registers + two shuffles ----
+        // ---- S^T tiles and their softmax ----
         f32x4 s[NT];
         float mx = -INFINITY, sum = 0.f;
         if (qt < NT) {
-            const attn_bf16x8 qb = pk8(f32x4{qr[0], qr[1], qr[2], qr[3]}, f32x4{qr[4], qr[5], qr[6], qr[7]});     // M16 only
-#pragma unroll
-            for (int kt = 0; kt < NT; ++kt) {
-                const float* kp = &Ks[(16 * kt + li) * LDT + 8 * kq];
-                const f32x4 k0 = *reinterpret_cast<const f32x4*>(kp);
-                const f32x4 k1 = *reinterpret_cast<const f32x4*>(kp + 4);
-                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-                if constexpr (M16) {
-                    acc = mfma32(pk8(k0, k1), qb, acc);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc = mfma4(k0[e], qr[e], acc);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc = mfma4(k1[e], qr[4 + e], acc);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    if (16 * kt + 4 * kq + r >= N) acc[r] = -INFINITY;
-                    mx = fmaxf(mx, acc[r]);
-                }
-                s[kt] = acc;
-            }
-            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-#pragma unroll
-            for (int kt = 0; kt < NT; ++kt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float e = __expf(s[kt][r] - mx);
-                    s[kt][r] = e;
-                    sum += e;
-                }
-            sum += __shfl_xor(sum, 16, 64);
-            sum += __shfl_xor(sum, 32, 64);
+            softmax_tiles<NT, M16>(s, Ks, N, li, kq, qr, mx, sum);
             if (p.drop_p > 0.f) {                      // attention dropout: P o M goes into P V, the statistics stay those of P
                 const unsigned keep = attn_keep_bits<4 * NT>(p, attn_unit_id(p, br, w.b, w.g, w.win), N,
                                                              [&](int i, int& q_, int& k_) { q_ = tq; k_ = 16 * (i >> 2) + 4 * kq + (i & 3); });
@@ -623,21 +636,7 @@ __global__ __launch_bounds__(64 * (QS == 2 ? (NT + 1) / 2 : NT), 4) void attn_fw
             const float inv = 1.0f / sum;
             f32x4 o[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
-            for (int kt = 0; kt < NT; ++kt) {
-                if constexpr (M16) {
-                    const float* vp = &Vs[(16 * kt + 4 * kq) * LDT + li];
-                    const attn_s16x4 pb = pk4(s[kt]);
-                    o[0] = mfma16(pk4(f32x4{vp[0], vp[LDT], vp[2 * LDT], vp[3 * LDT]}), pb, o[0]);
-                    o[1] = mfma16(pk4(f32x4{vp[16], vp[LDT + 16], vp[2 * LDT + 16], vp[3 * LDT + 16]}), pb, o[1]);
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float* vp = &Vs[(16 * kt + 4 * kq + r) * LDT + li];
-                        o[0] = mfma4(vp[0], s[kt][r], o[0]);
-                        o[1] = mfma4(vp[16], s[kt][r], o[1]);
-                    }
-                }
-            }
+            for (int kt = 0; kt < NT; ++kt) acc_imgT_x_tile<M16>(o, Vs, 16 * kt + 4 * kq, li, s[kt]);
             ATTN_STAMP(3);
             // lane holds O^T[d = 16 df + 4 kq + e][q = li]: LePE from the V image, scatter to (B, L, C)
             if (qvalid) {
@@ -757,10 +756,11 @@ __global__ __launch_bounds__(64 * NT, 4) void attn_bwd3_kernel(AttnParams p) {
             bbits[it] = 0;
             lrow[it] = -1;
             if (row < N) {
-                const int r = br.W_sp > 1 ? fdiv(row, br.m_Wsp) : row, c = row - r * br.W_sp;
+                int r, c;
+                token_rc(br, row, r, c);
                 bbits[it] = (r >= 1 ? 1 : 0) | (r <= br.H_sp - 2 ? 2 : 0) | (c >= 1 ? 4 : 0) | (c <= br.W_sp - 2 ? 8 : 0) | 16;
                 if (4 * c4 < p.hd) {
-                    lrow[it] = (w.ih * br.H_sp + r) * p.reso + w.iw * br.W_sp + c;
+                    lrow[it] = token_at(br, w, p.reso, r, c);
                     qv[it] = ldq_raw<Q16>(p, qkv_b + (long)lrow[it] * C3 + ch0 + 4 * c4);
                 }
             }
@@ -787,12 +787,7 @@ __global__ __launch_bounds__(64 * NT, 4) void attn_bwd3_kernel(AttnParams p) {
                 vv[it] = ldq_raw<Q16>(p, qkv_b + (long)lrow[it] * C3 + ch0 + 4 * c4 + 2 * p.C);
             }
         }
-        {
-            const int tap = tid / HD, ch = tid - tap * HD, cb = ch0 - br.c0 + ch;
-            wl0 = (tid >= 10 * HD || ch >= p.hd) ? 0.f : (tap < 9 ? br.lepe_w[cb * 9 + tap] : br.lepe_b[cb]);
-            const int i2 = tid + T, tap2 = i2 / HD, ch2 = i2 - tap2 * HD, cb2 = ch0 - br.c0 + ch2;
-            wl1 = (i2 >= 10 * HD || ch2 >= p.hd) ? 0.f : (tap2 < 9 ? br.lepe_w[cb2 * 9 + tap2] : br.lepe_b[cb2]);
-        }
+        lepe_fetch2<T>(p, br, ch0, tid, wl0, wl1);
     };
 
     ATTN_STAMP(0);
@@ -816,35 +811,15 @@ __global__ __launch_bounds__(64 * NT, 4) void attn_bwd3_kernel(AttnParams p) {
         }
         if (tid < NP) lse_s[tid] = lsev;
         float kf[8], vf[8];
-        {
-            const f32x4 k0 = qcv(k0r), k1 = qcv(k1r);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                kf[e] = k0[e];
-                kf[4 + e] = k1[e];
-            }
-        }
+        frag8(kf, qcv(k0r), qcv(k1r));
         lds_barrier();
         ATTN_STAMP(1);
         // ---- S tiles of all query tiles x this wave's keys (MFMA): they need q and k only, and run in the shadow of the dO / y0 /
         // v loads (at kernel start every workgroup of the launch waits for its loads at the same time: nothing else hides them)
-        const attn_bf16x8 kb = pk8(f32x4{kf[0], kf[1], kf[2], kf[3]}, f32x4{kf[4], kf[5], kf[6], kf[7]});       // M16 only
+        const attn_bf16x8 kb = pk8(kf);       // M16 only
         f32x4 Sq[NT];
 #pragma unroll
-        for (int qt = 0; qt < NT; ++qt) {
-            const float* qp = &QK[(16 * qt + li) * LDT + 8 * kq];
-            const f32x4 q0 = *reinterpret_cast<const f32x4*>(qp), q1 = *reinterpret_cast<const f32x4*>(qp + 4);
-            f32x4 sa = {0.f, 0.f, 0.f, 0.f};
-            if constexpr (M16) {
-                sa = mfma32(pk8(q0, q1), kb, sa);
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) sa = mfma4(q0[e], kf[e], sa);          // S[q][key] = sum_d Q[q][d] K[key][d]
-#pragma unroll
-                for (int e = 0; e < 4; ++e) sa = mfma4(q1[e], kf[4 + e], sa);
-            }
-            Sq[qt] = sa;
-        }
+        for (int qt = 0; qt < NT; ++qt) Sq[qt] = rows_x_frag<M16>(QK, qt, li, kq, kf, kb);       // S[q][key] = sum_d Q[q][d] K[key][d]
 
         // ---- A2: dO, V images; delta; border bits; zero row; LePE taps; bias gradient ----
 #pragma unroll
@@ -872,18 +847,12 @@ __global__ __launch_bounds__(64 * NT, 4) void attn_bwd3_kernel(AttnParams p) {
             }
             if (lane < 8) *reinterpret_cast<f32x4*>(&Gl[(9 + wave) * HD + 4 * lane]) = bs;
         }
-        if (tid < 10 * HD) Wl[tid] = wl0;
-        if (tid + T < 10 * HD) Wl[tid + T] = wl1;
+        lepe_store2<T>(Wl, tid, wl0, wl1);
         lds_barrier();
         ATTN_STAMP(2);
         {
             const float* vp = &VS[tk * LDT + 8 * kq];
-            const f32x4 v0 = *reinterpret_cast<const f32x4*>(vp), v1 = *reinterpret_cast<const f32x4*>(vp + 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                vf[e] = v0[e];
-                vf[4 + e] = v1[e];
-            }
+            frag8(vf, *reinterpret_cast<const f32x4*>(vp), *reinterpret_cast<const f32x4*>(vp + 4));
         }
 
         // ---- B: LePE conv weight gradient of this (window, head): dW[tap][ch] = sum_t dO[t][ch] V[nbr(t, tap)][ch] ----
@@ -996,31 +965,18 @@ __global__ __launch_bounds__(64 * NT, 4) void attn_bwd3_kernel(AttnParams p) {
         f32x4 dVt[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
         f32x4 dKt[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
         const bool colok = 16 * kw + li < S;               // dS columns beyond the stride would land in the next row
-        const attn_bf16x8 vb = pk8(f32x4{vf[0], vf[1], vf[2], vf[3]}, f32x4{vf[4], vf[5], vf[6], vf[7]});       // M16 only
-        auto dp_tile = [&](int qt, f32x4& da) {
-            const float* dp = &Ds[(16 * qt + li) * LDT + 8 * kq];
-            const f32x4 d0 = *reinterpret_cast<const f32x4*>(dp), d1 = *reinterpret_cast<const f32x4*>(dp + 4);
-            da = f32x4{0.f, 0.f, 0.f, 0.f};
-            if constexpr (M16) {
-                da = mfma32(pk8(d0, d1), vb, da);
-                return;
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) da = mfma4(d0[e], vf[e], da);               // dP[q][key] = sum_d dO[q][d] V[key][d]
-#pragma unroll
-            for (int e = 0; e < 4; ++e) da = mfma4(d1[e], vf[4 + e], da);
-        };
+        const attn_bf16x8 vb = pk8(vf);       // M16 only
+        auto dp_tile = [&](int qt) { return rows_x_frag<M16>(Ds, qt, li, kq, vf, vb); };       // dP[q][key] = sum_d dO[q][d] V[key][d]
         unsigned keep = ~0u;                                // attention dropout only: bit 4 qt + r = keep (query 16 qt + 4 kq + r, key tk)
         if (p.drop_p > 0.f)
             keep = attn_keep_bits<4 * NT>(p, attn_unit_id(p, br, w.b, w.g, w.win), N,
                                           [&](int i, int& q_, int& k_) { q_ = 16 * (i >> 2) + 4 * kq + (i & 3); k_ = tk; });
         {
-            f32x4 da;
-            dp_tile(0, da);
+            f32x4 da = dp_tile(0);
 #pragma unroll
             for (int qt = 0; qt < NT; ++qt) {
                 f32x4 dn = da;
-                if (qt + 1 < NT) dp_tile(qt + 1, dn);
+                if (qt + 1 < NT) dn = dp_tile(qt + 1);
                 const f32x4 sa = Sq[qt];
                 const f32x4 ls = *reinterpret_cast<const f32x4*>(&lse_s[16 * qt + 4 * kq]);
                 const f32x4 de = *reinterpret_cast<const f32x4*>(&del_s[16 * qt + 4 * kq]);
@@ -1039,25 +995,8 @@ __global__ __launch_bounds__(64 * NT, 4) void attn_bwd3_kernel(AttnParams p) {
                     }
                 }
                 const int q0row = 16 * qt + 4 * kq;
-                if constexpr (M16) {
-                    const float* dop = &Ds[q0row * LDT + li];
-                    const float* qp = &QK[q0row * LDT + li];
-                    const attn_s16x4 prb = pk4(pr), dsb = pk4(ds);
-                    dVt[0] = mfma16(pk4(f32x4{dop[0], dop[LDT], dop[2 * LDT], dop[3 * LDT]}), prb, dVt[0]);
-                    dVt[1] = mfma16(pk4(f32x4{dop[16], dop[LDT + 16], dop[2 * LDT + 16], dop[3 * LDT + 16]}), prb, dVt[1]);
-                    dKt[0] = mfma16(pk4(f32x4{qp[0], qp[LDT], qp[2 * LDT], qp[3 * LDT]}), dsb, dKt[0]);
-                    dKt[1] = mfma16(pk4(f32x4{qp[16], qp[LDT + 16], qp[2 * LDT + 16], qp[3 * LDT + 16]}), dsb, dKt[1]);
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float* dop = &Ds[(q0row + r) * LDT + li];
-                        const float* qp = &QK[(q0row + r) * LDT + li];
-                        dVt[0] = mfma4(dop[0], pr[r], dVt[0]);
-                        dVt[1] = mfma4(dop[16], pr[r], dVt[1]);
-                        dKt[0] = mfma4(qp[0], ds[r], dKt[0]);
-                        dKt[1] = mfma4(qp[16], ds[r], dKt[1]);
-                    }
-                }
+                acc_imgT_x_tile<M16>(dVt, Ds, q0row, li, pr);       // dV^T += dO^T P
+                acc_imgT_x_tile<M16>(dKt, QK, q0row, li, ds);       // dK^T += Q^T dS
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
                     if (colok && q0row + r < N) VS[(q0row + r) * S + 16 * kw + li] = ds[r];
@@ -1099,19 +1038,7 @@ __global__ __launch_bounds__(64 * NT, 4) void attn_bwd3_kernel(AttnParams p) {
             for (int kt = 0; kt < NT; ++kt) {
                 // columns beyond the stride read the head of the next row / the zeroed tail (finite) against K rows that are zero
                 const f32x4 ds = *reinterpret_cast<const f32x4*>(&VS[qrow * S + 16 * kt + 4 * kq]);
-                if constexpr (M16) {
-                    const float* kp = &QK[(16 * kt + 4 * kq) * LDT + li];
-                    const attn_s16x4 dsb = pk4(ds);
-                    dQt[0] = mfma16(pk4(f32x4{kp[0], kp[LDT], kp[2 * LDT], kp[3 * LDT]}), dsb, dQt[0]);
-                    dQt[1] = mfma16(pk4(f32x4{kp[16], kp[LDT + 16], kp[2 * LDT + 16], kp[3 * LDT + 16]}), dsb, dQt[1]);
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float* kp = &QK[(16 * kt + 4 * kq + r) * LDT + li];
-                        dQt[0] = mfma4(kp[0], ds[r], dQt[0]);
-                        dQt[1] = mfma4(kp[16], ds[r], dQt[1]);
-                    }
-                }
+                acc_imgT_x_tile<M16>(dQt, QK, 16 * kt + 4 * kq, li, ds);
             }
             if (tq < N) {
                 float* dst = dqkv_b + (long)token_of(br, w, p.reso, tq) * C3 + ch0 + 4 * kq;
@@ -1133,21 +1060,6 @@ __global__ __launch_bounds__(64 * NT, 4) void attn_bwd3_kernel(AttnParams p) {
 //   attn_bwd_q_kernel   one workgroup per 64 queries: dQ complete in registers over all key chunks (S, dP recomputed)
 //   lepe_wgrad_kernel   depthwise-conv weight/bias gradient partial slabs from global memory
 // 56 MFMAs per 16x16 tile pair instead of 40, no cross-workgroup reduction, deterministic.
-
-struct BigWg { int bi, b, win, g, blk, ih, iw, N; };
-
-__device__ __forceinline__ BigWg decode_big(const AttnParams& p, int wg, int nblk) {
-    BigWg w;
-    w.blk = wg % nblk;
-    const WgInfo i = decode_wg(p, wg / nblk);
-    w.bi = i.bi; w.b = i.b; w.win = i.win; w.g = i.g; w.ih = i.ih; w.iw = i.iw; w.N = i.N;
-    return w;
-}
-
-__device__ __forceinline__ int token_of2(const AttnBranch& br, int ih, int iw, int reso, int t) {
-    const int r = br.W_sp > 1 ? fdiv(t, br.m_Wsp) : t, c = t - r * br.W_sp;
-    return (ih * br.H_sp + r) * reso + iw * br.W_sp + c;
-}
 
 // grid: ceil(B * L * heads_total / 32) blocks of 256 threads; 8 lanes per (token, head)
 template <int ST>
@@ -1191,7 +1103,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_kernel(AttnParams p, int nblk
     __shared__ __attribute__((aligned(16))) float Dc[64 * LDT];
     __shared__ __attribute__((aligned(16))) float lse_c[64];
     __shared__ __attribute__((aligned(16))) float del_c[64];
-    const BigWg w = decode_big(p, blockIdx.x, nblk);
+    const WgInfo w = decode_wg(p, blockIdx.x, nblk);
     const AttnBranch& br = p.br[w.bi];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, kq = lane >> 4;
@@ -1203,7 +1115,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_kernel(AttnParams p, int nblk
     const long stat_base = ((long)w.b * p.heads_total + br.head0 + w.g) * L;
     const int tk = 64 * w.blk + 16 * wave + li;
     const bool kvalid = tk < N;
-    const int lk = kvalid ? token_of2(br, w.ih, w.iw, p.reso, tk) : 0;
+    const int lk = kvalid ? token_of(br, w, p.reso, tk) : 0;
     float kf[8], vf[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) kf[e] = vf[e] = 0.f;
@@ -1211,21 +1123,19 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_kernel(AttnParams p, int nblk
         const float* src = qkv_b + (long)lk * C3 + ch0 + 8 * kq;
         const auto k0r = ldq_raw<Q16>(p, src + p.C), k1r = ldq_raw<Q16>(p, src + p.C + 4);
         const auto v0r = ldq_raw<Q16>(p, src + 2 * p.C), v1r = ldq_raw<Q16>(p, src + 2 * p.C + 4);
-        const f32x4 k0 = qcv(k0r), k1 = qcv(k1r), v0 = qcv(v0r), v1 = qcv(v1r);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { kf[e] = k0[e]; kf[4 + e] = k1[e]; vf[e] = v0[e]; vf[4 + e] = v1[e]; }
+        frag8(kf, qcv(k0r), qcv(k1r));
+        frag8(vf, qcv(v0r), qcv(v1r));
     }
     f32x4 dVt[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
     f32x4 dKt[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    const attn_bf16x8 kb = pk8(f32x4{kf[0], kf[1], kf[2], kf[3]}, f32x4{kf[4], kf[5], kf[6], kf[7]});       // M16 only
-    const attn_bf16x8 vb = pk8(f32x4{vf[0], vf[1], vf[2], vf[3]}, f32x4{vf[4], vf[5], vf[6], vf[7]});
+    const attn_bf16x8 kb = pk8(kf), vb = pk8(vf);       // M16 only
     for (int q0 = 0; q0 < N; q0 += 64) {
         for (int idx = tid; idx < 64 * 8; idx += 256) {
             const int row = idx >> 3, c4 = idx & 7, tq = q0 + row;
             typename QRaw<Q16>::type qv = {};
             f32x4 dv = {0.f, 0.f, 0.f, 0.f};
             if (tq < N && 4 * c4 < p.hd) {
-                const int l = token_of2(br, w.ih, w.iw, p.reso, tq);
+                const int l = token_of(br, w, p.reso, tq);
                 qv = ldq_raw<Q16>(p, qkv_b + (long)l * C3 + ch0 + 4 * c4);
                 dv = *reinterpret_cast<const f32x4*>(dy_b + (long)l * p.C + ch0 + 4 * c4);
             }
@@ -1235,13 +1145,15 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_kernel(AttnParams p, int nblk
         if (tid < 128) {
             const int row = tid & 63, tq = q0 + row;
             const bool ok = tq < N;
-            const int l = ok ? token_of2(br, w.ih, w.iw, p.reso, tq) : 0;
+            const int l = ok ? token_of(br, w, p.reso, tq) : 0;
             if (tid < 64) lse_c[row] = ok ? p.lse[stat_base + l] : INFINITY;
             else del_c[row] = ok ? p.delta[stat_base + l] : 0.f;
         }
         __syncthreads();
 #pragma unroll
         for (int qt = 0; qt < 4; ++qt) {
+            // S and dP tiles, their 16x16x4 steps interleaved: as two rows_x_frag calls the compiler issues each accumulator's eight
+            // dependent steps back to back (profiles/attn_helpers_notes.md)
             const float* qp = &Qc[(16 * qt + li) * LDT + 8 * kq];
             const float* dp = &Dc[(16 * qt + li) * LDT + 8 * kq];
             f32x4 sa = {0.f, 0.f, 0.f, 0.f}, da = sa;
@@ -1272,6 +1184,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_kernel(AttnParams p, int nblk
                     pv[r] *= m;
                 }
             }
+            // written out: with the interleaved products above, two acc_imgT_x_tile calls take three more VGPRs here and <ST = 0> loses
+            // its fifth wave per SIMD
             if constexpr (M16) {
                 const float* dop = &Dc[(16 * qt + 4 * kq) * LDT + li];
                 const float* qq = &Qc[(16 * qt + 4 * kq) * LDT + li];
@@ -1296,7 +1210,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_kernel(AttnParams p, int nblk
         __syncthreads();
     }
     if (kvalid) {
-        const int rr = br.W_sp > 1 ? fdiv(tk, br.m_Wsp) : tk, cc = tk - rr * br.W_sp;
+        int rr, cc;
+        token_rc(br, tk, rr, cc);
 #pragma unroll
         for (int df = 0; df < 2; ++df) {
             const int d0 = 16 * df + 4 * kq, cb = w.g * p.hd + d0;
@@ -1307,7 +1222,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_kernel(AttnParams p, int nblk
                 for (int kx = 0; kx < 3; ++kx) {
                     const int r2 = rr - ky + 1, c2 = cc - kx + 1;
                     if (d0 < p.hd && (unsigned)r2 < (unsigned)br.H_sp && (unsigned)c2 < (unsigned)br.W_sp) {
-                        const int l2 = token_of2(br, w.ih, w.iw, p.reso, r2 * br.W_sp + c2);
+                        const int l2 = token_of(br, w, p.reso, r2 * br.W_sp + c2);
                         const f32x4 dv = *reinterpret_cast<const f32x4*>(dy_b + (long)l2 * p.C + ch0 + d0);
                         const int tap = ky * 3 + kx;
 #pragma unroll
@@ -1330,7 +1245,7 @@ __global__ __launch_bounds__(256) void attn_bwd_q_kernel(AttnParams p, int nblk)
     (void)Q16; (void)Y16; (void)M16;
     __shared__ __attribute__((aligned(16))) float Kc[64 * LDT];
     __shared__ __attribute__((aligned(16))) float Vc[64 * LDT];
-    const BigWg w = decode_big(p, blockIdx.x, nblk);
+    const WgInfo w = decode_wg(p, blockIdx.x, nblk);
     const AttnBranch& br = p.br[w.bi];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, kq = lane >> 4;
@@ -1342,7 +1257,7 @@ __global__ __launch_bounds__(256) void attn_bwd_q_kernel(AttnParams p, int nblk)
     const long stat_base = ((long)w.b * p.heads_total + br.head0 + w.g) * L;
     const int tq = 64 * w.blk + 16 * wave + li;
     const bool qvalid = tq < N;
-    const int lq = qvalid ? token_of2(br, w.ih, w.iw, p.reso, tq) : 0;
+    const int lq = qvalid ? token_of(br, w, p.reso, tq) : 0;
     float qr[8], dor[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) qr[e] = dor[e] = 0.f;
@@ -1356,20 +1271,18 @@ __global__ __launch_bounds__(256) void attn_bwd_q_kernel(AttnParams p, int nblk)
         const auto q0r = ldq_raw<Q16>(p, src), q1r = ldq_raw<Q16>(p, src + 4);
         const float* dsrc = dy_b + (long)lq * p.C + ch0 + 8 * kq;
         const f32x4 d0 = *reinterpret_cast<const f32x4*>(dsrc), d1 = *reinterpret_cast<const f32x4*>(dsrc + 4);
-        const f32x4 q0 = qcv(q0r), q1 = qcv(q1r);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { qr[e] = q0[e] * p.scale; qr[4 + e] = q1[e] * p.scale; dor[e] = d0[e]; dor[4 + e] = d1[e]; }
+        frag8(qr, qcv(q0r) * p.scale, qcv(q1r) * p.scale);
+        frag8(dor, d0, d1);
     }
     f32x4 dQt[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
     const long uid = attn_unit_id(p, br, w.b, w.g, w.win);      // attention dropout only
-    const attn_bf16x8 qb = pk8(f32x4{qr[0], qr[1], qr[2], qr[3]}, f32x4{qr[4], qr[5], qr[6], qr[7]});       // M16 only
-    const attn_bf16x8 dob = pk8(f32x4{dor[0], dor[1], dor[2], dor[3]}, f32x4{dor[4], dor[5], dor[6], dor[7]});
+    const attn_bf16x8 qb = pk8(qr), dob = pk8(dor);             // M16 only
     for (int k0 = 0; k0 < N; k0 += 64) {
         for (int idx = tid; idx < 64 * 8; idx += 256) {
             const int row = idx >> 3, c4 = idx & 7, tk = k0 + row;
             typename QRaw<Q16>::type kv = {}, vv = {};
             if (tk < N && 4 * c4 < p.hd) {
-                const float* src = qkv_b + (long)token_of2(br, w.ih, w.iw, p.reso, tk) * C3 + ch0 + 4 * c4;
+                const float* src = qkv_b + (long)token_of(br, w, p.reso, tk) * C3 + ch0 + 4 * c4;
                 kv = ldq_raw<Q16>(p, src + p.C);
                 vv = ldq_raw<Q16>(p, src + 2 * p.C);
             }
@@ -1379,41 +1292,29 @@ __global__ __launch_bounds__(256) void attn_bwd_q_kernel(AttnParams p, int nblk)
         __syncthreads();
 #pragma unroll
         for (int kt = 0; kt < 4; ++kt) {
+            // S^T / dP^T tiles: rows = keys, col = this lane's query; interleaved as in attn_bwd_kv_kernel
             const float* kp = &Kc[(16 * kt + li) * LDT + 8 * kq];
             const float* vp = &Vc[(16 * kt + li) * LDT + 8 * kq];
-            f32x4 sa = {0.f, 0.f, 0.f, 0.f}, da = sa;       // S^T / dP^T tiles: rows = keys, col = this lane's query
+            f32x4 sa = {0.f, 0.f, 0.f, 0.f}, da = sa;
             if constexpr (M16) {
                 sa = mfma32(pk8(*reinterpret_cast<const f32x4*>(kp), *reinterpret_cast<const f32x4*>(kp + 4)), qb, sa);
                 da = mfma32(pk8(*reinterpret_cast<const f32x4*>(vp), *reinterpret_cast<const f32x4*>(vp + 4)), dob, da);
-                f32x4 ds4;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const bool kok = k0 + 16 * kt + 4 * kq + r < N;
-                    const float pv = kok ? __expf(sa[r] - lse_q) : 0.f;
-                    const float m = p.drop_p > 0.f ? attn_keep(p, uid, N, tq, k0 + 16 * kt + 4 * kq + r) : 1.f;
-                    ds4[r] = pv * (da[r] * m - del_q);
-                }
-                const float* kk = &Kc[(16 * kt + 4 * kq) * LDT + li];
-                const attn_s16x4 dsb = pk4(ds4);
-                dQt[0] = mfma16(pk4(f32x4{kk[0], kk[LDT], kk[2 * LDT], kk[3 * LDT]}), dsb, dQt[0]);
-                dQt[1] = mfma16(pk4(f32x4{kk[16], kk[LDT + 16], kk[2 * LDT + 16], kk[3 * LDT + 16]}), dsb, dQt[1]);
             } else {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     sa = mfma4(kp[e], qr[e], sa);
                     da = mfma4(vp[e], dor[e], da);
                 }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const bool kok = k0 + 16 * kt + 4 * kq + r < N;
-                    const float pv = kok ? __expf(sa[r] - lse_q) : 0.f;
-                    const float m = p.drop_p > 0.f ? attn_keep(p, uid, N, tq, k0 + 16 * kt + 4 * kq + r) : 1.f;
-                    const float ds = pv * (da[r] * m - del_q);
-                    const float* kk = &Kc[(16 * kt + 4 * kq + r) * LDT + li];
-                    dQt[0] = mfma4(kk[0], ds, dQt[0]);
-                    dQt[1] = mfma4(kk[16], ds, dQt[1]);
-                }
             }
+            f32x4 ds;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const bool kok = k0 + 16 * kt + 4 * kq + r < N;
+                const float pv = kok ? __expf(sa[r] - lse_q) : 0.f;
+                const float m = p.drop_p > 0.f ? attn_keep(p, uid, N, tq, k0 + 16 * kt + 4 * kq + r) : 1.f;
+                ds[r] = pv * (da[r] * m - del_q);
+            }
+            acc_imgT_x_tile<M16>(dQt, Kc, 16 * kt + 4 * kq, li, ds);
         }
         __syncthreads();
     }
@@ -1453,8 +1354,9 @@ __global__ __launch_bounds__(256) void lepe_wgrad_kernel(AttnParams p) {
     if (live) {
 #pragma unroll 4
         for (int t = t0; t < t1; ++t) {
-            const int rr = br.W_sp > 1 ? fdiv(t, br.m_Wsp) : t, cc = t - rr * br.W_sp;
-            const f32x4 g4 = *reinterpret_cast<const f32x4*>(dy_b + (long)token_of(br, w, p.reso, t) * p.C);
+            int rr, cc;
+            token_rc(br, t, rr, cc);
+            const f32x4 g4 = *reinterpret_cast<const f32x4*>(dy_b + (long)token_at(br, w, p.reso, rr, cc) * p.C);
             if (tap == 9) {
                 acc += g4;
             } else {
@@ -1512,7 +1414,33 @@ __global__ void windows2img_kernel(const float* __restrict__ win, float* __restr
     }
 }
 
-struct HostBranch { int idx; int heads; const float* w; const float* b; float* dw; float* db; };
+// the mode and dropout arguments of both entry points: checked, then stored
+int fill_mode_dropout(AttnParams& p, const char* who, float drop_p, unsigned long long drop_seed, const unsigned long long* drop_epoch,
+                      int qkv_bf16) {
+    CSWIN_REQUIRE(drop_p >= 0.f && drop_p < 1.f, CSWIN_ERR_UNSUPPORTED, "%s: dropout probability %g outside [0, 1)", who, (double)drop_p);
+    p.drop_p = drop_p; p.drop_scale = 1.0f / (1.0f - drop_p); p.drop_thresh = (unsigned)(drop_p * 16777216.0f); p.drop_seed = drop_seed; p.drop_epoch = drop_epoch;
+    CSWIN_REQUIRE(qkv_bf16 == 0 || qkv_bf16 == 1 || qkv_bf16 == 3 || qkv_bf16 == 7, CSWIN_ERR_UNSUPPORTED,
+                  "attn: mode %d (0 = fp32, 1 = qkv / dqkv stored as bf16, 3 = also y, 7 = also bf16 MFMAs)", qkv_bf16);
+    p.qkv_bf16 = qkv_bf16;
+    return CSWIN_OK;
+}
+
+// f(mode as a compile-time constant) for the mode fill_mode_dropout accepted
+template <class F> int with_mode(int mode, F f) {
+    return mode == 7 ? f(std::integral_constant<int, 7>{}) : mode == 3 ? f(std::integral_constant<int, 3>{})
+         : mode ? f(std::integral_constant<int, 1>{}) : f(std::integral_constant<int, 0>{});
+}
+
+// dynamic-LDS opt-in of one kernel instantiation that needs more than 64 KB: once per process, thread-safe, idempotent (a function
+// attribute, not a stream operation: it stays out of graph captures).  `bytes` is a constant of the instantiation.
+template <auto KERNEL>
+int reserve_dynamic_lds(size_t bytes, const char* who) {
+    static std::once_flag once;
+    static hipError_t status = hipSuccess;
+    std::call_once(once, [&] { status = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); });
+    if (status != hipSuccess) { cswin_set_error("%s: cannot reserve %zu B LDS: %s", who, bytes, hipGetErrorString(status)); return CSWIN_ERR_HIP; }
+    return CSWIN_OK;
+}
 
 int fill_params(AttnParams& p, const char* who, int B, int reso, int C, int nbranch, const int* heads,
                 const int* idx, int split, float scale, int* ntile, int* nwg) {
@@ -1555,20 +1483,13 @@ int fill_params(AttnParams& p, const char* who, int B, int reso, int C, int nbra
     return CSWIN_OK;
 }
 
-template <int NT, int Q16>
-int launch_fwd_q(const AttnParams& p, int nwg, hipStream_t st) {
+template <int NT, int ST>
+int launch_fwd(const AttnParams& p, int nwg, hipStream_t st) {
     constexpr int NW = NT < 8 ? NT : 8;
-    const size_t lds = (size_t)(2 * 16 * NT * LDT + 10 * HD) * sizeof(float);
-    if (lds > 64 * 1024) {
-        // dynamic-LDS opt-in of this instantiation: once per process, thread-safe, idempotent (a function attribute, not a
-        // stream operation: it stays out of graph captures); the size is a constant of the template
-        static std::once_flag once;
-        static hipError_t status = hipSuccess;
-        std::call_once(once, [&] {
-            status = hipFuncSetAttribute((const void*)attn_fwd_kernel<NT, 1, Q16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (status == hipSuccess) status = hipFuncSetAttribute((const void*)attn_fwd_kernel<NT, 2, Q16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        });
-        if (status != hipSuccess) { cswin_set_error("attn_fwd: cannot reserve %zu B LDS: %s", lds, hipGetErrorString(status)); return CSWIN_ERR_HIP; }
+    constexpr size_t lds = (size_t)(2 * 16 * NT * LDT + 10 * HD) * sizeof(float);
+    if constexpr (lds > 64 * 1024) {            // both query splits, whichever is launched first
+        if (int rc = reserve_dynamic_lds<attn_fwd_kernel<NT, 1, ST>>(lds, "attn_fwd")) return rc;
+        if (int rc = reserve_dynamic_lds<attn_fwd_kernel<NT, 2, ST>>(lds, "attn_fwd")) return rc;
     }
     {
         // few units relative to the 256 CUs: split the query tiles over two workgroups per unit (see the kernel).  Large windows
@@ -1577,23 +1498,17 @@ int launch_fwd_q(const AttnParams& p, int nwg, hipStream_t st) {
         const bool split = force ? force == 2 : (NT <= 8 ? (nwg < 1024 && nwg % 256 != 0 && NT >= 6)   // measured: pays at N = 98, not at N = 49
                                                          : nwg <= 256);
         if (split) {
-            hipLaunchKernelGGL((attn_fwd_kernel<NT, 2, Q16>), dim3(2 * nwg), dim3(64 * ((NT + 1) / 2)), lds, st, p, nwg);
+            hipLaunchKernelGGL((attn_fwd_kernel<NT, 2, ST>), dim3(2 * nwg), dim3(64 * ((NT + 1) / 2)), lds, st, p, nwg);
             return CSWIN_OK;
         }
     }
-    hipLaunchKernelGGL((attn_fwd_kernel<NT, 1, Q16>), dim3(nwg), dim3(64 * NW), lds, st, p, nwg);
+    hipLaunchKernelGGL((attn_fwd_kernel<NT, 1, ST>), dim3(nwg), dim3(64 * NW), lds, st, p, nwg);
     return CSWIN_OK;
-}
-
-template <int NT>
-int launch_fwd(const AttnParams& p, int nwg, hipStream_t st) {
-    return p.qkv_bf16 == 7 ? launch_fwd_q<NT, 7>(p, nwg, st) : p.qkv_bf16 == 3 ? launch_fwd_q<NT, 3>(p, nwg, st)
-         : p.qkv_bf16 ? launch_fwd_q<NT, 1>(p, nwg, st) : launch_fwd_q<NT, 0>(p, nwg, st);
 }
 
 // forward for windows of up to 128 tokens: items = units, or 2 x units with the query tiles split over two workgroups
 template <int NT, int ST>
-int launch_fwd3_q(const AttnParams& p, int nwg, hipStream_t st) {
+int launch_fwd3(const AttnParams& p, int nwg, hipStream_t st) {
     const size_t lds = (size_t)(2 * 16 * NT * LDT + 10 * HD) * sizeof(float);
     static_assert((2 * 16 * NT * LDT + 10 * HD) * sizeof(float) <= 64 * 1024, "no dynamic-LDS opt-in on this path");
     if constexpr (NT >= 6) {
@@ -1606,12 +1521,6 @@ int launch_fwd3_q(const AttnParams& p, int nwg, hipStream_t st) {
     }
     hipLaunchKernelGGL((attn_fwd3_kernel<NT, 1, ST>), dim3(nwg), dim3(64 * NT), lds, st, p, nwg);
     return CSWIN_OK;
-}
-
-template <int NT>
-int launch_fwd3(const AttnParams& p, int nwg, hipStream_t st) {
-    return p.qkv_bf16 == 7 ? launch_fwd3_q<NT, 7>(p, nwg, st) : p.qkv_bf16 == 3 ? launch_fwd3_q<NT, 3>(p, nwg, st)
-         : p.qkv_bf16 ? launch_fwd3_q<NT, 1>(p, nwg, st) : launch_fwd3_q<NT, 0>(p, nwg, st);
 }
 
 inline int ds_stride_for(int N) {            // smallest stride >= N with stride = 4 (mod 8): 16-B aligned rows, and the four
@@ -1627,36 +1536,27 @@ inline int vs_floats_for(int NT, int N, int S) {     // V image [16 NT + 1][LDT]
 }
 
 template <int NT, int ST>
-int launch_bwd3_q(const AttnParams& p, int nwg, hipStream_t st) {
+int launch_bwd3(AttnParams& p, int nwg, hipStream_t st) {
     constexpr int NP = 16 * NT;
+    p.vs_floats = vs_floats_for(NT, p.br[0].H_sp * p.br[0].W_sp, p.ds_stride);
     const size_t lds = (size_t)(2 * NP * LDT + p.vs_floats + 2 * NP + (19 + NT) * HD) * sizeof(float);
     if (lds > 64 * 1024) {
-        // once per process and instantiation, thread-safe: reserve the largest footprint this NT can ask for (N = 16 NT tokens)
-        static std::once_flag once;
-        static hipError_t status = hipSuccess;
+        // reserve the largest footprint this NT can ask for (N = 16 NT tokens)
         constexpr int SMAX = ((NP + 3) / 4 * 4) + 8;
         constexpr size_t lds_max = (size_t)(2 * NP * LDT + (NP * SMAX + NP + 4 > (NP + 1) * LDT ? NP * SMAX + NP + 4 : (NP + 1) * LDT) + 2 * NP + (19 + NT) * HD) * sizeof(float);
-        std::call_once(once, [&] {
-            status = hipFuncSetAttribute((const void*)attn_bwd3_kernel<NT, ST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
-        });
-        if (status != hipSuccess) { cswin_set_error("attn_bwd: cannot reserve %zu B LDS: %s", lds_max, hipGetErrorString(status)); return CSWIN_ERR_HIP; }
+        if (int rc = reserve_dynamic_lds<attn_bwd3_kernel<NT, ST>>(lds_max, "attn_bwd")) return rc;
     }
     hipLaunchKernelGGL((attn_bwd3_kernel<NT, ST>), dim3(nwg), dim3(64 * NT), lds, st, p);
     return CSWIN_OK;
 }
 
-template <int NT>
-int launch_bwd3(const AttnParams& p, int nwg, hipStream_t st) {
-    return p.qkv_bf16 == 7 ? launch_bwd3_q<NT, 7>(p, nwg, st) : p.qkv_bf16 == 3 ? launch_bwd3_q<NT, 3>(p, nwg, st)
-         : p.qkv_bf16 ? launch_bwd3_q<NT, 1>(p, nwg, st) : launch_bwd3_q<NT, 0>(p, nwg, st);
-}
-
-template <int Q16>
-void launch_bwd_two_pass(const AttnParams& p, long items, int nwg, int nblk, hipStream_t st) {
-    hipLaunchKernelGGL(attn_delta_kernel<Q16>, dim3((unsigned)((items * 8 + 255) / 256)), dim3(256), 0, st, p);
-    hipLaunchKernelGGL(attn_bwd_kv_kernel<Q16>, dim3(nwg * nblk), dim3(256), 0, st, p, nblk);
-    hipLaunchKernelGGL(attn_bwd_q_kernel<Q16>, dim3(nwg * nblk), dim3(256), 0, st, p, nblk);
-    hipLaunchKernelGGL(lepe_wgrad_kernel<Q16>, dim3(nwg * LW_SUB), dim3(256), 0, st, p);
+template <int ST>
+int launch_bwd_two_pass(const AttnParams& p, long items, int nwg, int nblk, hipStream_t st) {
+    hipLaunchKernelGGL(attn_delta_kernel<ST>, dim3((unsigned)((items * 8 + 255) / 256)), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(attn_bwd_kv_kernel<ST>, dim3(nwg * nblk), dim3(256), 0, st, p, nblk);
+    hipLaunchKernelGGL(attn_bwd_q_kernel<ST>, dim3(nwg * nblk), dim3(256), 0, st, p, nblk);
+    hipLaunchKernelGGL(lepe_wgrad_kernel<ST>, dim3(nwg * LW_SUB), dim3(256), 0, st, p);
+    return CSWIN_OK;
 }
 
 long long* g_attn_stamps = nullptr;     // debug only (cswin_debug_set_attn_stamps)
@@ -1679,31 +1579,30 @@ int cswin_attn_fwd(const float* qkv, const float* const* lepe_w, const float* co
                    int B, int reso, int C, int nbranch, const int* heads, const int* idx, int split, float scale, float drop_p,
                    unsigned long long drop_seed, const unsigned long long* drop_epoch, int qkv_bf16, void* stream) {
     AttnParams p = {};
-    CSWIN_REQUIRE(drop_p >= 0.f && drop_p < 1.f, CSWIN_ERR_UNSUPPORTED, "attn_fwd: dropout probability %g outside [0, 1)", (double)drop_p);
-    p.drop_p = drop_p; p.drop_scale = 1.0f / (1.0f - drop_p); p.drop_thresh = (unsigned)(drop_p * 16777216.0f); p.drop_seed = drop_seed; p.drop_epoch = drop_epoch;
-    CSWIN_REQUIRE(qkv_bf16 == 0 || qkv_bf16 == 1 || qkv_bf16 == 3 || qkv_bf16 == 7, CSWIN_ERR_UNSUPPORTED,
-                  "attn: mode %d (0 = fp32, 1 = qkv / dqkv stored as bf16, 3 = also y, 7 = also bf16 MFMAs)", qkv_bf16);
-    p.qkv_bf16 = qkv_bf16;
     int nt, nwg;
-    int rc = fill_params(p, "attn_fwd", B, reso, C, nbranch, heads, idx, split, scale, &nt, &nwg);
+    int rc = fill_mode_dropout(p, "attn_fwd", drop_p, drop_seed, drop_epoch, qkv_bf16);
+    if (!rc) rc = fill_params(p, "attn_fwd", B, reso, C, nbranch, heads, idx, split, scale, &nt, &nwg);
     if (rc) return rc;
     CSWIN_REQUIRE(qkv && y && lse && lepe_w && lepe_b, CSWIN_ERR_SHAPE, "attn_fwd: null pointer");
     for (int i = 0; i < nbranch; ++i) { p.br[i].lepe_w = lepe_w[i]; p.br[i].lepe_b = lepe_b[i]; }
     p.qkv = qkv; p.y = y; p.y0 = y0; p.lse = lse;
     p.stamps = g_attn_stamps;
     hipStream_t st = (hipStream_t)stream;
-    switch (nt) {
-        case 1: case 2: case 3: case 4: rc = launch_fwd3<4>(p, nwg, st); break;
-        case 5: case 6: rc = launch_fwd3<6>(p, nwg, st); break;
-        case 7: rc = launch_fwd3<7>(p, nwg, st); break;
-        case 8: case 9: rc = launch_fwd<9>(p, nwg, st); break;
-        case 10: case 11: case 12: rc = launch_fwd<12>(p, nwg, st); break;
-        case 13: case 14: case 15: rc = launch_fwd<15>(p, nwg, st); break;
-        case 16: case 17: case 18: rc = launch_fwd<18>(p, nwg, st); break;
-        default:
-            cswin_set_error("attn_fwd: window of %d tokens unsupported", p.br[0].H_sp * p.br[0].W_sp);
-            return CSWIN_ERR_UNSUPPORTED;
-    }
+    rc = with_mode(p.qkv_bf16, [&](auto mode) {
+        constexpr int ST = decltype(mode)::value;
+        switch (nt) {
+            case 1: case 2: case 3: case 4: return launch_fwd3<4, ST>(p, nwg, st);
+            case 5: case 6: return launch_fwd3<6, ST>(p, nwg, st);
+            case 7: return launch_fwd3<7, ST>(p, nwg, st);
+            case 8: case 9: return launch_fwd<9, ST>(p, nwg, st);
+            case 10: case 11: case 12: return launch_fwd<12, ST>(p, nwg, st);
+            case 13: case 14: case 15: return launch_fwd<15, ST>(p, nwg, st);
+            case 16: case 17: case 18: return launch_fwd<18, ST>(p, nwg, st);
+            default:
+                cswin_set_error("attn_fwd: window of %d tokens unsupported", p.br[0].H_sp * p.br[0].W_sp);
+                return (int)CSWIN_ERR_UNSUPPORTED;
+        }
+    });
     if (rc) return rc;
     CSWIN_LAUNCH_CHECK();
     return CSWIN_OK;
@@ -1726,13 +1625,9 @@ int cswin_attn_bwd(const float* qkv, const float* const* lepe_w, const float* co
                    int split, float scale, cswin_reduce_job* deferred, float drop_p, unsigned long long drop_seed,
                    const unsigned long long* drop_epoch, int qkv_bf16, void* stream) {
     AttnParams p = {};
-    CSWIN_REQUIRE(drop_p >= 0.f && drop_p < 1.f, CSWIN_ERR_UNSUPPORTED, "attn_bwd: dropout probability %g outside [0, 1)", (double)drop_p);
-    p.drop_p = drop_p; p.drop_scale = 1.0f / (1.0f - drop_p); p.drop_thresh = (unsigned)(drop_p * 16777216.0f); p.drop_seed = drop_seed; p.drop_epoch = drop_epoch;
-    CSWIN_REQUIRE(qkv_bf16 == 0 || qkv_bf16 == 1 || qkv_bf16 == 3 || qkv_bf16 == 7, CSWIN_ERR_UNSUPPORTED,
-                  "attn: mode %d (0 = fp32, 1 = qkv / dqkv stored as bf16, 3 = also y, 7 = also bf16 MFMAs)", qkv_bf16);
-    p.qkv_bf16 = qkv_bf16;
     int nt, nwg;
-    int rc = fill_params(p, "attn_bwd", B, reso, C, nbranch, heads, idx, split, scale, &nt, &nwg);
+    int rc = fill_mode_dropout(p, "attn_bwd", drop_p, drop_seed, drop_epoch, qkv_bf16);
+    if (!rc) rc = fill_params(p, "attn_bwd", B, reso, C, nbranch, heads, idx, split, scale, &nt, &nwg);
     if (rc) return rc;
     CSWIN_REQUIRE(qkv && lse && dy && dqkv && lepe_w && dlepe_w && dlepe_b, CSWIN_ERR_SHAPE, "attn_bwd: null pointer");
     CSWIN_REQUIRE(workspace && ws_bytes >= cswin_attn_bwd_workspace(B, reso, C, nbranch, heads, idx, split), CSWIN_ERR_WORKSPACE, "attn_bwd: workspace too small");
@@ -1750,47 +1645,37 @@ int cswin_attn_bwd(const float* qkv, const float* const* lepe_w, const float* co
     p.delta = (float*)workspace + (size_t)nwg * 10 * HD * p.slab_rows;
     p.qkv = qkv; p.lse = const_cast<float*>(lse); p.dy = dy; p.dqkv = dqkv;
     hipStream_t st = (hipStream_t)stream;
-    if (two_pass) {
-        // windows of more than 112 tokens (384x384: N = 144, 288): two-pass path
-        const int N = p.br[0].H_sp * p.br[0].W_sp, nblk = (N + 63) / 64;
-        const long items = (long)B * p.heads_total * reso * reso;
-        if (p.qkv_bf16 == 7) launch_bwd_two_pass<7>(p, items, nwg, nblk, st);
-        else if (p.qkv_bf16 == 3) launch_bwd_two_pass<3>(p, items, nwg, nblk, st);
-        else if (p.qkv_bf16) launch_bwd_two_pass<1>(p, items, nwg, nblk, st);
-        else launch_bwd_two_pass<0>(p, items, nwg, nblk, st);
-        rc = CSWIN_OK;
-    } else {
-        const int Ntok = p.br[0].H_sp * p.br[0].W_sp;
-        switch (nt) {
-            case 1: case 2: case 3: case 4: p.vs_floats = vs_floats_for(4, Ntok, p.ds_stride); rc = launch_bwd3<4>(p, nwg, st); break;
-            case 5: case 6: p.vs_floats = vs_floats_for(6, Ntok, p.ds_stride); rc = launch_bwd3<6>(p, nwg, st); break;
-            default: p.vs_floats = vs_floats_for(7, Ntok, p.ds_stride); rc = launch_bwd3<7>(p, nwg, st); break;
+    rc = with_mode(p.qkv_bf16, [&](auto mode) {
+        constexpr int ST = decltype(mode)::value;
+        if (two_pass) {
+            // windows of more than 112 tokens (384x384: N = 144, 288): two-pass path
+            const int N = p.br[0].H_sp * p.br[0].W_sp, nblk = (N + 63) / 64;
+            return launch_bwd_two_pass<ST>(p, (long)B * p.heads_total * reso * reso, nwg, nblk, st);
         }
-    }
+        switch (nt) {
+            case 1: case 2: case 3: case 4: return launch_bwd3<4, ST>(p, nwg, st);
+            case 5: case 6: return launch_bwd3<6, ST>(p, nwg, st);
+            default: return launch_bwd3<7, ST>(p, nwg, st);
+        }
+    });
     if (rc) return rc;
     CSWIN_LAUNCH_CHECK();
-    // the slabs of each branch are a standard reduction job: rows = B * nWin, columns = [Cb * 9 | Cb]
-    ReduceJobs J = {};
-    int blocks = 0;
+    // the slabs of each branch are a standard reduction job: rows = B * nWin, columns = [Cb * 9 | Cb]; handed to the caller, or
+    // run now through the common job table in one launch (the same job either way)
+    cswin_reduce_job jobs[2] = {};
     for (int i = 0; i < nbranch; ++i) {
         const AttnBranch& br = p.br[i];
         const long cb = (long)br.heads * p.hd;
-        cswin_reduce_job job = {br.dw_part, dlepe_w[i], dlepe_b[i], cb * 9, cb * 10, cb * 10, B * br.nWin * p.slab_rows, 0};
-        if (deferred) {
-            deferred[i] = job;
-            continue;
-        }
-        job.reserved = reduce_job_vec_ok(job);
-        J.j[i] = job;
-        J.first_block[i] = blocks;
-        blocks += (int)((job.n + RS_COLS - 1) / RS_COLS);
+        jobs[i] = cswin_reduce_job{br.dw_part, dlepe_w[i], dlepe_b[i], cb * 9, cb * 10, cb * 10, B * br.nWin * p.slab_rows, 0};
+        if (deferred) deferred[i] = jobs[i];
     }
-    if (!deferred) {
-        J.first_block[nbranch] = blocks;
-        J.njobs = nbranch;
-        hipLaunchKernelGGL(rows_sum_multi_kernel, dim3(blocks), dim3(256), 0, st, J);
-        CSWIN_LAUNCH_CHECK();
-    }
+    if (deferred) return CSWIN_OK;
+    ReduceJobs J = {};
+    const int blocks = fill_reduce_table(jobs, nbranch, J.j, J.first_block);
+    CSWIN_REQUIRE(blocks >= 0, CSWIN_ERR_SHAPE, "attn_bwd: null gradient pointer");
+    J.njobs = nbranch;
+    hipLaunchKernelGGL(rows_sum_multi_kernel, dim3(blocks), dim3(256), 0, st, J);
+    CSWIN_LAUNCH_CHECK();
     return CSWIN_OK;
 }
 
