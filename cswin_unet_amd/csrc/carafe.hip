@@ -475,6 +475,11 @@ bool carafe_args_ok(int B, int H, int W, int Cz, int S) {
     return Cz % 4 == 0 && Cz >= 4;
 }
 
+// every pointer an entry point reads or writes as f32x4 (NULL, an absent bias, passes)
+bool carafe_aligned16(const void* a, const void* b, const void* c = nullptr) {
+    return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -484,6 +489,7 @@ int cswin_carafe_fwd(const float* e, const float* z, const float* bias, float* o
                      int Cz, int S, void* stream) {
     CSWIN_REQUIRE(e && z && out, CSWIN_ERR_SHAPE, "carafe_fwd: null pointer");
     CSWIN_REQUIRE(carafe_args_ok(B, H, W, Cz, S), CSWIN_ERR_UNSUPPORTED, "carafe_fwd: unsupported shape B=%d H=%d W=%d Cz=%d S=%d (Cz %% 4 == 0, S in {2,4})", B, H, W, Cz, S);
+    CSWIN_REQUIRE(carafe_aligned16(z, bias, out), CSWIN_ERR_ALIGN, "carafe_fwd: z, bias and out must be 16-B aligned");
     const int groups = 256 / carafe_lpr(Cz);
     hipStream_t st = (hipStream_t)stream;
     const long items = (long)B * H * W * S * S;
@@ -498,6 +504,7 @@ int cswin_carafe_fwd_nchw(const float* e, const float* z, const float* bias, flo
                           int Cz, int C, int S, void* stream) {
     CSWIN_REQUIRE(e && z && out, CSWIN_ERR_SHAPE, "carafe_fwd_nchw: null pointer");
     CSWIN_REQUIRE(carafe_args_ok(B, H, W, Cz, S) && C > 0 && C <= Cz, CSWIN_ERR_UNSUPPORTED, "carafe_fwd_nchw: unsupported shape B=%d H=%d W=%d Cz=%d C=%d S=%d (Cz %% 4 == 0, 0 < C <= Cz, S in {2,4})", B, H, W, Cz, C, S);
+    CSWIN_REQUIRE(carafe_aligned16(z, bias), CSWIN_ERR_ALIGN, "carafe_fwd_nchw: z and bias must be 16-B aligned");
     hipStream_t st = (hipStream_t)stream;
     const long pixels = (long)B * H * W;
     if (S == 2) hipLaunchKernelGGL(carafe_fwd_nchw_kernel<2>, dim3(grid_for(pixels, 64)), dim3(256), 0, st, e, z, bias, out, wt_save, B, H, W, Cz, C);
@@ -523,6 +530,7 @@ int cswin_carafe_bwd(const float* dout, const float* z, const float* wt_save, fl
     CSWIN_REQUIRE(dout && z && wt_save && de && dz, CSWIN_ERR_SHAPE, "carafe_bwd: null pointer");
     CSWIN_REQUIRE(carafe_args_ok(B, H, W, Cz, S), CSWIN_ERR_UNSUPPORTED, "carafe_bwd: unsupported shape");
     CSWIN_REQUIRE(!dbias || (workspace && ws_bytes >= cswin_carafe_bwd_workspace(B, H, W, Cz, S)), CSWIN_ERR_WORKSPACE, "carafe_bwd: workspace too small");
+    CSWIN_REQUIRE(carafe_aligned16(dout, z, dz), CSWIN_ERR_ALIGN, "carafe_bwd: dout, z and dz must be 16-B aligned");
     const int groups = 256 / carafe_lpr(Cz);
     hipStream_t st = (hipStream_t)stream;
     const long items = (long)B * H * W * S * S, pixels = (long)B * H * W;
@@ -574,7 +582,7 @@ int cswin_carafe_bwd_nchw(const float* dout, const float* z, const float* wt_sav
     CSWIN_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && C <= Cz && carafe4_fused_ok(H, W, Cz, S), CSWIN_ERR_UNSUPPORTED,
                   "carafe_bwd_nchw: needs S = 4, Cz = 16, C <= 16, H and W multiples of %d (got B=%d H=%d W=%d Cz=%d C=%d S=%d)", C4_T, B, H, W, Cz, C, S);
     CSWIN_REQUIRE(!dbias || (workspace && ws_bytes >= cswin_carafe_bwd_workspace(B, H, W, Cz, S)), CSWIN_ERR_WORKSPACE, "carafe_bwd_nchw: workspace too small");
-    CSWIN_REQUIRE(((uintptr_t)dout & 15) == 0, CSWIN_ERR_ALIGN, "carafe_bwd_nchw: dout must be 16-B aligned");
+    CSWIN_REQUIRE(carafe_aligned16(dout, z, dz), CSWIN_ERR_ALIGN, "carafe_bwd_nchw: dout, z and dz must be 16-B aligned");
     hipStream_t st = (hipStream_t)stream;
     const int tx = W / C4_T, ty = H / C4_T, nblk = B * tx * ty;
     hipLaunchKernelGGL(carafe4_bwd_fused_kernel<true>, dim3(nblk), dim3(64 * C4_WAVES), 0, st, dout, z, wt_save, de, dz,

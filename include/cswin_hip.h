@@ -240,7 +240,10 @@ int cswin_tokens_to_nchw(const float* x, float* y, int B, int C, int H, int W, i
 /* ---- CARAFE / CARAFE4 reassembly (cswin_unet.py:242-264, 292-314): softmax over the 9 taps + weighted
  *      3x3 neighbourhood sum + pixel_shuffle, on tokens.  e (B, H*W, 9*S*S) = encoder output, channel
  *      k*S*S + s;  z (B, H*W, Cz) = features to reassemble (the `out` 1x1 conv is applied BEFORE, at low
- *      resolution: it commutes with the reassembly);  out (B, (S*H)*(S*W), Cz) = bias + reassembly. ---- */
+ *      resolution: it commutes with the reassembly);  out (B, (S*H)*(S*W), Cz) = bias + reassembly.
+ *      Cz % 4 == 0, S in {2, 4} (CSWIN_ERR_UNSUPPORTED otherwise).  The kernels move channels 16 bytes at a time: z, bias,
+ *      the token-form out and dout, dz (and the plane-form dout) must be 16-byte aligned, CSWIN_ERR_ALIGN before any launch
+ *      otherwise; e, wt_save, de, dbias, the workspace and the plane-form out need their element's alignment only. ---- */
 int cswin_carafe_fwd(const float* e, const float* z, const float* bias, float* out, float* wt_save, int B, int H,
                      int W, int Cz, int S, void* stream);
 size_t cswin_carafe_bwd_workspace(int B, int H, int W, int Cz, int S);

@@ -1,0 +1,940 @@
+"""csrc/carafe.hip at every launch branch: the two forward forms, the three generic backward kernels, the fused MFMA backward in
+token and plane form and the column-sum kernel -- every lanes-per-item class, chunk pattern, map smaller than the stencil, tile
+class of the fused kernel, plane class count, and each grid-stride loop past its clamp.
+
+References are float64 on the CPU (carafe_ref below, itself checked against autograd of test_gpu_shapes.carafe_closed_form and
+against a plain loop).  N(0,1) and N(0, 8^2) logits are judged ELEMENT BY ELEMENT: |got - ref| <= u (K0 + K1 R) A with u = 2^-24,
+A the float64 sum of the magnitudes that went into the element, R the largest max_k e - e_k of the case and K0, K1 derived from
+the kernels' operation sequence (see bound_consts); the old max|diff| / rms(ref) metric cannot see an entry 25 orders of magnitude
+below the rms.  Logits whose weights underflow keep the global metric.  Every output is a view into a NaN-filled buffer whose
+guard words must survive, workspaces are exactly as large as the library says, every measured figure goes to the error log under
+a tag naming the case, and the entry points are called through cswin_unet_amd._lib.
+
+The tests at the top need no GPU."""
+import ctypes
+import functools
+import math
+import os
+from collections import namedtuple
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from oracle.determ import det_normal
+
+from test_gpu_parity import LOG, RTOL                    # the fp32 bound and the error log, neither of them new
+from test_gpu_shapes import D, carafe_closed_form, carafe_problem, measure
+from test_gpu_attn_shapes import GUARD, Guarded, settle  # NaN guard bands round an output; their check after a launch
+
+gpu = pytest.mark.gpu
+DEV = "cuda"
+U = 2.0 ** -24                                           # unit roundoff of fp32
+ERR_SHAPE, ERR_ALIGN, ERR_WORKSPACE, ERR_UNSUPPORTED = -1, -2, -3, -5       # include/cswin_hip.h
+
+
+def cdiv(a, b):
+    return -(-a // b)
+
+
+# ------------------------------------------------------------------------------------------------
+# launch rules (a transcription of the host code: it MUST FOLLOW csrc/carafe.hip)
+# ------------------------------------------------------------------------------------------------
+GRID_CLAMP, COLSUM_CLAMP, TILE = 8192, 512, 8
+
+
+def lpr(Cz):
+    """lanes per item: the largest power of two <= min(Cz / 4, 64)."""
+    l = 1
+    while 2 * l <= Cz // 4 and 2 * l <= 64:
+        l *= 2
+    return l
+
+
+def groups(Cz):
+    return 256 // lpr(Cz)
+
+
+def grid_for(items, grp):
+    return max(1, min(GRID_CLAMP, cdiv(items, grp)))
+
+
+def ppb(S):
+    """low-resolution pixels per workgroup of the plane forward."""
+    return 256 // (S * S)
+
+
+def colsum_lanes(C):
+    return min(C, 256)
+
+
+def colsum_blocks(rows, C):
+    rg = 256 // colsum_lanes(C)
+    return max(1, min(COLSUM_CLAMP, cdiv(rows, rg * 64)))
+
+
+def fused_ok(H, W, Cz, S):
+    return S == 4 and Cz == 16 and H % TILE == 0 and W % TILE == 0
+
+
+def bias_in_e(Cz):
+    return Cz <= 512
+
+
+def workspace_bytes(B, H, W, Cz, S):
+    items = B * H * W * S * S
+    generic = colsum_blocks(items, Cz) * Cz * 4
+    if bias_in_e(Cz):
+        generic = max(generic, grid_for(items, groups(Cz)) * Cz * 4)
+    fused = B * (H // TILE) * (W // TILE) * Cz * 4 if fused_ok(H, W, Cz, S) else 0
+    return max(generic, fused)
+
+
+def trips(total, per_trip):
+    """(fewest, most) trips of a group through a grid-stride loop over `total` items, `per_trip` = blocks * groups a trip."""
+    return total // per_trip, cdiv(total, per_trip)
+
+
+def chunk_pattern(Cz):
+    """(fewest, most) 16-B chunks a lane of an item takes."""
+    return (Cz // 4) // lpr(Cz), cdiv(Cz // 4, lpr(Cz))
+
+
+def launch_plan(B, H, W, S, Cz):
+    """{kernel: (workgroups, trips)} of one forward + backward in token form."""
+    items, pixels, g = B * H * W * S * S, B * H * W, groups(Cz)
+    plan = {"fwd": (grid_for(items, g), trips(items, grid_for(items, g) * g))}
+    if fused_ok(H, W, Cz, S):
+        plan["fused"] = (B * (H // TILE) * (W // TILE), (1, 1))
+        return plan
+    plan["bwd_e"] = plan["fwd"]
+    plan["bwd_z"] = (grid_for(pixels, g), trips(pixels, grid_for(pixels, g) * g))
+    if not bias_in_e(Cz):
+        nb, rg = colsum_blocks(items, Cz), 256 // colsum_lanes(Cz)
+        plan["colsum"] = (nb, trips(items, nb * rg))
+    return plan
+
+
+def plane_plan(B, H, W, S):
+    pixels = B * H * W
+    nb = grid_for(pixels, ppb(S))
+    return nb, trips(pixels, nb * ppb(S))
+
+
+def dbias_depth(B, H, W, S, Cz):
+    """Additions a term of dbias passes through, from the launch rules: the thread's own, the workgroup's, the slab reduction's
+    (16 row groups of ceil(rows / 16) slab rows on four accumulators, then the 16 group sums)."""
+    plan = launch_plan(B, H, W, S, Cz)
+    slab = lambda rows: cdiv(rows, 16) + 3 + 16
+    if "fused" in plan:             # a wave: at most 4 passes of 4 pixels, 4 additions each; 2 shuffles; 8 waves
+        return 64 + 2 + 8 + slab(plan["fused"][0])
+    if bias_in_e(Cz):               # a lane: one addition a trip and chunk slot; the groups of the workgroup in sequence
+        return plan["bwd_e"][1][1] + groups(Cz) + slab(plan["bwd_e"][0])
+    return plan["colsum"][1][1] + 256 // colsum_lanes(Cz) + slab(plan["colsum"][0])
+
+
+# ------------------------------------------------------------------------------------------------
+# case tables
+# ------------------------------------------------------------------------------------------------
+Case = namedtuple("Case", "tag B H W S Cz C logits")
+
+
+def case(tag, B, H, W, S, Cz, C=None, logits="normal"):
+    return Case(tag, B, H, W, S, Cz, C, logits)
+
+
+CHANNEL_CZ = [
+    (4, "lpr 1: no shuffle, 256 items a workgroup"),
+    (8, "lpr 2"),
+    (12, "lpr 2, 3 chunks: lane 0 takes a second one"),
+    (16, "lpr 4 (the head's width, here off the fused shape)"),
+    (28, "lpr 4, 7 chunks: lanes 0..2 take a second one"),
+    (64, "lpr 16"),
+    (96, "lpr 16, 24 chunks: lanes 0..7 take a second one"),
+    (256, "lpr 64, one chunk per lane on 64 lanes"),
+    (260, "65 chunks: lane 0 alone takes two"),
+    (508, "127 chunks: every lane but the last takes two"),
+    (512, "last size with dbias in bwd_e, two full chunks per lane"),
+    (516, "129 chunks (a third for lane 0); dbias by colsum_partial_kernel, three column passes, the last with 4 live lanes"),
+    (1028, "five column passes of colsum_partial_kernel, the last with 4 live lanes; 257 chunks"),
+]
+CHANNEL_S4 = (4, 16, 28, 260, 516)
+CHANNELS = [case(f"cz{c}.s{S}", 2, 3, 5, S, c) for c, _ in CHANNEL_CZ for S in (2, 4) if S == 2 or c in CHANNEL_S4]
+
+MAP_SHAPES = [
+    (2, 1, 1, "a single pixel: all eight neighbours outside"),
+    (2, 1, 5, "one row: the taps above and below never exist"),
+    (2, 5, 1, "one column"),
+    (2, 2, 2, "smaller than the stencil in both directions: every pixel is a corner"),
+    (2, 3, 5, "the smallest map with an interior pixel, not square"),
+    (3, 7, 13, "odd, not square, B = 3: the batch stride differs from every map stride"),
+    (1, 3, 3, "9 pixels: items fill whole groups and leave a ragged last one for bwd_e's items_pad"),
+]
+MAPS = [case(f"map{B}x{H}x{W}.s{S}", B, H, W, S, Cz) for B, H, W, _ in MAP_SHAPES for S, Cz in ((4, 16), (2, 8))]
+
+FUSED_SHAPES = [
+    (1, 8, 8, "one tile: every halo pixel outside the map"),
+    (2, 8, 16, "1 x 2 tiles, B = 2"),
+    (3, 16, 8, "2 x 1 tiles, B = 3"),
+    (2, 24, 8, "3 x 1 tiles: tiles_x != tiles_y != 1 fails only with this and the next"),
+    (2, 8, 24, "1 x 3 tiles"),
+    (1, 24, 24, "3 x 3 tiles: the centre tile's whole halo is inside"),
+]
+FUSED = [case(f"fused{B}x{H}x{W}", B, H, W, 4, 16) for B, H, W, _ in FUSED_SHAPES]
+# plane form: class counts 1, 3, 4, 9, 16 on the (8, 16) map (C < 4, C % 4 != 0, one chunk, three with a ragged last, C == Cz)
+FUSED_PLANES = [case(f"planes{B}x{H}x{W}.c{C}", B, H, W, 4, 16, C) for B, H, W, _ in FUSED_SHAPES
+                for C in ((1, 3, 4, 9, 16) if (H, W) == (8, 16) else (9,))]
+
+PLANE_FWD = [                                             # outside the fused shape: forward by the plane kernel, backward through tokens
+    case("pf.s2.c5", 2, 5, 9, 2, 8, 5),                  # 90 pixels: a ragged second block of PPB = 64; C % 4 != 0
+    case("pf.s2.c8", 2, 5, 9, 2, 8, 8),                  # C == Cz
+    case("pf.s4.c9", 1, 5, 9, 4, 16, 9),                 # S = 4 off the tile
+    case("pf.s4.c32", 1, 12, 12, 4, 32, 32),             # C == Cz = 32: eight chunks
+    case("pf.s4.c1", 1, 12, 12, 4, 32, 1),               # C < 4
+]
+
+LOGIT_KINDS = ("wide8", "wide40", "offset1e4", "equal")
+LOGITS = [case(f"{kind}.{'fused' if fz else 'generic'}", 2, *( (8, 16) if fz else (5, 9)), 4, 16, None, kind)
+          for kind in LOGIT_KINDS for fz in (False, True)]
+
+# delta gradients: (case, sample, hi-res row, hi-res column)
+DELTAS = [(case("delta.generic", 2, 5, 9, 4, 16), 1, 0, 0),            # a map corner
+          (case("delta.fused", 2, 16, 16, 4, 16), 1, 31, 31)]          # low-res (7, 7): its 3 x 3 reaches all four tiles
+
+BIG = [
+    case("stride256", 4, 91, 91, 2, 256),                # fwd / bwd_e: 33124 workgroups wanted, 8192 launched, 5 trips or 4; bwd_z: 33124 pixels / 4 groups = 8281 > 8192, 2 trips or 1
+    case("nchw_stride", 1, 363, 363, 4, 4, 1),           # 131769 pixels: one ragged trip past 8192 * 16; forward and wt_save only
+    case("colsum_clamp", 1, 46, 46, 4, 516),             # 33856 rows past 512 * 64: 67 trips or 66 at the clamp
+]
+
+SMALL = CHANNELS + MAPS + FUSED + FUSED_PLANES + PLANE_FWD + LOGITS
+ALL = {c.tag: c for c in SMALL + BIG + [d[0] for d in DELTAS]}
+PER_ELEMENT = ("normal", "wide8")
+
+
+# ------------------------------------------------------------------------------------------------
+# inputs and the float64 reference
+# ------------------------------------------------------------------------------------------------
+def to_sub(x, B, H, W, S):
+    """(B, (S*H)*(S*W), C) hi-res tokens -> (B, H, W, S*S, C), s = sy * S + sx."""
+    return x.view(B, H, S, W, S, -1).permute(0, 1, 3, 2, 4, 5).reshape(B, H, W, S * S, -1)
+
+
+def from_sub(x, B, H, W, S):
+    return x.view(B, H, W, S, S, -1).permute(0, 1, 3, 2, 4, 5).reshape(B, S * S * H * W, -1)
+
+
+def planes_to_tokens(p, Cz):
+    """(B, C, SH, SW) -> (B, SH*SW, Cz) tokens with channels >= C zero."""
+    B, C = p.shape[:2]
+    t = p.new_zeros(B, p.shape[2] * p.shape[3], Cz)
+    t[..., :C] = p.permute(0, 2, 3, 1).reshape(B, -1, C)
+    return t
+
+
+def tokens_to_planes(t, C, SH, SW):
+    return t[..., :C].view(t.shape[0], SH, SW, C).permute(0, 3, 1, 2).contiguous()
+
+
+@functools.lru_cache(maxsize=None)
+def inputs(tag):
+    """(e, z, bias, dout) of a case as float32 numpy; dout in the layout the case's backward takes (planes where C is set).
+    Computed once, never written."""
+    c = ALL[tag]
+    S2 = c.S * c.S
+    e, z, bias = carafe_problem(c.B, c.H, c.W, c.S, c.Cz)
+    name = f"carafe.{tag}"
+    if c.logits == "wide8":
+        e = det_normal(name + ".e", e.shape, 8.0)
+    elif c.logits == "wide40":
+        e = det_normal(name + ".e", e.shape, 40.0)
+    elif c.logits == "offset1e4":
+        e = (e + np.float32(1e4)).astype(np.float32)
+    elif c.logits == "equal":
+        e = np.repeat(e.reshape(c.B, c.H * c.W, 9, S2)[:, :, :1], 9, 2).reshape(e.shape).copy()
+    if c.C is None:
+        dout = det_normal(name + ".dout", (c.B, S2 * c.H * c.W, c.Cz))
+    else:
+        dout = det_normal(name + ".dout", (c.B, c.C, c.S * c.H, c.S * c.W))
+    for cc, b, y, x in DELTAS:
+        if cc.tag == tag:
+            row = dout[b, y * c.S * c.W + x].copy()
+            dout = np.zeros_like(dout)
+            dout[b, y * c.S * c.W + x] = row
+    return e, z, bias, dout
+
+
+WRONG_IN_REF = ("clamp_edge", "tap_swap", "sub_swap", "hw_swap", "drop_chunks", "tile_edge")
+
+
+def carafe_ref(e, z, bias, dout, H, W, S, dtype=torch.float64, wrong=None):
+    """The reassembly and its gradients from their definitions, in `dtype`, for tokens e (B, H*W, 9*S*S), z (B, H*W, Cz), bias
+    (Cz), dout (B, (S*H)*(S*W), Cz) or None.  Returns out, wt, R = the largest max_k e - e_k, and with dout de, dz, dbias; beside
+    every result X the magnitude sum A_X that its bound scales with:
+      A_out = |bias| + sum_k wt_k |z_k|          A_dz = sum wt |dout| over the terms of dz's own sum
+      A_de[k] = wt_k (a_k + sum_j wt_j a_j), a_k = sum_c |dout| |z_k|          A_dbias = sum |dout|
+    wrong (the sensitivity test alone): "clamp_edge" (neighbours outside the map clamp to the edge instead of reading zero),
+    "tap_swap" (tap row and column swapped), "sub_swap" (sy and sx swapped), "hw_swap" (H and W swapped in the pixel decode),
+    "drop_chunks" (channels >= 4 lpr floor(chunks / lpr) never visited), "tile_edge" (dz loses what crosses an 8 x 8 tile edge)."""
+    cv = lambda a: (torch.from_numpy(a) if isinstance(a, np.ndarray) else a).to(dtype)
+    e, z, bias = cv(e), cv(z), cv(bias)
+    B, _, Cz = z.shape
+    S2 = S * S
+    if wrong == "hw_swap":
+        H, W = W, H
+    if wrong == "drop_chunks":
+        cut = 4 * lpr(Cz) * ((Cz // 4) // lpr(Cz))
+        z = z.clone()
+        z[..., cut:] = 0
+    ev = e.view(B, H, W, 9, S2)
+    if wrong == "sub_swap":
+        ev = ev[..., [(s % S) * S + s // S for s in range(S2)]]
+    d = ev - ev.max(3, keepdim=True).values
+    wt = torch.exp(d)
+    wt = wt / wt.sum(3, keepdim=True)
+    zp = F.pad(z.view(B, H, W, Cz).permute(0, 3, 1, 2), (1, 1, 1, 1), mode="replicate" if wrong == "clamp_edge" else "constant").permute(0, 2, 3, 1)
+    taps = [(k % 3, k // 3) if wrong == "tap_swap" else (k // 3, k % 3) for k in range(9)]
+    nb = torch.stack([zp[:, ky:ky + H, kx:kx + W] for ky, kx in taps], 3)                  # (B, H, W, k, Cz)
+    up = torch.einsum("bhwks,bhwkc->bhwsc", wt, nb) + bias
+    if wrong == "drop_chunks":
+        up[..., cut:] = 0
+    r = dict(out=from_sub(up, B, H, W, S), wt=wt.reshape(B, H * W, 9 * S2), R=float(-d.min()),
+             A_out=from_sub(torch.einsum("bhwks,bhwkc->bhwsc", wt, nb.abs()) + bias.abs(), B, H, W, S), A_wt=wt.reshape(B, H * W, 9 * S2))
+    if dout is None:
+        return r
+    g = cv(dout)
+    if wrong == "drop_chunks":
+        g = g.clone()
+        g[..., cut:] = 0
+    g = to_sub(g, B, H, W, S)                                                               # (B, H, W, s, Cz)
+    dwt = torch.einsum("bhwsc,bhwkc->bhwks", g, nb)
+    a = torch.einsum("bhwsc,bhwkc->bhwks", g.abs(), nb.abs())
+    r["de"] = (wt * (dwt - (wt * dwt).sum(3, keepdim=True))).reshape(B, H * W, 9 * S2)
+    r["A_de"] = (wt * (a + (wt * a).sum(3, keepdim=True))).reshape(B, H * W, 9 * S2)
+    G, GA = torch.einsum("bhwks,bhwsc->bhwkc", wt, g), torch.einsum("bhwks,bhwsc->bhwkc", wt, g.abs())
+    dzp, azp = G.new_zeros(B, H + 2, W + 2, Cz), G.new_zeros(B, H + 2, W + 2, Cz)
+    hh, ww = torch.arange(H)[:, None], torch.arange(W)[None, :]
+    for k, (ky, kx) in enumerate(taps):
+        keep = 1.0
+        if wrong == "tile_edge":
+            keep = ((hh // TILE == (hh + ky - 1) // TILE) & (ww // TILE == (ww + kx - 1) // TILE)).to(dtype)[None, :, :, None]
+        dzp[:, ky:ky + H, kx:kx + W] += G[:, :, :, k] * keep
+        azp[:, ky:ky + H, kx:kx + W] += GA[:, :, :, k]
+    r["dz"], r["A_dz"] = dzp[:, 1:-1, 1:-1].reshape(B, H * W, Cz), azp[:, 1:-1, 1:-1].reshape(B, H * W, Cz)
+    r["dbias"], r["A_dbias"] = g.sum((0, 1, 2, 3)), g.abs().sum((0, 1, 2, 3))
+    return r
+
+
+def plane_view(r, c):
+    """What the plane form of case c gives, from the token reference r of the gradient laid out as tokens: out as C planes,
+    everything else unchanged (dz[..., C:] and dbias[C:] are exactly zero in r already)."""
+    r = dict(r)
+    for k in ("out", "A_out"):
+        r[k] = tokens_to_planes(r[k], c.C, c.S * c.H, c.S * c.W)
+    return r
+
+
+def token_dout(c, dout):
+    return dout if c.C is None or dout is None else planes_to_tokens(torch.from_numpy(dout), c.Cz).numpy()
+
+
+@functools.lru_cache(maxsize=None)
+def reference(tag, dtype=torch.float64, wrong=None):
+    """carafe_ref of a case, one sample at a time (the large rows' peak memory stays that of one sample); computed once per
+    process, shared by every test that uses the case, never written."""
+    c = ALL[tag]
+    e, z, bias, dout = inputs(tag)
+    dout = None if tag == "nchw_stride" else token_dout(c, dout)
+    parts = []
+    for b in range(c.B):
+        p = carafe_ref(e[b:b + 1], z[b:b + 1], bias, None if dout is None else dout[b:b + 1], c.H, c.W, c.S, dtype, wrong)
+        if c in BIG:                 # of a magnitude sum only the size matters, and N(0,1) inputs keep it far from fp32's limits
+            p.update({k: v.float() for k, v in p.items() if k.startswith("A_")})
+        parts.append(p)
+    r = {k: torch.cat([p[k] for p in parts]) for k in parts[0] if k not in ("R", "dbias", "A_dbias")}
+    r["R"] = max(p["R"] for p in parts)
+    if dout is not None:
+        r["dbias"], r["A_dbias"] = sum(p["dbias"] for p in parts), sum(p["A_dbias"] for p in parts)
+    return r if c.C is None else plane_view(r, c)
+
+
+def bound_consts(c, R):
+    """{output: K0 + K1 R} of case c: the roundings, in units of u = 2^-24 relative to A, that the kernels' operation sequence
+    can leave in an element.  Nothing here is fitted to a device.
+
+    A weight.  d_k = e_k - max <= 0 is rounded once (|d_k| u).  __expf(d) is v_exp_f32 of fl(d * fl(log2 e)): the constant is
+    0.23 u off, the product one rounding, so the argument moves by 2.25 |d_k| u in all and the result by that relative amount,
+    plus 1 ulp = 2 u of the instruction.  The nine-term sum inherits sum_j wt_j (2 + 2.25 |d_j|) <= 2 + 2.25 * 8 / e = 8.62
+    (x e^-x <= 1/e, and the largest term has d = 0) -- no R there -- and adds 8 roundings of its own; the reciprocal 2 (1 ulp of a
+    reciprocal instruction; a correctly rounded division is inside), the product by it 1:
+        rho = 22 + 2.25 R                                                                   [2 + 8.62 + 8 + 2 + 1 = 21.62]
+    out = bias + nine multiply-adds of wt_k z_k: rho on every term, 1 for the product where it is not contracted, 9 additions
+    of partial sums that A_out bounds:                                                       out: rho + 10
+    dz sums wt * dout over up to 9 S^2 terms in sequence (generic kernel): rho + 1 + 9 S^2.  The fused kernel contracts the 16
+    sub-pixels on the matrix pipe (four 16x16x4 steps of four products: <= 16 roundings) and adds nine such G from LDS: rho + 1 + 25.
+    de_k = wt_k (dwt_k - dot), dot = sum_j wt_j dwt_j.  dwt_k is off by n a_k, n = 1 + 4 ceil(chunks / lpr) + log2 lpr (the
+    product, four additions a chunk, the lane shuffles; fused: 1 + 16 on the matrix pipe).  dot: (rho + 1 + 9 + n) sum_j wt_j a_j.
+    The difference and the product add 2 (|dwt_k - dot| <= a_k + sum_j wt_j a_j) and wt_k brings rho of |dwt_k - dot|.  The
+    coefficient of a_k is rho + 2 + n, that of sum_j wt_j a_j is 2 rho + 12 + n; the larger covers both:   de: 2 rho + 12 + n
+    dbias: `depth` additions of terms that A_dbias bounds, depth from the launch rules (dbias_depth); no R."""
+    rho = 22 + 2.25 * R
+    fz = fused_ok(c.H, c.W, c.Cz, c.S)
+    n = 17 if fz else 1 + 4 * chunk_pattern(c.Cz)[1] + int(math.log2(lpr(c.Cz)))
+    return dict(wt=rho, out=rho + 10, dz=rho + 1 + (25 if fz else 9 * c.S * c.S), de=2 * rho + 12 + n,
+                dbias=float(dbias_depth(c.B, c.H, c.W, c.S, c.Cz)))
+
+
+def log_line(text):
+    print(text)
+    try:
+        os.makedirs(os.path.dirname(LOG), exist_ok=True)
+        with open(LOG, "a") as f:
+            f.write(text + "\n")
+    except OSError:
+        pass
+
+
+def worst_ratio(got, ref, A, K):
+    """max over elements of |got - ref| / (u K A) in float64; an element with A = 0 must be met exactly (inf otherwise)."""
+    err = (got.detach().double().cpu() - ref.double()).abs().reshape(-1)
+    bound = (U * K) * A.double().reshape(-1)
+    ratio = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, torch.full_like(err, float("inf")), torch.zeros_like(err)))
+    ratio = torch.where(torch.isnan(err), torch.full_like(err, float("inf")), ratio)
+    k = int(ratio.argmax())
+    return float(ratio[k]), k
+
+
+def within_bounds(c, got, ref, what, keys=None):
+    """Every output of `got` within its per-element bound; the largest err / bound of each is logged."""
+    K = bound_consts(c, ref["R"])
+    bad = []
+    for k in keys or [k for k in ("out", "wt", "de", "dz", "dbias") if k in got]:
+        assert got[k].shape == ref[k].shape, f"{what}.{k}: shape {tuple(got[k].shape)} vs {tuple(ref[k].shape)}"
+        ratio, at = worst_ratio(got[k], ref[k], ref["A_" + k], K[k])
+        log_line(f"carafe_shapes.{what}.{k}: err/bound = {ratio:.3e} (K = {K[k]:.1f}, R = {ref['R']:.1f})")
+        if not ratio <= 1.0:
+            bad.append(f"{k}: element {at}: got {float(got[k].reshape(-1)[at])!r} ref {float(ref[k].reshape(-1)[at])!r} err/bound {ratio:.3e}")
+    assert not bad, f"{what}: " + "; ".join(bad)
+
+
+def within_rtol(got, ref, what, keys):
+    for k in keys:
+        assert bool(torch.isfinite(got[k]).all()), f"{what}.{k} is not finite"
+        err = measure(got[k], ref[k], f"carafe_shapes.{what}.{k}")
+        assert err <= RTOL, f"{what}.{k}: max|diff|/rms = {err:.3e} > {RTOL}"
+
+
+# ------------------------------------------------------------------------------------------------
+# host tests: the tables, the reference, the bound
+# ------------------------------------------------------------------------------------------------
+def test_case_tables_reach_every_branch():
+    """From the transcription alone: the tables hold what each kernel's launch rules distinguish."""
+    tok = [c for c in SMALL + BIG if c.C is None or fused_ok(c.H, c.W, c.Cz, c.S)]
+    generic = [c for c in tok if not fused_ok(c.H, c.W, c.Cz, c.S)]
+    assert {lpr(c.Cz) for c in generic} == {1, 2, 4, 16, 64}
+    pats = {chunk_pattern(c.Cz) for c in generic}
+    assert (1, 1) in pats and (1, 2) in pats and (2, 2) in pats and any(hi > 2 for _, hi in pats)
+    assert {chunk_pattern(cz) for cz in (260, 508)} == {(1, 2)} and chunk_pattern(512) == (2, 2) and chunk_pattern(516) == (2, 3)
+    assert {bias_in_e(c.Cz) for c in generic} == {True, False} and bias_in_e(512) and not bias_in_e(516)
+    assert {fused_ok(c.H, c.W, c.Cz, c.S) for c in tok if (c.S, c.Cz) == (4, 16)} == {True, False}
+    for kernel in ("fwd", "bwd_e", "bwd_z", "colsum"):
+        assert {c.S for c in generic if kernel in launch_plan(c.B, c.H, c.W, c.S, c.Cz)} == {2, 4}, kernel
+    planes = PLANE_FWD + FUSED_PLANES + [c for c in BIG if c.C]
+    assert {c.S for c in planes} == {2, 4}
+    assert any(c.B * c.H * c.W % ppb(c.S) and c.B * c.H * c.W > ppb(c.S) for c in planes)            # a ragged plane block after a full one
+    assert {c.C for c in planes} >= {1, 3, 4, 9, 16} and any(c.C == c.Cz for c in planes) and any(c.C < 4 for c in planes)
+    assert any(c.B * c.H * c.W * c.S * c.S % groups(c.Cz) and c.B * c.H * c.W * c.S * c.S > groups(c.Cz) for c in MAPS)   # items_pad
+    big = {c.tag: c for c in BIG}
+    s = big["stride256"]
+    plan = launch_plan(s.B, s.H, s.W, s.S, s.Cz)
+    assert plan["fwd"] == plan["bwd_e"] == (8192, (4, 5))
+    assert plan["bwd_z"] == (8192, (1, 2)) and cdiv(s.B * s.H * s.W, groups(s.Cz)) == 8281
+    n = big["nchw_stride"]
+    assert plane_plan(n.B, n.H, n.W, n.S) == (8192, (1, 2)) and n.B * n.H * n.W == 131769
+    k = big["colsum_clamp"]
+    assert launch_plan(k.B, k.H, k.W, k.S, k.Cz)["colsum"] == (512, (66, 67)) and k.B * k.H * k.W * 16 == 33856 > 512 * 64
+    for c in SMALL:                                                                                  # and nothing small strides by accident
+        assert all(t[1][1] <= 1 or name == "colsum" for name, t in launch_plan(c.B, c.H, c.W, c.S, c.Cz).items()), c.tag
+    shapes = {(c.B, c.H // TILE, c.W // TILE) for c in FUSED}
+    assert (1, 1, 1) in shapes                                                                       # no halo pixel inside
+    assert any(ty >= 3 and tx >= 3 for _, ty, tx in shapes)                                          # a tile with all of it inside
+    assert any(B > 1 and tx != ty and tx > 1 for B, ty, tx in shapes) and any(B > 1 and tx != ty and ty > 1 for B, ty, tx in shapes)
+    assert {(c.H, c.W) for c in MAPS} >= {(1, 1), (1, 5), (5, 1), (2, 2), (3, 5), (7, 13)}
+    assert [c.Cz for c in CHANNELS if c.S == 2] == [4, 8, 12, 16, 28, 64, 96, 256, 260, 508, 512, 516, 1028]
+    assert len({c.tag for c in SMALL + BIG}) == len(SMALL + BIG)
+    for c in SMALL + BIG:
+        assert workspace_bytes(c.B, c.H, c.W, c.Cz, c.S) > 0
+    wide8_properties()
+
+
+def test_reference_equals_autograd_of_the_closed_form_and_a_plain_loop():
+    """carafe_ref's out / de / dz / dbias against autograd of test_gpu_shapes.carafe_closed_form, and the closed form restricted
+    to C channels and permuted to planes against an explicit loop over output pixels on a 2 x 3 map."""
+    for B, H, W, S, Cz in ((2, 3, 5, 2, 8), (1, 2, 3, 4, 12)):
+        e, z, bias = carafe_problem(B, H, W, S, Cz)
+        dout = det_normal("carafe.selfcheck.dout", (B, S * S * H * W, Cz))
+        er, zr, br = D(e), D(z), D(bias)
+        out = carafe_closed_form(er, zr, br, H, W, S)
+        out.backward(torch.from_numpy(dout).double())
+        r = carafe_ref(e, z, bias, dout, H, W, S)
+        for k, want in (("out", out.detach()), ("de", er.grad), ("dz", zr.grad), ("dbias", br.grad)):
+            assert float((r[k] - want).abs().max()) <= 1e-13 * (1 + float(want.abs().max())), k
+        assert bool((r["A_out"] >= r["out"].abs().float() * (1 - 1e-6)).all()) and bool((r["A_de"] >= r["de"].abs().float() * (1 - 1e-6)).all())
+    B, H, W, S, Cz, C = 2, 2, 3, 2, 8, 3
+    e, z, bias = (torch.from_numpy(a).double() for a in carafe_problem(B, H, W, S, Cz))
+    planes = tokens_to_planes(carafe_closed_form(e, z, bias, H, W, S), C, S * H, S * W)
+    for b in range(B):
+        for c in range(C):
+            for Y in range(S * H):
+                for X in range(S * W):
+                    h, w, s = Y // S, X // S, (Y % S) * S + X % S
+                    logit = torch.stack([e[b, h * W + w, k * S * S + s] for k in range(9)])
+                    p = torch.exp(logit - logit.max())
+                    p = p / p.sum()
+                    acc = bias[c].clone()
+                    for k in range(9):
+                        hh, ww = h + k // 3 - 1, w + k % 3 - 1
+                        if 0 <= hh < H and 0 <= ww < W:
+                            acc = acc + p[k] * z[b, hh * W + ww, c]
+                    assert abs(float(planes[b, c, Y, X] - acc)) <= 1e-13
+
+
+def drop_last_trip(c, ref, which):
+    """The reference with the last grid-stride trip of one kernel left out, placed by the transcribed launch rules."""
+    r = dict(ref)
+    plan = launch_plan(c.B, c.H, c.W, c.S, c.Cz)
+    S2, pixels = c.S * c.S, c.B * c.H * c.W
+    sub_rows = lambda: to_sub(torch.from_numpy(inputs(c.tag)[3]).double(), c.B, c.H, c.W, c.S).reshape(pixels * S2, c.Cz)
+    if which == "dz":
+        nb, (_, most) = plan["bwd_z"]
+        r["dz"] = ref["dz"].clone()
+        r["dz"].view(pixels, c.Cz)[(most - 1) * nb * groups(c.Cz):] = 0
+    elif which == "de":
+        nb, (_, most) = plan["bwd_e"]
+        de = ref["de"].reshape(pixels, 9, S2).permute(0, 2, 1).reshape(pixels * S2, 9).clone()       # rows in item order
+        de[(most - 1) * nb * groups(c.Cz):] = 0
+        r["de"] = de.view(pixels, S2, 9).permute(0, 2, 1).reshape(ref["de"].shape)
+    elif "colsum" in plan:
+        nb, (_, most) = plan["colsum"]
+        rows = torch.from_numpy(inputs(c.tag)[3]).double().reshape(pixels * S2, c.Cz)                # colsum walks dout's own rows
+        r["dbias"] = ref["dbias"] - rows[(most - 1) * nb * (256 // colsum_lanes(c.Cz)):].sum(0)
+    else:
+        nb, (_, most) = plan["bwd_e"]
+        r["dbias"] = ref["dbias"] - sub_rows()[(most - 1) * nb * groups(c.Cz):].sum(0)
+    return r
+
+
+# bug -> (cases meant to see it, outputs it must show in)
+SEEDED = {
+    "clamp_edge": (["map2x1x1.s4", "map2x2x2.s2", "cz64.s2", "fused1x8x8"], ("out", "de")),
+    "tap_swap": (["map2x3x5.s4", "map3x7x13.s2", "fused2x8x16"], ("out", "de", "dz")),
+    "sub_swap": (["map2x3x5.s4", "map2x3x5.s2", "fused1x8x8"], ("out", "dz")),
+    "hw_swap": (["map2x1x5.s4", "map3x7x13.s2", "fused2x8x16", "fused3x16x8"], ("out", "de", "dz")),
+    "drop_chunks": (["cz12.s2", "cz28.s4", "cz96.s2", "cz260.s2", "cz508.s2", "cz516.s4", "cz1028.s2"], ("out", "de", "dz", "dbias")),
+    "tile_edge": (["fused2x8x16", "fused3x16x8", "fused1x24x24", "planes2x24x8.c9"], ("dz",)),
+}
+
+
+def test_bound_sees_the_bugs_these_shapes_are_for():
+    """Each bug is seeded into the float64 REFERENCE; on the cases meant to see it the mutant leaves the per-element bound by a
+    factor of 4 at least, while the float32 evaluation of the same closed form stays inside the bound on every small case."""
+    def ratios(c, got, ref, keys):
+        K = bound_consts(c, ref["R"])
+        return {k: worst_ratio(got[k], ref[k], ref["A_" + k], K[k])[0] for k in keys}
+
+    for c in SMALL:
+        if c.logits in PER_ELEMENT:
+            rr = ratios(c, reference(c.tag, torch.float32), reference(c.tag), ("out", "wt", "de", "dz", "dbias"))
+            assert all(v <= 1.0 for v in rr.values()), (c.tag, rr)
+    for bug, (tags, keys) in SEEDED.items():
+        for tag in tags:
+            c = ALL[tag]
+            rr = ratios(c, reference(tag, torch.float64, bug), reference(tag), keys)
+            assert all(v >= 4.0 for v in rr.values()), (bug, tag, rr)
+    sq = ALL["fused1x8x8"]                                   # H == W: the swapped decode is the same decode
+    assert all(v == 0 for v in ratios(sq, reference(sq.tag, torch.float64, "hw_swap"), reference(sq.tag), ("out", "de", "dz")).values())
+    for tag, which in (("stride256", "dz"), ("stride256", "de"), ("stride256", "dbias"), ("colsum_clamp", "dbias")):
+        c, ref = ALL[tag], reference(tag)
+        assert ratios(c, drop_last_trip(c, ref, which), ref, (which,))[which] >= 4.0, (tag, which)
+    for tag in ("planes2x8x16.c1", "planes2x8x16.c3", "planes2x8x16.c9", "pf.s2.c5", "pf.s4.c1"):       # plane channels >= 4 floor(C / 4) dropped
+        c, ref = ALL[tag], reference(tag)
+        mut = dict(ref, out=ref["out"].clone())
+        mut["out"][:, 4 * (c.C // 4):] = 0
+        assert ratios(c, mut, ref, ("out",))["out"] >= 4.0, tag
+    for tag in ("planes2x8x16.c1", "planes2x8x16.c9", "planes1x24x24.c9"):                              # z[..., C:] leaking into de
+        c, ref = ALL[tag], reference(tag)
+        e, z, bias, dout = inputs(tag)
+        leak = planes_to_tokens(torch.from_numpy(dout), c.Cz)
+        leak[..., c.C:] = leak[..., :c.Cz - c.C].clone()
+        assert float(np.abs(z[..., c.C:]).min()) > 0 and float(np.abs(bias[c.C:]).min()) > 0
+        mut = carafe_ref(e, z, bias, leak, c.H, c.W, c.S)
+        assert ratios(c, mut, ref, ("de",))["de"] >= 4.0, tag
+    for tag in ("wide8.generic", "wide8.fused"):                                                        # de of tap 8 off by 1e-4
+        c, ref = ALL[tag], reference(tag)
+        de = ref["de"].reshape(c.B, c.H * c.W, 9, 16).clone()
+        de[:, :, 8] *= 1 + 1e-4
+        mut = dict(ref, de=de.reshape(ref["de"].shape))
+        assert ratios(c, mut, ref, ("de",))["de"] >= 4.0, tag
+        old = float((mut["de"] - ref["de"]).abs().max()) / float(ref["de"].pow(2).mean().sqrt())
+        print(f"{tag}: the old metric reads {old:.3e}")
+        # max|diff| / rms reads 1e-4 max|de_8| / rms(de): 9.1e-4 on the generic case, which passes RTOL.  On the fused case a
+        # single entry of tap 8 is 10.6 rms large and the reading is 1.06e-3: seen by that one heavy-tail entry alone, by a hair.
+        assert tag != "wide8.generic" or old <= RTOL, f"{tag}: the old metric reads {old:.3e}: it would have seen this"
+
+
+def wide8_properties():
+    """No weight of the wide8 cases underflows (e - max >= -87 everywhere), and de has entries whose own scale A_de is more than
+    12 orders of magnitude below rms(de): max|diff| / rms <= 1e-3 passes any error in them."""
+    for tag in ("wide8.generic", "wide8.fused"):
+        ref = reference(tag)
+        assert ref["R"] <= 87.0, (tag, ref["R"])
+        assert float(ref["A_de"].double().min()) < 1e-12 * float(ref["de"].pow(2).mean().sqrt()), tag
+    assert reference("wide40.generic")["R"] > 104                  # here weights do underflow (2^-150 = e^-104)
+
+
+def test_dbias_bound_is_a_few_dozen_roundings_of_what_was_summed():
+    """The depth the launch rules give is neither zero nor the number of terms: 20 to 300 on every small case (the upper
+    end is Cz = 4, whose 256 one-lane groups of a workgroup are added in sequence)."""
+    for c in SMALL:
+        assert 20 <= dbias_depth(c.B, c.H, c.W, c.S, c.Cz) <= 300, c.tag
+
+
+# ------------------------------------------------------------------------------------------------
+# the device side
+# ------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def hip():
+    if "CSWIN_CARAFE_GENERIC" in os.environ:
+        pytest.skip("CSWIN_CARAFE_GENERIC set: the launch plan these tests rely on does not hold")
+    from cswin_unet_amd import _lib
+
+    class Hip:
+        call, ptr, stream, lib, ReduceJob = staticmethod(_lib.call), staticmethod(_lib.ptr), staticmethod(_lib.stream), staticmethod(_lib.lib), _lib.ReduceJob
+
+        @staticmethod
+        def refused(code, what, bufs, name, *args):
+            got = getattr(_lib.lib(), name)(*args)
+            assert got == code, f"{what}: {name} returned {got}, expected {code}"
+            settle("refused " + what, bufs, untouched=True)
+    return Hip
+
+
+def put(a, off=0):
+    """Device copy of a numpy array / tensor, `off` elements past a 16-byte boundary."""
+    t = torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a.detach().cpu().contiguous()
+    buf = torch.zeros(t.numel() + 16, dtype=t.dtype, device=DEV)
+    v = buf[off:off + t.numel()].view(t.shape)
+    v.copy_(t)
+    assert v.data_ptr() % 16 == off * t.element_size()
+    return v
+
+
+class GuardedAt(Guarded):
+    """Guarded, with the view `off` elements past a 16-byte boundary."""
+
+    def __init__(self, shape, off=0):
+        self.n = math.prod(shape)
+        self.lo = GUARD + off
+        self.buf = torch.full((self.n + 2 * GUARD + 16,), float("nan"), device=DEV)
+        self.t = self.buf[self.lo:self.lo + self.n].view(shape)
+        assert self.t.data_ptr() % 16 == off * 4
+
+    def intact(self):
+        return bool(torch.isnan(self.buf[:self.lo]).all()) and bool(torch.isnan(self.buf[self.lo + self.n:]).all())
+
+
+def fwd_buffers(c, planes):
+    S2 = c.S * c.S
+    return dict(out=Guarded((c.B, c.C, c.S * c.H, c.S * c.W) if planes else (c.B, S2 * c.H * c.W, c.Cz)), wt=Guarded((c.B, c.H * c.W, 9 * S2)))
+
+
+def bwd_buffers(hip, c):
+    nbytes = hip.lib().cswin_carafe_bwd_workspace(c.B, c.H, c.W, c.Cz, c.S)
+    assert nbytes == workspace_bytes(c.B, c.H, c.W, c.Cz, c.S), "the transcribed launch rules no longer follow csrc/carafe.hip"
+    return dict(de=Guarded((c.B, c.H * c.W, 9 * c.S * c.S)), dz=Guarded((c.B, c.H * c.W, c.Cz)), dbias=Guarded((c.Cz,)), workspace=Guarded((nbytes // 4,))), nbytes
+
+
+def forward(hip, c, e, z, bias, what, planes=False, wt=True):
+    """cswin_carafe_fwd / _fwd_nchw on guarded buffers; {out, wt} as device tensors."""
+    o = fwd_buffers(c, planes)
+    if not wt:
+        del o["wt"]
+    args = (hip.ptr(e), hip.ptr(z), hip.ptr(bias), hip.ptr(o["out"].t), hip.ptr(o["wt"].t) if wt else None, c.B, c.H, c.W, c.Cz)
+    if planes:
+        hip.call("cswin_carafe_fwd_nchw", *args, c.C, c.S, hip.stream())
+    else:
+        hip.call("cswin_carafe_fwd", *args, c.S, hip.stream())
+    settle(what + ".fwd", o)
+    return {k: g.t for k, g in o.items()}
+
+
+def backward(hip, c, dout, z, wt, what, planes=False, dbias=True, job=None):
+    """cswin_carafe_bwd / _bwd_nchw on guarded buffers and an exact workspace; {de, dz, dbias} as device tensors."""
+    o, nbytes = bwd_buffers(hip, c)
+    if not dbias:
+        del o["dbias"], o["workspace"]
+    args = (hip.ptr(dout), hip.ptr(z), hip.ptr(wt), hip.ptr(o["de"].t), hip.ptr(o["dz"].t), hip.ptr(o["dbias"].t) if dbias else None,
+            hip.ptr(o["workspace"].t) if dbias else None, nbytes if dbias else 0, c.B, c.H, c.W, c.Cz)
+    if planes:
+        hip.call("cswin_carafe_bwd_nchw", *args, c.C, c.S, job, hip.stream())
+    else:
+        hip.call("cswin_carafe_bwd", *args, c.S, job, hip.stream())
+    if job is None:
+        settle(what + ".bwd", o)
+    return {k: g.t for k, g in o.items() if k != "workspace"}
+
+
+def run_case(hip, c, what=None, backward_too=True):
+    """Forward and backward of a case in the form its table asks for (planes where C is set and the plane backward exists,
+    the plane forward alone otherwise); the device tensors, and the inputs that must outlive the launches."""
+    what = what or c.tag
+    e, z, bias, dout = (put(a) for a in inputs(c.tag))
+    planes = c.C is not None
+    got = forward(hip, c, e, z, bias, what, planes)
+    if backward_too and (not planes or fused_ok(c.H, c.W, c.Cz, c.S)):
+        got.update(backward(hip, c, dout, z, got["wt"], what, planes))
+    torch.cuda.synchronize()
+    return {k: v.cpu() for k, v in got.items()}
+
+
+def judge(c, got, what=None):
+    ref = reference(c.tag)
+    what = what or c.tag
+    if c.logits in PER_ELEMENT:
+        within_bounds(c, got, ref, what)
+    else:
+        within_rtol(got, ref, what, [k for k in ("out", "de", "dz", "dbias") if k in got])
+
+
+ids = lambda c: c.tag
+
+
+@gpu
+@pytest.mark.parametrize("c", CHANNELS, ids=ids)
+def test_channel_classes(hip, c):
+    judge(c, run_case(hip, c))
+
+
+@gpu
+@pytest.mark.parametrize("c", MAPS, ids=ids)
+def test_map_classes(hip, c):
+    judge(c, run_case(hip, c))
+
+
+@gpu
+@pytest.mark.parametrize("c", FUSED, ids=ids)
+def test_fused_backward_token_form(hip, c):
+    judge(c, run_case(hip, c))
+
+
+@gpu
+@pytest.mark.parametrize("c", FUSED_PLANES, ids=ids)
+def test_fused_backward_plane_form(hip, c):
+    """z[..., C:] and bias[C:] are NOT zero here: de must still be that of the first C channels alone, and dz[..., C:] and
+    dbias[C:] exactly zero (their A is zero, so the bound asks for it; said once more in words below)."""
+    e, z, bias, _ = inputs(c.tag)
+    assert c.C == c.Cz or (float(np.abs(z[..., c.C:]).min()) > 0 and float(np.abs(bias[c.C:]).min()) > 0)
+    got = run_case(hip, c)
+    judge(c, got)
+    assert bool((got["dz"][..., c.C:] == 0).all()) and bool((got["dbias"][c.C:] == 0).all())
+
+
+@gpu
+@pytest.mark.parametrize("c", PLANE_FWD, ids=ids)
+def test_plane_forward_outside_the_fused_shape(hip, c):
+    """The plane kernel through the C API, then ops.carafe_reassemble_nchw (tokens plus adapter where no plane backward exists)
+    forward and backward against the same reference."""
+    from cswin_unet_amd import ops
+    assert not fused_ok(c.H, c.W, c.Cz, c.S)
+    judge(c, run_case(hip, c))
+    e, z, bias, dout = inputs(c.tag)
+    ed, zd, bd = (put(a).requires_grad_() for a in (e, z, bias))
+    out = ops.carafe_reassemble_nchw(ed, zd, bd, c.H, c.W, c.S, c.C)
+    out.backward(put(dout))
+    judge(c, dict(out=out.detach().cpu(), de=ed.grad.cpu(), dz=zd.grad.cpu(), dbias=bd.grad.cpu()), c.tag + ".ops")
+
+
+@gpu
+@pytest.mark.parametrize("c", LOGITS, ids=ids)
+def test_logit_classes(hip, c):
+    got = run_case(hip, c)
+    judge(c, got)
+    if c.logits == "equal":
+        assert bool((got["wt"] == np.float32(1.0) / np.float32(9.0)).all()), "nine equal logits must give fl(1/9) exactly"
+
+
+@gpu
+@pytest.mark.parametrize("c,b,y,x", DELTAS, ids=lambda v: v.tag if isinstance(v, Case) else None)
+def test_delta_gradient_stays_where_it_belongs(hip, c, b, y, x):
+    """dout is non-zero at one hi-res pixel: dz is EXACTLY zero outside the 3 x 3 low-res neighbourhood, de outside that pixel's
+    own sub-pixel column, and dbias is that row of dout."""
+    got = run_case(hip, c)
+    judge(c, got)
+    h, w, s = y // c.S, x // c.S, (y % c.S) * c.S + x % c.S
+    near = torch.zeros(c.B, c.H, c.W, dtype=torch.bool)
+    near[b, max(h - 1, 0):h + 2, max(w - 1, 0):w + 2] = True
+    dz = got["dz"].view(c.B, c.H, c.W, c.Cz)
+    assert bool((dz[~near] == 0).all()) and bool((dz[near] != 0).all())
+    own = torch.zeros(c.B, c.H * c.W, 9, c.S * c.S, dtype=torch.bool)
+    own[b, h * c.W + w, :, s] = True
+    assert bool((got["de"].view(own.shape)[~own] == 0).all()) and bool((got["de"].view(own.shape)[own] != 0).any())
+    assert torch.equal(got["dbias"], torch.from_numpy(inputs(c.tag)[3][b, y * c.S * c.W + x]))
+
+
+@gpu
+@pytest.mark.parametrize("c", BIG, ids=ids)
+def test_past_the_grid_clamps(hip, c):
+    """Every grid-stride loop on its second (fifth, 67th) trip, the last one ragged."""
+    got = run_case(hip, c, backward_too=c.tag != "nchw_stride")
+    judge(c, got)
+
+
+# ---- bit equality -----------------------------------------------------------------------------------------------------------
+BITS_PLANES = PLANE_FWD + [ALL["planes2x8x16.c3"], ALL["planes2x8x16.c9"], ALL["planes2x8x16.c16"], ALL["planes1x24x24.c9"]]
+
+
+@gpu
+@pytest.mark.parametrize("c", BITS_PLANES, ids=ids)
+def test_plane_forward_has_the_token_forward_s_bits(hip, c):
+    """include/cswin_hip.h: "Same bits as the token forms followed by those adapters"."""
+    e, z, bias, _ = (put(a) for a in inputs(c.tag))
+    tok, pl = forward(hip, c, e, z, bias, c.tag + ".tokens"), forward(hip, c, e, z, bias, c.tag + ".planes", planes=True)
+    adapted = Guarded((c.B, c.C, c.S * c.H, c.S * c.W))
+    hip.call("cswin_tokens_to_nchw", hip.ptr(tok["out"]), hip.ptr(adapted.t), c.B, c.C, c.S * c.H, c.S * c.W, c.Cz, hip.stream())
+    settle(c.tag + ".adapter", dict(out=adapted))
+    assert torch.equal(pl["out"], adapted.t) and torch.equal(pl["wt"], tok["wt"])
+
+
+@gpu
+@pytest.mark.parametrize("tag", ["planes2x8x16.c1", "planes2x8x16.c9", "planes2x8x16.c16", "planes3x16x8.c9", "planes1x24x24.c9"])
+def test_plane_backward_has_the_token_backward_s_bits(hip, tag):
+    """cswin_carafe_bwd_nchw == cswin_carafe_bwd on the same gradient laid out as tokens with channels >= C zero."""
+    c = ALL[tag]
+    e, z, bias, dout = inputs(tag)
+    ed, zd, bd, pd, td = put(e), put(z), put(bias), put(dout), put(token_dout(c, dout))
+    wt = forward(hip, c, ed, zd, bd, tag)["wt"]
+    a, b = backward(hip, c, pd, zd, wt, tag + ".planes", planes=True), backward(hip, c, td, zd, wt, tag + ".tokens")
+    for k in ("de", "dz", "dbias"):
+        assert torch.equal(a[k], b[k]), f"{tag}.{k}: max|diff| {float((a[k] - b[k]).abs().max()):.3e}"
+
+
+@gpu
+@pytest.mark.parametrize("tag", ["cz12.s2", "cz516.s4", "map3x7x13.s4", "fused2x8x16", "pf.s2.c5"])
+def test_optional_arguments_change_nothing_else(hip, tag):
+    """wt_save == NULL leaves out unchanged, bias == NULL is a zero bias, dbias == NULL (no workspace at all) leaves de and dz
+    unchanged, and a second run gives the same bits."""
+    c = ALL[tag]
+    e, z, bias, dout = inputs(tag)
+    ed, zd, bd, zero = put(e), put(z), put(bias), put(np.zeros_like(bias))
+    planes = c.C is not None
+    full = forward(hip, c, ed, zd, bd, tag, planes)
+    again = forward(hip, c, ed, zd, bd, tag + ".again", planes)
+    assert torch.equal(full["out"], again["out"]) and torch.equal(full["wt"], again["wt"])
+    assert torch.equal(forward(hip, c, ed, zd, bd, tag + ".nowt", planes, wt=False)["out"], full["out"])
+    assert torch.equal(forward(hip, c, ed, zd, None, tag + ".nobias", planes)["out"], forward(hip, c, ed, zd, zero, tag + ".zerobias", planes)["out"])
+    if planes:
+        return
+    gd = put(dout)
+    b1, b2 = backward(hip, c, gd, zd, full["wt"], tag), backward(hip, c, gd, zd, full["wt"], tag + ".again")
+    b3 = backward(hip, c, gd, zd, full["wt"], tag + ".nodbias", dbias=False)
+    for k in ("de", "dz", "dbias"):
+        assert torch.equal(b1[k], b2[k]), k
+    assert torch.equal(b1["de"], b3["de"]) and torch.equal(b1["dz"], b3["dz"])
+
+
+# ---- refusals ---------------------------------------------------------------------------------------------------------------
+def _refusal_kit(hip, c):
+    e, z, bias, dout = (put(a) for a in inputs(c.tag))
+    wt = put(reference(c.tag)["wt"].float())
+    o = fwd_buffers(c, False)
+    ob, nbytes = bwd_buffers(hip, c)
+    o.update(ob)
+    o["planes"] = Guarded((c.B, c.Cz, c.S * c.H, c.S * c.W))
+    return e, z, bias, dout, wt, o, nbytes
+
+
+@gpu
+def test_carafe_refusals_touch_nothing(hip):
+    c = ALL["map2x3x5.s4"]
+    B, H, W, S, Cz = c.B, c.H, c.W, c.S, c.Cz
+    e, z, bias, dout, wt, o, nbytes = _refusal_kit(hip, c)
+    p, st = hip.ptr, hip.stream()
+    out, wts, de, dz, db, ws, pl = (o[k].t for k in ("out", "wt", "de", "dz", "dbias", "workspace", "planes"))
+
+    def fwd(what, code, e_=e, z_=z, out_=out, B=B, H=H, W=W, Cz=Cz, S=S):
+        hip.refused(code, "fwd " + what, o, "cswin_carafe_fwd", p(e_), p(z_), p(bias), p(out_), p(wts), B, H, W, Cz, S, st)
+
+    def fwdp(what, code, e_=e, z_=z, out_=pl, B=B, H=H, W=W, Cz=Cz, C=9, S=S):
+        hip.refused(code, "fwd_nchw " + what, o, "cswin_carafe_fwd_nchw", p(e_), p(z_), p(bias), p(out_), p(wts), B, H, W, Cz, C, S, st)
+
+    def bwd(what, code, g=dout, z_=z, wt_=wt, de_=de, dz_=dz, db_=db, ws_=ws, nb=nbytes, B=B, H=H, W=W, Cz=Cz, S=S, job=None):
+        hip.refused(code, "bwd " + what, o, "cswin_carafe_bwd", p(g), p(z_), p(wt_), p(de_), p(dz_), p(db_), p(ws_), nb, B, H, W, Cz, S, job, st)
+
+    for what, kw in (("S=3", dict(S=3)), ("Cz=6", dict(Cz=6)), ("Cz=0", dict(Cz=0)), ("B=0", dict(B=0)), ("H=0", dict(H=0))):
+        fwd(what, ERR_UNSUPPORTED, **kw)
+        fwdp(what, ERR_UNSUPPORTED, **kw)
+        bwd(what, ERR_UNSUPPORTED, **kw)
+    fwdp("C=0", ERR_UNSUPPORTED, C=0)
+    fwdp("C=Cz+4", ERR_UNSUPPORTED, C=Cz + 4)
+    for name in ("e_", "z_", "out_"):
+        fwd("null " + name, ERR_SHAPE, **{name: None})
+        fwdp("null " + name, ERR_SHAPE, **{name: None})
+    for name in ("g", "z_", "wt_", "de_", "dz_"):
+        bwd("null " + name, ERR_SHAPE, **{name: None})
+    bwd("workspace one byte short", ERR_WORKSPACE, nb=nbytes - 1)
+    bwd("null workspace", ERR_WORKSPACE, ws_=None)
+    job = (hip.ReduceJob * 1)()
+    ctypes.memset(job, 0xFF, ctypes.sizeof(job))
+    bwd("S=3 with a job", ERR_UNSUPPORTED, S=3, job=ctypes.cast(job, ctypes.c_void_p))
+    assert bytes(job) == bytes(ctypes.sizeof(job)), "a refused call given `deferred` must leave a zeroed job"
+
+
+@gpu
+def test_carafe_plane_backward_refusals_touch_nothing(hip):
+    c = ALL["planes2x8x16.c9"]
+    B, H, W, S, Cz, C = c.B, c.H, c.W, c.S, c.Cz, c.C
+    e, z, bias, dout, wt, o, nbytes = _refusal_kit(hip, c)
+    p, st = hip.ptr, hip.stream()
+    de, dz, db, ws = (o[k].t for k in ("de", "dz", "dbias", "workspace"))
+
+    def bwdp(what, code, g=dout, z_=z, wt_=wt, de_=de, dz_=dz, ws_=ws, nb=nbytes, B=B, H=H, W=W, Cz=Cz, C=C, S=S, job=None):
+        hip.refused(code, "bwd_nchw " + what, o, "cswin_carafe_bwd_nchw", p(g), p(z_), p(wt_), p(de_), p(dz_), p(db), p(ws_), nb, B, H, W, Cz, C, S, job, st)
+
+    for what, kw in (("H=12", dict(H=12)), ("Cz=32", dict(Cz=32)), ("S=2", dict(S=2)), ("C=0", dict(C=0)), ("C=Cz+4", dict(C=Cz + 4)), ("B=0", dict(B=0))):
+        bwdp(what, ERR_UNSUPPORTED, **kw)
+    for name in ("g", "z_", "wt_", "de_", "dz_"):
+        bwdp("null " + name, ERR_SHAPE, **{name: None})
+    bwdp("workspace one byte short", ERR_WORKSPACE, nb=nbytes - 1)
+    bwdp("null workspace", ERR_WORKSPACE, ws_=None)
+    job = (hip.ReduceJob * 1)()
+    ctypes.memset(job, 0xFF, ctypes.sizeof(job))
+    bwdp("H=12 with a job", ERR_UNSUPPORTED, H=12, job=ctypes.cast(job, ctypes.c_void_p))
+    assert bytes(job) == bytes(ctypes.sizeof(job)), "a refused call given `deferred` must leave a zeroed job"
+    for Hh in (8, 12, 16):
+        for Ww in (8, 20, 24):
+            for Czz in (16, 32):
+                for Ss in (2, 4):
+                    assert hip.lib().cswin_carafe_bwd_nchw_ok(Hh, Ww, Czz, Ss) == int(fused_ok(Hh, Ww, Czz, Ss)), (Hh, Ww, Czz, Ss)
+
+
+@gpu
+def test_carafe_refuses_misaligned_buffers(hip):
+    """Every pointer an entry point reads or writes 16 bytes at a time, 4 bytes off a 16-byte boundary: CSWIN_ERR_ALIGN before
+    any launch.  e, wt_save and de are scalar accesses and may sit anywhere."""
+    c = ALL["planes2x8x16.c9"]
+    B, H, W, S, Cz, C = c.B, c.H, c.W, c.S, c.Cz, c.C
+    e, z, bias, dout, wt, o, nbytes = _refusal_kit(hip, c)
+    tdout = put(token_dout(c, inputs(c.tag)[3]))
+    off = dict(z=put(inputs(c.tag)[1], 1), bias=put(inputs(c.tag)[2], 1), dout=put(inputs(c.tag)[3], 1), tdout=put(token_dout(c, inputs(c.tag)[3]), 1))
+    o["out1"], o["dz1"] = GuardedAt(tuple(o["out"].t.shape), off=1), GuardedAt(tuple(o["dz"].t.shape), off=1)
+    p, st = hip.ptr, hip.stream()
+    out, wts, de, dz, db, ws, pl = (o[k].t for k in ("out", "wt", "de", "dz", "dbias", "workspace", "planes"))
+    for what, z_, b_, out_ in (("z", off["z"], bias, out), ("bias", z, off["bias"], out), ("out", z, bias, o["out1"].t)):
+        hip.refused(ERR_ALIGN, f"fwd {what} 4 bytes off", o, "cswin_carafe_fwd", p(e), p(z_), p(b_), p(out_), p(wts), B, H, W, Cz, S, st)
+    for what, z_, b_ in (("z", off["z"], bias), ("bias", z, off["bias"])):
+        hip.refused(ERR_ALIGN, f"fwd_nchw {what} 4 bytes off", o, "cswin_carafe_fwd_nchw", p(e), p(z_), p(b_), p(pl), p(wts), B, H, W, Cz, C, S, st)
+    for what, g, z_, dz_ in (("dout", off["tdout"], z, dz), ("z", tdout, off["z"], dz), ("dz", tdout, z, o["dz1"].t)):
+        hip.refused(ERR_ALIGN, f"bwd {what} 4 bytes off", o, "cswin_carafe_bwd", p(g), p(z_), p(wt), p(de), p(dz_), p(db), p(ws), nbytes, B, H, W, Cz, S, None, st)
+    for what, g, z_, dz_ in (("dout", off["dout"], z, dz), ("z", dout, off["z"], dz), ("dz", dout, z, o["dz1"].t)):
+        hip.refused(ERR_ALIGN, f"bwd_nchw {what} 4 bytes off", o, "cswin_carafe_bwd_nchw", p(g), p(z_), p(wt), p(de), p(dz_), p(db), p(ws), nbytes, B, H, W, Cz, C, S, None, st)
