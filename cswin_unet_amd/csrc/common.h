@@ -56,6 +56,14 @@ __device__ __forceinline__ int fdiv1(int n, unsigned m) { return m ? fdiv(n, m) 
 static inline unsigned fdiv_magic(int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); }
 static inline bool fdiv_exact(long nmax, long d) { return d >= 1 && nmax >= 0 && (d == 1 || nmax * d < (1L << 32)); }
 
+// XCD-aware block order: workgroups are dealt round-robin over the 8 XCDs (private L2 each), so give every XCD a CONTIGUOUS
+// range of the nblk logical blocks: blocks that re-read the same operand panel then share one L2 instead of fetching it eight
+// times.  Returns the logical block of workgroup bid.
+__device__ __forceinline__ int xcd_block_order(int bid, int nblk) {
+    const int xq = nblk >> 3, xr = nblk & 7, xcd = bid & 7;
+    return (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (bid >> 3);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

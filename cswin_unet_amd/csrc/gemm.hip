@@ -61,26 +61,32 @@ struct PlainSrc {
     __device__ const float* ptr(const Row& r, int j) const { return (r.base && j < cols) ? r.base + j : nullptr; }
 };
 
-// bf16 STORAGE of an operand (activations of the bf16 mode): only plain matrices; every source computes addresses in elements,
-// so the element offset of the fp32-typed pointer is re-applied to the bf16 base.
-template <class S> __device__ __forceinline__ bool src_is_bf16(const S&) { return false; }
-__device__ __forceinline__ bool src_is_bf16(const PlainSrc& s) { return s.bf16 != 0; }
-// 4 bf16 as two raw dwords (an INTEGER vector: see widen_bf16x4); they go to the LDS image as they are (stash below)
-template <class S> __device__ __forceinline__ u32x2 src_load4_bf16(const S&, const float*) { return u32x2{0u, 0u}; }
-__device__ __forceinline__ u32x2 src_load4_bf16(const PlainSrc& s, const float* p) {
-    return *reinterpret_cast<const u32x2*>(reinterpret_cast<const __bf16*>(s.p) + (p - s.p));
+// What only a plain matrix has: bf16 storage, a sample mask, a row scale.  For every other source these compile to nothing.
+template <class S> constexpr bool is_plain = std::is_same<S, PlainSrc>::value;
+// bf16 STORAGE of an operand (activations of the bf16 mode): every source computes addresses in elements, so the element offset
+// of the fp32-typed pointer is re-applied to the bf16 base.
+template <class S> __device__ __forceinline__ bool src_is_bf16(const S& s) {
+    if constexpr (is_plain<S>) return s.bf16 != 0;
+    else return false;
 }
-// a sample-masked reduction (RowMask below) maps its own rows: row < 0 = past the end, s = the row's DropPath factor.  Only plain
-// matrices are masked; the generic forms exist so that every source compiles.
-template <class S> __device__ __forceinline__ typename S::Row src_mapped_row(const S&, int, float) { return typename S::Row{}; }
-__device__ __forceinline__ PlainSrc::Row src_mapped_row(const PlainSrc& s, int row, float f) {
-    PlainSrc::Row r;
-    r.base = row >= 0 ? s.p + (long)row * s.ld : nullptr;
-    r.s = f;
+// 4 bf16 as two raw dwords (an INTEGER vector: see widen_bf16x4); they go to the LDS image as they are (chunk_bf16 below)
+template <class S> __device__ __forceinline__ u32x2 src_load4_bf16(const S& s, const float* p) {
+    if constexpr (is_plain<S>) return *reinterpret_cast<const u32x2*>(reinterpret_cast<const __bf16*>(s.p) + (p - s.p));
+    else return u32x2{0u, 0u};
+}
+// a sample-masked reduction (RowMask below) maps its own rows: row < 0 = past the end, f = the row's DropPath factor
+template <class S> __device__ __forceinline__ typename S::Row src_mapped_row(const S& s, int row, float f) {
+    typename S::Row r{};
+    if constexpr (is_plain<S>) {
+        r.base = row >= 0 ? s.p + (long)row * s.ld : nullptr;
+        r.s = f;
+    }
     return r;
 }
-template <class S> __device__ __forceinline__ const float* src_row_scale(const S&) { return nullptr; }
-__device__ __forceinline__ const float* src_row_scale(const PlainSrc& s) { return s.row_scale; }
+template <class S> __device__ __forceinline__ const float* src_row_scale(const S& s) {
+    if constexpr (is_plain<S>) return s.row_scale;
+    else return nullptr;
+}
 
 // cat([p0 (c0 cols), p1 (cols - c0)], dim=-1) without materialising it (skip-concat, cswin_unet.py:509-510)
 struct ConcatSrc {
@@ -248,26 +254,89 @@ struct TapRowsSrcT {
     __device__ const float* ptr(const Row& r, int j) const { return (r.base && j < cols) ? r.base + j : nullptr; }
 };
 
-// ------------------------------------------------------------------------------------
-// the kernel
-// ------------------------------------------------------------------------------------
-// SCALE_A: multiply the A operand rows by their Row::s (DropPath factor) when staging (weight gradients only)
-// KW: wave groups that split each reduction tile between them (workgroup = 4*KW waves; group g multiplies the k-slice
-// [g*BK/KW, (g+1)*BK/KW) of every tile, the groups' accumulators are summed through LDS at the end).  When M*N is too
-// small to give every SIMD >= 2 independent MFMA chains (stage-3/4 shapes with long K) this doubles / quadruples the
-// resident waves per workgroup without a global split-K reduction.
-// floats of LDS one tile configuration needs (operand images, or the waves' epilogue patches if those are larger).  The kernels own
-// the buffer and hand it to gemm_body, so that a launch which mixes two configurations (gemm_block_tail_kernel) holds ONE buffer
-// of the larger size instead of two static arrays.
-template <int BM, int BN, int BK, int KW, bool A_RC, bool B_RC>
-constexpr int gemm_lds_floats() {
-    constexpr int NW = (BM >= 64 ? 2 : 1) * (BN >= 64 ? 2 : 1);
-    constexpr int LDR = BK + 4;
-    constexpr int A_ELEMS = A_RC ? BM * LDR : BK * (BM + 4);
-    constexpr int B_ELEMS = B_RC ? BN * LDR : BK * (BN + 4);
-    return (A_ELEMS + B_ELEMS) > NW * EP_WAVE_FLOATS ? (A_ELEMS + B_ELEMS) : NW * EP_WAVE_FLOATS;
-}
+// ---- tile geometry ----
+// One operand's share of a tile: ROWS output rows x BK reduction values, staged by NTH threads in 16-byte chunks.
+// RC: the source is r-contiguous; its fp32 image is [row][r] with 16-B padded rows (conflict-free b128 reads), else [r][row].
+template <int ROWS, int BK, bool RC_, int NTH>
+struct OperandTile {
+    static constexpr bool RC = RC_;
+    static constexpr int LD = RC ? BK + 4 : ROWS + 4;        // leading dimension of the fp32 image
+    static constexpr int ELEMS = (RC ? ROWS : BK) * LD;      // its floats
+    static constexpr int Q = ROWS * BK / (4 * NTH);          // chunks per thread per tile
+    static constexpr int CPR = RC ? BK / 4 : ROWS / 4;       // chunks per source row
+    static constexpr int RPP = NTH / CPR;                    // source rows per pass of the workgroup
+    static_assert(Q >= 1, "tile too small for this many wave groups");
+};
 
+// One tile configuration.  Waves of one k-group: 2 x 2 for 64 x 64 tiles, 2 x 1 for 64 x 32 (for launches whose 64 x 64 tile count
+// is a poor multiple of the 256 CUs).  KW: wave groups that split each reduction tile between them (group g multiplies the k-slice
+// [g*BK/KW, (g+1)*BK/KW), the accumulators are summed through LDS at the end): more resident waves per workgroup where M*N is too
+// small to give every SIMD >= 2 independent MFMA chains, without a global split-K reduction.  LDS_FLOATS: the operand images, or the
+// waves' epilogue patches if larger; the kernels own the buffer, so a launch that mixes two configurations holds ONE of the larger.
+template <int BM_, int BN_, int BK_, int KW_, bool A_RC, bool B_RC>
+struct Tile {
+    static constexpr int BM = BM_, BN = BN_, BK = BK_, KW = KW_;
+    static constexpr int WGM = BM >= 64 ? 2 : 1, WGN = BN >= 64 ? 2 : 1, NW = WGM * WGN;   // wave grid of a k-group
+    static constexpr int WM = BM / WGM, WN = BN / WGN;                                      // a wave's share of the tile
+    static constexpr int FM = WM / 32, FN = WN / 32;                                        // 32x32 fragments per wave
+    static constexpr int THREADS = 64 * NW * KW;
+    typedef OperandTile<BM, BK, A_RC, THREADS> A;
+    typedef OperandTile<BN, BK, B_RC, THREADS> B;
+    // PREC == 1: both operands as [row][r] bf16 images (r-contiguous: one ds_read_b128 = the 8 k-values of a lane)
+    static constexpr int LD16 = BK + 8;              // in bf16 elements: 16-B aligned rows, 36-dword stride at BK = 64
+    static constexpr int PATCH = FM * FN * 16 * 64;  // a wave's accumulators, as the k-group reduction lays them out
+    static constexpr int LDS_FLOATS = A::ELEMS + B::ELEMS > NW * EP_WAVE_FLOATS ? A::ELEMS + B::ELEMS : NW * EP_WAVE_FLOATS;
+    static_assert((BK / KW) % 8 == 0, "tile too small for this many wave groups");
+    static_assert(KW == 1 || (KW / 2) * NW * PATCH <= LDS_FLOATS, "LDS too small for the k-group reduction");
+};
+
+// ---- registers -> LDS image (stash); global -> registers (fetch) is written out in gemm_body ----
+// the 4 values of a chunk as they go to a bf16 image, two packed dwords (plain integers: hipcc 7.2 miscompiles element extraction
+// from a bf16 vector that is merged from two branches -- all four stores received element 0).  Stored as bf16: the bits go to the
+// image unchanged, unless a row factor s applies.
+template <bool S16, bool SCALED> __device__ __forceinline__ u32x2 chunk_bf16(const f32x4& v, const u32x2& raw, float s) {
+    if constexpr (S16 && !SCALED) return raw;
+    else if constexpr (S16) return __builtin_bit_cast(u32x2, __builtin_convertvector(widen_bf16x4(raw) * s, bf16x4));
+    else if constexpr (SCALED) return __builtin_bit_cast(u32x2, __builtin_convertvector(v * s, bf16x4));
+    else return __builtin_bit_cast(u32x2, __builtin_convertvector(v, bf16x4));
+}
+// A from a row(m)-contiguous source: transpose chunk c of reduction row `row` into the [m][r] bf16 image, four 16-bit stores
+template <int LD16> __device__ __forceinline__ void store_a_transposed(unsigned short* img16, int c, int row, u32x2 h) {
+    unsigned short* col = &img16[4 * c * LD16 + row];
+    col[0] = (unsigned short)(h[0] & 0xffffu);
+    col[LD16] = (unsigned short)(h[0] >> 16);
+    col[2 * LD16] = (unsigned short)(h[1] & 0xffffu);
+    col[3 * LD16] = (unsigned short)(h[1] >> 16);
+}
+// B whose source rows run along the REDUCTION index (data gradient: W[r][k]): keep them as they arrive, [r][BN] bf16 rows of
+// 128 B, and let ds_read_b64_tr_b16 do the transpose when the fragments are read (main loop).  16-B chunks are XOR-swizzled with
+// bit 1 of the row so that the 4-row x 16-column transposed reads of a 32-lane half fall into 64 distinct banks.
+template <int BN> __device__ __forceinline__ void store_b_swizzled(unsigned short* img16, int c, int row, u32x2 h) {
+    static_assert(BN == 64, "transposed-read B image is laid out for 64-column tiles");
+    *reinterpret_cast<u32x2*>(&img16[row * BN + 8 * ((c >> 1) ^ (((row >> 1) & 1) << 2)) + 4 * (c & 1)]) = h;
+}
+// One operand's fetched chunks into its LDS image: the fp32 image (PREC 0), or the bf16 image (PREC 1): [row][r] for an
+// r-contiguous operand, else A's transposed and B's swizzled one.  p16 / ps are not touched unless S16 / SCALED (B passes no ps).
+template <class G, bool IS_A, int PREC, bool S16, bool SCALED, int LD16, int BN>
+__device__ __forceinline__ void stash_operand(float* img, unsigned short* img16, int c, int r, const f32x4* p, const u32x2* p16, const float* ps) {
+#pragma unroll
+    for (int q = 0; q < G::Q; ++q) {
+        const int row = r + q * G::RPP;
+        float s = 1.0f;
+        if constexpr (SCALED) s = ps[q];
+        if constexpr (PREC == 1) {
+            const u32x2 h = chunk_bf16<S16, SCALED>(p[q], p16[q], s);
+            if constexpr (G::RC) *reinterpret_cast<u32x2*>(&img16[row * LD16 + 4 * c]) = h;
+            else if constexpr (IS_A) store_a_transposed<LD16>(img16, c, row, h);
+            else store_b_swizzled<BN>(img16, c, row, h);
+        } else {
+            f32x4 v = p[q];
+            if constexpr (SCALED) v *= s;
+            *reinterpret_cast<f32x4*>(&img[row * G::LD + 4 * c]) = v;
+        }
+    }
+}
+// ---- the kernel ----
 // A weight gradient's sample mask (DropPath: a dropped sample's rows of row_scale . dy are exact zeros).  skip: nsamples per-sample
 // floats, 0 = the sample adds nothing; its rows_per_sample rows of BOTH operands are then not read.  The workgroup reduces over the
 // compacted index c in [0, nk * rows_per_sample) of the nk kept samples, shared out over the host's `splits` slabs:
@@ -277,94 +346,84 @@ constexpr int MASK_MAX_SAMPLES = 256;
 // the ascending list of kept samples and their DropPath factors (1 without row_scale), in LDS beside the operand images
 struct KeptList { int n; int idx[MASK_MAX_SAMPLES]; float scale[MASK_MAX_SAMPLES]; };
 
-// MASKED (weight gradients of plain matrices only): the reduction runs over the kept samples' rows (RowMask); a compile-time
-// variant, the unmasked form is untouched by it
-template <int BM, int BN, int BK, int KW, bool A_RC, bool B_RC, int VEC, int EPI, bool SCALE_A, int PREC, class ASrc, class BSrc,
-          bool MASKED = false>
+// The first wave lists the kept samples in ascending order (ballot + popcount); every workgroup builds the same list (gemm_body)
+__device__ __forceinline__ void build_kept_list(KeptList* kept, const RowMask& mk, const float* row_scale) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    if (tid >= 64) return;
+    int n = 0;
+    for (int s0 = 0; s0 < mk.nsamples; s0 += 64) {
+        const int s = s0 + lane;
+        const bool keep = s < mk.nsamples && mk.skip[s] != 0.0f;
+        const unsigned long long bal = __ballot(keep);
+        if (keep) {
+            const int at = n + __popcll(bal & ((1ull << lane) - 1ull));
+            kept->idx[at] = s;
+            kept->scale[at] = row_scale ? row_scale[s] : 1.0f;
+        }
+        n += __popcll(bal);
+    }
+    if (tid == 0) kept->n = n;
+}
+
+// debug stamps: thread 0 writes s_memtime to `slot` of the workgroup's row; slot 0 also the hardware id and s_memrealtime, slot 3 the latter
+__device__ __forceinline__ void stamp(const Epilogue& epi, int row, int slot) {
+    if (!epi.stamps || threadIdx.x != 0) return;
+    long long* s = epi.stamps + 8L * row;
+    s[slot] = __builtin_amdgcn_s_memtime();
+    if (slot == 0) { s[4] = __builtin_amdgcn_s_getreg(6164); s[5] = __builtin_amdgcn_s_memrealtime(); }
+    if (slot == 3) s[6] = __builtin_amdgcn_s_memrealtime();
+}
+
+// T: the tile configuration.  SCALE_A: multiply the A rows by their Row::s (DropPath factor) when staging (weight gradients only).
+// MASKED (weight gradients of plain matrices only): the reduction runs over the kept samples' rows (RowMask); a compile-time variant.
+template <class T, int VEC, int EPI, bool SCALE_A, int PREC, class ASrc, class BSrc, bool MASKED = false>
 __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc& B, const Epilogue& epi, int M, int N, int R,
                                           int r_per_split, int tiles_m, int tiles_n, int bid, int nblk, int stamp_row,
                                           const RowMask* mk = nullptr, KeptList* kept = nullptr) {
-    // waves of one k-group: 2 x 2 for 64 x 64 (and larger) tiles, 2 x 1 for 64 x 32: the narrow tile
-    // exists for launches whose 64 x 64 tile count is a poor multiple of the 256 CUs (every workgroup is resident at once,
-    // so the kernel ends with the most loaded CU)
-    constexpr int WGM = BM >= 64 ? 2 : 1, WGN = BN >= 64 ? 2 : 1, NW = WGM * WGN;
-    constexpr int WM = BM / WGM, WN = BN / WGN;
-    constexpr int FM = WM / 32, FN = WN / 32;        // 32x32 fragments per wave
-    constexpr int LDR = BK + 4;                      // [row][r] image: 16-B padded rows -> conflict-free b128 reads
-    constexpr int LDA = A_RC ? LDR : BM + 4;
-    constexpr int LDB = B_RC ? LDR : BN + 4;
-    constexpr int A_ELEMS = A_RC ? BM * LDR : BK * (BM + 4);
-    constexpr int B_ELEMS = B_RC ? BN * LDR : BK * (BN + 4);
-    constexpr int LDS_FLOATS = gemm_lds_floats<BM, BN, BK, KW, A_RC, B_RC>();
-    static_assert(LDS_FLOATS >= A_ELEMS + B_ELEMS && LDS_FLOATS >= NW * EP_WAVE_FLOATS, "gemm_lds_floats out of step with the tile geometry");
+    typedef typename T::A TA;
+    typedef typename T::B TB;
+    constexpr int BM = T::BM, BN = T::BN, BK = T::BK, KW = T::KW, NW = T::NW, FM = T::FM, FN = T::FN, LD16 = T::LD16;
+    constexpr bool A_RC = TA::RC, B_RC = TB::RC;
     float* As = lds;
-    float* Bs = lds + A_ELEMS;
-    // PREC == 1: both operands as [row][r] bf16 images (r-contiguous: one ds_read_b128 = the 8 k-values of a lane)
-    constexpr int LD16 = BK + 8;                     // in bf16 elements: 16-B aligned rows, 36-dword stride at BK = 64
+    float* Bs = lds + TA::ELEMS;
     unsigned short* As16 = reinterpret_cast<unsigned short*>(lds);
     unsigned short* Bs16 = As16 + BM * LD16;
-    static_assert(PREC == 0 || ((BM + BN) * LD16 * 2 <= LDS_FLOATS * 4 && (BK / KW) % 16 == 0), "bf16 tile does not fit");
+    static_assert(PREC == 0 || ((BM + BN) * LD16 * 2 <= T::LDS_FLOATS * 4 && (BK / KW) % 16 == 0), "bf16 tile does not fit");
 
-    constexpr int NTH = 64 * NW * KW;
     const int tid = threadIdx.x, lane = tid & 63, wave = (tid >> 6) % NW, kg = tid / (64 * NW);
     const int li = lane & 31, lh = lane >> 5;
-    // XCD-aware block order: workgroups are dealt round-robin over the 8 XCDs (private L2 each), so give every XCD a
-    // CONTIGUOUS range of logical blocks, ordered [split][m-tile][n-tile]: the blocks that re-read one A row panel
-    // (all n-tiles of an m-tile; all tiles of a split) then share one L2 instead of fetching it eight times.
-    const int xq = nblk >> 3, xr = nblk & 7, xcd = bid & 7;
-    const int lb = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (bid >> 3);
+    const int lb = xcd_block_order(bid, nblk);       // logical blocks are ordered [split][m-tile][n-tile]
     const int tiles = tiles_m * tiles_n;
     const int split = lb / tiles;
     const int tile = lb - split * tiles;
     const int m0 = (tile / tiles_n) * BM, n0 = (tile % tiles_n) * BN;
     if constexpr (MASKED) {
-        static_assert(!A_RC && !B_RC && VEC == 4 && BM == BN && std::is_same<ASrc, PlainSrc>::value && std::is_same<BSrc, PlainSrc>::value,
+        static_assert(!A_RC && !B_RC && VEC == 4 && BM == BN && is_plain<ASrc> && is_plain<BSrc>,
                       "the sample mask serves weight gradients of plain matrices (one row mapping for both operands)");
-        // One wave lists the kept samples in ascending order (ballot + popcount, 64 samples a pass).  Every workgroup of the problem
-        // builds the same list, and from its length the same split ranges: with S slabs, 8 * ceil(ceil(nk rps / S) / 8) rows each.
-        // With every sample kept that is the host's own r_per_split (choose_split makes rps from a count s >= S = ceil(M / rps): M / S
-        // <= rps, and rps - 8 < M / s <= M / S leaves no smaller multiple of 8), so the launch then sums exactly what the unmasked does.
-        if (tid < 64) {
-            int n = 0;
-            for (int s0 = 0; s0 < mk->nsamples; s0 += 64) {
-                const int s = s0 + lane;
-                const bool keep = s < mk->nsamples && mk->skip[s] != 0.0f;
-                const unsigned long long bal = __ballot(keep);
-                if (keep) {
-                    const int at = n + __popcll(bal & ((1ull << lane) - 1ull));
-                    kept->idx[at] = s;
-                    kept->scale[at] = src_row_scale(A) ? src_row_scale(A)[s] : 1.0f;
-                }
-                n += __popcll(bal);
-            }
-            if (tid == 0) kept->n = n;
-        }
+        // From the kept list's length the split ranges: with S slabs, 8 * ceil(ceil(nk rps / S) / 8) rows each.  With every sample
+        // kept that is the host's own r_per_split (choose_split makes rps from a count s >= S = ceil(M / rps): M / S <= rps, and
+        // rps - 8 < M / s <= M / S leaves no smaller multiple of 8), so the launch then sums exactly what the unmasked does.
+        build_kept_list(kept, *mk, src_row_scale(A));
         __syncthreads();
         R = __builtin_amdgcn_readfirstlane(kept->n) * mk->rows_per_sample;
         r_per_split = ((R + mk->splits - 1) / mk->splits + 7) / 8 * 8;
     }
     const int r_begin = split * r_per_split;
     const int r_end = min(R, r_begin + r_per_split);
-    const int wm0 = (wave / WGN) * WM, wn0 = (wave % WGN) * WN;
+    const int wm0 = (wave / T::WGN) * T::WM, wn0 = (wave % T::WGN) * T::WN;
 
-    // loader geometry
-    constexpr int QA = BM * BK / (4 * NTH), QB = BN * BK / (4 * NTH); // chunks (16 B) per thread per tile
-    static_assert(QA >= 1 && QB >= 1 && (BK / KW) % 8 == 0, "tile too small for this many wave groups");
-    constexpr int A_CPR = A_RC ? BK / 4 : BM / 4;           // chunks per LDS row
-    constexpr int B_CPR = B_RC ? BK / 4 : BN / 4;
-    constexpr int A_RPP = NTH / A_CPR, B_RPP = NTH / B_CPR; // rows per pass
-    const int a_c = tid % A_CPR, a_r = tid / A_CPR;
-    const int b_c = tid % B_CPR, b_r = tid / B_CPR;
+    const int a_c = tid % TA::CPR, a_r = tid / TA::CPR;
+    const int b_c = tid % TB::CPR, b_r = tid / TB::CPR;
 
-    typename ASrc::Row arow[QA];
-    typename BSrc::Row brow[QB];
+    typename ASrc::Row arow[TA::Q];
+    typename BSrc::Row brow[TB::Q];
     if (A_RC) {
 #pragma unroll
-        for (int q = 0; q < QA; ++q) arow[q] = A.row(m0 + a_r + q * A_RPP);
+        for (int q = 0; q < TA::Q; ++q) arow[q] = A.row(m0 + a_r + q * TA::RPP);
     }
     if (B_RC) {
 #pragma unroll
-        for (int q = 0; q < QB; ++q) brow[q] = B.row(n0 + b_r + q * B_RPP);
+        for (int q = 0; q < TB::Q; ++q) brow[q] = B.row(n0 + b_r + q * TB::RPP);
     }
 
     // An operand that is not r-contiguous keeps its column (the output index m0 / n0 + 4 * chunk) through the whole reduction: a
@@ -374,18 +433,19 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
 
     // register prefetch of the next tile: raw loads only -- nothing may consume pa/pb before stash(), or the
     // compiler waits for the loads in front of the MFMA section
-    f32x4 pa[QA], pb[QB];
-    u32x2 pa16[QA], pb16[QB];                        // an operand stored as bf16: its raw chunks (pa / pb is then unused)
-    float pas[QA];
+    f32x4 pa[TA::Q], pb[TB::Q];
+    u32x2 pa16[TA::Q], pb16[TB::Q];                  // an operand stored as bf16: its raw chunks (pa / pb is then unused)
+    float pas[TA::Q];
     // a16 (std::true_type / false_type): A is STORED as bf16.  A compile-time copy of the main loop per storage type: a run-time
     // choice between the 8-B and the 16-B load inside fetch() splits it into basic blocks and the loads end up waiting for one another.
+    // A and B stay written out here, and the ladder below: helpers cost time (profiles/gemm_body_notes.md).
     auto fetch = [&](int r0, auto a16, auto b16) {
-        int mrow[QA];                                    // MASKED: the rows of this thread's chunks (both operands'), < 0 past the end
-        float msc[QA];
+        int mrow[TA::Q];                                 // MASKED: the rows of this thread's chunks (both operands'), < 0 past the end
+        float msc[TA::Q];
         if constexpr (MASKED) {
 #pragma unroll
-            for (int q = 0; q < QA; ++q) {
-                const int c = r0 + a_r + q * A_RPP;
+            for (int q = 0; q < TA::Q; ++q) {
+                const int c = r0 + a_r + q * TA::RPP;
                 mrow[q] = -1;
                 msc[q] = 1.0f;
                 if (c < r_end) {
@@ -396,14 +456,14 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
             }
         }
 #pragma unroll
-        for (int q = 0; q < QA; ++q) {
+        for (int q = 0; q < TA::Q; ++q) {
             typename ASrc::Row rr;
             int j;
             if (A_RC) {
                 rr = arow[q];
                 j = r0 + 4 * a_c;
             } else {
-                const int r = r0 + a_r + q * A_RPP;
+                const int r = r0 + a_r + q * TA::RPP;
                 if constexpr (MASKED) rr = src_mapped_row(A, mrow[q], msc[q]);
                 else rr = A.row(r < r_end ? r : 0x7fffffff);
                 j = m0 + 4 * a_c;
@@ -427,14 +487,14 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
             }
         }
 #pragma unroll
-        for (int q = 0; q < QB; ++q) {
+        for (int q = 0; q < TB::Q; ++q) {
             typename BSrc::Row rr;
             int j;
             if (B_RC) {
                 rr = brow[q];
                 j = r0 + 4 * b_c;
             } else {
-                const int r = r0 + b_r + q * B_RPP;
+                const int r = r0 + b_r + q * TB::RPP;
                 if constexpr (MASKED) rr = src_mapped_row(B, mrow[q], 1.0f);
                 else rr = B.row(r < r_end ? r : 0x7fffffff);
                 j = n0 + 4 * b_c;
@@ -458,61 +518,8 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
         }
     };
     auto stash = [&](auto a16, auto b16) {
-#pragma unroll
-        for (int q = 0; q < QA; ++q) {
-            f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-            if constexpr (!decltype(a16)::value) v = pa[q];
-            if constexpr (PREC == 1) {
-                // the 4 bf16 of this chunk as two packed dwords (plain integers: hipcc 7.2 miscompiles element extraction from a
-                // bf16 vector that is merged from two branches -- all four stores received element 0)
-                unsigned h01, h23;
-                if constexpr (decltype(a16)::value) {    // stored as bf16: the bits go to the image unchanged
-                    h01 = pa16[q][0];
-                    h23 = pa16[q][1];
-                    if (SCALE_A) {
-                        const u32x2 u = __builtin_bit_cast(u32x2, __builtin_convertvector(widen_bf16x4(pa16[q]) * pas[q], bf16x4));
-                        h01 = u[0]; h23 = u[1];
-                    }
-                } else {
-                    if (SCALE_A) v *= pas[q];
-                    const u32x2 u = __builtin_bit_cast(u32x2, __builtin_convertvector(v, bf16x4));
-                    h01 = u[0]; h23 = u[1];
-                }
-                if (A_RC) {
-                    *reinterpret_cast<u32x2*>(&As16[(a_r + q * A_RPP) * LD16 + 4 * a_c]) = u32x2{h01, h23};
-                } else {                                 // source is row(m)-contiguous: transpose into the [m][r] image
-                    unsigned short* col = &As16[4 * a_c * LD16 + a_r + q * A_RPP];
-                    col[0] = (unsigned short)(h01 & 0xffffu);
-                    col[LD16] = (unsigned short)(h01 >> 16);
-                    col[2 * LD16] = (unsigned short)(h23 & 0xffffu);
-                    col[3 * LD16] = (unsigned short)(h23 >> 16);
-                }
-            } else {
-                if (SCALE_A) v *= pas[q];
-                *reinterpret_cast<f32x4*>(&As[(a_r + q * A_RPP) * LDA + 4 * a_c]) = v;
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < QB; ++q) {
-            if constexpr (PREC == 1) {
-                u32x2 hb;                                // 4 bf16 as two dwords (stored bf16: unchanged bits)
-                if constexpr (decltype(b16)::value) hb = pb16[q];
-                else hb = __builtin_bit_cast(u32x2, __builtin_convertvector(pb[q], bf16x4));
-                if (B_RC) {
-                    *reinterpret_cast<u32x2*>(&Bs16[(b_r + q * B_RPP) * LD16 + 4 * b_c]) = hb;
-                } else {
-                    // source rows run along the REDUCTION index (data gradient: W[r][k]): keep them as they arrive, [r][BN] bf16
-                    // rows of 128 B, and let ds_read_b64_tr_b16 do the transpose when the fragments are read (below).  16-B
-                    // chunks are XOR-swizzled with bit 1 of the row so that the 4-row x 16-column transposed reads of a
-                    // 32-lane half fall into 64 distinct banks.
-                    static_assert(B_RC || BN == 64, "transposed-read B image is laid out for 64-column tiles");
-                    const int row = b_r + q * B_RPP;
-                    *reinterpret_cast<u32x2*>(&Bs16[row * BN + 8 * ((b_c >> 1) ^ (((row >> 1) & 1) << 2)) + 4 * (b_c & 1)]) = hb;
-                }
-            } else {
-                *reinterpret_cast<f32x4*>(&Bs[(b_r + q * B_RPP) * LDB + 4 * b_c]) = pb[q];
-            }
-        }
+        stash_operand<TA, true, PREC, decltype(a16)::value, SCALE_A, LD16, BN>(As, As16, a_c, a_r, pa, pa16, pas);
+        stash_operand<TB, false, PREC, decltype(b16)::value, false, LD16, BN>(Bs, Bs16, b_c, b_r, pb, pb16, nullptr);
     };
 
     f32x16 acc[FM][FN];
@@ -526,12 +533,12 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
     float csum = 0.f;   // dbias partial (TN, A row-contiguous image: column tid of the A tile)
     const bool do_colsum = !A_RC && epi.colsum && n0 == 0 && tid < BM;
 
-    if (epi.stamps && tid == 0) { epi.stamps[8L * stamp_row + 0] = __builtin_amdgcn_s_memtime(); epi.stamps[8L * stamp_row + 4] = __builtin_amdgcn_s_getreg(6164); epi.stamps[8L * stamp_row + 5] = __builtin_amdgcn_s_memrealtime(); }
+    stamp(epi, stamp_row, 0);
     auto main_loop = [&](auto a16, auto b16) {
         fetch(r_begin, a16, b16);
         stash(a16, b16);
         __syncthreads();
-        if (epi.stamps && tid == 0) epi.stamps[8L * stamp_row + 1] = __builtin_amdgcn_s_memtime();
+        stamp(epi, stamp_row, 1);
         for (int r0 = r_begin; r0 < r_end; r0 += BK) {
             const bool more = r0 + BK < r_end;
             if (more) fetch(r0 + BK, a16, b16);
@@ -542,7 +549,7 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
                         csum += __builtin_bit_cast(float, (unsigned)As16[tid * LD16 + r] << 16);
                 } else {
 #pragma unroll 8
-                    for (int r = 0; r < BK; ++r) csum += As[r * LDA + tid];
+                    for (int r = 0; r < BK; ++r) csum += As[r * TA::LD + tid];
                 }
             }
             if constexpr (PREC == 1) {
@@ -581,23 +588,25 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
             } else
 #pragma unroll
             for (int kk = kg * (BK / KW); kk < (kg + 1) * (BK / KW); kk += 8) {
+                // one b128 from an r-contiguous image, four b32 from a row-contiguous one; written out per operand: through a
+                // helper the b32 reads come out paired (ds_read2_b32), not the parent's listing (profiles/gemm_body_notes.md)
                 f32x4 af[FM], bf[FN];
 #pragma unroll
                 for (int i = 0; i < FM; ++i) {
                     if (A_RC) {
-                        af[i] = *reinterpret_cast<const f32x4*>(&As[(wm0 + i * 32 + li) * LDA + kk + 4 * lh]);
+                        af[i] = *reinterpret_cast<const f32x4*>(&As[(wm0 + i * 32 + li) * TA::LD + kk + 4 * lh]);
                     } else {
 #pragma unroll
-                        for (int s = 0; s < 4; ++s) af[i][s] = As[(kk + 4 * lh + s) * LDA + wm0 + i * 32 + li];
+                        for (int s = 0; s < 4; ++s) af[i][s] = As[(kk + 4 * lh + s) * TA::LD + wm0 + i * 32 + li];
                     }
                 }
 #pragma unroll
                 for (int j = 0; j < FN; ++j) {
                     if (B_RC) {
-                        bf[j] = *reinterpret_cast<const f32x4*>(&Bs[(wn0 + j * 32 + li) * LDB + kk + 4 * lh]);
+                        bf[j] = *reinterpret_cast<const f32x4*>(&Bs[(wn0 + j * 32 + li) * TB::LD + kk + 4 * lh]);
                     } else {
 #pragma unroll
-                        for (int s = 0; s < 4; ++s) bf[j][s] = Bs[(kk + 4 * lh + s) * LDB + wn0 + j * 32 + li];
+                        for (int s = 0; s < 4; ++s) bf[j][s] = Bs[(kk + 4 * lh + s) * TB::LD + wn0 + j * 32 + li];
                     }
                 }
 #pragma unroll
@@ -617,8 +626,8 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
     };
     if (r_begin < r_end) {
         // storage variants (bf16 mode, forward / data-gradient Linears only): A (activations) and / or B (the weights' bf16 shadow)
-        constexpr bool CAN_A16 = PREC == 1 && A_RC && VEC == 4 && std::is_same<ASrc, PlainSrc>::value;
-        constexpr bool CAN_B16 = PREC == 1 && A_RC && VEC == 4 && std::is_same<BSrc, PlainSrc>::value;
+        constexpr bool CAN_A16 = PREC == 1 && A_RC && VEC == 4 && is_plain<ASrc>;
+        constexpr bool CAN_B16 = PREC == 1 && A_RC && VEC == 4 && is_plain<BSrc>;
         const bool a_is16 = CAN_A16 && src_is_bf16(A), b_is16 = CAN_B16 && src_is_bf16(B);
         if constexpr (CAN_A16 && CAN_B16) {
             if (a_is16 && b_is16) main_loop(std::true_type{}, std::true_type{});
@@ -633,15 +642,14 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
         }
     }
 
-    if (epi.stamps && tid == 0) epi.stamps[8L * stamp_row + 2] = __builtin_amdgcn_s_memtime();
+    stamp(epi, stamp_row, 2);
     if (KW > 1) {
-        // sum the wave groups' accumulators (native C/D layout, lane-contiguous LDS patches, binary tree)
-        static_assert(KW == 1 || (KW / 2) * NW * FM * FN * 16 * 64 <= LDS_FLOATS, "LDS too small for the k-group reduction");
-        constexpr int PATCH = FM * FN * 16 * 64;
+        // Sum the wave groups' accumulators into group 0's (native C/D layout, lane-contiguous LDS patches, binary tree).  In
+        // place: as a function the KW = 4 kernels' first stores come out paired, not the parent's listing (profiles/gemm_body_notes.md)
 #pragma unroll
         for (int half = KW / 2; half >= 1; half >>= 1) {
             if (kg >= half && kg < 2 * half) {
-                float* dst = lds + ((kg - half) * NW + wave) * PATCH + lane;
+                float* dst = lds + ((kg - half) * NW + wave) * T::PATCH + lane;
 #pragma unroll
                 for (int i = 0; i < FM; ++i)
 #pragma unroll
@@ -651,7 +659,7 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
             }
             __syncthreads();
             if (kg < half) {
-                const float* src = lds + (kg * NW + wave) * PATCH + lane;
+                const float* src = lds + (kg * NW + wave) * T::PATCH + lane;
 #pragma unroll
                 for (int i = 0; i < FM; ++i)
 #pragma unroll
@@ -675,24 +683,22 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
         else
             run_epilogue<EPI, FM, FN>(e, acc, M, N, m0 + wm0, n0 + wn0, lane, lds + wave * EP_WAVE_FLOATS, e.vec_store != 0);
     }
-    if (epi.stamps && tid == 0) { epi.stamps[8L * stamp_row + 3] = __builtin_amdgcn_s_memtime(); epi.stamps[8L * stamp_row + 6] = __builtin_amdgcn_s_memrealtime(); }
+    stamp(epi, stamp_row, 3);
     if (do_colsum && m0 + tid < M) epi.colsum[(long)split * epi.colsum_stride + m0 + tid] = csum;
 }
 
-// threads of a workgroup: KW groups of 2 x 2 (64 x 32 tile: 2 x 1) waves
-constexpr int gemm_threads(int BM, int BN, int KW) { return 64 * (BM >= 64 ? 2 : 1) * (BN >= 64 ? 2 : 1) * KW; }
-
 template <int BM, int BN, int BK, int KW, bool A_RC, bool B_RC, int VEC, int EPI, bool SCALE_A, int PREC, class ASrc, class BSrc>
-__global__ __launch_bounds__(gemm_threads(BM, BN, KW)) void gemm_kernel(ASrc A, BSrc B, Epilogue epi, int M, int N, int R,
+__global__ __launch_bounds__((Tile<BM, BN, BK, KW, A_RC, B_RC>::THREADS)) void gemm_kernel(ASrc A, BSrc B, Epilogue epi, int M, int N, int R,
                                                     int r_per_split, int tiles_m, int tiles_n) {
-    __shared__ __attribute__((aligned(16))) float lds[gemm_lds_floats<BM, BN, BK, KW, A_RC, B_RC>()];
-    gemm_body<BM, BN, BK, KW, A_RC, B_RC, VEC, EPI, SCALE_A, PREC, ASrc, BSrc>(lds, A, B, epi, M, N, R, r_per_split, tiles_m, tiles_n,
-                                                                              (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.x);
+    typedef Tile<BM, BN, BK, KW, A_RC, B_RC> T;
+    __shared__ __attribute__((aligned(16))) float lds[T::LDS_FLOATS];
+    gemm_body<T, VEC, EPI, SCALE_A, PREC, ASrc, BSrc>(lds, A, B, epi, M, N, R, r_per_split, tiles_m, tiles_n, (int)blockIdx.x, (int)gridDim.x,
+                                                      (int)blockIdx.x);
 }
 
-// Up to four independent weight-gradient problems (the four Linears of a CSWinBlock: same kernel configuration, operands all
-// alive at the end of the block's backward) in ONE launch: an empty launch costs ~3 us in-stream, and the four grids' tails
-// fill each other.  Each problem keeps its own XCD-aware block order inside its block range.
+// Up to four independent problems of one kernel configuration in ONE launch (the weight gradients of the four Linears of a
+// CSWinBlock: operands all alive at the end of the block's backward): an empty launch costs ~3 us in-stream, and the four grids'
+// tails fill each other.  Each problem keeps its own XCD-aware block order inside its block range.
 constexpr int WGRAD_BATCH = 4;
 template <class ASrc, class BSrc>
 struct GemmBatch {
@@ -706,35 +712,39 @@ struct GemmBatch {
 };
 typedef GemmBatch<PlainSrc, PlainSrc> WgradBatch;
 
-// workgroup bid of problem p of a weight-gradient batch (fp32) that has a problem with a sample mask: that problem takes the masked
-// form of the body, the others the same form as in an unmasked launch
-__device__ __forceinline__ void wgrad_masked_batch_body(float* lds, KeptList* kept, const WgradBatch& b, int p, int bid) {
-    if (b.mask[p].skip) {
-        gemm_body<64, 64, 64, 2, false, false, 4, EPI_PLAIN, true, 0, PlainSrc, PlainSrc, true>(
-            lds, b.A[p], b.B[p], b.e[p], b.M[p], b.N[p], b.R[p], b.rps[p], b.tm[p], b.tn[p], bid - b.first[p],
-            b.first[p + 1] - b.first[p], bid, &b.mask[p], kept);
-        return;
+// the problem whose block range holds workgroup bid
+template <class ASrc, class BSrc> __device__ __forceinline__ int batch_problem(const GemmBatch<ASrc, BSrc>& b, int bid) {
+    int p = 0;
+    while (p + 1 < b.n && bid >= b.first[p + 1]) ++p;
+    return p;
+}
+// workgroup bid of the launch as a workgroup of problem p (16-B loaders, plain epilogue; MASKED: with the problem's sample mask)
+template <class T, bool SCALE_A, int PREC, bool MASKED = false, class ASrc, class BSrc>
+__device__ __forceinline__ void batch_body(float* lds, const GemmBatch<ASrc, BSrc>& b, int p, int bid, KeptList* kept = nullptr) {
+    gemm_body<T, 4, EPI_PLAIN, SCALE_A, PREC, ASrc, BSrc, MASKED>(lds, b.A[p], b.B[p], b.e[p], b.M[p], b.N[p], b.R[p], b.rps[p], b.tm[p], b.tn[p],
+                                                                  bid - b.first[p], b.first[p + 1] - b.first[p], bid, MASKED ? &b.mask[p] : nullptr, kept);
+}
+
+typedef Tile<64, 64, 64, 2, false, false> WgradTile;   // the weight gradients' configuration: two k-groups of four waves
+// Workgroup bid of a weight-gradient batch.  MASKED: a problem of the launch with a sample mask takes the masked form of the body.
+template <int PREC, bool MASKED>
+__device__ __forceinline__ void wgrad_batch_body(float* lds, KeptList* kept, const WgradBatch& b, int bid) {
+    const int p = batch_problem(b, bid);
+    if constexpr (MASKED) {
+        if (b.mask[p].skip) return batch_body<WgradTile, true, PREC, true>(lds, b, p, bid, kept);
     }
-    gemm_body<64, 64, 64, 2, false, false, 4, EPI_PLAIN, true, 0, PlainSrc, PlainSrc>(
-        lds, b.A[p], b.B[p], b.e[p], b.M[p], b.N[p], b.R[p], b.rps[p], b.tm[p], b.tn[p], bid - b.first[p],
-        b.first[p + 1] - b.first[p], bid);
+    batch_body<WgradTile, true, PREC>(lds, b, p, bid);
 }
 
 template <int PREC>
-__global__ __launch_bounds__(512) void gemm_wgrad_batch_kernel(WgradBatch b) {
-    int p = 0;
-    while (p + 1 < b.n && (int)blockIdx.x >= b.first[p + 1]) ++p;
-    __shared__ __attribute__((aligned(16))) float lds[gemm_lds_floats<64, 64, 64, 2, false, false>()];
-    gemm_body<64, 64, 64, 2, false, false, 4, EPI_PLAIN, true, PREC, PlainSrc, PlainSrc>(
-        lds, b.A[p], b.B[p], b.e[p], b.M[p], b.N[p], b.R[p], b.rps[p], b.tm[p], b.tn[p], (int)blockIdx.x - b.first[p],
-        b.first[p + 1] - b.first[p], (int)blockIdx.x);
+__global__ __launch_bounds__(WgradTile::THREADS) void gemm_wgrad_batch_kernel(WgradBatch b) {
+    __shared__ __attribute__((aligned(16))) float lds[WgradTile::LDS_FLOATS];
+    wgrad_batch_body<PREC, false>(lds, nullptr, b, (int)blockIdx.x);
 }
-__global__ __launch_bounds__(512) void gemm_wgrad_batch_masked_kernel(WgradBatch b) {
-    int p = 0;
-    while (p + 1 < b.n && (int)blockIdx.x >= b.first[p + 1]) ++p;
-    __shared__ __attribute__((aligned(16))) float lds[gemm_lds_floats<64, 64, 64, 2, false, false>()];
+__global__ __launch_bounds__(WgradTile::THREADS) void gemm_wgrad_batch_masked_kernel(WgradBatch b) {
+    __shared__ __attribute__((aligned(16))) float lds[WgradTile::LDS_FLOATS];
     __shared__ KeptList kept;
-    wgrad_masked_batch_body(lds, &kept, b, p, (int)blockIdx.x);
+    wgrad_batch_body<0, true>(lds, &kept, b, (int)blockIdx.x);
 }
 
 // The tail of a CSWinBlock's backward in ONE launch: the data gradient of the qkv Linear (dqkv . Wqkv, the last Linear whose input
@@ -749,40 +759,31 @@ struct BlockTail {
     WgradBatch w;
     ReduceRiders r;          // pending slab reductions of EARLIER launches (the previous block's): the grid's last workgroups
 };
-constexpr int BLOCK_TAIL_LDS = gemm_lds_floats<64, 64, 64, 2, true, false>() > gemm_lds_floats<64, 64, 64, 2, false, false>()
-                                   ? gemm_lds_floats<64, 64, 64, 2, true, false>() : gemm_lds_floats<64, 64, 64, 2, false, false>();
+typedef Tile<64, 64, 64, 2, true, false> TailDgradTile;
+static_assert(TailDgradTile::THREADS == WgradTile::THREADS, "one workgroup size for both halves of the block tail");
+constexpr int BLOCK_TAIL_LDS = TailDgradTile::LDS_FLOATS > WgradTile::LDS_FLOATS ? TailDgradTile::LDS_FLOATS : WgradTile::LDS_FLOATS;
 template <bool MASKED>
 __device__ __forceinline__ void block_tail_body(float (&lds)[BLOCK_TAIL_LDS], KeptList* kept, const BlockTail& t) {
-    const WgradBatch& b = t.w;
-    const int nw = b.first[b.n];
-    if ((int)blockIdx.x >= nw + t.nd) {    // riders: 256-thread reduction workgroups (the upper four waves leave)
+    const int bid = (int)blockIdx.x, nw = t.w.first[t.w.n];
+    if (bid >= nw + t.nd) {                // riders: 256-thread reduction workgroups (the upper four waves leave)
         if (threadIdx.x >= 256) return;
         static_assert(sizeof(lds) >= sizeof(float) * RS_G * (RS_COLS + 1), "reduction scratch");
-        rows_sum_dispatch(t.r.j, t.r.first_block, t.r.njobs, (int)blockIdx.x - nw - t.nd, reinterpret_cast<float(*)[RS_COLS + 1]>(lds));
+        rows_sum_dispatch(t.r.j, t.r.first_block, t.r.njobs, bid - nw - t.nd, reinterpret_cast<float(*)[RS_COLS + 1]>(lds));
         return;
     }
-    if ((int)blockIdx.x >= nw) {           // the data gradient's tiles come after the weight gradients': they fill their tail
-        gemm_body<64, 64, 64, 2, true, false, 4, EPI_PLAIN, false, 0, PlainSrc, PlainSrc>(
-            lds, t.dA, t.dB, t.de, t.dM, t.dN, t.dR, t.drps, t.dtm, t.dtn, (int)blockIdx.x - nw, t.nd, (int)blockIdx.x);
+    if (bid >= nw) {                       // the data gradient's tiles come after the weight gradients': they fill their tail
+        gemm_body<TailDgradTile, 4, EPI_PLAIN, false, 0, PlainSrc, PlainSrc>(lds, t.dA, t.dB, t.de, t.dM, t.dN, t.dR, t.drps, t.dtm, t.dtn, bid - nw,
+                                                                             t.nd, bid);
         return;
     }
-    const int bid = (int)blockIdx.x;
-    int p = 0;
-    while (p + 1 < b.n && bid >= b.first[p + 1]) ++p;
-    if constexpr (MASKED) {
-        wgrad_masked_batch_body(lds, kept, b, p, bid);
-    } else {
-        gemm_body<64, 64, 64, 2, false, false, 4, EPI_PLAIN, true, 0, PlainSrc, PlainSrc>(
-            lds, b.A[p], b.B[p], b.e[p], b.M[p], b.N[p], b.R[p], b.rps[p], b.tm[p], b.tn[p], bid - b.first[p],
-            b.first[p + 1] - b.first[p], (int)blockIdx.x);
-    }
+    wgrad_batch_body<0, MASKED>(lds, kept, t.w, bid);
 }
-__global__ __launch_bounds__(512) void gemm_block_tail_kernel(BlockTail t) {
+__global__ __launch_bounds__(WgradTile::THREADS) void gemm_block_tail_kernel(BlockTail t) {
     __shared__ __attribute__((aligned(16))) float lds[BLOCK_TAIL_LDS];
     block_tail_body<false>(lds, nullptr, t);
 }
 // the same launch with a sample mask on at least one of its weight gradients
-__global__ __launch_bounds__(512) void gemm_block_tail_masked_kernel(BlockTail t) {
+__global__ __launch_bounds__(WgradTile::THREADS) void gemm_block_tail_masked_kernel(BlockTail t) {
     __shared__ __attribute__((aligned(16))) float lds[BLOCK_TAIL_LDS];
     __shared__ KeptList kept;
     block_tail_body<true>(lds, &kept, t);
@@ -790,14 +791,11 @@ __global__ __launch_bounds__(512) void gemm_block_tail_masked_kernel(BlockTail t
 
 // The four parity classes of a stride-2 3x3 convolution's data gradient (ConvTS2SrcT) are independent GEMMs over a quarter of
 // the pixels each: alone they fill 1.1 - 1.2 workgroups per CU (the launch ends with the CUs that got two); together 4.6.
+template <int KW> using S2DgradTile = Tile<64, 64, (KW == 1 ? 32 : 64), KW, true, false>;
 template <int KW, int PREC, bool FAST>
-__global__ __launch_bounds__(256 * KW) void gemm_conv_s2_dgrad_batch_kernel(GemmBatch<ConvTS2SrcT<FAST>, TapRowsSrcT<FAST>> b) {
-    int p = 0;
-    while (p + 1 < b.n && (int)blockIdx.x >= b.first[p + 1]) ++p;
-    __shared__ __attribute__((aligned(16))) float lds[gemm_lds_floats<64, 64, (KW == 1 ? 32 : 64), KW, true, false>()];
-    gemm_body<64, 64, (KW == 1 ? 32 : 64), KW, true, false, 4, EPI_PLAIN, false, PREC, ConvTS2SrcT<FAST>, TapRowsSrcT<FAST>>(
-        lds, b.A[p], b.B[p], b.e[p], b.M[p], b.N[p], b.R[p], b.rps[p], b.tm[p], b.tn[p], (int)blockIdx.x - b.first[p],
-        b.first[p + 1] - b.first[p], (int)blockIdx.x);
+__global__ __launch_bounds__(S2DgradTile<KW>::THREADS) void gemm_conv_s2_dgrad_batch_kernel(GemmBatch<ConvTS2SrcT<FAST>, TapRowsSrcT<FAST>> b) {
+    __shared__ __attribute__((aligned(16))) float lds[S2DgradTile<KW>::LDS_FLOATS];
+    batch_body<S2DgradTile<KW>, false, PREC>(lds, b, batch_problem(b, (int)blockIdx.x), (int)blockIdx.x);
 }
 
 // ======================================================================================
@@ -809,7 +807,7 @@ void launch_cfg(const ASrc& A, const BSrc& B, const Epilogue& epi, int M, int N,
     int tm = cdiv(M, BM), tn = cdiv(N, BN);
     dim3 grid(tm * tn * splits);
     const int pad_lds = cswin_tuning().gemm_pad_lds;                                                    // tuning aid: caps residency
-    hipLaunchKernelGGL((gemm_kernel<BM, BN, BK, KW, A_RC, B_RC, VEC, EPI, SCALE_A, PREC, ASrc, BSrc>), grid, dim3(gemm_threads(BM, BN, KW)), pad_lds, st, A, B, epi,
+    hipLaunchKernelGGL((gemm_kernel<BM, BN, BK, KW, A_RC, B_RC, VEC, EPI, SCALE_A, PREC, ASrc, BSrc>), grid, dim3((Tile<BM, BN, BK, KW, A_RC, B_RC>::THREADS)), pad_lds, st, A, B, epi,
                        M, N, R, r_per_split, tm, tn);
 }
 

@@ -69,9 +69,8 @@ __global__ __launch_bounds__(MODE == 0 ? 256 : 512) void gemm16_kernel(G16Params
     const int li = lane & 31, lh = lane >> 5;
     constexpr int A_IMG = TM * 128;                  // bytes of the A image of a step
     constexpr int SLOT = KG * (A_IMG + G16_IMG);     // bytes of a ring slot
-    // XCD-aware block order (as gemm.hip): each XCD takes a contiguous range of tiles, ordered [m-tile][n-tile]
-    const int bid = blockIdx.x, xq = p.nblk >> 3, xr = p.nblk & 7, xcd = bid & 7;
-    const int lb = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (bid >> 3);
+    // each XCD takes a contiguous range of tiles, ordered [m-tile][n-tile]
+    const int bid = blockIdx.x, lb = xcd_block_order(bid, p.nblk);
     const int m0 = (lb / p.tiles_n) * TM, n0 = (lb % p.tiles_n) * G16_T;
     const int wm0 = (wave >> 1) * 32, wn0 = (wave & 1) * 32;         // MODE 2: wave 0 .. 7 -> rows 0 .. 96
     const int nsteps = (p.R + G16_T * KG - 1) / (G16_T * KG);        // loop iterations (KG steps of 64 each)

@@ -22,6 +22,41 @@ def timed(fn, reps=20, rounds=5):
 B = int(os.environ.get("BATCH", "24"))
 import cswin_unet_amd
 cswin_unet_amd.set_matmul_precision(os.environ.get("MATMUL", "fp32"))      # MATMUL=bf16: bf16 operands (streaming-bound proxy)
+
+def conv_mode():
+    """`gemm_bench.py conv`: the three conv entry points at the convolutions of configs/cswin_tiny_224_lite.yaml (E = 64, 224 x 224):
+    the 7x7 stride-4 stem on 4-channel tokens (no input gradient), the three stride-2 merges, the stride-1 CARAFE encoders of the
+    decoder and of the head, whose input gradient is a forward convolution of dy with the mirrored weights, as ops.conv_tokens runs it."""
+    E = 64
+    cases = [("stem", 224, 4, E, 7, 4, 2)]
+    cases += [(f"merge{i+1}", 56 >> i, E << i, 2 * E << i, 3, 2, 1) for i in range(3)]
+    cases += [(f"up{4-i}.enc", 7 << i, 2 * E >> i, 36, 3, 1, 1) for i in range(3)] + [("head.enc", 56, E // 4, 144, 3, 1, 1)]
+    R = lambda *s: torch.randn(*s, device="cuda")
+    for name, side, Cin, Cout, ks, stride, pad in cases:
+        O = (side + 2 * pad - ks) // stride + 1
+        x, dy, b, w = R(B, side * side, Cin), R(B, O * O, Cout), R(Cout), R(Cout, Cin, ks, ks)
+        wp, wpt, wf = torch.empty(Cout, ks * ks, Cin, device="cuda"), torch.empty(ks * ks, Cout, Cin, device="cuda"), torch.empty(Cin, ks * ks, Cout, device="cuda")
+        call("cswin_conv_weight_permute", ptr(w), ptr(wp), ptr(wpt), Cout, Cin, ks, Cin, stream())
+        call("cswin_conv_weight_flipT", ptr(w), ptr(wf), Cout, Cin, ks, stream())
+        y, dx, dw, db = torch.empty(B, O * O, Cout, device="cuda"), torch.empty_like(x), torch.empty_like(w), torch.empty(Cout, device="cuda")
+        nbytes = lib().cswin_conv_tok_bwd_weight_workspace(B, side, side, Cin, Cout, ks, stride, pad)
+        ws = torch.empty(nbytes // 4 + 4, device="cuda")
+        geo = (B, side, side, Cin, Cout, ks, stride, pad)
+        tf = timed(lambda: call("cswin_conv_tok_fwd", ptr(x), ptr(wp), ptr(b), ptr(y), *geo, precision(), stream()))
+        if name == "stem":
+            tdx = 0.0
+        elif stride == 1:
+            tdx = timed(lambda: call("cswin_conv_tok_fwd", ptr(dy), ptr(wf), None, ptr(dx), B, side, side, Cout, Cin, ks, 1, pad, precision(), stream()))
+        else:
+            tdx = timed(lambda: call("cswin_conv_tok_bwd_data", ptr(dy), ptr(wpt), ptr(dx), *geo, precision(), stream()))
+        tdw = timed(lambda: call("cswin_conv_tok_bwd_weight", ptr(dy), ptr(x), ptr(dw), ptr(db), ptr(ws), nbytes, *geo, 1, None, precision(), stream()))
+        fl = 2.0 * B * O * O * Cout * ks * ks * Cin
+        tf_s = lambda t: f"{t*1e6:7.1f}us {fl/t/1e12:6.1f}TF" if t else "      -              "
+        print(f"{name:9s} {side:3d}x{side:<3d} Cin={Cin:4d} Cout={Cout:4d} k{ks} s{stride}  fwd {tf_s(tf)} | dx {tf_s(tdx)} | dw {tf_s(tdw)}")
+
+if sys.argv[1:2] == ["conv"]:
+    conv_mode()
+    sys.exit(0)
 shapes = []
 for si, (L, C) in enumerate([(3136, 64), (784, 128), (196, 256), (49, 512)]):
     M = B * L
