@@ -72,6 +72,8 @@ SIGNATURES = {
     "cswin_chunk_sumsq": (I, [P, P, P, I, P, P]),
     "cswin_norm_finalize": (I, [P, P, I, F, F, P, P, P]),
     "cswin_adamw_flat": (I, [P, P, P, P, P, I, P, P, P, D, D, D, F, F, D, D, P, P]),
+    "cswin_rate_finalize": (I, [P, P, I, F, F, P, P, P, I, I, F, P, P, P, P, P]),
+    "cswin_adam_flat": (I, [P, P, P, P, P, I, P, P, P, D, D, D, F, F, D, D, I, P, P]),
     "cswin_tpgm_chunk_stats": (I, [P, P, P, P, I, I, P, P]),
     "cswin_tpgm_finalize": (I, [P, P, I, I, P, P, P, P, D, D, D, D, I, P, P, P, P]),
     "cswin_tpgm_project": (I, [P, P, P, P, P, I, P, P]),

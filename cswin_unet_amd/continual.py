@@ -13,6 +13,11 @@ and the "surgical" mode's learning rate per parameter tensor (universal_train.py
     w = surgical_lr_weights(model, engine.opt, batches, distill, method="eb-criterion")     # or: 1 where mean(g^2 / (var_0(g) + 1e-8)) >= 0.95, else 0
     engine.set_lr_weights(w)                                        # FlatAdamW's per-tensor multipliers; unnamed tensors get 0
 
+or that loop's finer-grained relative, finetune.py's surgical trainer, whose rates are renewed at every step on the device
+(trainer.surgical_trainer runs the whole loop):
+
+    engine.set_auto_rates(finetune_groups(model))                   # its 22 parameter groups: rate_k = lr * ||g_k|| / max_j ||g_j||, per step
+
 and TPGM, the trainable projection toward the pretrained weights (universal_train.py:391-615, 898-902, 972-974):
 
     tpgm = TPGM(trainer)                                            # BEFORE fine-tuning: the anchor is the weights as they are now
@@ -41,7 +46,7 @@ import numpy as np
 import torch
 from torch import nn
 
-__all__ = ["expand_classes", "new_label_map", "extreme_class_weights", "freeze_teacher", "Distill", "rgn_weights", "eb_weights", "eb_metrics", "surgical_lr_weights", "TPGM", "tpgm_due",
+__all__ = ["expand_classes", "new_label_map", "extreme_class_weights", "freeze_teacher", "Distill", "rgn_weights", "eb_weights", "eb_metrics", "surgical_lr_weights", "finetune_groups", "FINETUNE_GROUPS", "FINETUNE_GRID", "TPGM", "tpgm_due",
            "task_class_indices", "task_level", "checkpoint_num_classes", "strip_wrapper_prefixes", "evaluate_tasks", "scan_labels",
            "PositiveSampling", "REFERENCE_TASKS", "REFERENCE_STAGE_CLASSES", "KITS23_RULE", "LITS17_RULE"]
 
@@ -240,6 +245,24 @@ def surgical_lr_weights(model, opt, batches, distill, method="RGN", return_metri
     if not return_metrics:
         return weights
     return weights, (eb_metrics(names, host) if eb else rgn_weights(names, host, normalise=False))
+
+
+# finetune.py:82-113: the 22 parameter groups of its surgical fine-tuning, each one attribute of the core network, in its order
+FINETUNE_GROUPS = (("stem", "stage1_conv_embed"), ("encoder1", "stage1"), ("merge1", "merge1"), ("encoder2", "stage2"), ("merge2", "merge2"),
+                   ("encoder3", "stage3"), ("merge3", "merge3"), ("encoder4", "stage4"), ("bottleneck", "norm"),
+                   ("decoder4", "stage_up4"), ("upsample4", "upsample4"), ("concat4", "concat_linear4"),
+                   ("decoder3", "stage_up3"), ("upsample3", "upsample3"), ("concat3", "concat_linear3"),
+                   ("decoder2", "stage_up2"), ("upsample2", "upsample2"), ("concat2", "concat_linear2"),
+                   ("decoder1", "stage_up1"), ("upsample1", "upsample1"), ("norm_up", "norm_up"), ("output", "output"))
+FINETUNE_GRID = ((1e-3, 1e-4), (1e-4, 1e-4), (1e-5, 1e-4))         # finetune.py:152-156: the (lr, weight decay) pairs it sweeps
+
+
+def finetune_groups(model):
+    """{group: [parameter names]} of finetune.py's get_parameter_groups (:77-114) for `model` (the CSwinUnet wrapper or the core
+    network), the 22 groups in the reference's order and the names as model.named_parameters() gives them, in that order: what
+    HipEngine.set_auto_rates takes."""
+    core, prefix = _core(model), "cswin_unet." if hasattr(model, "cswin_unet") else ""
+    return {group: [f"{prefix}{attr}.{n}" for n, _ in getattr(core, attr).named_parameters()] for group, attr in FINETUNE_GROUPS}
 
 
 def tpgm_due(epoch, start_epoch, frequency):

@@ -58,16 +58,28 @@ __device__ __forceinline__ void tensor_sums(const float* __restrict__ partial, c
     }
 }
 
-// Second step, called by every thread once per trip: total (thread 0's) += the values of tensors base .. base + 255 in tensor order
-__device__ __forceinline__ void tensor_order_add(float& total, float mine, int base, int ntensors) {
+// Second step, called by every thread once per trip: thread 0 folds the values of items base .. base + 255 (tensors, or groups) into
+// its acc in item order, fold(acc, value)
+template <class Fold>
+__device__ __forceinline__ void item_order_fold(float& acc, float mine, int base, int nitems, Fold fold) {
     __shared__ float slot[256];
     slot[threadIdx.x] = mine;
     __syncthreads();
     if (threadIdx.x == 0) {
-        const int cnt = ntensors - base < 256 ? ntensors - base : 256;
-        for (int k = 0; k < cnt; ++k) total += slot[k];
+        const int cnt = nitems - base < 256 ? nitems - base : 256;
+        for (int k = 0; k < cnt; ++k) fold(acc, slot[k]);
     }
     __syncthreads();
+}
+
+// total (thread 0's) += the values of tensors base .. base + 255 in tensor order
+__device__ __forceinline__ void tensor_order_add(float& total, float mine, int base, int ntensors) {
+    item_order_fold(total, mine, base, ntensors, [](float& acc, float x) { acc += x; });
+}
+
+// The maximum as the rates want it: a NaN value makes acc NaN and it stays one (reported, not repaired)
+__device__ __forceinline__ void nan_keeping_max(float& acc, float x) {
+    if (acc == acc && !(x <= acc)) acc = x;
 }
 
 // min(1, max_norm / (norm + 1e-6)), torch.nn.utils.clip_grad_norm_'s rule; a NaN norm stays a NaN coefficient (torch.clamp keeps it too)

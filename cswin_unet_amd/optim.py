@@ -1,6 +1,6 @@
 """The optimisers of the training loops on flat buffers: SGD(momentum, weight_decay) of the reference's trainer.py:42,60-63
-(FlatSGD), clip_grad_norm_ + AdamW with a learning rate per tensor of its universal_train.py:693-725, 934-939 (FlatAdamW), and
-the trainable projection toward the pretrained weights of its :391-615 (FlatTPGM, over either of the two).
+(FlatSGD), clip_grad_norm_ + AdamW with a learning rate per tensor of its universal_train.py:693-725, 934-939 (FlatAdamW; with
+decoupled=False and set_auto_rates the Adam with per-step group rates of its finetune.py:183, 223-239), and the trainable projection toward the pretrained weights of its :391-615 (FlatTPGM, over either of the two).
 
 All parameters are re-pointed into ONE flat fp32 buffer (32-B aligned slots), the optimiser state and the gradients live in
 more of the same layout.  A step is a multi-tensor gather of the per-parameter .grad tensors into the flat gradient buffer (the
@@ -204,16 +204,59 @@ def column_tiles(shapes, offsets):
     return rows, np.array(first, dtype=np.int32)
 
 
+RATE_STATISTICS = ("grad", "ratio")    # cswin_rate_finalize's `statistic`, by index
+ADAM_MOMENTS = ("kept", "fresh")
+ADAM_COUPLED, ADAM_FRESH = 1, 2        # the bits of cswin_adam_flat's flags
+
+
+def group_table(groups, ntensors, statistic="grad"):
+    """The static table of cswin_rate_finalize (csrc/adamw.hip): (group_first, group_tensors, group_of, names).  groups: one entry
+    per tensor, a hashable group id or None for a tensor in no group; the groups are numbered in order of first appearance
+    (names[k] is group k's id).  group_first: int32 (G + 1,); group_tensors: int32 CSR list, group k's tensors are
+    group_tensors[group_first[k] .. group_first[k + 1] - 1] in tensor order (they need not be contiguous); group_of: int32 (T,), -1
+    for a tensor in no group.  This is the table's only producer, so the kernel's preconditions are checked here, and `statistic`
+    with them."""
+    if statistic not in RATE_STATISTICS:
+        raise ValueError(f"group_table: statistic must be one of {RATE_STATISTICS}, got {statistic!r}")
+    groups = list(groups)
+    if len(groups) != ntensors:
+        raise ValueError(f"group_table: {len(groups)} group entries for {ntensors} parameter tensors")
+    index, members = {}, []
+    group_of = np.full(ntensors, -1, np.int32)
+    for t, g in enumerate(groups):
+        if g is None:
+            continue
+        if g not in index:
+            index[g] = len(members)
+            members.append([])
+        group_of[t] = index[g]
+        members[index[g]].append(t)
+    if not members:
+        raise ValueError("group_table: no tensor is in a group")
+    first = np.cumsum([0] + [len(m) for m in members]).astype(np.int32)
+    tensors = np.array([t for m in members for t in m], dtype=np.int32)
+    return first, tensors, group_of, list(index)
+
+
 class FlatAdamW(_FlatBuffers):
     """torch.optim.AdamW (decoupled weight decay) on the flat buffers, with torch.nn.utils.clip_grad_norm_(max_grad_norm) fused
     in front of it when max_grad_norm is given and an optional learning-rate multiplier per parameter tensor (set_lr_weights).
     apply() is three launches (two without clipping), no host sync and no allocation; the step count lives on the host, where
-    the bias corrections 1 - beta^t are formed in Python floats as torch forms them."""
+    the bias corrections 1 - beta^t are formed in Python floats as torch forms them.
 
-    def __init__(self, params, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, max_grad_norm=None):
+    decoupled=False: torch.optim.Adam(weight_decay), the decay added to the gradient (finetune.py:183).  moments="fresh": m and v
+    are zero at every step and never touched, which is an optimiser built anew for every step (finetune.py:237); "kept" is Adam.
+    set_auto_rates: the multipliers are formed on the device from every step's own gradient (cswin_rate_finalize in the place of
+    cswin_norm_finalize, so still three launches and no host sync)."""
+
+    def __init__(self, params, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, max_grad_norm=None, decoupled=True, moments="kept"):
         self.betas, self.eps, self.weight_decay = (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
         if not (0.0 <= self.betas[0] < 1.0 and 0.0 <= self.betas[1] < 1.0):
             raise ValueError(f"FlatAdamW: betas {betas} must lie in [0, 1)")
+        if moments not in ADAM_MOMENTS:
+            raise ValueError(f"FlatAdamW: moments must be one of {ADAM_MOMENTS}, got {moments!r}")
+        self.decoupled, self.moments = bool(decoupled), moments
+        self._auto = None                                                                 # set_auto_rates()'s table and settings
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         super().__init__(params, lr)
         dev, T = self.flat_param.device, len(self.params)
@@ -239,13 +282,49 @@ class FlatAdamW(_FlatBuffers):
         """Per-tensor learning-rate multipliers aligned with self.params (None: all 1).  A multiplier of exactly 0 freezes the
         tensor bit for bit; its moments still move."""
         if w is None:
-            self._use_mult = False
+            self._use_mult, self._auto = False, None
             return
         w = torch.as_tensor(w, dtype=torch.float32).reshape(-1)
         if w.numel() != len(self.params):
             raise ValueError(f"FlatAdamW.set_lr_weights: {w.numel()} weights for {len(self.params)} parameter tensors")
         self._lr_mult.copy_(w)
+        self._use_mult, self._auto = True, None
+
+    def set_auto_rates(self, groups, statistic="grad", default=0.0):
+        """Per-step rates (finetune.py:223-236): from now on every apply() gives tensor t the multiplier n_k / max_j n_j of its
+        group k, formed on the device from that step's flat_grad * grad_scale.  groups: one entry per tensor of self.params, a group
+        id or None; statistic "grad": n_k = the norm of the group's concatenated gradient; "ratio": that over the norm of the
+        group's parameters (0 where that is <= 1e-8).  A tensor in no group gets `default`.  None turns the rates off (all
+        multipliers 1).  Replaces set_lr_weights' multipliers, as those replace these.  The table is built and uploaded here, once."""
+        if groups is None:
+            self._use_mult, self._auto = False, None
+            return
+        first, tensors, group_of, names = group_table(groups, len(self.params), statistic)
+        dev = self.flat_param.device
+        self._auto = {"groups": list(groups), "statistic": statistic, "default": float(default), "names": names, "n": len(names),
+                      "first": torch.from_numpy(first).to(dev), "tensors": torch.from_numpy(tensors).to(dev),
+                      "of": torch.from_numpy(group_of).to(dev), "stat": torch.zeros(len(names), dtype=torch.float32, device=dev)}
         self._use_mult = True
+
+    @property
+    def group_stats(self):
+        """Device (G,) tensor of the groups' statistics of the last apply() under set_auto_rates, the groups in order of first
+        appearance (no sync)."""
+        if self._auto is None:
+            raise RuntimeError("FlatAdamW.group_stats: no auto rates are set (set_auto_rates)")
+        return self._auto["stat"]
+
+    @property
+    def group_names(self):
+        """The group ids set_auto_rates was given, entry k for row k of group_stats."""
+        if self._auto is None:
+            raise RuntimeError("FlatAdamW.group_names: no auto rates are set (set_auto_rates)")
+        return list(self._auto["names"])
+
+    @property
+    def lr_weights(self):
+        """Device (T,) view of the multipliers the last apply() used (set_lr_weights', or that step's auto rates); None: all 1."""
+        return self._lr_mult if self._use_mult else None
 
     def _sumsq(self, with_params, tensor_sumsq, scalars, grad_scale, max_norm):
         call("cswin_chunk_sumsq", ptr(self.flat_grad), ptr(self.flat_param) if with_params else None, ptr(self.chunks), self.nchunks,
@@ -254,15 +333,31 @@ class FlatAdamW(_FlatBuffers):
              ptr(tensor_sumsq), ptr(scalars), stream())
 
     def apply(self, grad_scale=1.0):
-        """p, m, v <- AdamW(clip(flat_grad * grad_scale))."""
+        """p, m, v <- AdamW(clip(flat_grad * grad_scale)) -- Adam with decoupled=False, from zero moments with moments="fresh",
+        at this step's own rates under set_auto_rates."""
         bc1, bc2 = _next_bias_corrections(self, "FlatAdamW.apply()", self.betas)
-        clip = self.max_grad_norm is not None
-        if clip:
+        clip, auto = self.max_grad_norm is not None, self._auto
+        if auto is not None:
+            ratio = auto["statistic"] == "ratio"
+            call("cswin_chunk_sumsq", ptr(self.flat_grad), ptr(self.flat_param) if ratio else None, ptr(self.chunks), self.nchunks,
+                 ptr(self._partial), stream())
+            call("cswin_rate_finalize", ptr(self._partial), ptr(self.first_chunk), len(self.params), float(grad_scale),
+                 self.max_grad_norm if clip else float("inf"), ptr(auto["first"]), ptr(auto["tensors"]), ptr(auto["of"]), auto["n"],
+                 int(ratio), auto["default"], ptr(self.tensor_sumsq), ptr(self.scalars), ptr(auto["stat"]), ptr(self._lr_mult), stream())
+        elif clip:
             self._sumsq(False, self.tensor_sumsq, self.scalars, grad_scale, self.max_grad_norm)
-        call("cswin_adamw_flat", ptr(self.flat_param), ptr(self.flat_grad), ptr(self.flat_m), ptr(self.flat_v), ptr(self.chunks), self.nchunks,
-             ptr(self.lr_dev), ptr(self._lr_mult) if self._use_mult else None, ptr(self.scalars) if clip else None, *self.betas, self.eps,
-             self.weight_decay, float(grad_scale), bc1, bc2,
-             ptr(self.flat_param16) if precision() == 1 else None, stream())
+        fresh = self.moments == "fresh"
+        flags = (0 if self.decoupled else ADAM_COUPLED) | (ADAM_FRESH if fresh else 0)
+        if fresh:
+            bc1, bc2 = 1.0 - self.betas[0], 1.0 - self.betas[1]                           # every step is a new optimiser's first
+        head = (ptr(self.flat_param), ptr(self.flat_grad), None if fresh else ptr(self.flat_m), None if fresh else ptr(self.flat_v),
+                ptr(self.chunks), self.nchunks, ptr(self.lr_dev), ptr(self._lr_mult) if self._use_mult else None,
+                ptr(self.scalars) if clip else None, *self.betas, self.eps, self.weight_decay, float(grad_scale), bc1, bc2)
+        tail = (ptr(self.flat_param16) if precision() == 1 else None, stream())
+        if flags:
+            call("cswin_adam_flat", *head, flags, *tail)
+        else:
+            call("cswin_adamw_flat", *head, *tail)
 
     def tensor_norms(self):
         """(T, 2) device tensor of (||g||, ||p||) per parameter tensor, of flat_grad and flat_param as they are (no sync)."""
@@ -287,15 +382,30 @@ class FlatAdamW(_FlatBuffers):
         return out
 
     def state_dict(self):
-        return {"m": self.flat_m.clone(), "v": self.flat_v.clone(), "step": self.step_count, "lr": self.lr,
-                "lr_weights": self._lr_mult.clone() if self._use_mult else None}
+        """The keys "decoupled", "moments" and "auto_rates" are there only when one of them departs from AdamW with kept moments and
+        no auto rates: that optimiser's dict is the one it always wrote."""
+        auto = self._auto
+        sd = {"m": self.flat_m.clone(), "v": self.flat_v.clone(), "step": self.step_count, "lr": self.lr,
+              "lr_weights": self._lr_mult.clone() if self._use_mult else None}
+        if not self.decoupled or self.moments != "kept" or auto is not None:
+            sd.update(decoupled=self.decoupled, moments=self.moments,
+                      auto_rates=None if auto is None else {k: auto[k] for k in ("groups", "statistic", "default")})
+        return sd
 
     def load_state_dict(self, sd):
+        """A dict without the keys "decoupled", "moments" and "auto_rates" (one written before they existed) loads as it always
+        did and leaves the first two as this optimiser was built."""
+        moments = sd.get("moments", self.moments)
+        if moments not in ADAM_MOMENTS:
+            raise ValueError(f"FlatAdamW.load_state_dict: moments must be one of {ADAM_MOMENTS}, got {moments!r}")
         self.flat_m.copy_(sd["m"])
         self.flat_v.copy_(sd["v"])
         self.step_count = int(sd["step"])
         self.set_lr(sd["lr"])
+        self.decoupled, self.moments = bool(sd.get("decoupled", self.decoupled)), moments
         self.set_lr_weights(sd["lr_weights"])
+        if sd.get("auto_rates") is not None:
+            self.set_auto_rates(**sd["auto_rates"])
 
 
 TPGM_BETAS, TPGM_EPS = (0.9, 0.999), 1e-8       # torch.optim.Adam's defaults, which universal_train.py:552 takes; csrc/tpgm.hip holds the same constants

@@ -30,7 +30,7 @@ import torch.distributed as dist
 from ._lib import call, ptr, stream
 from .continual import Distill
 from .ops import CeDiceObjective, ContinualObjective, augment_batch, engine_backward
-from .optim import FlatAdamW, FlatSGD
+from .optim import ADAM_MOMENTS, FlatAdamW, FlatSGD
 
 
 def init_distributed():
@@ -74,6 +74,7 @@ def scale_lr_for_batch(base_lr, batch_size):
     return base_lr * batch_size / 24 if (batch_size != 24 and batch_size % 6 == 0) else base_lr
 
 
+ENGINE_OPTIMIZERS = ("sgd", "adamw", "adam")
 DECODER_PREFIXES = ("stage_up", "upsample", "concat_linear", "norm_up", "output")
 
 
@@ -90,21 +91,28 @@ class HipEngine:
 
     optimizer: "sgd" (FlatSGD, the reference's trainer.py) or "adamw" (FlatAdamW, its universal_train.py: `momentum` is ignored,
     `weight_decay` is AdamW's decoupled decay, max_grad_norm clips the global gradient norm first).  Under data parallelism the
-    update runs after the all-reduce, so the norm is the averaged gradient's and every rank forms the same coefficient."""
+    update runs after the all-reduce, so the norm is the averaged gradient's and every rank forms the same coefficient.
+    "adam" is the reference's finetune.py:183: torch.optim.Adam, whose `weight_decay` is added to the gradient (coupled L2); it
+    clips like "adamw" when max_grad_norm is given.  moments ("adamw" and "adam"): "kept" is the optimiser as torch runs it, "fresh"
+    takes both moments as zero at every step, which is finetune.py:237's optimiser built anew for every step.  set_auto_rates
+    turns on that loop's per-step learning rates."""
 
     def __init__(self, model, num_classes, lr, momentum, weight_decay, w_ce, w_dice, use_graph=True, distill=None, optimizer="sgd",
-                 max_grad_norm=None, betas=(0.9, 0.999), eps=1e-8):
-        if optimizer not in ("sgd", "adamw"):
-            raise ValueError(f'HipEngine: optimizer must be "sgd" or "adamw", got {optimizer!r}')
+                 max_grad_norm=None, betas=(0.9, 0.999), eps=1e-8, moments="kept"):
+        if optimizer not in ENGINE_OPTIMIZERS:
+            raise ValueError(f"HipEngine: optimizer must be one of {ENGINE_OPTIMIZERS}, got {optimizer!r}")
         if optimizer == "sgd" and max_grad_norm is not None:
-            raise ValueError('HipEngine: max_grad_norm needs optimizer="adamw" (FlatSGD does not clip)')
+            raise ValueError('HipEngine: max_grad_norm needs optimizer="adamw" or "adam" (FlatSGD does not clip)')
+        if moments not in ADAM_MOMENTS or (optimizer == "sgd" and moments != "kept"):
+            raise ValueError(f'HipEngine: moments must be one of {ADAM_MOMENTS} ("fresh" with optimizer="adamw" or "adam" only), got {moments!r}')
         self.model, self.ncls, self.w_ce, self.w_dice = model, num_classes, w_ce, w_dice
         self.distill = Distill.of(distill)
         self.core = model.cswin_unet if hasattr(model, "cswin_unet") else model
         names = [n for n, p in model.named_parameters() if p.requires_grad]
         self.param_names = names                        # aligned with self.opt.params
-        if optimizer == "adamw":
-            self.opt = FlatAdamW(model.parameters(), lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+        if optimizer != "sgd":
+            self.opt = FlatAdamW(model.parameters(), lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
+                                 decoupled=optimizer == "adamw", moments=moments)
         else:
             self.opt = FlatSGD(model.parameters(), lr=lr, momentum=momentum, weight_decay=weight_decay)
         is_dec = [any(seg.startswith(DECODER_PREFIXES) for seg in n.split(".")[:2]) for n in names]
@@ -150,6 +158,39 @@ class HipEngine:
         if unknown:
             raise KeyError(f"HipEngine.set_lr_weights: no trainable parameter named {sorted(unknown)[:4]}")
         self.opt.set_lr_weights([float(weights.get(n, default)) for n in self.param_names])
+
+    def set_auto_rates(self, groups, statistic="grad", default=0.0):
+        """Per-step learning rates (finetune.py:223-236): every step gives the tensors of group k the rate lr * n_k / max_j n_j,
+        n the groups' statistics of that step's own gradient, formed on the device (FlatAdamW.set_auto_rates: no host read, the
+        same three launches).  groups: {group: [parameter names]} (continual.finetune_groups), or "tensors" for one group per
+        tensor; statistic: "grad", the norm of the group's gradient, or "ratio", that over the norm of its parameters; a tensor
+        in no group gets the multiplier `default`.  None turns the rates off.  Replaces set_lr_weights, and is replaced by it.
+        optimizer="adamw" or "adam" only.  Under data parallelism the update runs after the all-reduce, so every rank forms the
+        same rates from the same averaged flat_grad and the replicas stay bit-identical.  opt.group_stats holds the statistics
+        of the last step, one per entry of opt.group_names (the groups in the order their first tensor has among the parameters),
+        opt.lr_weights the multipliers."""
+        if not hasattr(self.opt, "set_auto_rates"):
+            raise ValueError('HipEngine.set_auto_rates needs optimizer="adamw" or "adam"')
+        if groups is None:
+            self.opt.set_auto_rates(None)
+            return
+        if isinstance(groups, str):
+            if groups != "tensors":
+                raise ValueError(f'HipEngine.set_auto_rates: groups must be {{group: [parameter names]}} or "tensors", got {groups!r}')
+            per_tensor = list(range(len(self.param_names)))
+        else:
+            named = [n for members in groups.values() for n in members]
+            unknown = set(named) - set(self.param_names)
+            if unknown:
+                raise KeyError(f"HipEngine.set_auto_rates: no trainable parameter named {sorted(unknown)[:4]}")
+            if len(named) != len(set(named)):
+                raise ValueError("HipEngine.set_auto_rates: a parameter is named in more than one group")
+            empty = [g for g, members in groups.items() if not members]
+            if empty:
+                raise ValueError(f"HipEngine.set_auto_rates: group {empty[0]!r} has no parameter")
+            where = {n: g for g, members in groups.items() for n in members}
+            per_tensor = [where.get(n) for n in self.param_names]
+        self.opt.set_auto_rates(per_tensor, statistic, default)
 
     # ---- eager pieces -------------------------------------------------------------------------------------------
     def _forward_sums(self, img, lab):
@@ -317,15 +358,20 @@ class DataParallelTrainer:
 
     def __init__(self, model=None, num_classes=9, base_lr=0.05, max_iterations=1000, momentum=0.9, weight_decay=1e-4,
                  group=None, use_graph=True, buckets=2, w_ce=0.4, w_dice=0.6, engine=None, force_collectives=False,
-                 allreduce_dtype=None, distill=None, optimizer="sgd", max_grad_norm=None, lr_schedule="poly"):
+                 allreduce_dtype=None, distill=None, optimizer="sgd", max_grad_norm=None, lr_schedule="poly", moments="kept"):
         if lr_schedule not in ("poly", "constant"):
             raise ValueError(f'DataParallelTrainer: lr_schedule must be "poly" or "constant", got {lr_schedule!r}')
+        if engine is None and optimizer not in ("sgd", "adamw"):
+            # this argument keeps its two values; the fine-tuning loop's coupled Adam comes in as an engine of its own
+            raise ValueError(f'DataParallelTrainer: optimizer must be "sgd" or "adamw", got {optimizer!r} '
+                             f'(torch.optim.Adam\'s coupled decay: pass engine=HipEngine(..., optimizer="adam"))')
         self.lr_schedule = lr_schedule                  # "constant": the step leaves the rate alone (an outer loop sets it, cosine_lr)
         self.group = group
         self.world = dist.get_world_size(group) if group is not None else 1
         self.base_lr, self.max_iterations, self.iter_num = base_lr, max_iterations, 0
         self.engine = engine if engine is not None else HipEngine(model, num_classes, base_lr, momentum, weight_decay,
-                                                                 w_ce, w_dice, use_graph, distill, optimizer, max_grad_norm)
+                                                                 w_ce, w_dice, use_graph, distill, optimizer, max_grad_norm,
+                                                                 moments=moments)
         self.model = model
         self.nbuckets = max(1, buckets)
         # torch.bfloat16: gradients travel as bf16 (47 MB instead of 94 MB per step, BASELINE configs[2]); the sum is formed
@@ -341,6 +387,11 @@ class DataParallelTrainer:
     @property
     def stats(self):
         return self.engine.stats
+
+    def set_auto_rates(self, groups, statistic="grad", default=0.0):
+        """HipEngine.set_auto_rates.  The update runs after the all-reduce, so every rank forms the same rates from the same
+        averaged flat_grad: nothing more travels, and the replicas stay bit-identical."""
+        self.engine.set_auto_rates(groups, statistic, default)
 
     # ---- per-phase timing of the backward / all-reduce / update part of a step (bench.py's dp_diagnostics) ----
     _timing = None
@@ -479,7 +530,35 @@ class _Prefetcher:
         return img, lab
 
 
-def trainer_synapse(args, model, snapshot_path, group=None, log_every=1):
+def _step_options(args):
+    """The optional attributes of trainer_synapse's `args` that choose the step, each defaulting to trainer.py's own; checked
+    before any file or device is touched."""
+    from fractions import Fraction
+
+    from .optim import RATE_STATISTICS
+    o = dict(optimizer=getattr(args, "optimizer", "sgd"), weight_decay=getattr(args, "weight_decay", 1e-4), w_ce=getattr(args, "w_ce", 0.4),
+             w_dice=getattr(args, "w_dice", 0.6), lr_schedule=getattr(args, "lr_schedule", "poly"), moments=getattr(args, "moments", "kept"),
+             auto_rates=getattr(args, "auto_rates", None), subset=getattr(args, "subset_fraction", None))
+    if o["optimizer"] not in ENGINE_OPTIMIZERS:
+        raise ValueError(f"trainer_synapse: optimizer must be one of {ENGINE_OPTIMIZERS}, got {o['optimizer']!r}")
+    if o["lr_schedule"] not in ("poly", "constant"):
+        raise ValueError(f'trainer_synapse: lr_schedule must be "poly" or "constant", got {o["lr_schedule"]!r}')
+    if o["moments"] not in ADAM_MOMENTS or (o["optimizer"] == "sgd" and o["moments"] != "kept"):
+        raise ValueError(f'trainer_synapse: moments must be one of {ADAM_MOMENTS} ("fresh" with optimizer="adamw" or "adam" only), got {o["moments"]!r}')
+    if o["auto_rates"] is not None:
+        if o["auto_rates"] not in RATE_STATISTICS:
+            raise ValueError(f"trainer_synapse: auto_rates must be None or one of {RATE_STATISTICS}, got {o['auto_rates']!r}")
+        if o["optimizer"] == "sgd":
+            raise ValueError('trainer_synapse: auto_rates needs optimizer="adamw" or "adam" (FlatSGD has one rate)')
+    if o["subset"] is not None:
+        if not 0.0 < float(o["subset"]) <= 1.0:
+            raise ValueError(f"trainer_synapse: subset_fraction must lie in (0, 1], got {o['subset']!r}")
+        f = Fraction(o["subset"]).limit_denominator(1000)               # 0.2 is 1/5: n // 5 slices, as finetune.py:167 counts them
+        o["subset"] = (f.numerator, f.denominator)
+    return o
+
+
+def trainer_synapse(args, model, snapshot_path, group=None, log_every=1, checkpoint=None):
     """Counterpart of the reference's ``trainer_synapse(args, model, snapshot_path)`` (trainer.py:20-95) on the HIP engine.
 
     args: root_path, list_dir, img_size, num_classes, batch_size (per GPU), base_lr, max_epochs, optionally num_workers and
@@ -492,7 +571,14 @@ def trainer_synapse(args, model, snapshot_path, group=None, log_every=1):
     of the second half and at the end, :79-90).  Differences, all execution-side: one process per GPU (pass the process
     group; each rank reads its own shard through a DistributedSampler) instead of nn.DataParallel; batches are prefetched
     to the device on a side stream; the last incomplete batch of an epoch is dropped because the step is a captured
-    hipGraph with a fixed batch shape; tensorboard image logging is not reproduced."""
+    hipGraph with a fixed batch shape; tensorboard image logging is not reproduced.
+
+    Further optional attributes of args choose another step, each defaulting to the above (surgical_trainer sets them all):
+    optimizer ("sgd", "adamw", "adam": HipEngine's), weight_decay (1e-4), w_ce / w_dice (0.4 / 0.6), lr_schedule ("poly", or
+    "constant": the rate stays base_lr), moments ("kept" / "fresh": HipEngine's), auto_rates (None, or "grad" / "ratio": per-step
+    rates over continual.finetune_groups(model) with that statistic, HipEngine.set_auto_rates), subset_fraction (None, or the part
+    of the slices to train on, torch.randperm(n, generator=manual_seed(seed))[:n * fraction], finetune.py:166-169).
+    checkpoint: None for the schedule above, or a function epoch -> file name or None."""
     import logging
     import random
     import sys
@@ -510,6 +596,7 @@ def trainer_synapse(args, model, snapshot_path, group=None, log_every=1):
     if blur_sigma is not None:
         from .utils import gaussian_taps
         gaussian_taps(blur_sigma)                                       # ValueError for a sigma neither path takes
+    opts = _step_options(args)
     os.makedirs(snapshot_path, exist_ok=True)
     logging.basicConfig(filename=os.path.join(snapshot_path, "log.txt"), level=logging.INFO,
                         format='[%(asctime)s.%(msecs)03d] %(message)s', datefmt='%H:%M:%S')
@@ -522,8 +609,14 @@ def trainer_synapse(args, model, snapshot_path, group=None, log_every=1):
     db_train = Synapse_dataset(base_dir=args.root_path, list_dir=args.list_dir, split="train",
                                transform=RawSliceParams(output_size=[args.img_size, args.img_size]) if augment == "hip" else
                                RandomGenerator(output_size=[args.img_size, args.img_size], blur_sigma=blur_sigma))
-    print("The length of train set is: {}".format(len(db_train)))
     seed = getattr(args, "seed", 1234)
+    if opts["subset"] is not None:
+        # finetune.py:166-169: a fixed random part of the slices, drawn once from the seed
+        num, den = opts["subset"]
+        n_all = len(db_train)
+        keep = torch.randperm(n_all, generator=torch.Generator().manual_seed(seed))[:n_all * num // den]
+        db_train = torch.utils.data.Subset(db_train, keep.tolist())
+    print("The length of train set is: {}".format(len(db_train)))
 
     n_workers = getattr(args, "num_workers", 8)
 
@@ -544,7 +637,17 @@ def trainer_synapse(args, model, snapshot_path, group=None, log_every=1):
                          f"(the captured step has a fixed batch shape, the last incomplete batch is dropped)")
     logging.info("{} iterations per epoch. {} max iterations ".format(len(loader), max_iterations))
     model.train()
-    trainer = DataParallelTrainer(model, args.num_classes, base_lr=args.base_lr, max_iterations=max_iterations, group=group)
+    step = dict(weight_decay=opts["weight_decay"], w_ce=opts["w_ce"], w_dice=opts["w_dice"])
+    if opts["optimizer"] == "adam":                  # DataParallelTrainer's own `optimizer` keeps its two values: the engine is handed in
+        engine = HipEngine(model, args.num_classes, args.base_lr, 0.9, use_graph=True, optimizer="adam", moments=opts["moments"], **step)
+        step = dict(engine=engine)
+    else:
+        step.update(optimizer=opts["optimizer"], moments=opts["moments"])
+    trainer = DataParallelTrainer(model, args.num_classes, base_lr=args.base_lr, max_iterations=max_iterations, group=group,
+                                  lr_schedule=opts["lr_schedule"], **step)
+    if opts["auto_rates"] is not None:
+        from .continual import finetune_groups
+        trainer.set_auto_rates(finetune_groups(model), opts["auto_rates"])
     iter_num = 0
     for epoch_num in range(max_epoch):
         if sampler is not None:
@@ -555,10 +658,47 @@ def trainer_synapse(args, model, snapshot_path, group=None, log_every=1):
             if log_every and iter_num % log_every == 0 and rank == 0:
                 loss, loss_ce, _ = stats.tolist()                    # the only host sync of the loop
                 logging.info('iteration %d : loss : %f, loss_ce: %f' % (iter_num, loss, loss_ce))
-        save_interval = 3
-        last = epoch_num >= max_epoch - 1
-        if rank == 0 and (last or (epoch_num > int(max_epoch / 2) and (epoch_num + 1) % save_interval == 0)):
-            save_mode_path = os.path.join(snapshot_path, 'epoch_' + str(epoch_num) + '.pth')
+                if opts["auto_rates"] is not None:                   # finetune.py:236 logs every group's rate; same sync point
+                    opt = trainer.engine.opt
+                    rates = dict(zip(opt.group_names, (opt.group_stats / opt.group_stats.max() * opt.lr_dev).tolist()))
+                    logging.info('iteration %d : group rates : %s' % (iter_num, rates))
+        if checkpoint is not None:
+            name = checkpoint(epoch_num)
+        else:
+            save_interval = 3
+            last = epoch_num >= max_epoch - 1
+            name = 'epoch_' + str(epoch_num) + '.pth' if last or (epoch_num > int(max_epoch / 2) and (epoch_num + 1) % save_interval == 0) else None
+        if rank == 0 and name is not None:
+            save_mode_path = os.path.join(snapshot_path, name)
             save_checkpoint(model, save_mode_path)
             logging.info("save model to {}".format(save_mode_path))
     return "Training Finished!"
+
+
+def surgical_trainer(args, model, snapshot_path, group=None, log_every=1):
+    """Counterpart of the reference's ``surgical_trainer(args, model, snapshot_path)`` (finetune.py:146-254), its surgical
+    fine-tuning on the blurred Synapse slices, for ONE (lr, weight decay) pair: args.base_lr and args.weight_decay (default 1e-4).
+    The reference sweeps continual.FINETUNE_GRID from one pretrained model; that sweep is the caller's loop, a fresh copy of the
+    model per pair.
+
+    It is trainer_synapse with: loss 0.2 CE + 0.8 Dice (:205); torch.optim.Adam with coupled weight decay (:183, optimizer="adam");
+    a constant rate; every step's rate of each of the 22 groups of continual.finetune_groups set to lr * n_k / max_j n_j, n the
+    norm of the group's gradient (:116-144, 225-236; auto_rates="grad", formed on the device); a fifth of the slices, drawn once
+    from args.seed (:166-169); a checkpoint model_lr{lr}_wd{wd}_epoch{epoch}.pth whenever epoch % args.save_interval == 0 (:250-251,
+    save_interval defaults to 1).  args.moments ("kept" by default) chooses between Adam with running moments and the reference
+    as written, which builds a new optimiser every step ("fresh").  args.auto_rates and args.subset_fraction override the
+    statistic and the part.  Deviations: one forward/backward per step, whose gradient is both measured and
+    applied, where the reference measures on a second batch and steps with that batch's gradient; the per-step tune_metrics.pt
+    and the debug image are not written (the group rates are logged every log_every steps)."""
+    import copy
+
+    args = copy.copy(args)
+    lr, wd = args.base_lr, getattr(args, "weight_decay", 1e-4)
+    interval = getattr(args, "save_interval", 1)
+    args.optimizer, args.weight_decay, args.w_ce, args.w_dice, args.lr_schedule = "adam", wd, 0.2, 0.8, "constant"
+    args.moments = getattr(args, "moments", "kept")
+    args.auto_rates = getattr(args, "auto_rates", "grad")
+    args.subset_fraction = getattr(args, "subset_fraction", 0.2)
+    trainer_synapse(args, model, snapshot_path, group=group, log_every=log_every,
+                    checkpoint=lambda epoch: f"model_lr{lr}_wd{wd}_epoch{epoch}.pth" if epoch % interval == 0 else None)
+    return "Surgical Training Finished!"

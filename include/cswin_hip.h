@@ -30,7 +30,7 @@ extern "C" {
  * cswin_attn_fwd writes y0, cswin_attn_bwd reads it).  cswin_abi_version() returns the value the library was built with: a consumer
  * compiled against another header must refuse to call it.  Entry points that are only ADDED (cswin_seg_metrics*, cswin_resize_banded, cswin_argmax_zoom_back, cswin_augment_*,
  * cswin_chunk_sumsq, cswin_norm_finalize, cswin_adamw_flat, cswin_tpgm_*, cswin_argmax_zoom_back_classes, cswin_class_counts, cswin_gaussian_blur, cswin_eb_tiles,
- * cswin_eb_finalize) do not bump it: every prototype an older consumer binds is unchanged. */
+ * cswin_eb_finalize, cswin_rate_finalize, cswin_adam_flat) do not bump it: every prototype an older consumer binds is unchanged. */
 #define CSWIN_ABI_VERSION 4
 
 #define CSWIN_OK 0
@@ -360,6 +360,32 @@ int cswin_norm_finalize(const float* partial, const int* first_chunk, int ntenso
 int cswin_adamw_flat(float* p, const float* g, float* m, float* v, const void* chunks, int nchunks, const float* lr_dev,
                      const float* lr_mult, const float* scalars, double beta1, double beta2, double eps, float weight_decay,
                      float grad_scale, double bc1, double bc2, void* shadow_bf16, void* stream);
+
+/* ---- per-step rates of the surgical fine-tuning loop (finetune.py:116-144, 223-239): every parameter group's learning rate is
+ * lr * n_k / max_j n_j of this step's gradient, and the step is torch.optim.Adam(weight_decay) ----
+ *
+ * One workgroup, in place of cswin_norm_finalize: tensor_sumsq and scalars come out bit for bit as that entry point writes them, and then
+ * over the static group table (group k's tensors are group_tensors[group_first[k] .. group_first[k + 1] - 1], in tensor order, not
+ * necessarily contiguous; group_of[t] is tensor t's group, or -1; the table is the caller's, optim.group_table builds and checks it):
+ *   sums of group k = its tensors' (sum g^2, sum p^2) added in the table's order;
+ *   statistic 0: group_stat[k] = grad_scale * sqrt(sum g^2), the norm of the group's concatenated gradient (finetune.py:135-140);
+ *   statistic 1: that divided by sqrt(sum p^2) where sqrt(sum p^2) > 1e-8, else 0 (universal_train.py:661-690); cswin_chunk_sumsq must
+ *     have been given the parameters;
+ *   top = the maximum of group_stat in group order; lr_mult[t] = group_stat[group_of[t]] / top, default_mult where group_of[t] == -1.
+ * top <= 0 makes every grouped multiplier 0.  A NaN statistic makes top NaN and with it every grouped multiplier: reported, not
+ * repaired.  No float atomics, every sum in a fixed order.  Any ntensors >= 1 and ngroups >= 1. */
+int cswin_rate_finalize(const float* partial, const int* first_chunk, int ntensors, float grad_scale, float max_norm,
+                        const int* group_first, const int* group_tensors, const int* group_of, int ngroups, int statistic,
+                        float default_mult, float* tensor_sumsq, float* scalars, float* group_stat, float* lr_mult, void* stream);
+/* cswin_adamw_flat with flags; flags == 0 is cswin_adamw_flat itself, bit for bit.
+ *   bit 0, coupled L2 decay (torch.optim.Adam's grad.add(param, alpha=wd)): g' = (grad_scale * clip_coef) g + wd p, the moments and
+ *     the quotient as above, p -= (lr_t / bc1) m / (sqrt(v) / sqrt(bc2) + eps); there is no decay factor.
+ *   bit 1, fresh moments (an optimiser built anew for every step, finetune.py:237): m and v are taken as 0, neither read nor
+ *     written, and may be NULL; the caller passes bc1 = 1 - beta1, bc2 = 1 - beta2.  12 bytes move per element instead of 28.
+ * The frozen rule (lr_mult[t] == 0: p and its shadow are not stored), the shadow and the alignment are cswin_adamw_flat's. */
+int cswin_adam_flat(float* p, const float* g, float* m, float* v, const void* chunks, int nchunks, const float* lr_dev,
+                    const float* lr_mult, const float* scalars, double beta1, double beta2, double eps, float weight_decay,
+                    float grad_scale, double bc1, double bc2, int flags, void* shadow_bf16, void* stream);
 
 /* ---- TPGM, the trainable projection of the continual-learning loop (universal_train.py:391-615; the gradient of the radii is
  * tpgm.py:47-56's), on the flat buffers and the chunk table above.  Per tensor t, with d = p - anchor:
