@@ -85,6 +85,9 @@ SIGNATURES = {
     "cswin_seg_metrics_nbins": (I, [I, I, I]),
     "cswin_seg_metrics_workspace": (SZ, [I, I, I, I, I]),
     "cswin_seg_metrics": (I, [P, P, P, P, P, SZ, I, I, I, I, I, P]),
+    "cswin_components_workspace": (SZ, [I, I, I]),
+    "cswin_components_label": (I, [P, P, P, P, SZ, I, I, I, I, P]),
+    "cswin_components_filter": (I, [P, P, P, P, P, P, P, SZ, I, I, I, I, P]),
     "cswin_resize_banded": (I, [P, P, P, P, I, P, P, I, I, I, I, I, I, I, P]),
     "cswin_argmax_zoom_back": (I, [P, P, P, P, I, I, I, I, I, I, P]),
     "cswin_argmax_zoom_back_classes": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P]),

@@ -17,7 +17,7 @@ from ._lib import AugmentDesc, ConvImageJob, CswinHipError, ReduceJob, WgradDesc
 
 __all__ = ["layer_norm", "linear", "linear_pair", "mlp", "stripe_attention", "cswin_block", "conv_tokens", "patch_embed_conv", "carafe_reassemble",
            "carafe_reassemble_nchw", "conv_weight_images", "head_compose", "tokens_to_nchw", "matmul_nn", "ce_dice_loss", "continual_loss", "dropout", "img2windows", "windows2img",
-           "seg_metrics", "resize_slices", "argmax_zoom_back", "augment_batch", "class_counts", "gaussian_blur"]
+           "seg_metrics", "connected_components", "filter_components", "COMPONENT_TILE", "resize_slices", "argmax_zoom_back", "augment_batch", "class_counts", "gaussian_blur"]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1217,6 +1217,73 @@ def seg_metrics(pred, label, ncls, ndim=None):
     ws = torch.empty(nbytes, dtype=torch.uint8, device=pred.device)
     call("cswin_seg_metrics", ptr(pred), ptr(label), ptr(counts), ptr(hist), ptr(ws), nbytes, D, H, W, ndim, int(ncls), stream())
     return counts, hist
+
+
+# ------------------------------------------------------------------------------------------------
+# connected components of a label volume and the per-class size filter
+# ------------------------------------------------------------------------------------------------
+COMPONENT_TILE = (4, 16, 64)          # (z, y, x) tile of the labelling's tile pass (csrc/components_uf.h: CC_TZ, CC_TY, CC_TX)
+
+
+def _component_volume(vol, ncls, what):
+    if not vol.is_cuda:
+        raise CswinHipError(f"{what} volume is on {vol.device}: the cswin_unet_amd ops run on a HIP device only (no CPU fallback)")
+    if vol.dtype != torch.uint8:
+        raise CswinHipError(f"{what} volume has dtype {vol.dtype}; class ids are passed as uint8")
+    if vol.dim() not in (2, 3):
+        raise CswinHipError(f"{what}: volume {tuple(vol.shape)} must be (D, H, W) or (H, W)")
+    vol = vol.contiguous()
+    D, H, W = (1,) * (3 - vol.dim()) + tuple(vol.shape)
+    h = lib()
+    nbytes = h.cswin_components_workspace(D, H, W)
+    if nbytes == 0:
+        raise CswinHipError(f"{what}: {h.cswin_last_error().decode()}")
+    return vol, (D, H, W), int(ncls), nbytes
+
+
+def _label_components(vol, dims, ncls, nbytes, want_sizes):
+    labels = torch.empty(vol.shape, dtype=torch.int32, device=vol.device)
+    sizes = torch.empty(vol.shape, dtype=torch.int32, device=vol.device) if want_sizes else None
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=vol.device)
+    call("cswin_components_label", ptr(vol), ptr(labels), ptr(sizes), ptr(ws), nbytes, *dims, ncls, stream())
+    return labels, sizes, ws
+
+
+def connected_components(vol, ncls, return_sizes=False):
+    """Face-connected components of every foreground class of a label volume (csrc/components.hip): what
+    scipy.ndimage.label(vol == c) finds for every c in 1..ncls-1, in one call.  vol: uint8 HIP tensor (D, H, W) or (H, W); ids 0
+    and >= ncls are background.  Returns int32 `labels` of vol's shape: 0 for background, else 1 + the smallest flat index of the
+    voxel's component (the same bits on every run); with return_sizes also int32 `sizes`: the voxel count of a component at its
+    smallest flat index, 0 elsewhere.  ncls in 2..255, each dimension in 1..2048.  No host sync."""
+    vol, dims, ncls, nbytes = _component_volume(vol, ncls, "connected_components")
+    labels, sizes, _ = _label_components(vol, dims, ncls, nbytes, return_sizes)
+    return (labels, sizes) if return_sizes else labels
+
+
+_rule_tables = {}
+
+
+def filter_components(vol, ncls, rule, out=None):
+    """vol with the small components of each class set to 0 (csrc/components.hip).  rule: "largest", or a mapping
+    {class_id: {"min_size": int, "min_fraction": float}} (utils.component_rule_tables; ValueError for a bad one): a component of
+    class c stays iff it has at least max(min_size, ceil(min_fraction * largest component of c)) voxels; classes the rule does not
+    name, background and ids >= ncls pass through.  vol: uint8 HIP tensor (D, H, W) or (H, W).  out: None (a new tensor), vol
+    itself (in place) or another contiguous uint8 tensor of vol's shape.  Returns out.  No host sync once the rule's two small
+    tables are on the device (uploaded once per rule and device); utils.filter_components_host is the same rule in scipy."""
+    from .utils import component_rule_tables
+    ms, mf = component_rule_tables(rule, ncls)
+    vol, dims, ncls, nbytes = _component_volume(vol, ncls, "filter_components")
+    if out is None:
+        out = torch.empty_like(vol)
+    elif not (out.is_cuda and out.dtype == torch.uint8 and out.shape == vol.shape and out.is_contiguous()):
+        raise CswinHipError(f"filter_components: out must be a contiguous uint8 HIP tensor of shape {tuple(vol.shape)}")
+    key = (ms.tobytes(), mf.tobytes(), torch.device(vol.device))
+    if key not in _rule_tables:
+        _rule_tables[key] = (torch.from_numpy(ms.copy()).to(vol.device), torch.from_numpy(mf.copy()).to(vol.device))
+    dms, dmf = _rule_tables[key]
+    labels, sizes, ws = _label_components(vol, dims, ncls, nbytes, True)
+    call("cswin_components_filter", ptr(vol), ptr(labels), ptr(sizes), ptr(dms), ptr(dmf), ptr(out), ptr(ws), nbytes, *dims, ncls, stream())
+    return out
 
 
 # ------------------------------------------------------------------------------------------------

@@ -18,6 +18,9 @@ Mirrors the reference's utils.py names and call signatures:
     over ``net(x)[:, class_indices]``, on the device through the class list of ops.argmax_zoom_back.
     ``blur_sigma`` scores on the blurred copy of the data (apply_blur_test.py:79-81: ``gaussian_filter`` of every slice) without
     writing that copy: scipy per slice on the host path, ops.gaussian_blur (csrc/blur.hip, same bits) with ``resize="hip"``.
+    ``components`` (not in the reference) drops, per class, the small face-connected components of the finished prediction before
+    it is scored: ``filter_components_host`` (scipy.ndimage.label) on the host path, ops.filter_components (csrc/components.hip,
+    same result) on the resident volume with ``resize="hip"``.
 """
 import functools
 import logging
@@ -26,6 +29,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 from scipy.ndimage import binary_erosion, distance_transform_edt, gaussian_filter, gaussian_filter1d, generate_binary_structure, rotate, zoom
+from scipy.ndimage import label as ndimage_label
 
 from . import ops
 
@@ -295,9 +299,64 @@ def gaussian_taps_device(sigma, truncate, device):
     return _device_tables[key]
 
 
-def _predict_volume_hip(vol, net, patch_size, batch_slices, device, class_indices=None, blur_sigma=None):
+def component_rule_tables(rule, ncls):
+    """The per-class tables of a component filter rule: ``(min_size int64 [ncls], min_fraction float64 [ncls])``.  rule is
+    "largest" (min_fraction 1 for every foreground class) or a mapping {class_id: {"min_size": int, "min_fraction": float}} with
+    either key optional; classes that are not named get (0, 0.0) and stay untouched, entry 0 (background) is never used.  A
+    component of class c is kept iff its voxel count is >= max(min_size[c], ceil(min_fraction[c] * largest component of c)).
+    ValueError for ncls outside 2..255, another rule, a class id outside 1..ncls-1, a negative or non-integral min_size, a
+    min_fraction outside [0, 1] and an unknown key."""
+    ncls = int(ncls)
+    if not 2 <= ncls <= 255:
+        raise ValueError(f"component rule: ncls={ncls} outside 2..255")
+    ms, mf = np.zeros(ncls, np.int64), np.zeros(ncls, np.float64)
+    if isinstance(rule, str):
+        if rule != "largest":
+            raise ValueError(f'component rule: {rule!r} is not "largest" or a mapping of class ids')
+        mf[1:] = 1.0
+        return ms, mf
+    if not hasattr(rule, "items"):
+        raise ValueError(f'component rule: {rule!r} is not "largest" or a mapping of class ids')
+    for c, spec in rule.items():
+        if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 1 <= c < ncls:
+            raise ValueError(f"component rule: {c!r} is not a foreground class id in [1, {ncls})")
+        if not hasattr(spec, "items") or set(spec) - {"min_size", "min_fraction"}:
+            raise ValueError(f'component rule: class {c}: {spec!r} must be a mapping with the keys "min_size" and / or "min_fraction"')
+        size, frac = spec.get("min_size", 0), spec.get("min_fraction", 0.0)
+        if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or not 0 <= size < 2 ** 63:
+            raise ValueError(f"component rule: class {c}: min_size={size!r} must be a non-negative integer")
+        if isinstance(frac, bool) or not isinstance(frac, (int, float, np.integer, np.floating)) or not 0.0 <= frac <= 1.0:
+            raise ValueError(f"component rule: class {c}: min_fraction={frac!r} must lie in [0, 1]")
+        ms[c], mf[c] = int(size), float(frac)
+    return ms, mf
+
+
+def filter_components_host(vol, ncls, rule):
+    """The component filter in scipy: per class c the rule names, ``scipy.ndimage.label(vol == c)`` (face neighbours), the
+    threshold max(min_size, ceil(min_fraction * largest)) in float64, and every smaller component set to 0.  vol: integer array
+    (D, H, W) or (H, W); ids 0 and >= ncls pass through.  Returns a new array of vol's dtype.  The host path of
+    predict_volume(components=...) and what ops.filter_components computes on the device."""
+    ms, mf = component_rule_tables(rule, ncls)
+    vol = np.asarray(vol)
+    out = vol.copy()
+    for c in range(1, int(ncls)):
+        if ms[c] == 0 and mf[c] == 0.0:
+            continue
+        lab, n = ndimage_label(vol == c)
+        if n == 0:
+            continue
+        sizes = np.bincount(lab.ravel(), minlength=n + 1)
+        thr = max(int(ms[c]), int(np.ceil(np.float64(mf[c]) * np.float64(sizes[1:].max()))))
+        keep = sizes >= thr
+        keep[0] = True                                                  # everything that is not class c
+        out[~keep[lab]] = 0
+    return out
+
+
+def _predict_volume_hip(vol, net, patch_size, batch_slices, device, class_indices=None, blur_sigma=None, components=None):
     """predict_volume's loop with the volume resident on the device: upload once, per batch (gaussian_blur ->) resize_slices ->
-    net -> argmax_zoom_back (over class_indices, if given) into a uint8 (D, H, W) device volume."""
+    net -> argmax_zoom_back (over class_indices, if given) into a uint8 (D, H, W) device volume, which filter_components then
+    cleans in place if a component rule is given."""
     D, x, y = vol.shape
     if blur_sigma is not None and vol.dtype != np.float32:
         raise ValueError(f'predict_volume: blur_sigma with resize="hip" takes float32 volumes, got {vol.dtype} (scipy blurs in the '
@@ -312,13 +371,21 @@ def _predict_volume_hip(vol, net, patch_size, batch_slices, device, class_indice
         if blur_sigma is not None:
             sl = ops.gaussian_blur(sl, blur_sigma)
         inp = ops.resize_slices(sl, patch_size) if resize else sl
-        pred[d0:d0 + batch_slices] = ops.argmax_zoom_back(net(inp.unsqueeze(1)), (x, y), classes=class_indices)
+        logits = net(inp.unsqueeze(1))
+        pred[d0:d0 + batch_slices] = ops.argmax_zoom_back(logits, (x, y), classes=class_indices)
+    if components is not None and D > 0:
+        ops.filter_components(pred, _class_count(logits, class_indices), components, out=pred)
     return pred
+
+
+def _class_count(logits, class_indices):
+    """How many classes a finished class map can hold: the listed output channels, or all of them."""
+    return logits.shape[1] if class_indices is None else len(class_indices)
 
 
 @torch.no_grad()
 def predict_volume(image, net, patch_size=(224, 224), batch_slices=16, device="cuda", resize="host", return_device=False,
-                   class_indices=None, blur_sigma=None):
+                   class_indices=None, blur_sigma=None, components=None):
     """image (D, H, W) or (H, W) numpy -> integer class map of the same shape.  Per slice: cubic zoom to patch_size if the
     size differs, network, argmax over classes (softmax is monotonic, utils.py:75), nearest zoom back (:70-81).
     resize: "host" = scipy's zooms per slice around batched network calls; "hip" = the volume is uploaded once, both zooms and
@@ -330,19 +397,25 @@ def predict_volume(image, net, patch_size=(224, 224), batch_slices=16, device="c
     (universal_test.py:50-54); the hip path passes the list to ops.argmax_zoom_back instead of slicing the logits.
     blur_sigma: None, or the sigma of scipy.ndimage.gaussian_filter applied to every slice on its own before the cubic zoom
     (apply_blur_test.py:79-81): scipy in the volume's own dtype on the host path, ops.gaussian_blur per batch of slices with
-    resize="hip" (also when nothing is resized), which takes float32 volumes only (ValueError otherwise)."""
+    resize="hip" (also when nothing is resized), which takes float32 volumes only (ValueError otherwise).
+    components: None (nothing is filtered), or a component filter rule (component_rule_tables: "largest" or a mapping per class id)
+    applied to the finished class map of the whole volume -- with class_indices that means the dataset's own ids: per class, the
+    face-connected components smaller than the rule's threshold become 0.  scipy on the host path (filter_components_host),
+    ops.filter_components on the resident volume with resize="hip".  ValueError for a rule that names a class the map cannot hold."""
     if resize not in ("host", "hip"):
         raise ValueError(f'predict_volume: resize must be "host" or "hip", got {resize!r}')
     if return_device and resize != "hip":
         raise ValueError('predict_volume: return_device needs resize="hip"')
     if blur_sigma is not None:
         gaussian_taps(blur_sigma)                                       # ValueError for a sigma neither path takes
+    if components is not None:
+        component_rule_tables(components, 255 if class_indices is None else max(2, len(class_indices)))      # malformed rules fail before the network runs
     image = np.asarray(image)
     single = image.ndim == 2
     vol = image[None] if single else image
     net.eval()
     if resize == "hip":
-        pred = _predict_volume_hip(vol, net, tuple(patch_size), batch_slices, device, class_indices, blur_sigma)
+        pred = _predict_volume_hip(vol, net, tuple(patch_size), batch_slices, device, class_indices, blur_sigma, components)
         pred = pred if return_device else pred.cpu().numpy()
         return pred[0] if single else pred
     D, x, y = vol.shape
@@ -359,28 +432,35 @@ def predict_volume(image, net, patch_size=(224, 224), batch_slices=16, device="c
         out = torch.argmax(logits if class_indices is None else logits[:, list(class_indices)], dim=1).cpu().numpy()
         for i, o in enumerate(out):
             pred[d0 + i] = zoom(o, (x / patch_size[0], y / patch_size[1]), order=0) if resize else o
+    if components is not None and D > 0:
+        pred = filter_components_host(pred, _class_count(logits, class_indices), components)
     return pred[0] if single else pred
 
 
 def test_single_volume(image, label, net, classes, patch_size=[256, 256], test_save_path=None, case=None, z_spacing=1,
-                       batch_slices=16, device="cuda", metrics="host", resize="host", class_indices=None, blur_sigma=None):
+                       batch_slices=16, device="cuda", metrics="host", resize="host", class_indices=None, blur_sigma=None,
+                       components=None):
     """Per-class (dice, hd95) of one volume, classes 1..classes-1 (utils.py:61-102).  image / label: (1, D, H, W) tensors
     as the DataLoader yields them.  With test_save_path the volumes are written as .npz (SimpleITK, which the reference
     uses for .nii.gz, is not installed here).  metrics: "host" = the per-class scipy loop, "hip" = one volume_metrics call on
     the device (same values).  resize: predict_volume's; with resize="hip" and metrics="hip" the prediction goes from the one to
     the other as a device tensor and is downloaded only to be saved.  class_indices: predict_volume's; it must name `classes`
     channels (ValueError otherwise), the labels being that dataset's own ids 0..classes-1.  blur_sigma: predict_volume's; the
-    saved .npz keeps the image as it was passed in."""
+    saved .npz keeps the image as it was passed in.  components: predict_volume's component filter rule, checked against
+    `classes` (ValueError for a class id >= classes); the prediction is filtered before it is scored -- on the device with
+    resize="hip", so with metrics="hip" it still never leaves it -- and the saved .npz holds the filtered prediction."""
     if class_indices is not None and len(class_indices) != classes:
         raise ValueError(f"test_single_volume: class_indices has {len(class_indices)} entries for classes={classes}")
     if metrics not in ("host", "hip"):
         raise ValueError(f'test_single_volume: metrics must be "host" or "hip", got {metrics!r}')
     if resize not in ("host", "hip"):
         raise ValueError(f'test_single_volume: resize must be "host" or "hip", got {resize!r}')
+    if components is not None:
+        component_rule_tables(components, classes)
     image, label = image.squeeze(0).cpu().detach().numpy(), label.squeeze(0).cpu().detach().numpy()
     on_device = resize == "hip" and metrics == "hip"
     prediction = predict_volume(image, net, tuple(patch_size), batch_slices, device, resize=resize, return_device=on_device,
-                                class_indices=class_indices, blur_sigma=blur_sigma)
+                                class_indices=class_indices, blur_sigma=blur_sigma, components=components)
     if not on_device:
         prediction = prediction.astype(label.dtype)
     if metrics == "hip":
@@ -400,11 +480,11 @@ test_single_volume.__test__ = False     # not a pytest test (the name is the ref
 
 
 def evaluate_volumes(loader, net, classes, patch_size, metrics="hip", test_save_path=None, z_spacing=1, batch_slices=16,
-                     device="cuda", resize="host", class_indices=None, blur_sigma=None):
+                     device="cuda", resize="host", class_indices=None, blur_sigma=None, components=None):
     """The volume loop of the reference's inference() (test.py:155-164): test_single_volume per batch of `loader` (dicts with
     "image", "label" (1, D, H, W) and "case_name", batch size 1), the per-volume and final lines it logs.  Returns
     (per_volume, class_mean, mean_dice, mean_hd95): the metric list of every volume, the (classes-1, 2) table of per-class
-    means over the volumes, and that table's column means.  class_indices, blur_sigma: test_single_volume's."""
+    means over the volumes, and that table's column means.  class_indices, blur_sigma, components: test_single_volume's."""
     per_volume = []
     for i_batch, batch in enumerate(loader):
         name = batch["case_name"]
@@ -412,7 +492,7 @@ def evaluate_volumes(loader, net, classes, patch_size, metrics="hip", test_save_
         metric_i = test_single_volume(batch["image"], batch["label"], net, classes=classes, patch_size=list(patch_size),
                                       test_save_path=test_save_path, case=name, z_spacing=z_spacing, batch_slices=batch_slices,
                                       device=device, metrics=metrics, resize=resize, class_indices=class_indices,
-                                      blur_sigma=blur_sigma)
+                                      blur_sigma=blur_sigma, components=components)
         per_volume.append(metric_i)
         m = np.mean(metric_i, axis=0)
         logging.info('idx %d case %s mean_dice %f mean_hd95 %f' % (i_batch, name, m[0], m[1]))

@@ -30,7 +30,7 @@ extern "C" {
  * cswin_attn_fwd writes y0, cswin_attn_bwd reads it).  cswin_abi_version() returns the value the library was built with: a consumer
  * compiled against another header must refuse to call it.  Entry points that are only ADDED (cswin_seg_metrics*, cswin_resize_banded, cswin_argmax_zoom_back, cswin_augment_*,
  * cswin_chunk_sumsq, cswin_norm_finalize, cswin_adamw_flat, cswin_tpgm_*, cswin_argmax_zoom_back_classes, cswin_class_counts, cswin_gaussian_blur, cswin_eb_tiles,
- * cswin_eb_finalize, cswin_rate_finalize, cswin_adam_flat) do not bump it: every prototype an older consumer binds is unchanged. */
+ * cswin_eb_finalize, cswin_rate_finalize, cswin_adam_flat, cswin_components_*) do not bump it: every prototype an older consumer binds is unchanged. */
 #define CSWIN_ABI_VERSION 4
 
 #define CSWIN_OK 0
@@ -463,6 +463,29 @@ int    cswin_seg_metrics_nbins(int D, int H, int W);
 size_t cswin_seg_metrics_workspace(int D, int H, int W, int ndim, int ncls);
 int    cswin_seg_metrics(const unsigned char* pred, const unsigned char* label, long long* counts, unsigned int* hist,
                          void* workspace, size_t ws_bytes, int D, int H, int W, int ndim, int ncls, void* stream);
+
+/* ---- evaluation: connected components of a predicted label volume and the per-class size filter (csrc/components.hip) ----
+ * vol: dense (D, H, W) uint8 class ids, N = D H W; ids 0 and >= ncls are background.  A component is a maximal set of voxels of
+ * one foreground id joined by face neighbours (scipy.ndimage.label(vol == c), default structure, for every c; a 2-D slice is
+ * D = 1).  labels[v] = 0 for background, else 1 + the smallest flat index of v's component; sizes[r] = voxel count of the
+ * component whose smallest flat index is r, 0 at every other index.  Both are N int32 written in full; sizes may be NULL for the
+ * label call.  Union-find with integer atomics only: the result does not depend on scheduling and is bit-reproducible.
+ * cswin_components_filter(labels, sizes of the same vol): per class c in 1..ncls-1, thr_c = max(min_size[c],
+ * ceil(min_fraction[c] * (double)largest_c)) in float64 on the device, largest_c = the biggest component of class c; out[v] = 0
+ * where v's component is smaller than thr_c, vol[v] elsewhere (background and ids >= ncls pass through).  min_size (int64 >= 0),
+ * min_fraction (float64 in [0, 1]): device tables of ncls entries, entry 0 ignored; (0, 0.0) leaves a class untouched,
+ * min_fraction = 1 keeps the largest component and every other of the same size.  out == vol is allowed, any other overlap of
+ * out or the workspace with an argument is CSWIN_ERR_UNSUPPORTED.
+ * Both calls take a workspace of cswin_components_workspace(D, H, W) bytes (host-only; 0 with a message for an unsupported
+ * shape), 16-B aligned; the other pointers need their element's alignment only.  Each of D, H, W in 1..2048 (CSWIN_ERR_SHAPE),
+ * N <= 2^31 - 2 and ncls in 2..255 (CSWIN_ERR_UNSUPPORTED), a short workspace is CSWIN_ERR_WORKSPACE: all checked before any
+ * launch.  No host synchronisation, no allocation; every launch goes to `stream` and can be captured into a graph. */
+size_t cswin_components_workspace(int D, int H, int W);
+int    cswin_components_label(const unsigned char* vol, int* labels, int* sizes, void* workspace, size_t ws_bytes, int D, int H,
+                              int W, int ncls, void* stream);
+int    cswin_components_filter(const unsigned char* vol, const int* labels, const int* sizes, const long long* min_size,
+                               const double* min_fraction, unsigned char* out, void* workspace, size_t ws_bytes, int D, int H,
+                               int W, int ncls, void* stream);
 
 /* ---- evaluation: the two resizes around the network (utils.py:70-81: scipy.ndimage.zoom(order=3) of each slice to the network's
  *      input size, argmax and scipy.ndimage.zoom(order=0) back) ----
