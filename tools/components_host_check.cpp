@@ -161,6 +161,26 @@ Vol serpentine(int D, int H, int W) {
     return v;
 }
 
+// two tiles along `axis` (0 = z, 1 = y, 2 = x) and lanes across the seam between them: class 1 behind blocks of the ids a and b
+// (both >= ncls) that face each other, class 1 facing such an id either way round, and one legal link as the control
+Vol seam_lanes(int axis, int a, int b) {
+    const int lanes[5][4] = {{1, a, b, 1}, {1, a, a, 1}, {0, 1, a, 0}, {0, a, 1, 0}, {2, 1, 1, 2}};
+    const int T[3] = {CC_TZ, CC_TY, CC_TX}, t = T[axis], half = t / 2;
+    int dim[3], k = 0;
+    for (int d = 0; d < 3; ++d) dim[d] = d == axis ? 2 * t : (k++ == 0 ? 21 : 5);
+    Vol v = make(dim[0], dim[1], dim[2]);
+    for (int lane = 0; lane < 5; ++lane)
+        for (int q = 0; q < 4; ++q)
+            for (int s = q * half; s < (q + 1) * half; ++s)
+                for (int u = 4 * lane + 1; u < 4 * lane + 4; ++u)
+                    for (int w = 1; w < 4; ++w) {
+                        int c[3], m = 0;
+                        for (int d = 0; d < 3; ++d) c[d] = d == axis ? s : (m++ == 0 ? u : w);
+                        v.id[((long)c[0] * v.H + c[1]) * v.W + c[2]] = (unsigned char)lanes[lane][q];
+                    }
+    return v;
+}
+
 }  // namespace
 
 int main() {
@@ -183,6 +203,14 @@ int main() {
     check("row", make(1, 1, 3 * X + 7, 1), 2);
     check("column", make(1, 3 * Y + 5, 1, 1), 2);
     check("pillar", make(3 * Z + 2, 1, 1, 1), 2);
+    // both ids above the site-percolation threshold (0.36 each): a spanning component per class among thousands of small ones.
+    // ~10^5 voxels: there is no path compression, and one thread makes the chains as deep as they get
+    check("noise percolating", noise(2 * Z + 1, 3 * Y + 2, 3 * X + 18, 1, 0.72, 4), 3);
+    check("noise W % 4 == 2", noise(Z + 1, Y + 3, X + 2, 2, 0.8, 5), 3);
+    for (int axis = 0; axis < 3; ++axis) {
+        check("ids at and past ncls", seam_lanes(axis, 3, 200), 3);
+        check("one id past ncls", seam_lanes(axis, 255, 255), 3);
+    }
     if (failures) printf("%d case(s) FAILED\n", failures);
     else printf("all cases agree with the flood fill\n");
     return failures != 0;
