@@ -38,6 +38,10 @@ SIGNATURES = {
     "cswin_linear_bwd_tail": (I, [P, P, P, I, I, I, P, I, P, P, I, P]),
     "cswin_linear_bwd_weight_batch_masked": (I, [P, I, P, P, I, P, P, P]),
     "cswin_linear_bwd_tail_masked": (I, [P, P, P, I, I, I, P, I, P, P, I, P, P, P]),
+    "cswin_drop_path_order": (I, [P, P, P, P, I, I, P]),
+    "cswin_linear_fwd_skip": (I, [P, P, I, P, P, P, P, P, P, I, I, I, I, I, I, P, I, P]),
+    "cswin_linear_bwd_data_skip": (I, [P, P, P, P, I, P, P, I, P, I, I, I, I, I, P, I, P]),
+    "cswin_linear_bwd_tail_skip": (I, [P, P, P, I, I, I, P, I, P, P, I, P, P, P, I, P]),
     "cswin_rows_sum_multi": (I, [P, I, P]),
     "cswin_conv_tok_fwd": (I, [P, P, P, P, I, I, I, I, I, I, I, I, I, P]),
     "cswin_conv_tok_bwd_data": (I, [P, P, P, I, I, I, I, I, I, I, I, I, P]),

@@ -365,6 +365,42 @@ __device__ __forceinline__ void build_kept_list(KeptList* kept, const RowMask& m
     if (tid == 0) kept->n = n;
 }
 
+// A forward or data-gradient Linear's row map (DropPath: what a dropped sample's rows of the result hold does not depend on the A
+// operand).  order: 1 + nsamples ints, [0] = nk, the number of kept samples, then the kept samples ascending, then the dropped
+// ones ascending (drop_path_order_kernel below).  Logical row m of the launch stands for the physical row
+//   j = m / rows_per_sample (magic: fdiv, bound checked by the host),  phys = order[1 + j] * rows_per_sample + (m - j * rows_per_sample)
+// of A and of everything the epilogue addresses, so the kept samples' rows fill the first row tiles.  nk == nsamples: the identity,
+// whatever the rest of `order` holds (the launch is then the unmapped one, bit for bit).
+struct RowMap { const int* order; int nsamples, rows_per_sample; unsigned magic; };
+
+// One wave per row r of the step's DropPath draws u (rows, B): scales[r][s] = (u < keep[r]) / keep[r], the factors as torch computes
+// them from the same draws (one correctly rounded division), and order[r] as RowMap reads it.
+__global__ __launch_bounds__(64) void drop_path_order_kernel(const float* __restrict__ u, const float* __restrict__ keep,
+                                                             float* __restrict__ scales, int* __restrict__ order, int B) {
+    const int r = blockIdx.x, lane = threadIdx.x;
+    const float k = keep[r];
+    const float* ur = u + (long)r * B;
+    int* ord = order + (long)r * (B + 1);
+    int nk = 0;
+    for (int s0 = 0; s0 < B; s0 += 64) {
+        const int s = s0 + lane;
+        const bool kept = s < B && ur[s] < k;
+        const unsigned long long bal = __ballot(kept);
+        if (kept) ord[1 + nk + __popcll(bal & ((1ull << lane) - 1ull))] = s;
+        if (s < B) scales[(long)r * B + s] = __fdiv_rn(kept ? 1.0f : 0.0f, k);
+        nk += __popcll(bal);
+    }
+    if (lane == 0) ord[0] = nk;
+    int nd = nk;
+    for (int s0 = 0; s0 < B; s0 += 64) {
+        const int s = s0 + lane;
+        const bool dropped = s < B && !(ur[s] < k);
+        const unsigned long long bal = __ballot(dropped);
+        if (dropped) ord[1 + nd + __popcll(bal & ((1ull << lane) - 1ull))] = s;
+        nd += __popcll(bal);
+    }
+}
+
 // debug stamps: thread 0 writes s_memtime to `slot` of the workgroup's row; slot 0 also the hardware id and s_memrealtime, slot 3 the latter
 __device__ __forceinline__ void stamp(const Epilogue& epi, int row, int slot) {
     if (!epi.stamps || threadIdx.x != 0) return;
@@ -376,10 +412,15 @@ __device__ __forceinline__ void stamp(const Epilogue& epi, int row, int slot) {
 
 // T: the tile configuration.  SCALE_A: multiply the A rows by their Row::s (DropPath factor) when staging (weight gradients only).
 // MASKED (weight gradients of plain matrices only): the reduction runs over the kept samples' rows (RowMask); a compile-time variant.
-template <class T, int VEC, int EPI, bool SCALE_A, int PREC, class ASrc, class BSrc, bool MASKED = false>
+// MAPPED (forward / data-gradient Linears of plain fp32 matrices, one split): the launch's rows are LOGICAL rows (RowMap), the kept
+// samples' first.  Row tiles past the kept rows are fill tiles: no k-loop, their zero accumulators go through the epilogue.  The live
+// tiles are the launch's first workgroups and take the XCD order among themselves, so that a launch with dropped samples is a
+// shorter launch of the same shape, not the same launch with idle CUs in one XCD.  ord: the samples in the launch's order, in LDS.
+template <class T, int VEC, int EPI, bool SCALE_A, int PREC, class ASrc, class BSrc, bool MASKED = false, bool MAPPED = false>
 __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc& B, const Epilogue& epi, int M, int N, int R,
                                           int r_per_split, int tiles_m, int tiles_n, int bid, int nblk, int stamp_row,
-                                          const RowMask* mk = nullptr, KeptList* kept = nullptr) {
+                                          const RowMask* mk = nullptr, KeptList* kept = nullptr, const RowMap* rm = nullptr,
+                                          int* ord = nullptr) {
     typedef typename T::A TA;
     typedef typename T::B TB;
     constexpr int BM = T::BM, BN = T::BN, BK = T::BK, KW = T::KW, NW = T::NW, FM = T::FM, FN = T::FN, LD16 = T::LD16;
@@ -392,11 +433,28 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
 
     const int tid = threadIdx.x, lane = tid & 63, wave = (tid >> 6) % NW, kg = tid / (64 * NW);
     const int li = lane & 31, lh = lane >> 5;
-    const int lb = xcd_block_order(bid, nblk);       // logical blocks are ordered [split][m-tile][n-tile]
+    bool mapped = false;                             // MAPPED: at least one sample is dropped (else the launch is the unmapped one)
+    int kept_rows = M, nlive = nblk;                 // the kept samples' rows and the tiles that hold them
+    if constexpr (MAPPED) {
+        static_assert(A_RC && VEC == 4 && PREC == 0 && !MASKED && !SCALE_A && is_plain<ASrc> && is_plain<BSrc> && EPI != EPI_SPLIT2,
+                      "the row map serves forward and data-gradient Linears of plain fp32 matrices");
+        // the list goes to LDS while the kept count arrives (one load latency in front of the first operand loads, not two)
+        for (int s = tid; s < rm->nsamples; s += T::THREADS) ord[s] = min(max(rm->order[1 + s], 0), rm->nsamples - 1);
+        const int nk = __builtin_amdgcn_readfirstlane(rm->order[0]);
+        mapped = nk < rm->nsamples;
+        if (mapped) {
+            kept_rows = max(nk, 0) * rm->rows_per_sample;
+            nlive = (kept_rows + BM - 1) / BM * tiles_n;
+        }
+    }
+    const int lb = (!MAPPED || bid < nlive) ? xcd_block_order(bid, nlive) : bid;       // logical blocks are ordered [split][m-tile][n-tile]
     const int tiles = tiles_m * tiles_n;
     const int split = lb / tiles;
     const int tile = lb - split * tiles;
     const int m0 = (tile / tiles_n) * BM, n0 = (tile % tiles_n) * BN;
+    if constexpr (MAPPED) {
+        if (mapped) __syncthreads();
+    }
     if constexpr (MASKED) {
         static_assert(!A_RC && !B_RC && VEC == 4 && BM == BN && is_plain<ASrc> && is_plain<BSrc>,
                       "the sample mask serves weight gradients of plain matrices (one row mapping for both operands)");
@@ -409,7 +467,7 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
         r_per_split = ((R + mk->splits - 1) / mk->splits + 7) / 8 * 8;
     }
     const int r_begin = split * r_per_split;
-    const int r_end = min(R, r_begin + r_per_split);
+    const int r_end = (MAPPED && mapped && m0 >= kept_rows) ? r_begin : min(R, r_begin + r_per_split);     // a fill tile: no k-loop
     const int wm0 = (wave / T::WGN) * T::WM, wn0 = (wave % T::WGN) * T::WN;
 
     const int a_c = tid % TA::CPR, a_r = tid / TA::CPR;
@@ -419,7 +477,19 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
     typename BSrc::Row brow[TB::Q];
     if (A_RC) {
 #pragma unroll
-        for (int q = 0; q < TA::Q; ++q) arow[q] = A.row(m0 + a_r + q * TA::RPP);
+        for (int q = 0; q < TA::Q; ++q) {
+            if constexpr (MAPPED) {      // a dropped sample's rows (the mixed tile has some) are not read: a null row loads zeros
+                const int m = m0 + a_r + q * TA::RPP;
+                int row = -1;
+                if (mapped && m < kept_rows) {
+                    const int j = fdiv1(m, rm->magic);
+                    row = ord[j] * rm->rows_per_sample + (m - j * rm->rows_per_sample);
+                }
+                arow[q] = mapped ? src_mapped_row(A, row, 1.0f) : A.row(m);
+            } else {
+                arow[q] = A.row(m0 + a_r + q * TA::RPP);
+            }
+        }
     }
     if (B_RC) {
 #pragma unroll
@@ -673,7 +743,10 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
     }
     Epilogue e = epi;
     e.C += (long)split * e.split_stride;
-    if constexpr (EPI == EPI_GELUBWD) {
+    if constexpr (MAPPED) {
+        run_epilogue<EPI, FM, FN, false, false, true>(e, acc, M, N, m0 + wm0, n0 + wn0, lane, lds + wave * EP_WAVE_FLOATS, true, 0, 0,
+                                                      mapped ? ord : nullptr, kept_rows, rm->rows_per_sample, rm->magic);
+    } else if constexpr (EPI == EPI_GELUBWD) {
         if (e.pre_bf16) run_epilogue<EPI, FM, FN, true>(e, acc, M, N, m0 + wm0, n0 + wn0, lane, lds + wave * EP_WAVE_FLOATS, e.vec_store != 0);
         else run_epilogue<EPI, FM, FN, false>(e, acc, M, N, m0 + wm0, n0 + wn0, lane, lds + wave * EP_WAVE_FLOATS, e.vec_store != 0);
     } else {
@@ -694,6 +767,17 @@ __global__ __launch_bounds__((Tile<BM, BN, BK, KW, A_RC, B_RC>::THREADS)) void g
     __shared__ __attribute__((aligned(16))) float lds[T::LDS_FLOATS];
     gemm_body<T, VEC, EPI, SCALE_A, PREC, ASrc, BSrc>(lds, A, B, epi, M, N, R, r_per_split, tiles_m, tiles_n, (int)blockIdx.x, (int)gridDim.x,
                                                       (int)blockIdx.x);
+}
+
+// the same launch with a row map (16-B loaders, fp32, plain matrices: see gemm_body)
+template <int BM, int BN, int BK, int KW, bool B_RC, int EPI>
+__global__ __launch_bounds__((Tile<BM, BN, BK, KW, true, B_RC>::THREADS)) void gemm_mapped_kernel(PlainSrc A, PlainSrc B, Epilogue epi, int M, int N, int R,
+                                                    int r_per_split, int tiles_m, int tiles_n, RowMap rm) {
+    typedef Tile<BM, BN, BK, KW, true, B_RC> T;
+    __shared__ __attribute__((aligned(16))) float lds[T::LDS_FLOATS];
+    __shared__ int ord[MASK_MAX_SAMPLES];
+    gemm_body<T, 4, EPI, false, 0, PlainSrc, PlainSrc, false, true>(lds, A, B, epi, M, N, R, r_per_split, tiles_m, tiles_n, (int)blockIdx.x,
+                                                                    (int)gridDim.x, (int)blockIdx.x, nullptr, nullptr, &rm, ord);
 }
 
 // Up to four independent problems of one kernel configuration in ONE launch (the weight gradients of the four Linears of a
@@ -762,8 +846,9 @@ struct BlockTail {
 typedef Tile<64, 64, 64, 2, true, false> TailDgradTile;
 static_assert(TailDgradTile::THREADS == WgradTile::THREADS, "one workgroup size for both halves of the block tail");
 constexpr int BLOCK_TAIL_LDS = TailDgradTile::LDS_FLOATS > WgradTile::LDS_FLOATS ? TailDgradTile::LDS_FLOATS : WgradTile::LDS_FLOATS;
-template <bool MASKED>
-__device__ __forceinline__ void block_tail_body(float (&lds)[BLOCK_TAIL_LDS], KeptList* kept, const BlockTail& t) {
+template <bool MASKED, bool MAPPED = false>
+__device__ __forceinline__ void block_tail_body(float (&lds)[BLOCK_TAIL_LDS], KeptList* kept, const BlockTail& t, const RowMap* rm = nullptr,
+                                                int* ord = nullptr) {
     const int bid = (int)blockIdx.x, nw = t.w.first[t.w.n];
     if (bid >= nw + t.nd) {                // riders: 256-thread reduction workgroups (the upper four waves leave)
         if (threadIdx.x >= 256) return;
@@ -772,8 +857,12 @@ __device__ __forceinline__ void block_tail_body(float (&lds)[BLOCK_TAIL_LDS], Ke
         return;
     }
     if (bid >= nw) {                       // the data gradient's tiles come after the weight gradients': they fill their tail
-        gemm_body<TailDgradTile, 4, EPI_PLAIN, false, 0, PlainSrc, PlainSrc>(lds, t.dA, t.dB, t.de, t.dM, t.dN, t.dR, t.drps, t.dtm, t.dtn, bid - nw,
-                                                                             t.nd, bid);
+        if constexpr (MAPPED)
+            gemm_body<TailDgradTile, 4, EPI_PLAIN, false, 0, PlainSrc, PlainSrc, false, true>(lds, t.dA, t.dB, t.de, t.dM, t.dN, t.dR, t.drps, t.dtm,
+                                                                                              t.dtn, bid - nw, t.nd, bid, nullptr, nullptr, rm, ord);
+        else
+            gemm_body<TailDgradTile, 4, EPI_PLAIN, false, 0, PlainSrc, PlainSrc>(lds, t.dA, t.dB, t.de, t.dM, t.dN, t.dR, t.drps, t.dtm, t.dtn, bid - nw,
+                                                                                 t.nd, bid);
         return;
     }
     wgrad_batch_body<0, MASKED>(lds, kept, t.w, bid);
@@ -787,6 +876,13 @@ __global__ __launch_bounds__(WgradTile::THREADS) void gemm_block_tail_masked_ker
     __shared__ __attribute__((aligned(16))) float lds[BLOCK_TAIL_LDS];
     __shared__ KeptList kept;
     block_tail_body<true>(lds, &kept, t);
+}
+// the masked launch whose data gradient takes a row map (the BlockTail block itself is the other two kernels')
+__global__ __launch_bounds__(WgradTile::THREADS) void gemm_block_tail_skip_kernel(BlockTail t, RowMap rm) {
+    __shared__ __attribute__((aligned(16))) float lds[BLOCK_TAIL_LDS];
+    __shared__ KeptList kept;
+    __shared__ int ord[MASK_MAX_SAMPLES];
+    block_tail_body<true, true>(lds, &kept, t, &rm, ord);
 }
 
 // The four parity classes of a stride-2 3x3 convolution's data gradient (ConvTS2SrcT) are independent GEMMs over a quarter of
@@ -803,10 +899,18 @@ __global__ __launch_bounds__(S2DgradTile<KW>::THREADS) void gemm_conv_s2_dgrad_b
 // ======================================================================================
 template <int BM, int BN, int BK, int KW, bool A_RC, bool B_RC, int VEC, int EPI, bool SCALE_A, int PREC, class ASrc, class BSrc>
 void launch_cfg(const ASrc& A, const BSrc& B, const Epilogue& epi, int M, int N, int R, int splits, int r_per_split,
-                hipStream_t st) {
+                hipStream_t st, const RowMap* rm = nullptr) {
     int tm = cdiv(M, BM), tn = cdiv(N, BN);
     dim3 grid(tm * tn * splits);
     const int pad_lds = cswin_tuning().gemm_pad_lds;                                                    // tuning aid: caps residency
+    // rm: the launch's row-mapped form (the callers pass one only with what gemm_mapped_kernel is made for)
+    if constexpr (A_RC && VEC == 4 && PREC == 0 && !SCALE_A && is_plain<ASrc> && is_plain<BSrc> && EPI != EPI_SPLIT2 && (B_RC || EPI != EPI_RES)) {
+        if (rm) {
+            hipLaunchKernelGGL((gemm_mapped_kernel<BM, BN, BK, KW, B_RC, EPI>), grid, dim3((Tile<BM, BN, BK, KW, A_RC, B_RC>::THREADS)), pad_lds, st, A, B,
+                               epi, M, N, R, r_per_split, tm, tn, *rm);
+            return;
+        }
+    }
     hipLaunchKernelGGL((gemm_kernel<BM, BN, BK, KW, A_RC, B_RC, VEC, EPI, SCALE_A, PREC, ASrc, BSrc>), grid, dim3((Tile<BM, BN, BK, KW, A_RC, B_RC>::THREADS)), pad_lds, st, A, B, epi,
                        M, N, R, r_per_split, tm, tn);
 }
@@ -825,7 +929,7 @@ int one_split(int R) { return cdiv(R, BKMAX) * BKMAX; }
 // tile choice (measured on MI355X, tools/gemm_bench.py): the largest tile that still yields >= ~1.5 workgroups per CU
 template <bool A_RC, bool B_RC, int VEC, int EPI, bool SCALE_A, class ASrc, class BSrc>
 void launch_gemm(const ASrc& A, const BSrc& B, const Epilogue& epi_in, int M, int N, int R, int splits, int r_per_split,
-                 int precision, hipStream_t st) {
+                 int precision, hipStream_t st, const RowMap* rm = nullptr) {
     Epilogue epi = epi_in;
     epi.vec_store = epilogue_vec_ok(epi, N);
     auto blocks = [&](int bm, int bn) { return (long)cdiv(M, bm) * cdiv(N, bn) * splits; };
@@ -854,15 +958,15 @@ void launch_gemm(const ASrc& A, const BSrc& B, const Epilogue& epi_in, int M, in
     }
     if (tile == 2) {
         if (k_groups(blocks(64, 32), r_len) >= 2)
-            return launch_cfg<64, 32, 64, 2, A_RC, B_RC, VEC, EPI, SCALE_A, 0>(A, B, epi, M, N, R, splits, r_per_split, st);
-        return launch_cfg<64, 32, 32, 1, A_RC, B_RC, VEC, EPI, SCALE_A, 0>(A, B, epi, M, N, R, splits, r_per_split, st);
+            return launch_cfg<64, 32, 64, 2, A_RC, B_RC, VEC, EPI, SCALE_A, 0>(A, B, epi, M, N, R, splits, r_per_split, st, rm);
+        return launch_cfg<64, 32, 32, 1, A_RC, B_RC, VEC, EPI, SCALE_A, 0>(A, B, epi, M, N, R, splits, r_per_split, st, rm);
     }
     int kw = k_groups(blocks(64, 64), r_len);
     if (wgrad && r_len >= 256 && kw < 2) kw = 2;               // weight gradients: measured 5-8 % faster
     if (forced_kw) kw = forced_kw;
-    if (kw == 4) launch_cfg<64, 64, 64, 4, A_RC, B_RC, VEC, EPI, SCALE_A, 0>(A, B, epi, M, N, R, splits, r_per_split, st);
-    else if (kw == 2) launch_cfg<64, 64, 64, 2, A_RC, B_RC, VEC, EPI, SCALE_A, 0>(A, B, epi, M, N, R, splits, r_per_split, st);
-    else launch_cfg<64, 64, 32, 1, A_RC, B_RC, VEC, EPI, SCALE_A, 0>(A, B, epi, M, N, R, splits, r_per_split, st);
+    if (kw == 4) launch_cfg<64, 64, 64, 4, A_RC, B_RC, VEC, EPI, SCALE_A, 0>(A, B, epi, M, N, R, splits, r_per_split, st, rm);
+    else if (kw == 2) launch_cfg<64, 64, 64, 2, A_RC, B_RC, VEC, EPI, SCALE_A, 0>(A, B, epi, M, N, R, splits, r_per_split, st, rm);
+    else launch_cfg<64, 64, 32, 1, A_RC, B_RC, VEC, EPI, SCALE_A, 0>(A, B, epi, M, N, R, splits, r_per_split, st, rm);
 }
 
 // launch_gemm with the loaders' width chosen at run time: vec = 16-B loads are legal (alignment, sizes multiples of 4)
@@ -987,7 +1091,25 @@ struct TailExtras {
     const char* who; const float* dy; const float* w; float* dx; int M, N, K; const cswin_reduce_job* jobs; int njobs;
     // sample masks of the weight gradients (NULL: none): skip[i] (NULL: problem i has none) holds nsamples[i] floats, see RowMask
     const float* const* skip; const int* nsamples;
+    // sample order of the data gradient (NULL: none), over order_samples samples of M / order_samples rows: see RowMap
+    const int* order; int order_samples;
 };
+
+// The row map of a forward / data-gradient Linear over M rows, or why the launch cannot take one: a refusal, never an unmapped run
+// (the caller's contract is that a dropped sample's rows of A are NOT READ).  No HIP call is made before these checks.
+int row_map_checked(RowMap* rm, const char* who, const int* order, int nsamples, int rows_per_sample, int M, int precision, int io_bf16,
+                    bool two_part, bool add) {
+    CSWIN_REQUIRE(precision == 0 && io_bf16 == 0, CSWIN_ERR_UNSUPPORTED, "%s: a sample order needs precision 0 and fp32 storage", who);
+    CSWIN_REQUIRE(!two_part, CSWIN_ERR_UNSUPPORTED, "%s: a sample order takes no concat / split operand", who);
+    CSWIN_REQUIRE(!add, CSWIN_ERR_UNSUPPORTED, "%s: a sample order takes no add operand", who);
+    CSWIN_REQUIRE(order && nsamples >= 1 && nsamples <= MASK_MAX_SAMPLES, CSWIN_ERR_SHAPE, "%s: the order must list 1..%d samples", who,
+                  MASK_MAX_SAMPLES);
+    CSWIN_REQUIRE(M > 0 && rows_per_sample > 0 && (long)nsamples * rows_per_sample == M, CSWIN_ERR_SHAPE,
+                  "%s: nsamples * rows_per_sample != M", who);
+    CSWIN_REQUIRE(fdiv_exact((long)M + 63, rows_per_sample), CSWIN_ERR_UNSUPPORTED, "%s: M * rows_per_sample must stay below 2^32", who);
+    *rm = RowMap{order, nsamples, rows_per_sample, fdiv_magic(rows_per_sample)};
+    return CSWIN_OK;
+}
 
 int wgrad_batch_impl(const cswin_wgrad_desc* d, int n, cswin_reduce_job* deferred, const TailExtras& x, void* stream) {
     CSWIN_REQUIRE(x.njobs >= 0 && x.njobs <= CSWIN_TAIL_RIDER_JOBS && (x.njobs == 0 || x.jobs), CSWIN_ERR_SHAPE,
@@ -995,6 +1117,14 @@ int wgrad_batch_impl(const cswin_wgrad_desc* d, int n, cswin_reduce_job* deferre
     CSWIN_REQUIRE(d && deferred && n >= 1 && n <= WGRAD_BATCH, CSWIN_ERR_SHAPE, "linear_bwd_weight_batch: 1..%d problems and their deferred slots", WGRAD_BATCH);
     bool fast = true, any_bf16 = false, any_mask = false;
     const int precision = d[0].precision;
+    RowMap dmap = {};
+    if (x.order) {
+        CSWIN_REQUIRE(x.dy && x.order_samples >= 1 && x.M % x.order_samples == 0, CSWIN_ERR_SHAPE, "%s: nsamples * rows_per_sample != M", x.who);
+        int rc = row_map_checked(&dmap, x.who, x.order, x.order_samples, x.M / x.order_samples, x.M, precision, 0, false, false);
+        if (rc) return rc;
+        CSWIN_REQUIRE(x.N % 4 == 0 && x.K % 4 == 0 && aligned16(x.dy) && aligned16(x.w) && aligned16(x.dx), CSWIN_ERR_ALIGN,
+                      "%s: a sample order needs N, K multiples of 4 and 16-B aligned operands", x.who);
+    }
     CSWIN_CHECK_PRECISION(precision, "linear_bwd_weight_batch");
     for (int i = 0; i < n; ++i) {
         CSWIN_REQUIRE(d[i].precision == precision, CSWIN_ERR_UNSUPPORTED, "linear_bwd_weight_batch: problems of one launch share one precision");
@@ -1028,8 +1158,11 @@ int wgrad_batch_impl(const cswin_wgrad_desc* d, int n, cswin_reduce_job* deferre
     const bool jobs_ride16 = merge_on && w16_path && x.njobs > 0;                     // bf16 mode: the reductions ride in wgrad16's grid
     if (extra && !ride) {                   // the data gradient (and the pending reductions) as launches of their own, then the batch as usual
         if (has_dgrad) {
-            launch_gemm_vec<true, false, EPI_PLAIN, false>(g_vec, gA, gB, plain_epilogue(x.dx, x.K), x.M, x.K, x.N, 1, one_split(x.N), precision,
-                                                           (hipStream_t)stream);
+            if (x.order)
+                launch_gemm<true, false, 4, EPI_PLAIN, false>(gA, gB, plain_epilogue(x.dx, x.K), x.M, x.K, x.N, 1, one_split(x.N), 0, (hipStream_t)stream, &dmap);
+            else
+                launch_gemm_vec<true, false, EPI_PLAIN, false>(g_vec, gA, gB, plain_epilogue(x.dx, x.K), x.M, x.K, x.N, 1, one_split(x.N), precision,
+                                                               (hipStream_t)stream);
             CSWIN_LAUNCH_CHECK();
         }
         if (x.njobs > 0 && !jobs_ride16) {
@@ -1125,7 +1258,9 @@ int wgrad_batch_impl(const cswin_wgrad_desc* d, int n, cswin_reduce_job* deferre
             t.r.njobs = x.njobs;
         }
         static_assert(sizeof(BlockTail) <= 4096, "kernel argument block");
-        if (any_mask) hipLaunchKernelGGL(gemm_block_tail_masked_kernel, dim3(blocks + t.nd + rblocks), dim3(512), 0, (hipStream_t)stream, t);
+        static_assert(sizeof(BlockTail) + sizeof(RowMap) <= 4096, "kernel argument block");
+        if (x.order) hipLaunchKernelGGL(gemm_block_tail_skip_kernel, dim3(blocks + t.nd + rblocks), dim3(512), 0, (hipStream_t)stream, t, dmap);
+        else if (any_mask) hipLaunchKernelGGL(gemm_block_tail_masked_kernel, dim3(blocks + t.nd + rblocks), dim3(512), 0, (hipStream_t)stream, t);
         else hipLaunchKernelGGL(gemm_block_tail_kernel, dim3(blocks + t.nd + rblocks), dim3(512), 0, (hipStream_t)stream, t);
     } else if (any_mask) {
         hipLaunchKernelGGL(gemm_wgrad_batch_masked_kernel, dim3(blocks), dim3(512), 0, (hipStream_t)stream, b);
@@ -1200,6 +1335,10 @@ int cswin_linear_bwd_weight_batch_masked(const cswin_wgrad_desc* d, int n, cswin
 int cswin_linear_bwd_tail_masked(const float* dy, const float* w, float* dx, int M, int N, int K, const cswin_wgrad_desc* d, int n,
                                  cswin_reduce_job* deferred, const cswin_reduce_job* pending, int npending, const float* const* skip,
                                  const int* nsamples, void* stream);
+
+int cswin_linear_bwd_tail_skip(const float* dy, const float* w, float* dx, int M, int N, int K, const cswin_wgrad_desc* d, int n,
+                               cswin_reduce_job* deferred, const cswin_reduce_job* pending, int npending, const float* const* skip,
+                               const int* nsamples, const int* order, int order_samples, void* stream);
 
 int cswin_linear_fwd(const float* x, const float* x2, int k_split, const float* w, const float* bias, float* y,
                      float* y_act, const float* residual, const float* row_scale, int rows_per_sample, int M, int N,
@@ -1287,6 +1426,60 @@ int cswin_linear_bwd_data(const float* dy, const float* w, float* dx, float* dx2
     return CSWIN_OK;
 }
 
+// The two calls above with a SAMPLE ORDER (row map, see RowMap): plain fp32 matrices with 16-B accesses only, everything else is refused
+int cswin_linear_fwd_skip(const float* x, const float* x2, int k_split, const float* w, const float* bias, float* y, float* y_act,
+                          const float* residual, const float* row_scale, int rows_per_sample, int M, int N, int K, int precision,
+                          int io_bf16, const int* order, int nsamples, void* stream) {
+    RowMap rm;
+    int rc = row_map_checked(&rm, "linear_fwd_skip", order, nsamples, rows_per_sample, M, precision, io_bf16, x2 != nullptr, false);
+    if (rc) return rc;
+    CSWIN_REQUIRE(x && w && y && N > 0 && K > 0, CSWIN_ERR_SHAPE, "linear_fwd_skip: bad arguments M=%d N=%d K=%d", M, N, K);
+    CSWIN_REQUIRE(!(y_act && residual), CSWIN_ERR_UNSUPPORTED, "linear_fwd_skip: activation and residual epilogues are exclusive");
+    Epilogue e = plain_epilogue(y, N);
+    e.bias = bias;
+    e.Cact = y_act; e.ldact = N;
+    e.residual = residual; e.ldres = N;
+    e.row_scale = row_scale; e.rows_per_sample = rows_per_sample;
+    CSWIN_REQUIRE(K % 4 == 0 && aligned16(x) && aligned16(w) && epilogue_vec_ok(e, N), CSWIN_ERR_ALIGN,
+                  "linear_fwd_skip: a sample order needs N, K multiples of 4 and 16-B aligned operands");
+    const PlainSrc A = {x, K, M, K, nullptr, 1, 0}, B = {w, K, N, K, nullptr, 1, 0};
+    hipStream_t st = (hipStream_t)stream;
+    if (y_act) launch_gemm<true, true, 4, EPI_ACT, false>(A, B, e, M, N, K, 1, one_split(K), 0, st, &rm);
+    else if (residual) launch_gemm<true, true, 4, EPI_RES, false>(A, B, e, M, N, K, 1, one_split(K), 0, st, &rm);
+    else launch_gemm<true, true, 4, EPI_PLAIN, false>(A, B, e, M, N, K, 1, one_split(K), 0, st, &rm);
+    CSWIN_LAUNCH_CHECK();
+    return CSWIN_OK;
+}
+
+int cswin_linear_bwd_data_skip(const float* dy, const float* w, float* dx, float* dx2, int k_split, const float* gelu_pre,
+                               const float* row_scale, int rows_per_sample, const float* add, int M, int N, int K, int precision,
+                               int io_bf16, const int* order, int nsamples, void* stream) {
+    RowMap rm;
+    int rc = row_map_checked(&rm, "linear_bwd_data_skip", order, nsamples, rows_per_sample, M, precision, io_bf16, dx2 != nullptr, add != nullptr);
+    if (rc) return rc;
+    CSWIN_REQUIRE(dy && w && dx && N > 0 && K > 0, CSWIN_ERR_SHAPE, "linear_bwd_data_skip: bad arguments");
+    Epilogue e = plain_epilogue(dx, K);
+    e.gelu_pre = gelu_pre; e.ldpre = K;
+    e.row_scale = row_scale; e.rows_per_sample = rows_per_sample;
+    CSWIN_REQUIRE(N % 4 == 0 && aligned16(dy) && aligned16(w) && epilogue_vec_ok(e, K), CSWIN_ERR_ALIGN,
+                  "linear_bwd_data_skip: a sample order needs N, K multiples of 4 and 16-B aligned operands");
+    const PlainSrc A = {dy, N, M, N, nullptr, 1, 0}, B = {w, K, N, K, nullptr, 1, 0};
+    hipStream_t st = (hipStream_t)stream;
+    if (gelu_pre) launch_gemm<true, false, 4, EPI_GELUBWD, false>(A, B, e, M, K, N, 1, one_split(N), 0, st, &rm);
+    else launch_gemm<true, false, 4, EPI_PLAIN, false>(A, B, e, M, K, N, 1, one_split(N), 0, st, &rm);
+    CSWIN_LAUNCH_CHECK();
+    return CSWIN_OK;
+}
+
+// scales (rows, B) = (u < keep[row]) / keep[row] and order (rows, 1 + B) from one step's DropPath draws u (rows, B): see drop_path_order_kernel
+int cswin_drop_path_order(const float* u, const float* keep, float* scales, int* order, int rows, int B, void* stream) {
+    CSWIN_REQUIRE(u && keep && scales && order && rows > 0, CSWIN_ERR_SHAPE, "drop_path_order: bad arguments");
+    CSWIN_REQUIRE(B >= 1 && B <= MASK_MAX_SAMPLES, CSWIN_ERR_SHAPE, "drop_path_order: 1..%d samples", MASK_MAX_SAMPLES);
+    hipLaunchKernelGGL(drop_path_order_kernel, dim3(rows), dim3(64), 0, (hipStream_t)stream, u, keep, scales, order, B);
+    CSWIN_LAUNCH_CHECK();
+    return CSWIN_OK;
+}
+
 size_t cswin_linear_bwd_weight_workspace(int M, int N, int K) { return WgradSlabs::bytes(M, N, K); }
 
 // dw[N,K] = (row_scale . dy)^T @ [x | x2];  dbias[N] = colsum(row_scale . dy)
@@ -1343,6 +1536,18 @@ int cswin_linear_bwd_tail_masked(const float* dy, const float* w, float* dx, int
                                  const int* nsamples, void* stream) {
     CSWIN_REQUIRE(dy && w && dx && M > 0 && N > 0 && K > 0, CSWIN_ERR_SHAPE, "linear_bwd_tail: bad data-gradient arguments");
     return wgrad_batch_impl(d, n, deferred, TailExtras{"linear_bwd_tail", dy, w, dx, M, N, K, pending, npending, skip, nsamples}, stream);
+}
+
+// order: the data gradient's sample order over order_samples samples of M / order_samples rows (see RowMap); the weight gradients
+// keep their masks.  What the order cannot serve (precision 1, unaligned operands) is refused.
+int cswin_linear_bwd_tail_skip(const float* dy, const float* w, float* dx, int M, int N, int K, const cswin_wgrad_desc* d, int n,
+                               cswin_reduce_job* deferred, const cswin_reduce_job* pending, int npending, const float* const* skip,
+                               const int* nsamples, const int* order, int order_samples, void* stream) {
+    CSWIN_REQUIRE(dy && w && dx && M > 0 && N > 0 && K > 0, CSWIN_ERR_SHAPE, "linear_bwd_tail_skip: bad data-gradient arguments");
+    CSWIN_REQUIRE(order, CSWIN_ERR_SHAPE, "linear_bwd_tail_skip: the order must list 1..%d samples", MASK_MAX_SAMPLES);
+    CSWIN_REQUIRE(d && n >= 1 && n <= WGRAD_BATCH, CSWIN_ERR_SHAPE, "linear_bwd_tail_skip: 1..%d weight-gradient problems", WGRAD_BATCH);
+    return wgrad_batch_impl(d, n, deferred, TailExtras{"linear_bwd_tail_skip", dy, w, dx, M, N, K, pending, npending, skip, nsamples, order, order_samples},
+                            stream);
 }
 
 // -------- convolutions on the (B, H*W, C) token layout (NHWC), implicit GEMM -----------------------------------

@@ -51,9 +51,15 @@ constexpr int EP_WAVE_FLOATS = 32 * EP_LD;
 // kernels of the FAST gather sources, which carry them: the launch's host side has checked fdiv's bound for M + 63 rows).
 // Compile-time, and off for the dense kernels, whose epilogue and Epilogue struct are exactly what they were: hoisting their row
 // divisions cost the residual-epilogue kernels registers and a step of occupancy (profiles/conv_gather_notes.md).
-template <int EPI, int FM, int FN, bool PRE16 = false, bool FDIV = false>
+// MAPPED (gemm.hip's row-mapped launches, vector path only): output row m of the launch is LOGICAL.  ord (NULL: the identity) lists
+// the samples in the launch's order: with j = m / map_rps (by map_magic), sample ord[j] is the row_scale index and
+// ord[j] * map_rps + (m - j * map_rps) the row of every matrix the epilogue addresses.  Rows from kept_rows on belong to dropped
+// samples: their accumulators are zeros by construction, gelu_pre is not read for them, and a residual epilogue stores their
+// residual row as it is.
+template <int EPI, int FM, int FN, bool PRE16 = false, bool FDIV = false, bool MAPPED = false>
 __device__ __forceinline__ void run_epilogue(const Epilogue& e, f32x16 (&acc)[FM][FN], int M, int N, int mb, int nb,
-                                             int lane, float* wbuf, bool vec, unsigned m_hw = 0, unsigned m_w2 = 0) {
+                                             int lane, float* wbuf, bool vec, unsigned m_hw = 0, unsigned m_w2 = 0,
+                                             const int* ord = nullptr, int kept_rows = 0, int map_rps = 1, unsigned map_magic = 0) {
     const int li = lane & 31, lh = lane >> 5;
     const int rrow = lane >> 3, rcol = (lane & 7) * 4;
     const bool has_rs = e.row_scale != nullptr;
@@ -82,11 +88,30 @@ __device__ __forceinline__ void run_epilogue(const Epilogue& e, f32x16 (&acc)[FM
                 f32x4 v[4], aux[4];
                 u32x2 aux16[4];
                 float rs[4];
+                int pm[4];                                 // MAPPED: the rows' places in memory
 #pragma unroll
                 for (int p = 0; p < 4; ++p) {
                     const int m = mb + i * 32 + rrow + 8 * p;
                     const bool ok = m < M && n < N;
                     v[p] = *reinterpret_cast<const f32x4*>(&wbuf[(rrow + 8 * p) * EP_LD + rcol]);
+                    if constexpr (MAPPED) {
+                        pm[p] = m;
+                        int smp = 0;
+                        if (ord && m < M) {
+                            const int j = fdiv1(m, map_magic);
+                            smp = ord[j];
+                            pm[p] = smp * map_rps + (m - j * map_rps);
+                        }
+                        const bool dropped = ord && m >= kept_rows;
+                        rs[p] = (has_rs && ok) ? e.row_scale[ord ? smp : m / e.rows_per_sample] : 1.0f;
+                        if (EPI == EPI_RES || EPI == EPI_GELUBWD) {
+                            const float* ap = EPI == EPI_RES ? e.residual : e.gelu_pre;
+                            const long ld = EPI == EPI_RES ? e.ldres : e.ldpre;
+                            aux[p] = f32x4{0.f, 0.f, 0.f, 0.f};
+                            if (ok && !(EPI == EPI_GELUBWD && dropped)) aux[p] = *reinterpret_cast<const f32x4*>(ap + (long)pm[p] * ld + n);
+                        }
+                        continue;
+                    }
                     rs[p] = (has_rs && ok) ? e.row_scale[m / e.rows_per_sample] : 1.0f;
                     if (EPI == EPI_RES || EPI == EPI_GELUBWD) {
                         const float* ap = EPI == EPI_RES ? e.residual : e.gelu_pre;
@@ -110,6 +135,19 @@ __device__ __forceinline__ void run_epilogue(const Epilogue& e, f32x16 (&acc)[FM
                         for (int c = 0; c < 4; ++c) o[c] *= gelu_grad_f(pre[c]);
                     }
                     if (has_rs) o *= rs[p];
+                    if constexpr (MAPPED) {
+                        static_assert(EPI != EPI_SPLIT2 && !PRE16 && !FDIV, "row-mapped launches: one fp32 output matrix");
+                        if (EPI == EPI_RES && ord && m >= kept_rows) o = f32x4{0.f, 0.f, 0.f, 0.f};
+                        if (EPI == EPI_RES) o += aux[p];
+                        *reinterpret_cast<f32x4*>(e.C + (long)pm[p] * e.ldc + n) = o;
+                        if (EPI == EPI_ACT) {
+                            f32x4 a;
+#pragma unroll
+                            for (int c = 0; c < 4; ++c) a[c] = gelu_f(o[c]);
+                            *reinterpret_cast<f32x4*>(e.Cact + (long)pm[p] * e.ldact + n) = a;
+                        }
+                        continue;
+                    }
                     if (EPI == EPI_RES) o += aux[p];
                     if (EPI == EPI_SPLIT2 && n >= e.col_split)
                         *reinterpret_cast<f32x4*>(e.C2 + (long)m * e.ldc2 + (n - e.col_split)) = o;

@@ -118,6 +118,14 @@ class CSWinBlock(nn.Module):
             return dp.sample_scale(x.shape[0], x.device), dp.sample_scale(x.shape[0], x.device)
         return None, None
 
+    def _keep_orders(self, rs1):
+        """The sample orders that belong to the pre-drawn factors (CSWinTransformer._predraw_drop_path), or None: with them the
+        block's Linears leave the dropped samples' rows out.  A block that drew its own factors has none."""
+        preset = getattr(self, "_dp_preset", None)
+        if preset and len(preset) == 4 and preset[2] is not None and rs1 is preset[0]:
+            return preset[2], preset[3]
+        return None
+
     def forward(self, x):
         B, L, C = x.shape
         if L != self.patches_resolution ** 2:
@@ -138,7 +146,8 @@ class CSWinBlock(nn.Module):
             return self.mlp(ops.layer_norm(x, n2.weight, n2.bias, n2.eps), residual=x, row_scale=rs2)
         return ops.cswin_block(x, self.patches_resolution, self.split_size, [m.idx for m in a], [m.num_heads for m in a],
                                a[0].scale, self.norm1, self.qkv, self.proj, self.norm2, self.mlp.fc1, self.mlp.fc2,
-                               [m.get_v.weight for m in a], [m.get_v.bias for m in a], rs1, rs2, attn_drop=ad)
+                               [m.get_v.weight for m in a], [m.get_v.bias for m in a], rs1, rs2, attn_drop=ad,
+                               orders=self._keep_orders(rs1))
 
 
 def img2windows(img, H_sp, W_sp):
@@ -311,7 +320,8 @@ class CSWinTransformer(nn.Module):
         return x
 
     def _predraw_drop_path(self, batch, device):
-        """One Bernoulli launch for the stochastic-depth factors of every block (2 per block: attention and MLP branch)."""
+        """One Bernoulli launch for the stochastic-depth factors of every block (2 per block: attention and MLP branch), and one
+        that turns the draws into the factors and the blocks' sample orders (ops.drop_path_order)."""
         blocks = [b for st in (self.stage1, self.stage2, self.stage3, self.stage4, self.stage_up4, self.stage_up3,
                                self.stage_up2, self.stage_up1) for b in st]
         live = [b for b in blocks if isinstance(b.drop_path, DropPath) and b.drop_path.drop_prob > 0.]
@@ -326,9 +336,15 @@ class CSWinTransformer(nn.Module):
                                  device=device)[:, None]
             self._dp_keep = cache
         keep = cache
-        scales = (torch.rand(keep.shape[0], batch, device=device) < keep).to(torch.float32) / keep
+        u = torch.rand(keep.shape[0], batch, device=device)
+        if u.is_cuda and batch <= ops.MAX_MASK_SAMPLES:
+            scales, order = ops.drop_path_order(u, keep)        # the same factors, bit for bit
+        else:
+            scales, order = (u < keep).to(torch.float32) / keep, None
         for i, b in enumerate(live):
             b._dp_preset = [scales[2 * i], scales[2 * i + 1]]
+            if order is not None:
+                b._dp_preset += [order[2 * i], order[2 * i + 1]]
 
     # encoder and bottleneck
     def forward_features(self, x, pe_weight=None):

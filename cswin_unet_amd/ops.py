@@ -245,25 +245,35 @@ def _wsrc(w):
     return ptr(w), 0
 
 
-def _linear_fwd(x, w, b, N, *, dtype=torch.float32, gelu=False, x2=None, residual=None, row_scale=None):
-    """y (..., N) = [x | x2] @ w^T + b as `dtype`;  residual: y = residual + row_scale[sample] * (...);  gelu: (y, GELU(y))."""
+def _linear_fwd(x, w, b, N, *, dtype=torch.float32, gelu=False, x2=None, residual=None, row_scale=None, order=None):
+    """y (..., N) = [x | x2] @ w^T + b as `dtype`;  residual: y = residual + row_scale[sample] * (...);  gelu: (y, GELU(y)).
+    order: the sample order of a DropPath branch (drop_path_order): the dropped samples' rows of x are not read."""
     pw, w16 = w if isinstance(w, tuple) else (ptr(w), 0)
     K1 = x.shape[-1]
     K = K1 + (x2.shape[-1] if x2 is not None else 0)
     y = torch.empty(x.shape[:-1] + (N,), dtype=dtype, device=x.device)
     y_act = torch.empty_like(y) if gelu else None
-    call("cswin_linear_fwd", ptr(x), ptr(x2), K1 if x2 is not None else 0, pw, ptr(b), ptr(y), ptr(y_act), ptr(residual), ptr(row_scale),
-         _rows_per_sample(x), x.numel() // K1, N, K, precision(), _stored16(x, y) | w16, stream())
+    args = (ptr(x), ptr(x2), K1 if x2 is not None else 0, pw, ptr(b), ptr(y), ptr(y_act), ptr(residual), ptr(row_scale),
+            _rows_per_sample(x), x.numel() // K1, N, K, precision(), _stored16(x, y) | w16)
+    if order is not None:
+        call("cswin_linear_fwd_skip", *args, ptr(order), x.shape[0], stream())
+    else:
+        call("cswin_linear_fwd", *args, stream())
     return (y, y_act) if gelu else y
 
 
-def _linear_bwd_data(dy, w, dx, *, dx2=None, gelu_pre=None, row_scale=None, add=None):
-    """[dx | dx2] = add + row_scale[sample] * ((dy @ w) * gelu'(gelu_pre)); also plain c = a @ b for row-major b."""
+def _linear_bwd_data(dy, w, dx, *, dx2=None, gelu_pre=None, row_scale=None, add=None, order=None):
+    """[dx | dx2] = add + row_scale[sample] * ((dy @ w) * gelu'(gelu_pre)); also plain c = a @ b for row-major b.
+    order: as for _linear_fwd; the dropped samples' rows of dy and gelu_pre are not read, their rows of dx are zeros."""
     pw, w16 = w if isinstance(w, tuple) else (ptr(w), 0)
     N, K1 = dy.shape[-1], dx.shape[-1]
     K = K1 + (dx2.shape[-1] if dx2 is not None else 0)
-    call("cswin_linear_bwd_data", ptr(dy), pw, ptr(dx), ptr(dx2), K1 if dx2 is not None else 0, ptr(gelu_pre), ptr(row_scale),
-         _rows_per_sample(dy), ptr(add), dy.numel() // N, N, K, precision(), _stored16(dy, dx, None, gelu_pre) | w16, stream())
+    args = (ptr(dy), pw, ptr(dx), ptr(dx2), K1 if dx2 is not None else 0, ptr(gelu_pre), ptr(row_scale),
+            _rows_per_sample(dy), ptr(add), dy.numel() // N, N, K, precision(), _stored16(dy, dx, None, gelu_pre) | w16)
+    if order is not None:
+        call("cswin_linear_bwd_data_skip", *args, ptr(order), dy.shape[0], stream())
+    else:
+        call("cswin_linear_bwd_data", *args, stream())
 
 
 def _linear_bwd_weight(dy, x, dw, db, slab=None, *, x2=None, row_scale=None):
@@ -279,7 +289,19 @@ def _linear_bwd_weight(dy, x, dw, db, slab=None, *, x2=None, row_scale=None):
          ptr(dw), ptr(db), ws, nbytes, M, N, K, job, precision(), stream())
 
 
-MAX_MASK_SAMPLES = 256     # nsamples bound of the *_masked weight-gradient entry points (include/cswin_hip.h)
+MAX_MASK_SAMPLES = 256     # nsamples bound of the *_masked weight-gradient and the *_skip entry points (include/cswin_hip.h)
+
+
+def drop_path_order(u, keep):
+    """DropPath factors and sample orders of one step from its uniform draws u (rows, B) and keep probabilities keep (rows[, 1]):
+    (scales (rows, B) = (u < keep) / keep, order (rows, 1 + B) int32 = per row the kept count, the kept samples, the dropped ones)."""
+    u, keep = dev_f32(u, "DropPath draws"), dev_f32(keep, "keep probabilities")
+    rows, B = u.shape
+    assert keep.numel() == rows and B <= MAX_MASK_SAMPLES
+    scales = torch.empty_like(u)
+    order = torch.empty(rows, 1 + B, dtype=torch.int32, device=u.device)
+    call("cswin_drop_path_order", ptr(u), ptr(keep), ptr(scales), ptr(order), rows, B, stream())
+    return scales, order
 
 
 def _fill_wgrad(d, dy, x, row_scale, dw, dbias, workspace, ws_bytes):
@@ -585,7 +607,7 @@ class _CSWinBlock(Function):
     block become one."""
 
     @staticmethod
-    def forward(ctx, x, reso, split, idx, heads, scale, eps1, eps2, rs1, rs2, drop, g1, b1, wqkv, bqkv, wp, bp, g2, b2, w1, bb1,
+    def forward(ctx, x, reso, split, idx, heads, scale, eps1, eps2, rs1, rs2, orders, drop, g1, b1, wqkv, bqkv, wp, bp, g2, b2, w1, bb1,
                 w2, bb2, *lepe):
         x = dev_f32(x, "block input")
         B, L, C = x.shape
@@ -605,15 +627,21 @@ class _CSWinBlock(Function):
         E16 = lambda *shape: torch.empty(*shape, dtype=t16, device=dev)
         sq, sp, s1, s2 = (_wsrc(w) if s16 else w for w in (wqkv, wp, w1, w2))
         attn = (reso, split, tuple(idx), tuple(heads), scale, drop, ATTN_MFMA16 if s16 else ATTN_FP32)
+        # fp32 with the step's sample orders (drop_path_order): the eight forward / data-gradient Linears leave the dropped samples'
+        # rows out.  Their rows of qkv / pre / act then hold the bias's image and of x1 / y the residual: finite, and never used.
+        o1 = o2 = None
+        if orders is not None and precision() == 0 and B <= MAX_MASK_SAMPLES and C % 4 == 0 and w1.shape[0] % 4 == 0:
+            o1, o2 = orders
+        ctx.orders = (o1, o2)
         h1, m1, r1 = _layernorm_fwd(x, g1, b1, eps1, t16)
-        qkv = _linear_fwd(h1, sq, bqkv, 3 * C, dtype=t16)
+        qkv = _linear_fwd(h1, sq, bqkv, 3 * C, dtype=t16, order=o1)
         att, lse = E16(B, L, C), torch.empty(B, sum(heads), L, dtype=torch.float32, device=dev)
         att0 = E16(B, L, C) if any(ctx.needs_input_grad) else None       # P V without LePE: the attention backward's delta term
         _attn_fwd(qkv, lw, lb, att, att0, lse, *attn)
-        x1 = _linear_fwd(att, sp, bp, C, residual=x, row_scale=rs1)
+        x1 = _linear_fwd(att, sp, bp, C, residual=x, row_scale=rs1, order=o1)
         h2, m2, r2 = _layernorm_fwd(x1, g2, b2, eps2, t16)
-        pre, act = _linear_fwd(h2, s1, bb1, w1.shape[0], dtype=t16, gelu=True)
-        y = _linear_fwd(act, s2, bb2, C, residual=x1, row_scale=rs2)
+        pre, act = _linear_fwd(h2, s1, bb1, w1.shape[0], dtype=t16, gelu=True, order=o2)
+        y = _linear_fwd(act, s2, bb2, C, residual=x1, row_scale=rs2, order=o2)
         ctx.save_for_backward(x, m1, r1, h1, qkv, lse, att, att0, x1, m2, r2, h2, pre, act, rs1, rs2, g1, wqkv, wp, g2, w1, w2, *lw, *lb)
         ctx.attn = attn
         ctx.keys = _param_keys(g1, b1, wqkv, bqkv, wp, bp, g2, b2, w1, bb1, w2, bb2, *lepe)
@@ -626,6 +654,7 @@ class _CSWinBlock(Function):
         nb = len(lwb) // 2
         lw, lb = lwb[:nb], lwb[nb:]
         dy = dev_f32(dy)
+        o1, o2 = ctx.orders
         B, L, C = x.shape
         M, Hd = B * L, w1.shape[0]
         dev, h = x.device, lib()
@@ -643,7 +672,7 @@ class _CSWinBlock(Function):
         dyg = dy16 if dy16 is not None else dy          # what the GEMMs read
         # ---- MLP branch ----
         dpre = torch.empty_like(pre)
-        _linear_bwd_data(dyg, s2, dpre, gelu_pre=pre, row_scale=rs2)
+        _linear_bwd_data(dyg, s2, dpre, gelu_pre=pre, row_scale=rs2, order=o2)
         # the four weight gradients are off the critical path: they run as ONE batched launch once all operands exist
         wg = (WgradDesc * 4)()
         kg1, kb1, kwqkv, kbqkv, kwp, kbp, kg2, kb2, kw1, kbb1, kw2, kbb2, *klepe = ctx.keys
@@ -653,14 +682,14 @@ class _CSWinBlock(Function):
         dw1, db1 = G(kw1, *w1.shape), G(kbb1, Hd)
         _fill_wgrad(wg[1], dpre, h2, None, dw1, db1, wsp[1], sizes[1])
         dh2 = torch.empty_like(x)                                      # fp32 (x is)
-        _linear_bwd_data(dpre, s1, dh2)
+        _linear_bwd_data(dpre, s1, dh2, order=o2)
         dx1, dg2, dbt2 = torch.empty_like(x), G(kg2, C), G(kb2, C)
         dx1_16 = torch.empty_like(x, dtype=torch.bfloat16) if s16 else None      # the GEMMs below read the twin, the residual path dx1
         _layernorm_bwd(dh2, x1, m2, r2, g2, dx1, dg2, dbt2, (wsp[2], sizes[2], _job_ptr(jobs, 2)), dres=dy, dx16=dx1_16)
         dx1g = dx1_16 if s16 else dx1
         # ---- attention branch ----
         datt = dh2                                                     # reuse
-        _linear_bwd_data(dx1g, sp, datt, row_scale=rs1)
+        _linear_bwd_data(dx1g, sp, datt, row_scale=rs1, order=o1)
         dwp, dbp = G(kwp, *wp.shape), G(kbp, C)
         _fill_wgrad(wg[2], dx1g, att, rs1, dwp, dbp, wsp[3], sizes[3])
         dqkv = torch.empty_like(qkv)
@@ -685,7 +714,10 @@ class _CSWinBlock(Function):
                 # DropPath: a sample with rs2 == 0 has zero rows in rs2 . dy and in dpre, one with rs1 == 0 in rs1 . dx1 and in dqkv
                 # (the attention backward of datt = 0), so the factors are the sample masks of the weight gradients those feed
                 skip = (ctypes.c_void_p * 4)(*[m.data_ptr() if m is not None else None for m in masks])
-                call("cswin_linear_bwd_tail_masked", *tail, skip, _int_array([B] * 4), stream())
+                if o1 is not None:
+                    call("cswin_linear_bwd_tail_skip", *tail, skip, _int_array([B] * 4), ptr(o1), B, stream())
+                else:
+                    call("cswin_linear_bwd_tail_masked", *tail, skip, _int_array([B] * 4), stream())
             else:
                 call("cswin_linear_bwd_tail", *tail, stream())
         else:
@@ -699,15 +731,17 @@ class _CSWinBlock(Function):
         if s16:
             _twin_put(dx, dx16)
         _pass.reduce(jobs, (ws, aws))
-        grads = (dx, None, None, None, None, None, None, None, None, None, None, dg1, dbt1, dwqkv, dbqkv, dwp, dbp, dg2, dbt2, dw1, db1,
+        grads = (dx, None, None, None, None, None, None, None, None, None, None, None, dg1, dbt1, dwqkv, dbqkv, dwp, dbp, dg2, dbt2, dw1, db1,
                  dw2, db2)
         return grads + tuple(d.view(d.shape[0], 1, 3, 3) for d in dlw) + tuple(dlb)
 
 
-def cswin_block(x, reso, split, idx, heads, scale, norm1, qkv, proj, norm2, fc1, fc2, lepe_w, lepe_b, rs1=None, rs2=None, attn_drop=0.0):
+def cswin_block(x, reso, split, idx, heads, scale, norm1, qkv, proj, norm2, fc1, fc2, lepe_w, lepe_b, rs1=None, rs2=None, attn_drop=0.0,
+                orders=None):
     """Fused CSWinBlock forward/backward.  norm*/qkv/proj/fc*: nn.Modules holding the parameters.  attn_drop: dropout probability
-    on the attention probabilities (pass 0 outside training)."""
-    return _CSWinBlock.apply(x, reso, split, tuple(idx), tuple(heads), scale, norm1.eps, norm2.eps, rs1, rs2, _attn_drop(attn_drop),
+    on the attention probabilities (pass 0 outside training).  orders: None, or the rows of drop_path_order's order that belong to
+    (rs1, rs2): the block's Linears then skip the dropped samples' rows (fp32)."""
+    return _CSWinBlock.apply(x, reso, split, tuple(idx), tuple(heads), scale, norm1.eps, norm2.eps, rs1, rs2, orders, _attn_drop(attn_drop),
                              norm1.weight, norm1.bias, qkv.weight, qkv.bias, proj.weight, proj.bias, norm2.weight,
                              norm2.bias, fc1.weight, fc1.bias, fc2.weight, fc2.bias, *lepe_w, *lepe_b)
 

@@ -30,7 +30,7 @@ extern "C" {
  * cswin_attn_fwd writes y0, cswin_attn_bwd reads it).  cswin_abi_version() returns the value the library was built with: a consumer
  * compiled against another header must refuse to call it.  Entry points that are only ADDED (cswin_seg_metrics*, cswin_resize_banded, cswin_argmax_zoom_back, cswin_augment_*,
  * cswin_chunk_sumsq, cswin_norm_finalize, cswin_adamw_flat, cswin_tpgm_*, cswin_argmax_zoom_back_classes, cswin_class_counts, cswin_gaussian_blur, cswin_eb_tiles,
- * cswin_eb_finalize, cswin_rate_finalize, cswin_adam_flat, cswin_components_*) do not bump it: every prototype an older consumer binds is unchanged. */
+ * cswin_eb_finalize, cswin_rate_finalize, cswin_adam_flat, cswin_components_*, cswin_drop_path_order, cswin_linear_*_skip) do not bump it: every prototype an older consumer binds is unchanged. */
 #define CSWIN_ABI_VERSION 4
 
 #define CSWIN_OK 0
@@ -188,6 +188,28 @@ int cswin_linear_bwd_weight_batch_masked(const cswin_wgrad_desc* problems, int n
 int cswin_linear_bwd_tail_masked(const float* dy, const float* w, float* dx, int M, int N, int K, const cswin_wgrad_desc* problems, int n,
                                  cswin_reduce_job* deferred, const cswin_reduce_job* pending, int npending, const float* const* skip,
                                  const int* nsamples, void* stream);
+/* ---- DropPath: the forward and data-gradient Linears of a residual branch without the dropped samples' rows ----
+ * One wave per row of the step's draws: scales (rows, B) = (u (rows, B) < keep[row]) / keep[row], bit for bit the factors torch
+ * computes from the same draws, and order (rows, 1 + B): order[r][0] = the number of kept samples, then the kept sample indices
+ * ascending, then the dropped ones ascending.  B <= 256. */
+int cswin_drop_path_order(const float* u, const float* keep, float* scales, int* order, int rows, int B, void* stream);
+/* cswin_linear_fwd / cswin_linear_bwd_data / cswin_linear_bwd_tail_masked with a SAMPLE ORDER: order = one row of
+ * cswin_drop_path_order's output (1 + nsamples ints), M == nsamples * rows_per_sample.  The launch computes the kept samples' rows
+ * -- bit for bit what the unmapped call gives them -- in its first workgroups; the A rows (x / dy) and the gelu_pre rows of a
+ * dropped sample are NOT READ, and its rows of the result hold what zero A rows give: y = bias, y_act = GELU(bias), with a residual
+ * y = the residual row itself, dx = +0.  With every sample kept the whole result equals the unmapped call's bit for bit.  An order
+ * needs precision 0, io_bf16 0, no x2 / dx2 / add, nsamples <= 256, N and K multiples of 4 and 16-B aligned operands: anything
+ * else is an error return, never an unmapped run.  The tail's order (over nsamples_order samples of M / nsamples_order rows) maps its
+ * data gradient; skip / nsamples stay the weight gradients' masks. */
+int cswin_linear_fwd_skip(const float* x, const float* x2, int k_split, const float* w, const float* bias, float* y,
+                          float* y_act, const float* residual, const float* row_scale, int rows_per_sample, int M, int N,
+                          int K, int precision, int io_bf16, const int* order, int nsamples, void* stream);
+int cswin_linear_bwd_data_skip(const float* dy, const float* w, float* dx, float* dx2, int k_split, const float* gelu_pre,
+                               const float* row_scale, int rows_per_sample, const float* add, int M, int N, int K,
+                               int precision, int io_bf16, const int* order, int nsamples, void* stream);
+int cswin_linear_bwd_tail_skip(const float* dy, const float* w, float* dx, int M, int N, int K, const cswin_wgrad_desc* problems, int n,
+                               cswin_reduce_job* deferred, const cswin_reduce_job* pending, int npending, const float* const* skip,
+                               const int* nsamples, const int* order, int nsamples_order, void* stream);
 /* jobs: host array of 1..48 pending reductions (the workspaces they point into must still be alive) */
 int cswin_rows_sum_multi(const cswin_reduce_job* jobs, int njobs, void* stream);
 
