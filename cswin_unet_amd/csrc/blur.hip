@@ -11,17 +11,11 @@
 //   mode "reflect", d c b a | a b c d | d c b a: index i -> m = i mod 2n, m < n ? m : 2n - 1 - m, computed here from n alone, so
 //   a radius larger than the axis reflects as often as it has to and no index can leave the slice.
 #include "common.h"
-#include <initializer_list>
+#include "blur_plan.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-constexpr int BL_MAX_DIM = 2048;           // per dimension (and slices per call)
-constexpr int BL_MAX_RADIUS = 32;          // sigma <= 8.1 at truncate = 4
-constexpr int BL_LDS_ELEMS = 16384;        // floats = 64 KiB, the dynamic LDS a kernel gets without opt-in
-constexpr int BL_MAX_TR = 32;
-constexpr int BL_RB = 4;                   // outputs per thread and tap: TR is a multiple of it
 
 struct BlurArgs {
     const float* x;
@@ -116,31 +110,6 @@ __global__ __launch_bounds__(256) void gaussian_blur_kernel(BlurArgs a) {
     }
 }
 
-// Tile rows and chunk width for (W, r): (TR + 2r) CW + TR W floats of LDS.  The kernel waits on memory and on barriers more than
-// it computes, so it is the number of resident workgroups that sets its speed: 24 KiB per workgroup (six on a CU) is where a
-// 148 x 512 x 512 batch stops getting faster (DESIGN.md has the sweep; 64 KiB tiles take 1.7 times as long), and a wider
-// or longer-tapped slice takes the next budget that holds a tile.  The chunk starts at the widest one the loads can fill
-// (256 lanes x VEC, no wider than W needs) and is halved while the tile is shorter than 4r rows: the 2r halo rows are read
-// again by the neighbouring tile, and a narrower stage leaves room for more rows.  At CW = 64 and the whole 64 KiB the largest
-// case, W = 2048 with r = 32, has 5 rows, so a tile of BL_RB rows always exists.
-struct BlurPlan { int TR, cw_log2; };
-BlurPlan bl_plan(int H, int W, int r, int vec) {
-    for (int budget : {BL_LDS_ELEMS * 3 / 8, BL_LDS_ELEMS * 5 / 8, BL_LDS_ELEMS}) {
-        auto rows = [&](int cwl) { return (budget - 2 * r * (1 << cwl)) / ((1 << cwl) + W); };
-        int cwl = vec == 2 ? 9 : 8;
-        while (cwl > 6 && (1 << (cwl - 1)) >= W) --cwl;
-        const int Hr = cdiv(H, BL_RB) * BL_RB;                          // the whole slice in row groups
-        while (cwl > 6 && rows(cwl) < 4 * r && rows(cwl) < Hr) --cwl;
-        int TR = rows(cwl) / BL_RB * BL_RB;
-        if (TR < BL_RB) continue;
-        TR = TR > BL_MAX_TR ? BL_MAX_TR : TR;
-        return {TR > Hr ? Hr : TR, cwl};
-    }
-    return {0, 0};
-}
-
-bool bl_dim_ok(int n) { return n >= 1 && n <= BL_MAX_DIM; }
-
 }  // namespace
 
 extern "C" {
@@ -159,7 +128,7 @@ int cswin_gaussian_blur(const float* x, float* y, const double* taps, int radius
     CSWIN_REQUIRE(p.TR >= 1, CSWIN_ERR_UNSUPPORTED, "gaussian_blur: no tile of W=%d, radius=%d fits the LDS", W, radius);
     const BlurArgs a = {x, y, taps, radius, H, W, p.TR, p.cw_log2, fdiv_magic(W)};
     const dim3 grid(cdiv(H, p.TR), D), block(256);
-    const size_t lds = ((size_t)p.TR * W + (size_t)(p.TR + 2 * radius) * (1 << p.cw_log2)) * sizeof(float);
+    const size_t lds = (size_t)bl_lds_bytes(p, W, radius);
     hipStream_t st = (hipStream_t)stream;
     if (radius == 4) {                 // sigma = 1 at truncate = 4, the reference's shift
         if (vec == 2) hipLaunchKernelGGL((gaussian_blur_kernel<2, 4>), grid, block, lds, st, a);
