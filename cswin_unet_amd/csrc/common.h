@@ -326,12 +326,15 @@ struct ReduceRiders {
     int first_block[CSWIN_TAIL_RIDER_JOBS + 1];
     int njobs;
 };
+// what a job must meet before a launch takes it: the entry points check it on every job, before they enqueue anything
+static inline bool reduce_job_ok(const cswin_reduce_job& j) {
+    return j.part && j.out && j.n > 0 && j.rows > 0 && (j.conv_kk == 0) == (j.conv_cin == 0) && j.conv_kk >= 0;
+}
 // validate + flag the jobs of a table and give every job its workgroup range; returns the number of workgroups or -1
 static inline int fill_reduce_table(const cswin_reduce_job* jobs, int njobs, cswin_reduce_job* out, int* first_block) {
     int blocks = 0;
     for (int i = 0; i < njobs; ++i) {
-        if (!(jobs[i].part && jobs[i].out && jobs[i].n > 0 && jobs[i].rows > 0)) return -1;
-        if ((jobs[i].conv_kk == 0) != (jobs[i].conv_cin == 0) || jobs[i].conv_kk < 0) return -1;
+        if (!reduce_job_ok(jobs[i])) return -1;
         out[i] = jobs[i];
         first_block[i] = blocks;
         blocks += flag_reduce_job(out[i]);
@@ -345,6 +348,3 @@ static inline void reduce_now_or_defer(const cswin_reduce_job& job, cswin_reduce
     if (deferred) *deferred = job;
     else launch_reduce_job(job, st);
 }
-
-// floats between the split-M slabs of a weight gradient dw[N,K]: slab s = [dw partial (N*K) | dbias partial (N)] (gemm.hip's WgradSlabs)
-static inline long wgrad_slab_stride(int N, int K) { return (long)N * K + N; }

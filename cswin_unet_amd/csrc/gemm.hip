@@ -23,23 +23,22 @@
 #include <type_traits>
 #include "common.h"
 #include "gemm_epilogue.h"
+#include "gemm_plan.h"
 
-// both operands stored as bf16 (gemm16.hip); 0 = launched, 1 = not covered
-int cswin_gemm16(int mode, int epi_mode, const void* A, const void* B, const void* epilogue, int M, int NO, int R, void* stream);
+// both operands stored as bf16 (gemm16.hip), launched as plan (Kernel::gemm16) says; 0 = launched, 1 = a HIP error
+int cswin_gemm16(const gp::Plan& plan, int mode, int epi_mode, const void* A, const void* B, const void* epilogue, int M, int NO, int R, void* stream);
 // wgrad16.hip: bf16-operand weight gradients with transposing LDS reads (bf16 matmul mode)
-int cswin_wgrad16_batch(const cswin_wgrad_desc* d, int n, const int* splits, const int* rows_per_split, const cswin_reduce_job* pending,
-                        int npending, void* stream, long long* stamps);
+void cswin_wgrad16_batch(const cswin_wgrad_desc* d, int n, const gp::Plan* plans, const cswin_reduce_job* pending, int npending, void* stream,
+                         long long* stamps);
 
 namespace {
-
-constexpr int BKMAX = 64;     // largest reduction tile (split sizes are multiples of it)
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // matmul precision is an ARGUMENT of every entry point (no library state): 0 = exact fp32 MFMA (the parity path);
 // 1 = operands rounded to bf16 while they are staged into LDS, v_mfma_f32_32x32x16_bf16, fp32 accumulation and fp32
 // storage everywhere (BASELINE configs 3-5 name bf16)
-#define CSWIN_CHECK_PRECISION(p, who) CSWIN_REQUIRE((p) == 0 || (p) == 1, CSWIN_ERR_UNSUPPORTED, who ": precision %d (0 = fp32, 1 = bf16 operands)", (p))
+#define CSWIN_CHECK_PRECISION(p, who) CSWIN_REQUIRE((p) == 0 || (p) == 1, CSWIN_ERR_UNSUPPORTED, "%s: precision %d (0 = fp32, 1 = bf16 operands)", who, (p))
 
 // ------------------------------------------------------------------------------------
 // operand sources: a logical matrix S(i, j) whose fast (contiguous) index is j
@@ -783,7 +782,7 @@ __global__ __launch_bounds__((Tile<BM, BN, BK, KW, true, B_RC>::THREADS)) void g
 // Up to four independent problems of one kernel configuration in ONE launch (the weight gradients of the four Linears of a
 // CSWinBlock: operands all alive at the end of the block's backward): an empty launch costs ~3 us in-stream, and the four grids'
 // tails fill each other.  Each problem keeps its own XCD-aware block order inside its block range.
-constexpr int WGRAD_BATCH = 4;
+constexpr int WGRAD_BATCH = gp::WGRAD_BATCH;
 template <class ASrc, class BSrc>
 struct GemmBatch {
     ASrc A[WGRAD_BATCH];
@@ -895,8 +894,10 @@ __global__ __launch_bounds__(S2DgradTile<KW>::THREADS) void gemm_conv_s2_dgrad_b
 }
 
 // ======================================================================================
-// host side: launch policy (tile, k-groups, splits, batches), then the C ABI
+// host side: the launches of what gemm_plan.h decides (tile, k-groups, widths, splits, routes), then the C ABI
 // ======================================================================================
+using gp::one_split;
+
 template <int BM, int BN, int BK, int KW, bool A_RC, bool B_RC, int VEC, int EPI, bool SCALE_A, int PREC, class ASrc, class BSrc>
 void launch_cfg(const ASrc& A, const BSrc& B, const Epilogue& epi, int M, int N, int R, int splits, int r_per_split,
                 hipStream_t st, const RowMap* rm = nullptr) {
@@ -915,66 +916,45 @@ void launch_cfg(const ASrc& A, const BSrc& B, const Epilogue& epi, int M, int N,
                        M, N, R, r_per_split, tm, tn);
 }
 
-// Wave groups (KW) for a launch of `blocks` workgroups whose reduction is r_len long: with fewer than ~2 workgroups per CU and
-// a long reduction, split the k-range of each tile over 2 or 4 wave groups so every SIMD still has independent MFMA chains.
-int k_groups(long blocks, int r_len) {
-    if (blocks < 320 && r_len >= 512) return 4;
-    if (blocks < 640 && r_len >= 256) return 2;
-    return 1;
-}
-
-// a reduction of R in one split: r_per_split is a whole number of k-tiles
-int one_split(int R) { return cdiv(R, BKMAX) * BKMAX; }
-
-// tile choice (measured on MI355X, tools/gemm_bench.py): the largest tile that still yields >= ~1.5 workgroups per CU
+// The launch of a plan of the tiled family (gp::tiled_plan) at the loader width VEC: the plan's tile, k-tile, wave groups, split and
+// epilogue width.  These seven configurations are all the family has.
 template <bool A_RC, bool B_RC, int VEC, int EPI, bool SCALE_A, class ASrc, class BSrc>
-void launch_gemm(const ASrc& A, const BSrc& B, const Epilogue& epi_in, int M, int N, int R, int splits, int r_per_split,
-                 int precision, hipStream_t st, const RowMap* rm = nullptr) {
+void launch_gemm(const gp::Plan& p, const ASrc& A, const BSrc& B, const Epilogue& epi_in, int M, int N, int R, int precision,
+                 hipStream_t st, const RowMap* rm = nullptr) {
     Epilogue epi = epi_in;
-    epi.vec_store = epilogue_vec_ok(epi, N);
-    auto blocks = [&](int bm, int bn) { return (long)cdiv(M, bm) * cdiv(N, bn) * splits; };
-    const int forced_kw = cswin_tuning().gemm_kw;                                                               // tuning aid
-    // Tile choice.  64 x 64 is the most efficient tile (profiles/round1_gemm_bench.txt), but every workgroup of these
-    // launches is resident at once and the kernel ends with the most loaded CU: with t tiles the critical CU does
-    // ceil(t / 256) of them.  When that is a poor multiple (stage 3: 296 tiles -> 2 where 1.16 would do) a smaller tile
-    // shortens the critical path although it is a little less efficient per flop (penalties measured with gemm_bench).
-    const int forced_tile = cswin_tuning().gemm_tile;                                                // tuning aid: 1 = 64x64, 2 = 64x32
-    // measured (profiles/round1_gemm_tiles.txt): a 64 x 32 tile costs ~1.2x per flop, so it only pays where it cuts the
-    // critical CU's share by more than that (296 -> 592 tiles: 2 -> 1.5 units); 32 x 32 single-wave tiles never paid.
-    const double pen2 = cswin_tuning().gemm_pen2;
-    auto cost = [&](int bm, int bn, double pen) { return (double)((blocks(bm, bn) + 255) / 256) * bm * bn * pen; };
-    int tile = 1;
-    if (splits == 1 && cost(64, 32, pen2) < cost(64, 64, 1.0)) tile = 2;
-    if (forced_tile) tile = forced_tile;
-    const int r_len = r_per_split < R ? r_per_split : R;
-    const bool wgrad = !A_RC && !B_RC;
+    epi.vec_store = p.store == 4;
     if (precision == 1) {
-        // bf16 operands: 16x fewer MFMA cycles per tile, the kernel is bound by staging and barriers: one k-tile of 64,
-        // and two wave groups only where a long reduction meets few workgroups
-        if (k_groups(blocks(64, 64), r_len) >= 2 || (wgrad && r_len >= 256))
-            launch_cfg<64, 64, 64, 2, A_RC, B_RC, VEC, EPI, SCALE_A, 1>(A, B, epi, M, N, R, splits, r_per_split, st);
-        else launch_cfg<64, 64, 64, 1, A_RC, B_RC, VEC, EPI, SCALE_A, 1>(A, B, epi, M, N, R, splits, r_per_split, st);
+        if (p.kw == 2) launch_cfg<64, 64, 64, 2, A_RC, B_RC, VEC, EPI, SCALE_A, 1>(A, B, epi, M, N, R, p.splits, p.rows, st);
+        else launch_cfg<64, 64, 64, 1, A_RC, B_RC, VEC, EPI, SCALE_A, 1>(A, B, epi, M, N, R, p.splits, p.rows, st);
         return;
     }
-    if (tile == 2) {
-        if (k_groups(blocks(64, 32), r_len) >= 2)
-            return launch_cfg<64, 32, 64, 2, A_RC, B_RC, VEC, EPI, SCALE_A, 0>(A, B, epi, M, N, R, splits, r_per_split, st, rm);
-        return launch_cfg<64, 32, 32, 1, A_RC, B_RC, VEC, EPI, SCALE_A, 0>(A, B, epi, M, N, R, splits, r_per_split, st, rm);
+    if (p.bn == 32) {
+        if (p.kw == 2) return launch_cfg<64, 32, 64, 2, A_RC, B_RC, VEC, EPI, SCALE_A, 0>(A, B, epi, M, N, R, p.splits, p.rows, st, rm);
+        return launch_cfg<64, 32, 32, 1, A_RC, B_RC, VEC, EPI, SCALE_A, 0>(A, B, epi, M, N, R, p.splits, p.rows, st, rm);
     }
-    int kw = k_groups(blocks(64, 64), r_len);
-    if (wgrad && r_len >= 256 && kw < 2) kw = 2;               // weight gradients: measured 5-8 % faster
-    if (forced_kw) kw = forced_kw;
-    if (kw == 4) launch_cfg<64, 64, 64, 4, A_RC, B_RC, VEC, EPI, SCALE_A, 0>(A, B, epi, M, N, R, splits, r_per_split, st, rm);
-    else if (kw == 2) launch_cfg<64, 64, 64, 2, A_RC, B_RC, VEC, EPI, SCALE_A, 0>(A, B, epi, M, N, R, splits, r_per_split, st, rm);
-    else launch_cfg<64, 64, 32, 1, A_RC, B_RC, VEC, EPI, SCALE_A, 0>(A, B, epi, M, N, R, splits, r_per_split, st, rm);
+    if (p.kw == 4) launch_cfg<64, 64, 64, 4, A_RC, B_RC, VEC, EPI, SCALE_A, 0>(A, B, epi, M, N, R, p.splits, p.rows, st, rm);
+    else if (p.kw == 2) launch_cfg<64, 64, 64, 2, A_RC, B_RC, VEC, EPI, SCALE_A, 0>(A, B, epi, M, N, R, p.splits, p.rows, st, rm);
+    else launch_cfg<64, 64, 32, 1, A_RC, B_RC, VEC, EPI, SCALE_A, 0>(A, B, epi, M, N, R, p.splits, p.rows, st, rm);
 }
 
-// launch_gemm with the loaders' width chosen at run time: vec = 16-B loads are legal (alignment, sizes multiples of 4)
+// launch_gemm at the plan's loader width (a row map only goes with 16-B loads: the entry points refuse it otherwise)
 template <bool A_RC, bool B_RC, int EPI, bool SCALE_A, class ASrc, class BSrc>
-void launch_gemm_vec(bool vec, const ASrc& A, const BSrc& B, const Epilogue& epi, int M, int N, int R, int splits, int r_per_split,
-                     int precision, hipStream_t st) {
-    if (vec) launch_gemm<A_RC, B_RC, 4, EPI, SCALE_A>(A, B, epi, M, N, R, splits, r_per_split, precision, st);
-    else launch_gemm<A_RC, B_RC, 1, EPI, SCALE_A>(A, B, epi, M, N, R, splits, r_per_split, precision, st);
+void launch_gemm_vec(const gp::Plan& p, const ASrc& A, const BSrc& B, const Epilogue& epi, int M, int N, int R, int precision,
+                     hipStream_t st, const RowMap* rm = nullptr) {
+    if (p.vec == 4) launch_gemm<A_RC, B_RC, 4, EPI, SCALE_A>(p, A, B, epi, M, N, R, precision, st, rm);
+    else launch_gemm<A_RC, B_RC, 1, EPI, SCALE_A>(p, A, B, epi, M, N, R, precision, st);
+}
+
+// launch_gemm_vec at the epilogue mode epi_mode, one of EPIS: the modes the caller's forms can take (each is its own set of kernels)
+template <bool A_RC, bool B_RC, int... EPIS, class ASrc, class BSrc>
+void launch_gemm_epi(int epi_mode, const gp::Plan& p, const ASrc& A, const BSrc& B, const Epilogue& epi, int M, int N, int R,
+                     int precision, hipStream_t st, const RowMap* rm = nullptr) {
+    ((epi_mode == EPIS ? launch_gemm_vec<A_RC, B_RC, EPIS, false>(p, A, B, epi, M, N, R, precision, st, rm) : (void)0), ...);
+}
+
+// the plan of a launch with 16-B loaders whose reduction is one split (the convolutions' forward and data gradient)
+gp::Plan one_split_plan(const Epilogue& e, int M, int N, int R, int precision) {
+    return gp::tiled_plan(cswin_tuning(), M, N, R, 1, one_split(R), false, precision, true, epilogue_vec_ok(e, N));
 }
 
 long long* g_stamps = nullptr;     // debug only (cswin_debug_set_stamps)
@@ -988,47 +968,23 @@ Epilogue plain_epilogue(float* C, long ldc) {
 }
 
 // problem (A, B, e) with M x N outputs and a reduction of R in `splits` slices of rps as the next slot of a batch; its 64 x 64
-// tiles take the next workgroups (first[b.n] is the launch's workgroup count so far)
+// tiles take the next workgroups (first[b.n] is the launch's workgroup count so far).  vec_store: its epilogue's 16-B accesses are legal
 template <class ASrc, class BSrc>
-void push(GemmBatch<ASrc, BSrc>& b, const ASrc& A, const BSrc& B, Epilogue e, int M, int N, int R, int rps, int splits) {
+void push(GemmBatch<ASrc, BSrc>& b, const ASrc& A, const BSrc& B, Epilogue e, int M, int N, int R, int rps, int splits, bool vec_store) {
     const int i = b.n++;
-    e.vec_store = epilogue_vec_ok(e, N);
+    e.vec_store = vec_store;
     b.A[i] = A; b.B[i] = B; b.e[i] = e;
     b.M[i] = M; b.N[i] = N; b.R[i] = R; b.rps[i] = rps;
     b.tm[i] = cdiv(M, 64); b.tn[i] = cdiv(N, 64);
     b.first[i + 1] = b.first[i] + b.tm[i] * b.tn[i] * splits;
 }
 
-// split count for the M-reduction of a weight gradient: enough workgroups to fill the chip
-void choose_split(int M, int out_rows, int out_cols, int* splits, int* r_per_split, int target_override = 0) {
-    // Every workgroup is resident at once and the kernel ends with the most loaded CU, so aim at a workgroup count
-    // that is a whole multiple of the 256 CUs (3 per CU): slices need not be multiples of the k-tile (the loaders mask
-    // the ragged last tile), only of 8.
-    const int target_env = cswin_tuning().gemm_split_wgs;                                                       // tuning aid
-    const int target = target_override > 0 ? target_override : target_env;
-    long tiles = (long)cdiv(out_rows, 64) * cdiv(out_cols, 64);
-    int s = (int)(target / tiles);
-    if (s < 1) s = 1;
-    int max_s = cdiv(M, 2 * BKMAX);
-    if (s > max_s) s = max_s;
-    if (s < 1) s = 1;
-    int rps = cdiv(cdiv(M, s), 8) * 8;
-    *splits = cdiv(M, rps);
-    *r_per_split = rps;
-}
-
 // The workspace of a split-M weight gradient dw[N,K] (+ dbias[N]): slab s = [dw partial (N*K) | dbias partial (N)], the slabs
-// wgrad_slab_stride(N, K) apart, so that one reduction launch serves both.  The GEMM's epilogue writes the slabs, the job sums them.
+// gp::slab_stride(N, K) apart, so that one reduction launch serves both.  The GEMM's epilogue writes the slabs, the job sums them.
+// (Its size is gp::wgrad_workspace_bytes.)
 struct WgradSlabs {
     float* base; long stride; int N, K;
-    WgradSlabs(void* workspace, int N_, int K_) : base((float*)workspace), stride(wgrad_slab_stride(N_, K_)), N(N_), K(K_) {}
-    // covers the stand-alone split policy and the batched one (up to 1024 workgroups for a single problem)
-    static size_t bytes(int M, int N, int K) {
-        int s0, s1, rps;
-        choose_split(M, N, K, &s0, &rps);
-        choose_split(M, N, K, &s1, &rps, 1024);
-        return (size_t)(s0 > s1 ? s0 : s1) * wgrad_slab_stride(N, K) * sizeof(float);
-    }
+    WgradSlabs(void* workspace, int N_, int K_) : base((float*)workspace), stride(gp::slab_stride(N_, K_)), N(N_), K(K_) {}
     Epilogue epilogue(bool with_dbias) const {
         Epilogue e = plain_epilogue(base, K);
         e.split_stride = stride;
@@ -1043,46 +999,61 @@ struct WgradSlabs {
     }
 };
 
+bool reduce_jobs_ok(const cswin_reduce_job* jobs, int njobs) {
+    for (int i = 0; i < njobs; ++i)
+        if (!reduce_job_ok(jobs[i])) return false;
+    return true;
+}
+
+// one launch for njobs (<= CSWIN_MAX_REDUCE_JOBS) reductions that reduce_jobs_ok has passed
+void launch_rows_sum(const cswin_reduce_job* jobs, int njobs, hipStream_t st) {
+    ReduceJobs J = {};
+    const int blocks = fill_reduce_table(jobs, njobs, J.j, J.first_block);
+    J.njobs = njobs;
+    hipLaunchKernelGGL(rows_sum_multi_kernel, dim3(blocks), dim3(256), 0, st, J);
+}
+
 // jobs: HOST array of njobs (<= CSWIN_MAX_REDUCE_JOBS = 48) reductions left pending by *_bwd_weight / layernorm_bwd calls with `deferred` set
 int rows_sum_multi(const cswin_reduce_job* jobs, int njobs, void* stream) {
     CSWIN_REQUIRE(jobs && njobs > 0 && njobs <= CSWIN_MAX_REDUCE_JOBS, CSWIN_ERR_SHAPE, "rows_sum_multi: 1..%d jobs", CSWIN_MAX_REDUCE_JOBS);
-    ReduceJobs J = {};
-    const int blocks = fill_reduce_table(jobs, njobs, J.j, J.first_block);
-    CSWIN_REQUIRE(blocks >= 0, CSWIN_ERR_SHAPE, "rows_sum_multi: bad job (part / out / n / rows, or conv_kk without conv_cin)");
-    J.njobs = njobs;
-    hipLaunchKernelGGL(rows_sum_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, J);
+    CSWIN_REQUIRE(reduce_jobs_ok(jobs, njobs), CSWIN_ERR_SHAPE, "rows_sum_multi: bad job (part / out / n / rows, or conv_kk without conv_cin)");
+    launch_rows_sum(jobs, njobs, (hipStream_t)stream);
     CSWIN_LAUNCH_CHECK();
     return CSWIN_OK;
 }
 
-// One weight gradient dw[N,K] = (row_scale . dy)^T @ [x | x2] through the tiled GEMM (arguments checked by the caller); its slab
-// reduction runs at once or goes to *deferred
-int wgrad_tiled(const float* dy, const float* x, const float* x2, int k_split, const float* row_scale, int rows_per_sample, float* dw,
-                float* dbias, void* workspace, int M, int N, int K, cswin_reduce_job* deferred, int precision, hipStream_t st) {
-    int splits, rps;
-    choose_split(M, N, K, &splits, &rps);
+// One weight gradient dw[N,K] = (row_scale . dy)^T @ [x | x2] through the tiled GEMM as plan (gp::wgrad_tiled_plan) says; arguments
+// checked by the caller.  Its slab reduction runs at once or goes to *deferred
+int wgrad_tiled(const gp::Plan& plan, const float* dy, const float* x, const float* x2, int k_split, const float* row_scale, int rows_per_sample,
+                float* dw, float* dbias, void* workspace, int M, int N, int K, cswin_reduce_job* deferred, int precision, hipStream_t st) {
     const WgradSlabs slabs(workspace, N, K);
     const Epilogue e = slabs.epilogue(dbias != nullptr);
     PlainSrc A = {dy, N, M, N, row_scale, rows_per_sample};      // S(i = m (reduction), j = n)
     if (x2) {
         ConcatSrc B = {x, x2, k_split, K - k_split, M, K, k_split};
-        bool vec = (N % 4 == 0) && (K % 4 == 0) && (k_split % 4 == 0) && aligned16(dy) && aligned16(x) && aligned16(x2);
-        launch_gemm_vec<false, false, EPI_PLAIN, true>(vec, A, B, e, N, K, M, splits, rps, precision, st);
+        launch_gemm_vec<false, false, EPI_PLAIN, true>(plan, A, B, e, N, K, M, precision, st);
     } else {
         PlainSrc B = {x, K, M, K, nullptr, 1};
-        bool vec = (N % 4 == 0) && (K % 4 == 0) && aligned16(dy) && aligned16(x);
-        if (row_scale) launch_gemm_vec<false, false, EPI_PLAIN, true>(vec, A, B, e, N, K, M, splits, rps, precision, st);
-        else launch_gemm_vec<false, false, EPI_PLAIN, false>(vec, A, B, e, N, K, M, splits, rps, precision, st);
+        if (row_scale) launch_gemm_vec<false, false, EPI_PLAIN, true>(plan, A, B, e, N, K, M, precision, st);
+        else launch_gemm_vec<false, false, EPI_PLAIN, false>(plan, A, B, e, N, K, M, precision, st);
     }
     CSWIN_LAUNCH_CHECK();
-    reduce_now_or_defer(slabs.job(dw, dbias, splits), deferred, st);
+    reduce_now_or_defer(slabs.job(dw, dbias, plan.splits), deferred, st);
     CSWIN_LAUNCH_CHECK();
     return CSWIN_OK;
 }
 
-// what the batch kernels require of a problem: 16-B loads of both operands and 16-B stores to the slabs
-bool wgrad_aligned(const cswin_wgrad_desc& p) {
-    return p.N % 4 == 0 && p.K % 4 == 0 && aligned16(p.dy) && aligned16(p.x) && aligned16(p.workspace);
+// a problem of a weight-gradient call as the policy sees it
+gp::WgradProblem wgrad_problem(const cswin_wgrad_desc& p, bool has_mask) {
+    gp::WgradProblem q = {};
+    q.M = p.M; q.N = p.N; q.K = p.K; q.io_bf16 = p.io_bf16;
+    q.loads_aligned = aligned16(p.dy) && aligned16(p.x);
+    q.ws_aligned = aligned16(p.workspace);
+    q.has_scale = p.row_scale != nullptr;
+    q.rows_per_sample = p.rows_per_sample;
+    q.has_mask = has_mask;
+    q.ws_bytes = p.ws_bytes;
+    return q;
 }
 
 // what may ride at the end of the weight-gradient batch's grid: a plain fp32 data gradient dx[M,K] = dy[M,N] @ w[N,K] (dy == NULL:
@@ -1095,181 +1066,186 @@ struct TailExtras {
     const int* order; int order_samples;
 };
 
-// The row map of a forward / data-gradient Linear over M rows, or why the launch cannot take one: a refusal, never an unmapped run
-// (the caller's contract is that a dropped sample's rows of A are NOT READ).  No HIP call is made before these checks.
+// What a per-sample table over the M rows of a launch must meet -- `what` names it: the sample order of a forward / data-gradient
+// Linear (RowMap) or the sample mask of a weight gradient (RowMask) --, or why the launch cannot take it: a refusal, never a run
+// without it (the caller's contract is that a dropped sample's rows are NOT READ).  slack: rows past M that the kernel divides before
+// it tests them.  The 16-B accesses both need are the caller's to check, on its plan.
+int samples_checked(const char* who, const char* what, const void* table, int nsamples, int rows_per_sample, int M, int slack, int precision) {
+    CSWIN_REQUIRE(precision == 0, CSWIN_ERR_UNSUPPORTED, "%s: a %s needs precision 0", who, what);
+    CSWIN_REQUIRE(table && nsamples >= 1 && nsamples <= MASK_MAX_SAMPLES, CSWIN_ERR_SHAPE, "%s: the %s must list 1..%d samples", who, what,
+                  MASK_MAX_SAMPLES);
+    CSWIN_REQUIRE(M > 0 && rows_per_sample > 0 && (long)nsamples * rows_per_sample == M, CSWIN_ERR_SHAPE,
+                  "%s: the %s: nsamples * rows_per_sample != M", who, what);
+    CSWIN_REQUIRE(fdiv_exact((long)M + slack, rows_per_sample), CSWIN_ERR_UNSUPPORTED, "%s: the %s: M * rows_per_sample must stay below 2^32", who,
+                  what);
+    return CSWIN_OK;
+}
+
+// The row map of a forward / data-gradient Linear over M rows.  No HIP call is made before these checks.
 int row_map_checked(RowMap* rm, const char* who, const int* order, int nsamples, int rows_per_sample, int M, int precision, int io_bf16,
                     bool two_part, bool add) {
     CSWIN_REQUIRE(precision == 0 && io_bf16 == 0, CSWIN_ERR_UNSUPPORTED, "%s: a sample order needs precision 0 and fp32 storage", who);
     CSWIN_REQUIRE(!two_part, CSWIN_ERR_UNSUPPORTED, "%s: a sample order takes no concat / split operand", who);
     CSWIN_REQUIRE(!add, CSWIN_ERR_UNSUPPORTED, "%s: a sample order takes no add operand", who);
-    CSWIN_REQUIRE(order && nsamples >= 1 && nsamples <= MASK_MAX_SAMPLES, CSWIN_ERR_SHAPE, "%s: the order must list 1..%d samples", who,
-                  MASK_MAX_SAMPLES);
-    CSWIN_REQUIRE(M > 0 && rows_per_sample > 0 && (long)nsamples * rows_per_sample == M, CSWIN_ERR_SHAPE,
-                  "%s: nsamples * rows_per_sample != M", who);
-    CSWIN_REQUIRE(fdiv_exact((long)M + 63, rows_per_sample), CSWIN_ERR_UNSUPPORTED, "%s: M * rows_per_sample must stay below 2^32", who);
+    int rc = samples_checked(who, "sample order", order, nsamples, rows_per_sample, M, 63, precision);
+    if (rc) return rc;
     *rm = RowMap{order, nsamples, rows_per_sample, fdiv_magic(rows_per_sample)};
     return CSWIN_OK;
 }
 
-int wgrad_batch_impl(const cswin_wgrad_desc* d, int n, cswin_reduce_job* deferred, const TailExtras& x, void* stream) {
-    CSWIN_REQUIRE(x.njobs >= 0 && x.njobs <= CSWIN_TAIL_RIDER_JOBS && (x.njobs == 0 || x.jobs), CSWIN_ERR_SHAPE,
-                  "%s: 0..%d pending reductions", x.who, CSWIN_TAIL_RIDER_JOBS);
-    CSWIN_REQUIRE(d && deferred && n >= 1 && n <= WGRAD_BATCH, CSWIN_ERR_SHAPE, "linear_bwd_weight_batch: 1..%d problems and their deferred slots", WGRAD_BATCH);
-    bool fast = true, any_bf16 = false, any_mask = false;
-    const int precision = d[0].precision;
-    RowMap dmap = {};
-    if (x.order) {
-        CSWIN_REQUIRE(x.dy && x.order_samples >= 1 && x.M % x.order_samples == 0, CSWIN_ERR_SHAPE, "%s: nsamples * rows_per_sample != M", x.who);
-        int rc = row_map_checked(&dmap, x.who, x.order, x.order_samples, x.M / x.order_samples, x.M, precision, 0, false, false);
-        if (rc) return rc;
-        CSWIN_REQUIRE(x.N % 4 == 0 && x.K % 4 == 0 && aligned16(x.dy) && aligned16(x.w) && aligned16(x.dx), CSWIN_ERR_ALIGN,
-                      "%s: a sample order needs N, K multiples of 4 and 16-B aligned operands", x.who);
-    }
-    CSWIN_CHECK_PRECISION(precision, "linear_bwd_weight_batch");
-    for (int i = 0; i < n; ++i) {
-        CSWIN_REQUIRE(d[i].precision == precision, CSWIN_ERR_UNSUPPORTED, "linear_bwd_weight_batch: problems of one launch share one precision");
-        CSWIN_REQUIRE(d[i].io_bf16 == 0 || (precision == 1 && (d[i].io_bf16 & ~3) == 0), CSWIN_ERR_UNSUPPORTED, "linear_bwd_weight_batch: bf16 storage needs precision 1");
-        CSWIN_REQUIRE(d[i].dy && d[i].x && d[i].dw && d[i].M > 0 && d[i].N > 0 && d[i].K > 0, CSWIN_ERR_SHAPE, "linear_bwd_weight_batch: bad problem %d", i);
-        CSWIN_REQUIRE(!d[i].row_scale || d[i].rows_per_sample > 0, CSWIN_ERR_SHAPE, "linear_bwd_weight_batch: rows_per_sample must be > 0");
-        size_t need = WgradSlabs::bytes(d[i].M, d[i].N, d[i].K);
-        CSWIN_REQUIRE(d[i].workspace && d[i].ws_bytes >= need, CSWIN_ERR_WORKSPACE, "linear_bwd_weight_batch: workspace %zu < %zu", d[i].ws_bytes, need);
-        fast = fast && wgrad_aligned(d[i]);
-        any_bf16 = any_bf16 || d[i].io_bf16;
-        if (x.skip && x.skip[i]) {
-            // the contract of a mask is that a dropped sample's rows are NOT READ: what cannot keep it is refused, not run unmasked
-            any_mask = true;
-            CSWIN_REQUIRE(precision == 0, CSWIN_ERR_UNSUPPORTED, "%s: a sample mask needs precision 0", x.who);
-            CSWIN_REQUIRE(x.nsamples && x.nsamples[i] >= 1 && x.nsamples[i] <= MASK_MAX_SAMPLES, CSWIN_ERR_SHAPE,
-                          "%s: problem %d's mask must have 1..%d samples", x.who, i, MASK_MAX_SAMPLES);
-            CSWIN_REQUIRE(d[i].rows_per_sample > 0 && (long)x.nsamples[i] * d[i].rows_per_sample == d[i].M, CSWIN_ERR_SHAPE,
-                          "%s: problem %d's mask: nsamples * rows_per_sample != M", x.who, i);
-            CSWIN_REQUIRE(fdiv_exact(d[i].M, d[i].rows_per_sample), CSWIN_ERR_UNSUPPORTED,
-                          "%s: problem %d's mask: M * rows_per_sample must stay below 2^32", x.who, i);
-        }
-    }
-    CSWIN_REQUIRE(!any_mask || fast, CSWIN_ERR_ALIGN, "%s: a sample mask needs N, K multiples of 4 and 16-B aligned operands", x.who);
-    const bool has_dgrad = x.dy != nullptr, extra = has_dgrad || x.njobs > 0;
-    // the data gradient as a GEMM problem (as cswin_linear_bwd_data poses it): M x K outputs, reduction N in one split
-    const PlainSrc gA = {x.dy, x.N, x.M, x.N, nullptr, 1, 0}, gB = {x.w, x.K, x.N, x.K, nullptr, 1, 0};      // gB: S(i = n (reduction), j = k)
-    const bool g_vec = x.N % 4 == 0 && x.K % 4 == 0 && aligned16(x.dy) && aligned16(x.w);
-    const bool merge_on = cswin_tuning().gemm_tail_merge != 0;                                                  // tuning aid
-    const bool ride = extra && merge_on && fast && precision == 0 && (!has_dgrad || (g_vec && aligned16(x.dx)));
-    const bool w16_path = fast && precision == 1 && (cswin_tuning().wgrad16_on || any_bf16);
-    const bool jobs_ride16 = merge_on && w16_path && x.njobs > 0;                     // bf16 mode: the reductions ride in wgrad16's grid
-    if (extra && !ride) {                   // the data gradient (and the pending reductions) as launches of their own, then the batch as usual
-        if (has_dgrad) {
-            if (x.order)
-                launch_gemm<true, false, 4, EPI_PLAIN, false>(gA, gB, plain_epilogue(x.dx, x.K), x.M, x.K, x.N, 1, one_split(x.N), 0, (hipStream_t)stream, &dmap);
-            else
-                launch_gemm_vec<true, false, EPI_PLAIN, false>(g_vec, gA, gB, plain_epilogue(x.dx, x.K), x.M, x.K, x.N, 1, one_split(x.N), precision,
-                                                               (hipStream_t)stream);
-            CSWIN_LAUNCH_CHECK();
-        }
-        if (x.njobs > 0 && !jobs_ride16) {
-            int rc = rows_sum_multi(x.jobs, x.njobs, stream);
-            if (rc) return rc;
-        }
-    }
-    if (!fast) {
-        // Separate launches.  In bf16 mode a problem that is aligned by itself still goes through the batch path, as a batch of one.
-        for (int i = 0; i < n; ++i) CSWIN_REQUIRE(d[i].io_bf16 == 0, CSWIN_ERR_ALIGN, "linear_bwd_weight_batch: bf16 storage needs N, K multiples of 4 and 16-B alignment");
-        const TailExtras none = {x.who};
-        for (int i = 0; i < n; ++i) {
-            int rc = precision == 1 && wgrad_aligned(d[i])
-                         ? wgrad_batch_impl(&d[i], 1, &deferred[i], none, stream)
-                         : wgrad_tiled(d[i].dy, d[i].x, nullptr, 0, d[i].row_scale, d[i].rows_per_sample, d[i].dw, d[i].dbias, d[i].workspace,
-                                       d[i].M, d[i].N, d[i].K, &deferred[i], precision, (hipStream_t)stream);
-            if (rc) return rc;
-        }
-        return CSWIN_OK;
-    }
-    if (w16_path) {
-        // bf16 operands: 128 x 128 tiles, ~3 workgroups per CU over the whole batch (load-bound: see wgrad16.hip)
-        // Workgroups are shared out in proportion to the work (rows x tiles), so that every workgroup of the launch walks the same
-        // number of rows: with equal shares per problem the C x C problem's workgroups finished after 10 k cycles and the C x 4C
-        // ones after 37 k (in-kernel stamps, tools/wgrad16_stamps.py), and the launch lasts as long as its slowest workgroup.
-        int splits[WGRAD_BATCH], rps[WGRAD_BATCH];
-        double work_total = 0.0;
-        for (int i = 0; i < n; ++i) work_total += (double)d[i].M * cdiv(d[i].N, 128) * cdiv(d[i].K, 128);
-        for (int i = 0; i < n; ++i) {
-            const int M = d[i].M, N = d[i].N, K = d[i].K;
-            const WgradSlabs slabs(d[i].workspace, N, K);
-            const int tiles = cdiv(N, 128) * cdiv(K, 128);
-            const int w16_wgs = cswin_tuning().w16_wgs, w16_even = cswin_tuning().w16_even;                // tuning aids (1 = equal share per problem)
-            int s = w16_even ? (w16_wgs / n) / tiles : (int)(w16_wgs * ((double)M * tiles / work_total) / tiles + 0.5);
-            const int cap = (int)(d[i].ws_bytes / (slabs.stride * (long)sizeof(float)));
-            if (s > cap) s = cap;
-            if (s > M / 64) s = M / 64;
-            if (s < 1) s = 1;
-            rps[i] = cdiv(cdiv(M, s), 32) * 32;
-            splits[i] = cdiv(M, rps[i]);
-            deferred[i] = slabs.job(d[i].dw, d[i].dbias, splits[i]);
-        }
-        CSWIN_REQUIRE(cswin_wgrad16_batch(d, n, splits, rps, jobs_ride16 ? x.jobs : nullptr, jobs_ride16 ? x.njobs : 0, stream, g_stamps) == 0,
-                      CSWIN_ERR_SHAPE, "linear_bwd_weight_batch: bad pending reduction");
+// The launch of n aligned weight gradients as route r says (gp::aligned_batch_plans): wgrad16's grid, or the form r.kernel of the
+// batch kernel with what rides in its grid -- the data gradient of x (with its row map dmap) and x's pending reductions.
+// deferred[i] receives problem i's slab reduction.  Everything was checked by the caller: nothing here refuses.
+int launch_wgrad_batch(const gp::BatchRoute& r, const cswin_wgrad_desc* d, int n, cswin_reduce_job* deferred, const TailExtras& x,
+                       const RowMap& dmap, int precision, hipStream_t st) {
+    for (int i = 0; i < n; ++i) deferred[i] = WgradSlabs(d[i].workspace, d[i].N, d[i].K).job(d[i].dw, d[i].dbias, r.problem[i].splits);
+    if (r.kernel == gp::BatchKernel::wgrad16) {
+        cswin_wgrad16_batch(d, n, r.problem, r.jobs_ride ? x.jobs : nullptr, r.jobs_ride ? x.njobs : 0, st, g_stamps);
         CSWIN_LAUNCH_CHECK();
         return CSWIN_OK;
     }
     WgradBatch b = {};
     for (int i = 0; i < n; ++i) {
         const int M = d[i].M, N = d[i].N, K = d[i].K;
-        int splits, rps;
-        // 1024 workgroups per launch, i.e. exactly 4 per CU, shared by the problems (measured with four problems: 192 / 256 /
-        // 320 per problem -> 13.80 / 13.55 / 14.09 ms per step); a quarter of the slab traffic of four stand-alone launches
-        const int batch_env = cswin_tuning().gemm_batch_wgs;                                                      // tuning aid
-        // Equal shares per problem (the C x C problem then has 294-row workgroups beside the 1176-row ones of the C x 4C problems).
-        // Shares in proportion to the work (CSWIN_GEMM_BATCH_EVEN=0), which pays for the load-bound bf16 kernel above, measured
-        // SLOWER here: 13.70 against 13.28 ms/step -- this kernel is matrix-pipe bound and the extra slabs cost more than the tail.
-        const int batch_even = cswin_tuning().gemm_batch_even;                                                      // tuning aid
-        const int total_wgs = batch_env > 0 ? (batch_env < 1024 ? batch_env : 1024) * n : 1024;
-        int batch_target = total_wgs / n;                                                            // the workspace query covers <= 1024
-        if (!batch_even) {
-            double work = 0.0;
-            for (int j = 0; j < n; ++j) work += (double)d[j].M * cdiv(d[j].N, 64) * cdiv(d[j].K, 64);
-            batch_target = (int)(total_wgs * ((double)M * cdiv(N, 64) * cdiv(K, 64) / work) + 0.5);
-            if (batch_target > 1024) batch_target = 1024;
-            if (batch_target < 1) batch_target = 1;
-        }
-        choose_split(M, N, K, &splits, &rps, batch_target);
-        const WgradSlabs slabs(d[i].workspace, N, K);
-        CSWIN_REQUIRE((size_t)splits * slabs.stride * sizeof(float) <= d[i].ws_bytes, CSWIN_ERR_WORKSPACE,
-                      "linear_bwd_weight_batch: %d slabs do not fit problem %d's workspace", splits, i);
         push(b, PlainSrc{d[i].dy, N, M, N, d[i].row_scale, d[i].row_scale ? d[i].rows_per_sample : 1},   // S(i = m (reduction), j = n)
-             PlainSrc{d[i].x, K, M, K, nullptr, 1}, slabs.epilogue(d[i].dbias != nullptr), N, K, M, rps, splits);
-        deferred[i] = slabs.job(d[i].dw, d[i].dbias, splits);
-        if (x.skip && x.skip[i]) b.mask[i] = RowMask{x.skip[i], x.nsamples[i], d[i].rows_per_sample, splits, fdiv_magic(d[i].rows_per_sample)};
+             PlainSrc{d[i].x, K, M, K, nullptr, 1}, WgradSlabs(d[i].workspace, N, K).epilogue(d[i].dbias != nullptr), N, K, M, r.problem[i].rows,
+             r.problem[i].splits, r.problem[i].store == 4);
+        if (x.skip && x.skip[i])
+            b.mask[i] = RowMask{x.skip[i], x.nsamples[i], d[i].rows_per_sample, r.problem[i].splits, fdiv_magic(d[i].rows_per_sample)};
     }
     const int blocks = b.first[n];
-    if (ride) {
-        BlockTail t = {};
-        if (has_dgrad) {       // one more problem, in fields of its own: 64 x 64 tiles
-            t.dA = gA; t.dB = gB;
+    BlockTail t = {};
+    int rblocks = 0;
+    const auto fill_tail = [&] {
+        if (x.dy) {            // one more problem, in fields of its own: 64 x 64 tiles (r.dgrad is Kernel::tail)
+            t.dA = PlainSrc{x.dy, x.N, x.M, x.N, nullptr, 1, 0};
+            t.dB = PlainSrc{x.w, x.K, x.N, x.K, nullptr, 1, 0};      // S(i = n (reduction), j = k)
             t.de = plain_epilogue(x.dx, x.K);
-            t.de.vec_store = epilogue_vec_ok(t.de, x.K);
-            t.dM = x.M; t.dN = x.K; t.dR = x.N; t.drps = one_split(x.N);
+            t.de.vec_store = r.dgrad.store == 4;
+            t.dM = x.M; t.dN = x.K; t.dR = x.N; t.drps = r.dgrad.rows;
             t.dtm = cdiv(x.M, 64); t.dtn = cdiv(x.K, 64);
             t.nd = t.dtm * t.dtn;
         }
         t.w = b;
-        int rblocks = 0;
         if (x.njobs > 0) {
             rblocks = fill_reduce_table(x.jobs, x.njobs, t.r.j, t.r.first_block);
-            CSWIN_REQUIRE(rblocks >= 0, CSWIN_ERR_SHAPE, "linear_bwd_tail: bad pending reduction");
             t.r.njobs = x.njobs;
         }
-        static_assert(sizeof(BlockTail) <= 4096, "kernel argument block");
-        static_assert(sizeof(BlockTail) + sizeof(RowMap) <= 4096, "kernel argument block");
-        if (x.order) hipLaunchKernelGGL(gemm_block_tail_skip_kernel, dim3(blocks + t.nd + rblocks), dim3(512), 0, (hipStream_t)stream, t, dmap);
-        else if (any_mask) hipLaunchKernelGGL(gemm_block_tail_masked_kernel, dim3(blocks + t.nd + rblocks), dim3(512), 0, (hipStream_t)stream, t);
-        else hipLaunchKernelGGL(gemm_block_tail_kernel, dim3(blocks + t.nd + rblocks), dim3(512), 0, (hipStream_t)stream, t);
-    } else if (any_mask) {
-        hipLaunchKernelGGL(gemm_wgrad_batch_masked_kernel, dim3(blocks), dim3(512), 0, (hipStream_t)stream, b);
-    } else if (precision == 1) {
-        hipLaunchKernelGGL(gemm_wgrad_batch_kernel<1>, dim3(blocks), dim3(512), 0, (hipStream_t)stream, b);
-    } else {
-        hipLaunchKernelGGL(gemm_wgrad_batch_kernel<0>, dim3(blocks), dim3(512), 0, (hipStream_t)stream, b);
+    };
+    static_assert(sizeof(BlockTail) <= 4096, "kernel argument block");
+    static_assert(sizeof(BlockTail) + sizeof(RowMap) <= 4096, "kernel argument block");
+    switch (r.kernel) {
+        case gp::BatchKernel::tail_order:
+            fill_tail();
+            hipLaunchKernelGGL(gemm_block_tail_skip_kernel, dim3(blocks + t.nd + rblocks), dim3(512), 0, st, t, dmap);
+            break;
+        case gp::BatchKernel::tail_masked:
+            fill_tail();
+            hipLaunchKernelGGL(gemm_block_tail_masked_kernel, dim3(blocks + t.nd + rblocks), dim3(512), 0, st, t);
+            break;
+        case gp::BatchKernel::tail:
+            fill_tail();
+            hipLaunchKernelGGL(gemm_block_tail_kernel, dim3(blocks + t.nd + rblocks), dim3(512), 0, st, t);
+            break;
+        case gp::BatchKernel::masked:
+            hipLaunchKernelGGL(gemm_wgrad_batch_masked_kernel, dim3(blocks), dim3(512), 0, st, b);
+            break;
+        default:
+            if (precision == 1) hipLaunchKernelGGL(gemm_wgrad_batch_kernel<1>, dim3(blocks), dim3(512), 0, st, b);
+            else hipLaunchKernelGGL(gemm_wgrad_batch_kernel<0>, dim3(blocks), dim3(512), 0, st, b);
     }
     CSWIN_LAUNCH_CHECK();
+    return CSWIN_OK;
+}
+
+// One weight gradient without a concat input as plan (gp::linear_wgrad_plan) says: the tiled family, or the batch path as a batch of one
+int launch_wgrad_one(const gp::Plan& plan, const cswin_wgrad_desc& p, cswin_reduce_job* deferred, hipStream_t st) {
+    if (plan.kernel == gp::Kernel::tiled)
+        return wgrad_tiled(plan, p.dy, p.x, nullptr, 0, p.row_scale, p.rows_per_sample, p.dw, p.dbias, p.workspace, p.M, p.N, p.K, deferred,
+                           p.precision, st);
+    gp::BatchRoute one = {};
+    one.kernel = plan.kernel == gp::Kernel::wgrad16 ? gp::BatchKernel::wgrad16 : gp::BatchKernel::plain;
+    one.problem[0] = plan;
+    cswin_reduce_job job;
+    int rc = launch_wgrad_batch(one, &p, 1, &job, TailExtras{}, RowMap{}, p.precision, st);
+    if (rc) return rc;
+    reduce_now_or_defer(job, deferred, st);
+    CSWIN_LAUNCH_CHECK();
+    return CSWIN_OK;
+}
+
+// n (<= 4) weight gradients and what x adds to them, in three phases: check, plan (gp::batch_route), launch.  An error return means
+// that nothing was enqueued: the pending reductions of x "must not be run again" once a call has taken them, and a caller that
+// sees an error could not know whether it had.
+int wgrad_batch_impl(const cswin_wgrad_desc* d, int n, cswin_reduce_job* deferred, const TailExtras& x, void* stream) {
+    // ---- check: everything that can refuse
+    CSWIN_REQUIRE(x.njobs >= 0 && x.njobs <= CSWIN_TAIL_RIDER_JOBS && (x.njobs == 0 || x.jobs), CSWIN_ERR_SHAPE,
+                  "%s: 0..%d pending reductions", x.who, CSWIN_TAIL_RIDER_JOBS);
+    CSWIN_REQUIRE(d && deferred && n >= 1 && n <= WGRAD_BATCH, CSWIN_ERR_SHAPE, "linear_bwd_weight_batch: 1..%d problems and their deferred slots", WGRAD_BATCH);
+    const int precision = d[0].precision;
+    const bool has_dgrad = x.dy != nullptr;
+    gp::TailRequest tail = {};
+    tail.dgrad = has_dgrad;
+    tail.M = x.M; tail.N = x.N; tail.K = x.K;
+    tail.loads_aligned = aligned16(x.dy) && aligned16(x.w);
+    tail.dx_aligned = aligned16(x.dx);
+    tail.order = x.order != nullptr;
+    tail.njobs = x.njobs;
+    RowMap dmap = {};
+    if (x.order) {
+        CSWIN_REQUIRE(x.dy && x.order_samples >= 1 && x.M % x.order_samples == 0, CSWIN_ERR_SHAPE, "%s: nsamples * rows_per_sample != M", x.who);
+        int rc = row_map_checked(&dmap, x.who, x.order, x.order_samples, x.M / x.order_samples, x.M, precision, 0, false, false);
+        if (rc) return rc;
+        CSWIN_REQUIRE(x.N % 4 == 0 && x.K % 4 == 0 && tail.loads_aligned && tail.dx_aligned, CSWIN_ERR_ALIGN,
+                      "%s: a sample order needs N, K multiples of 4 and 16-B aligned operands", x.who);
+    }
+    CSWIN_CHECK_PRECISION(precision, "linear_bwd_weight_batch");
+    gp::WgradProblem problems[WGRAD_BATCH];
+    bool fast = true, any_mask = false;
+    for (int i = 0; i < n; ++i) {
+        CSWIN_REQUIRE(d[i].precision == precision, CSWIN_ERR_UNSUPPORTED, "linear_bwd_weight_batch: problems of one launch share one precision");
+        CSWIN_REQUIRE(d[i].io_bf16 == 0 || (precision == 1 && (d[i].io_bf16 & ~3) == 0), CSWIN_ERR_UNSUPPORTED, "linear_bwd_weight_batch: bf16 storage needs precision 1");
+        CSWIN_REQUIRE(d[i].dy && d[i].x && d[i].dw && d[i].M > 0 && d[i].N > 0 && d[i].K > 0, CSWIN_ERR_SHAPE, "linear_bwd_weight_batch: bad problem %d", i);
+        CSWIN_REQUIRE(!d[i].row_scale || d[i].rows_per_sample > 0, CSWIN_ERR_SHAPE, "linear_bwd_weight_batch: rows_per_sample must be > 0");
+        size_t need = gp::wgrad_workspace_bytes(cswin_tuning(), d[i].M, d[i].N, d[i].K);
+        CSWIN_REQUIRE(d[i].workspace && d[i].ws_bytes >= need, CSWIN_ERR_WORKSPACE, "linear_bwd_weight_batch: workspace %zu < %zu", d[i].ws_bytes, need);
+        const bool masked = x.skip && x.skip[i];
+        problems[i] = wgrad_problem(d[i], masked);
+        fast = fast && problems[i].aligned();
+        if (masked) {
+            any_mask = true;
+            char what[40];
+            snprintf(what, sizeof(what), "sample mask of problem %d", i);
+            int rc = samples_checked(x.who, what, x.nsamples ? x.skip[i] : nullptr, x.nsamples ? x.nsamples[i] : 0, d[i].rows_per_sample, d[i].M, 0,
+                                     precision);
+            if (rc) return rc;
+        }
+    }
+    CSWIN_REQUIRE(!any_mask || fast, CSWIN_ERR_ALIGN, "%s: a sample mask needs N, K multiples of 4 and 16-B aligned operands", x.who);
+    CSWIN_REQUIRE(reduce_jobs_ok(x.jobs, x.njobs), CSWIN_ERR_SHAPE, "%s: bad pending reduction", x.who);
+    for (int i = 0; i < n && !fast; ++i)      // separate launches take no bf16-stored problem
+        CSWIN_REQUIRE(d[i].io_bf16 == 0, CSWIN_ERR_ALIGN, "linear_bwd_weight_batch: bf16 storage needs N, K multiples of 4 and 16-B alignment");
+    // ---- plan (pure: what it gives is still only checked)
+    const gp::BatchRoute r = gp::batch_route(cswin_tuning(), problems, n, precision, tail);
+    for (int i = 0; i < n; ++i)
+        CSWIN_REQUIRE((size_t)r.problem[i].splits * gp::slab_stride(d[i].N, d[i].K) * sizeof(float) <= d[i].ws_bytes, CSWIN_ERR_WORKSPACE,
+                      "linear_bwd_weight_batch: %d slabs do not fit problem %d's workspace", r.problem[i].splits, i);
+    // ---- launch
+    hipStream_t st = (hipStream_t)stream;
+    if (r.dgrad_first) {      // the data gradient as a GEMM problem (as cswin_linear_bwd_data poses it): M x K outputs, reduction N in one split
+        const PlainSrc gA = {x.dy, x.N, x.M, x.N, nullptr, 1, 0}, gB = {x.w, x.K, x.N, x.K, nullptr, 1, 0};      // gB: S(i = n (reduction), j = k)
+        launch_gemm_vec<true, false, EPI_PLAIN, false>(r.dgrad, gA, gB, plain_epilogue(x.dx, x.K), x.M, x.K, x.N, precision, st, x.order ? &dmap : nullptr);
+        CSWIN_LAUNCH_CHECK();
+    }
+    if (r.jobs_first) {
+        launch_rows_sum(x.jobs, x.njobs, st);
+        CSWIN_LAUNCH_CHECK();
+    }
+    if (r.kernel != gp::BatchKernel::separate) return launch_wgrad_batch(r, d, n, deferred, x, dmap, precision, st);
+    for (int i = 0; i < n; ++i) {
+        int rc = launch_wgrad_one(r.problem[i], d[i], &deferred[i], st);
+        if (rc) return rc;
+    }
     return CSWIN_OK;
 }
 
@@ -1298,21 +1274,112 @@ int conv_wgrad_impl(const float* dy, const float* x, float* dw_perm, float* dbia
     CSWIN_REQUIRE(!torch_layout || Cin < 65536, CSWIN_ERR_UNSUPPORTED, "conv_tok_bwd_weight: torch_layout needs Cin < 65536");
     int OH = (H + 2 * pad - ks) / stride + 1, OW = (W + 2 * pad - ks) / stride + 1;
     int M = B * OH * OW, K = ks * ks * Cin;
-    size_t need = WgradSlabs::bytes(M, Cout, K);
+    size_t need = gp::wgrad_workspace_bytes(cswin_tuning(), M, Cout, K);
     CSWIN_REQUIRE(workspace && ws_bytes >= need, CSWIN_ERR_WORKSPACE, "conv_tok_bwd_weight: workspace %zu < %zu", ws_bytes, need);
     hipStream_t st = (hipStream_t)stream;
-    int splits, rps;
-    choose_split(M, Cout, K, &splits, &rps);
+    const gp::Split s = gp::choose_split(cswin_tuning(), M, Cout, K);
     const WgradSlabs slabs(workspace, Cout, K);
+    const Epilogue e = slabs.epilogue(dbias != nullptr);
+    const gp::Plan plan = gp::tiled_plan(cswin_tuning(), Cout, K, M, s.splits, s.rows, true, precision, true, epilogue_vec_ok(e, K));
     PlainSrc A = {dy, Cout, M, Cout, nullptr, 1};
     ConvMagics mg;
     with_fast_div(conv_magics(&mg, M, OH * OW, OW, K, Cin, ks, 0, 0), [&](auto fast) {
         ConvSrcT<decltype(fast)::value> Bm = {x, B, H, W, Cin, OH, OW, ks, stride, pad, M, K, mg};   // S(i = pixel m (reduction), j = (tap, ci))
-        launch_gemm<false, false, 4, EPI_PLAIN, false>(A, Bm, slabs.epilogue(dbias != nullptr), Cout, K, M, splits, rps, precision, st);
+        launch_gemm<false, false, 4, EPI_PLAIN, false>(plan, A, Bm, e, Cout, K, M, precision, st);
     });
     CSWIN_LAUNCH_CHECK();
-    reduce_now_or_defer(slabs.job(dw_perm, dbias, splits, torch_layout ? ks * ks : 0,
+    reduce_now_or_defer(slabs.job(dw_perm, dbias, s.splits, torch_layout ? ks * ks : 0,
                                   torch_layout ? (Cin | (Cin_param != Cin ? Cin_param << 16 : 0)) : 0), deferred, st);
+    CSWIN_LAUNCH_CHECK();
+    return CSWIN_OK;
+}
+
+// y[M,N] = [x | x2][M,K] @ w[N,K]^T + bias (optionally GELU to y_act, or + row_scale . residual): cswin_linear_fwd, and with
+// mapped its twin with a SAMPLE ORDER (row map, see RowMap) -- plain fp32 matrices with 16-B accesses only, everything else is refused
+int linear_fwd_impl(const char* who, const float* x, const float* x2, int k_split, const float* w, const float* bias, float* y, float* y_act,
+                    const float* residual, const float* row_scale, int rows_per_sample, int M, int N, int K, int precision, int io_bf16,
+                    bool mapped, const int* order, int nsamples, void* stream) {
+    RowMap rm = {};
+    if (mapped) {
+        int rc = row_map_checked(&rm, who, order, nsamples, rows_per_sample, M, precision, io_bf16, x2 != nullptr, false);
+        if (rc) return rc;
+    }
+    CSWIN_CHECK_PRECISION(precision, who);
+    CSWIN_REQUIRE(io_bf16 == 0 || (precision == 1 && (!x2 || !(io_bf16 & 1)) && (io_bf16 & ~7) == 0 && K % 4 == 0 && N % 4 == 0 && !((io_bf16 & 2) && residual)), CSWIN_ERR_UNSUPPORTED,
+                  "%s: bf16 storage (io_bf16 = %d: 1 = x, 2 = y / y_act, 4 = w) needs precision 1, a plain input for bit 1, K and N multiples of 4; a residual output stays fp32", who, io_bf16);
+    CSWIN_REQUIRE(x && w && y && M > 0 && N > 0 && K > 0, CSWIN_ERR_SHAPE, "%s: bad arguments M=%d N=%d K=%d", who, M, N, K);
+    CSWIN_REQUIRE(!x2 || (k_split > 0 && k_split < K), CSWIN_ERR_SHAPE, "%s: bad concat split %d of K=%d", who, k_split, K);
+    CSWIN_REQUIRE(!row_scale || rows_per_sample > 0, CSWIN_ERR_SHAPE, "%s: rows_per_sample must be > 0", who);
+    CSWIN_REQUIRE(!(y_act && residual), CSWIN_ERR_UNSUPPORTED, "%s: activation and residual epilogues are exclusive", who);
+    CSWIN_REQUIRE(!(x2 && y_act), CSWIN_ERR_UNSUPPORTED, "%s: concat input does not support the activation epilogue", who);
+    Epilogue e = plain_epilogue(y, N);
+    e.bias = bias;
+    e.Cact = y_act; e.ldact = N;
+    e.residual = residual; e.ldres = N;
+    e.row_scale = row_scale; e.rows_per_sample = rows_per_sample;
+    e.c_bf16 = (io_bf16 & 2) != 0;
+    const gp::Plan plan = gp::linear_fwd_plan(cswin_tuning(), M, N, K, x2 ? k_split : 0, precision, io_bf16,
+                                              aligned16(x) && aligned16(w) && aligned16(x2), epilogue_ptrs_aligned(e));
+    const bool vec_all = plan.vec == 4 && plan.store == 4;
+    CSWIN_REQUIRE(!mapped || vec_all, CSWIN_ERR_ALIGN, "%s: a sample order needs N, K multiples of 4 and 16-B aligned operands", who);
+    if (x2) CSWIN_REQUIRE(io_bf16 == 0 || (io_bf16 == 4 && plan.vec == 4), CSWIN_ERR_UNSUPPORTED, "%s: a concat input takes only the bf16 weight flag (4), with 16-B aligned operands", who);
+    else CSWIN_REQUIRE(io_bf16 == 0 || (plan.vec == 4 && aligned16(y) && aligned16(y_act) && aligned16(bias)), CSWIN_ERR_ALIGN, "%s: bf16 storage needs 16-B aligned operands", who);
+    hipStream_t st = (hipStream_t)stream;
+    const int epi_mode = y_act ? EPI_ACT : (residual ? EPI_RES : EPI_PLAIN);
+    const PlainSrc B = {w, K, N, K, nullptr, 1, (io_bf16 >> 2) & 1};
+    if (plan.kernel == gp::Kernel::gemm16) {
+        CSWIN_REQUIRE(cswin_gemm16(plan, 0, epi_mode, x, w, &e, M, N, K, stream) == 0, CSWIN_ERR_HIP, "%s: the LDS-DMA kernel could not be set up", who);
+    } else if (x2) {
+        const ConcatSrc A = {x, x2, k_split, K - k_split, M, K, k_split};
+        launch_gemm_epi<true, true, EPI_RES, EPI_PLAIN>(epi_mode, plan, A, B, e, M, N, K, precision, st);
+    } else {
+        const PlainSrc A = {x, K, M, K, nullptr, 1, io_bf16 & 1};
+        launch_gemm_epi<true, true, EPI_ACT, EPI_RES, EPI_PLAIN>(epi_mode, plan, A, B, e, M, N, K, precision, st, mapped ? &rm : nullptr);
+    }
+    CSWIN_LAUNCH_CHECK();
+    return CSWIN_OK;
+}
+
+// dx[M,K] = (row_scale . dy)[M,N] @ w[N,K]   (optionally * gelu'(gelu_pre), + add; optionally split into dx | dx2): cswin_linear_bwd_data,
+// and with mapped its twin with a sample order
+int linear_dgrad_impl(const char* who, const float* dy, const float* w, float* dx, float* dx2, int k_split, const float* gelu_pre,
+                      const float* row_scale, int rows_per_sample, const float* add, int M, int N, int K, int precision, int io_bf16,
+                      bool mapped, const int* order, int nsamples, void* stream) {
+    RowMap rm = {};
+    if (mapped) {
+        int rc = row_map_checked(&rm, who, order, nsamples, rows_per_sample, M, precision, io_bf16, dx2 != nullptr, add != nullptr);
+        if (rc) return rc;
+    }
+    CSWIN_CHECK_PRECISION(precision, who);
+    CSWIN_REQUIRE(io_bf16 == 0 || (precision == 1 && ((!dx2 && !add) || (io_bf16 & ~4) == 0) && (io_bf16 & ~15) == 0 && K % 4 == 0 && N % 4 == 0), CSWIN_ERR_UNSUPPORTED,
+                  "%s: bf16 storage (io_bf16 = %d: 1 = dy, 2 = dx, 4 = w, 8 = gelu_pre) needs precision 1, K and N multiples of 4; split / add outputs take only the weight flag", who, io_bf16);
+    CSWIN_REQUIRE(dy && w && dx && M > 0 && N > 0 && K > 0, CSWIN_ERR_SHAPE, "%s: bad arguments", who);
+    CSWIN_REQUIRE(!dx2 || (k_split > 0 && k_split < K), CSWIN_ERR_SHAPE, "%s: bad concat split", who);
+    CSWIN_REQUIRE(!row_scale || rows_per_sample > 0, CSWIN_ERR_SHAPE, "%s: rows_per_sample must be > 0", who);
+    Epilogue e = plain_epilogue(dx, dx2 ? k_split : K);
+    e.C2 = dx2; e.ldc2 = K - k_split; e.col_split = dx2 ? k_split : 0;
+    e.gelu_pre = gelu_pre; e.ldpre = K;
+    e.row_scale = row_scale; e.rows_per_sample = rows_per_sample;
+    e.residual = add; e.ldres = K;
+    e.c_bf16 = (io_bf16 & 2) != 0;
+    e.pre_bf16 = (io_bf16 & 8) != 0;
+    CSWIN_REQUIRE(io_bf16 == 0 || (aligned16(dy) && aligned16(w) && aligned16(dx) && aligned16(gelu_pre)), CSWIN_ERR_ALIGN,
+                  "%s: bf16 storage needs 16-B aligned operands", who);
+    const int modes = (dx2 != nullptr) + (gelu_pre != nullptr) + (add != nullptr);
+    CSWIN_REQUIRE(modes <= 1, CSWIN_ERR_UNSUPPORTED, "%s: dx2 / gelu_pre / add are mutually exclusive", who);
+    const gp::Plan plan = gp::linear_dgrad_plan(cswin_tuning(), M, N, K, dx2 ? k_split : 0, add != nullptr, precision, io_bf16,
+                                                aligned16(dy) && aligned16(w), epilogue_ptrs_aligned(e));
+    CSWIN_REQUIRE(!mapped || (plan.vec == 4 && plan.store == 4), CSWIN_ERR_ALIGN,
+                  "%s: a sample order needs N, K multiples of 4 and 16-B aligned operands", who);
+    hipStream_t st = (hipStream_t)stream;
+    const int epi_mode = dx2 ? EPI_SPLIT2 : (gelu_pre ? EPI_GELUBWD : (add ? EPI_RES : EPI_PLAIN));
+    if (plan.kernel == gp::Kernel::gemm16) {
+        CSWIN_REQUIRE(cswin_gemm16(plan, 1, epi_mode, dy, w, &e, M, K, N, stream) == 0, CSWIN_ERR_HIP, "%s: the LDS-DMA kernel could not be set up", who);
+    } else {
+        const PlainSrc A = {dy, N, M, N, nullptr, 1, io_bf16 & 1};
+        const PlainSrc B = {w, K, N, K, nullptr, 1, (io_bf16 >> 2) & 1};     // S(i = n (reduction), j = k): row-contiguous image
+        launch_gemm_epi<true, false, EPI_SPLIT2, EPI_GELUBWD, EPI_RES, EPI_PLAIN>(epi_mode, plan, A, B, e, M, K, N, precision, st, mapped ? &rm : nullptr);
+    }
     CSWIN_LAUNCH_CHECK();
     return CSWIN_OK;
 }
@@ -1329,146 +1396,33 @@ extern "C" {
 // at start / end (7 unused)
 void cswin_debug_set_stamps(void* p) { g_stamps = (long long*)p; }
 
-// the unmasked batch entry points are the masked ones without masks (defined below, beside them)
-int cswin_linear_bwd_weight_batch_masked(const cswin_wgrad_desc* d, int n, cswin_reduce_job* deferred, const cswin_reduce_job* pending,
-                                         int npending, const float* const* skip, const int* nsamples, void* stream);
-int cswin_linear_bwd_tail_masked(const float* dy, const float* w, float* dx, int M, int N, int K, const cswin_wgrad_desc* d, int n,
-                                 cswin_reduce_job* deferred, const cswin_reduce_job* pending, int npending, const float* const* skip,
-                                 const int* nsamples, void* stream);
-
-int cswin_linear_bwd_tail_skip(const float* dy, const float* w, float* dx, int M, int N, int K, const cswin_wgrad_desc* d, int n,
-                               cswin_reduce_job* deferred, const cswin_reduce_job* pending, int npending, const float* const* skip,
-                               const int* nsamples, const int* order, int order_samples, void* stream);
-
 int cswin_linear_fwd(const float* x, const float* x2, int k_split, const float* w, const float* bias, float* y,
                      float* y_act, const float* residual, const float* row_scale, int rows_per_sample, int M, int N,
                      int K, int precision, int io_bf16, void* stream) {
-    CSWIN_CHECK_PRECISION(precision, "linear_fwd");
-    CSWIN_REQUIRE(io_bf16 == 0 || (precision == 1 && (!x2 || !(io_bf16 & 1)) && (io_bf16 & ~7) == 0 && K % 4 == 0 && N % 4 == 0 && !((io_bf16 & 2) && residual)), CSWIN_ERR_UNSUPPORTED,
-                  "linear_fwd: bf16 storage (io_bf16 = %d: 1 = x, 2 = y / y_act, 4 = w) needs precision 1, a plain input for bit 1, K and N multiples of 4; a residual output stays fp32", io_bf16);
-    CSWIN_REQUIRE(x && w && y && M > 0 && N > 0 && K > 0, CSWIN_ERR_SHAPE, "linear_fwd: bad arguments M=%d N=%d K=%d", M, N, K);
-    CSWIN_REQUIRE(!x2 || (k_split > 0 && k_split < K), CSWIN_ERR_SHAPE, "linear_fwd: bad concat split %d of K=%d", k_split, K);
-    CSWIN_REQUIRE(!row_scale || rows_per_sample > 0, CSWIN_ERR_SHAPE, "linear_fwd: rows_per_sample must be > 0");
-    hipStream_t st = (hipStream_t)stream;
-    Epilogue e = plain_epilogue(y, N);
-    e.bias = bias;
-    e.Cact = y_act; e.ldact = N;
-    e.residual = residual; e.ldres = N;
-    e.row_scale = row_scale; e.rows_per_sample = rows_per_sample;
-    e.c_bf16 = (io_bf16 & 2) != 0;
-    PlainSrc B = {w, K, N, K, nullptr, 1, (io_bf16 >> 2) & 1};
-    CSWIN_REQUIRE(!(y_act && residual), CSWIN_ERR_UNSUPPORTED, "linear_fwd: activation and residual epilogues are exclusive");
-    const int rk = one_split(K);
-    if (x2) {
-        CSWIN_REQUIRE(!y_act, CSWIN_ERR_UNSUPPORTED, "linear_fwd: concat input does not support the activation epilogue");
-        ConcatSrc A = {x, x2, k_split, K - k_split, M, K, k_split};
-        bool vec = (k_split % 4 == 0) && (K % 4 == 0) && aligned16(x) && aligned16(x2) && aligned16(w);
-        CSWIN_REQUIRE(io_bf16 == 0 || (io_bf16 == 4 && vec), CSWIN_ERR_UNSUPPORTED, "linear_fwd: a concat input takes only the bf16 weight flag (4), with 16-B aligned operands");
-        if (residual) launch_gemm_vec<true, true, EPI_RES, false>(vec, A, B, e, M, N, K, 1, rk, precision, st);
-        else launch_gemm_vec<true, true, EPI_PLAIN, false>(vec, A, B, e, M, N, K, 1, rk, precision, st);
-    } else {
-        if (precision == 1 && (io_bf16 & 5) == 5) {             // both operands stored as bf16: LDS-DMA kernel (gemm16.hip)
-            if (cswin_gemm16(0, y_act ? EPI_ACT : (residual ? EPI_RES : EPI_PLAIN), x, w, &e, M, N, K, stream) == 0) {
-                CSWIN_LAUNCH_CHECK();
-                return CSWIN_OK;
-            }
-        }
-        PlainSrc A = {x, K, M, K, nullptr, 1, io_bf16 & 1};
-        bool vec = (K % 4 == 0) && aligned16(x) && aligned16(w);
-        CSWIN_REQUIRE(io_bf16 == 0 || (vec && aligned16(y) && (!y_act || aligned16(y_act)) && (!bias || aligned16(bias))), CSWIN_ERR_ALIGN,
-                      "linear_fwd: bf16 storage needs 16-B aligned operands");
-        if (y_act) launch_gemm_vec<true, true, EPI_ACT, false>(vec, A, B, e, M, N, K, 1, rk, precision, st);
-        else if (residual) launch_gemm_vec<true, true, EPI_RES, false>(vec, A, B, e, M, N, K, 1, rk, precision, st);
-        else launch_gemm_vec<true, true, EPI_PLAIN, false>(vec, A, B, e, M, N, K, 1, rk, precision, st);
-    }
-    CSWIN_LAUNCH_CHECK();
-    return CSWIN_OK;
+    return linear_fwd_impl("linear_fwd", x, x2, k_split, w, bias, y, y_act, residual, row_scale, rows_per_sample, M, N, K, precision, io_bf16,
+                           false, nullptr, 0, stream);
 }
 
-// dx[M,K] = (row_scale . dy)[M,N] @ w[N,K]   (optionally * gelu'(gelu_pre), + add; optionally split into dx | dx2)
 int cswin_linear_bwd_data(const float* dy, const float* w, float* dx, float* dx2, int k_split, const float* gelu_pre,
                           const float* row_scale, int rows_per_sample, const float* add, int M, int N, int K,
                           int precision, int io_bf16, void* stream) {
-    CSWIN_CHECK_PRECISION(precision, "linear_bwd_data");
-    CSWIN_REQUIRE(io_bf16 == 0 || (precision == 1 && ((!dx2 && !add) || (io_bf16 & ~4) == 0) && (io_bf16 & ~15) == 0 && K % 4 == 0 && N % 4 == 0), CSWIN_ERR_UNSUPPORTED,
-                  "linear_bwd_data: bf16 storage (io_bf16 = %d: 1 = dy, 2 = dx, 4 = w, 8 = gelu_pre) needs precision 1, K and N multiples of 4; split / add outputs take only the weight flag", io_bf16);
-    CSWIN_REQUIRE(dy && w && dx && M > 0 && N > 0 && K > 0, CSWIN_ERR_SHAPE, "linear_bwd_data: bad arguments");
-    CSWIN_REQUIRE(!dx2 || (k_split > 0 && k_split < K), CSWIN_ERR_SHAPE, "linear_bwd_data: bad concat split");
-    CSWIN_REQUIRE(!row_scale || rows_per_sample > 0, CSWIN_ERR_SHAPE, "linear_bwd_data: rows_per_sample must be > 0");
-    hipStream_t st = (hipStream_t)stream;
-    Epilogue e = plain_epilogue(dx, dx2 ? k_split : K);
-    e.C2 = dx2; e.ldc2 = K - k_split; e.col_split = dx2 ? k_split : 0;
-    e.gelu_pre = gelu_pre; e.ldpre = K;
-    e.row_scale = row_scale; e.rows_per_sample = rows_per_sample;
-    e.residual = add; e.ldres = K;
-    e.c_bf16 = (io_bf16 & 2) != 0;
-    e.pre_bf16 = (io_bf16 & 8) != 0;
-    CSWIN_REQUIRE(io_bf16 == 0 || (aligned16(dy) && aligned16(w) && aligned16(dx) && (!gelu_pre || aligned16(gelu_pre))), CSWIN_ERR_ALIGN,
-                  "linear_bwd_data: bf16 storage needs 16-B aligned operands");
-    PlainSrc A = {dy, N, M, N, nullptr, 1, io_bf16 & 1};
-    PlainSrc B = {w, K, N, K, nullptr, 1, (io_bf16 >> 2) & 1};     // S(i = n (reduction), j = k): row-contiguous image
-    bool vec = (N % 4 == 0) && (K % 4 == 0) && aligned16(dy) && aligned16(w);
-    // output rows = M, output cols = K, reduction = N
-    const int rn = one_split(N);
-    const int modes = (dx2 != nullptr) + (gelu_pre != nullptr) + (add != nullptr);
-    CSWIN_REQUIRE(modes <= 1, CSWIN_ERR_UNSUPPORTED, "linear_bwd_data: dx2 / gelu_pre / add are mutually exclusive");
-    if (precision == 1 && !dx2 && !add && (io_bf16 & 5) == 5) {  // both operands stored as bf16: LDS-DMA kernel (gemm16.hip)
-        if (cswin_gemm16(1, gelu_pre ? EPI_GELUBWD : EPI_PLAIN, dy, w, &e, M, K, N, stream) == 0) {
-            CSWIN_LAUNCH_CHECK();
-            return CSWIN_OK;
-        }
-    }
-    if (dx2) launch_gemm_vec<true, false, EPI_SPLIT2, false>(vec, A, B, e, M, K, N, 1, rn, precision, st);
-    else if (gelu_pre) launch_gemm_vec<true, false, EPI_GELUBWD, false>(vec, A, B, e, M, K, N, 1, rn, precision, st);
-    else if (add) launch_gemm_vec<true, false, EPI_RES, false>(vec, A, B, e, M, K, N, 1, rn, precision, st);
-    else launch_gemm_vec<true, false, EPI_PLAIN, false>(vec, A, B, e, M, K, N, 1, rn, precision, st);
-    CSWIN_LAUNCH_CHECK();
-    return CSWIN_OK;
+    return linear_dgrad_impl("linear_bwd_data", dy, w, dx, dx2, k_split, gelu_pre, row_scale, rows_per_sample, add, M, N, K, precision,
+                             io_bf16, false, nullptr, 0, stream);
 }
 
-// The two calls above with a SAMPLE ORDER (row map, see RowMap): plain fp32 matrices with 16-B accesses only, everything else is refused
+// The two calls above with a sample order: an order is refused where the launch cannot take it, never run unmapped
 int cswin_linear_fwd_skip(const float* x, const float* x2, int k_split, const float* w, const float* bias, float* y, float* y_act,
                           const float* residual, const float* row_scale, int rows_per_sample, int M, int N, int K, int precision,
                           int io_bf16, const int* order, int nsamples, void* stream) {
-    RowMap rm;
-    int rc = row_map_checked(&rm, "linear_fwd_skip", order, nsamples, rows_per_sample, M, precision, io_bf16, x2 != nullptr, false);
-    if (rc) return rc;
-    CSWIN_REQUIRE(x && w && y && N > 0 && K > 0, CSWIN_ERR_SHAPE, "linear_fwd_skip: bad arguments M=%d N=%d K=%d", M, N, K);
-    CSWIN_REQUIRE(!(y_act && residual), CSWIN_ERR_UNSUPPORTED, "linear_fwd_skip: activation and residual epilogues are exclusive");
-    Epilogue e = plain_epilogue(y, N);
-    e.bias = bias;
-    e.Cact = y_act; e.ldact = N;
-    e.residual = residual; e.ldres = N;
-    e.row_scale = row_scale; e.rows_per_sample = rows_per_sample;
-    CSWIN_REQUIRE(K % 4 == 0 && aligned16(x) && aligned16(w) && epilogue_vec_ok(e, N), CSWIN_ERR_ALIGN,
-                  "linear_fwd_skip: a sample order needs N, K multiples of 4 and 16-B aligned operands");
-    const PlainSrc A = {x, K, M, K, nullptr, 1, 0}, B = {w, K, N, K, nullptr, 1, 0};
-    hipStream_t st = (hipStream_t)stream;
-    if (y_act) launch_gemm<true, true, 4, EPI_ACT, false>(A, B, e, M, N, K, 1, one_split(K), 0, st, &rm);
-    else if (residual) launch_gemm<true, true, 4, EPI_RES, false>(A, B, e, M, N, K, 1, one_split(K), 0, st, &rm);
-    else launch_gemm<true, true, 4, EPI_PLAIN, false>(A, B, e, M, N, K, 1, one_split(K), 0, st, &rm);
-    CSWIN_LAUNCH_CHECK();
-    return CSWIN_OK;
+    return linear_fwd_impl("linear_fwd_skip", x, x2, k_split, w, bias, y, y_act, residual, row_scale, rows_per_sample, M, N, K, precision,
+                           io_bf16, true, order, nsamples, stream);
 }
 
 int cswin_linear_bwd_data_skip(const float* dy, const float* w, float* dx, float* dx2, int k_split, const float* gelu_pre,
                                const float* row_scale, int rows_per_sample, const float* add, int M, int N, int K, int precision,
                                int io_bf16, const int* order, int nsamples, void* stream) {
-    RowMap rm;
-    int rc = row_map_checked(&rm, "linear_bwd_data_skip", order, nsamples, rows_per_sample, M, precision, io_bf16, dx2 != nullptr, add != nullptr);
-    if (rc) return rc;
-    CSWIN_REQUIRE(dy && w && dx && N > 0 && K > 0, CSWIN_ERR_SHAPE, "linear_bwd_data_skip: bad arguments");
-    Epilogue e = plain_epilogue(dx, K);
-    e.gelu_pre = gelu_pre; e.ldpre = K;
-    e.row_scale = row_scale; e.rows_per_sample = rows_per_sample;
-    CSWIN_REQUIRE(N % 4 == 0 && aligned16(dy) && aligned16(w) && epilogue_vec_ok(e, K), CSWIN_ERR_ALIGN,
-                  "linear_bwd_data_skip: a sample order needs N, K multiples of 4 and 16-B aligned operands");
-    const PlainSrc A = {dy, N, M, N, nullptr, 1, 0}, B = {w, K, N, K, nullptr, 1, 0};
-    hipStream_t st = (hipStream_t)stream;
-    if (gelu_pre) launch_gemm<true, false, 4, EPI_GELUBWD, false>(A, B, e, M, K, N, 1, one_split(N), 0, st, &rm);
-    else launch_gemm<true, false, 4, EPI_PLAIN, false>(A, B, e, M, K, N, 1, one_split(N), 0, st, &rm);
-    CSWIN_LAUNCH_CHECK();
-    return CSWIN_OK;
+    return linear_dgrad_impl("linear_bwd_data_skip", dy, w, dx, dx2, k_split, gelu_pre, row_scale, rows_per_sample, add, M, N, K, precision,
+                             io_bf16, true, order, nsamples, stream);
 }
 
 // scales (rows, B) = (u < keep[row]) / keep[row] and order (rows, 1 + B) from one step's DropPath draws u (rows, B): see drop_path_order_kernel
@@ -1480,7 +1434,7 @@ int cswin_drop_path_order(const float* u, const float* keep, float* scales, int*
     return CSWIN_OK;
 }
 
-size_t cswin_linear_bwd_weight_workspace(int M, int N, int K) { return WgradSlabs::bytes(M, N, K); }
+size_t cswin_linear_bwd_weight_workspace(int M, int N, int K) { return gp::wgrad_workspace_bytes(cswin_tuning(), M, N, K); }
 
 // dw[N,K] = (row_scale . dy)^T @ [x | x2];  dbias[N] = colsum(row_scale . dy)
 int cswin_linear_bwd_weight(const float* dy, const float* x, const float* x2, int k_split, const float* row_scale,
@@ -1490,64 +1444,70 @@ int cswin_linear_bwd_weight(const float* dy, const float* x, const float* x2, in
     CSWIN_REQUIRE(dy && x && dw && M > 0 && N > 0 && K > 0, CSWIN_ERR_SHAPE, "linear_bwd_weight: bad arguments");
     CSWIN_REQUIRE(!x2 || (k_split > 0 && k_split < K), CSWIN_ERR_SHAPE, "linear_bwd_weight: bad concat split");
     CSWIN_REQUIRE(!row_scale || rows_per_sample > 0, CSWIN_ERR_SHAPE, "linear_bwd_weight: rows_per_sample must be > 0");
-    size_t need = WgradSlabs::bytes(M, N, K);
+    size_t need = gp::wgrad_workspace_bytes(cswin_tuning(), M, N, K);
     CSWIN_REQUIRE(workspace && ws_bytes >= need, CSWIN_ERR_WORKSPACE, "linear_bwd_weight: workspace %zu < %zu", ws_bytes, need);
     hipStream_t st = (hipStream_t)stream;
     const cswin_wgrad_desc d1 = {dy, x, row_scale, dw, dbias, workspace, ws_bytes, rows_per_sample, M, N, K, precision, 0};
-    if (precision == 1 && !x2 && wgrad_aligned(d1)) {
-        // bf16 mode: the transposing-read kernel (wgrad16.hip) through the batch path, as a batch of one
-        cswin_reduce_job job;
-        int rc = wgrad_batch_impl(&d1, 1, &job, TailExtras{"linear_bwd_weight_batch"}, stream);
-        if (rc) return rc;
-        reduce_now_or_defer(job, deferred, st);
-        CSWIN_LAUNCH_CHECK();
-        return CSWIN_OK;
-    }
-    return wgrad_tiled(dy, x, x2, k_split, row_scale, rows_per_sample, dw, dbias, workspace, M, N, K, deferred, precision, st);
+    const gp::Plan plan = gp::linear_wgrad_plan(cswin_tuning(), wgrad_problem(d1, false), x2 ? k_split : 0, precision, aligned16(x2));
+    if (x2) return wgrad_tiled(plan, dy, x, x2, k_split, row_scale, rows_per_sample, dw, dbias, workspace, M, N, K, deferred, precision, st);
+    return launch_wgrad_one(plan, d1, deferred, st);
 }
 
 // n (<= 4) weight gradients without concat sources in one launch (see gemm_wgrad_batch_kernel); deferred[i] receives problem
 // i's slab reduction (run them with cswin_rows_sum_multi).  Falls back to separate launches when a problem is not 16-B
 // aligned / a multiple of 4 in N and K.
+// With sample masks: skip[i] (or NULL) = nsamples[i] per-sample floats of problem i, M = nsamples[i] * rows_per_sample; a
+// sample whose float is 0 adds nothing to dw / dbias and its rows of dy and x are not read (fp32, aligned problems only)
+int cswin_linear_bwd_weight_batch_masked(const cswin_wgrad_desc* d, int n, cswin_reduce_job* deferred, const cswin_reduce_job* pending,
+                                         int npending, const float* const* skip, const int* nsamples, void* stream) {
+    TailExtras x = {};
+    x.who = "linear_bwd_weight_batch";
+    x.jobs = pending; x.njobs = npending;
+    x.skip = skip; x.nsamples = nsamples;
+    return wgrad_batch_impl(d, n, deferred, x, stream);
+}
+
 int cswin_linear_bwd_weight_batch(const cswin_wgrad_desc* d, int n, cswin_reduce_job* deferred, const cswin_reduce_job* pending, int npending,
                                   void* stream) {
     return cswin_linear_bwd_weight_batch_masked(d, n, deferred, pending, npending, nullptr, nullptr, stream);
 }
 
-// The same with sample masks: skip[i] (or NULL) = nsamples[i] per-sample floats of problem i, M = nsamples[i] * rows_per_sample; a
-// sample whose float is 0 adds nothing to dw / dbias and its rows of dy and x are not read (fp32, aligned problems only)
-int cswin_linear_bwd_weight_batch_masked(const cswin_wgrad_desc* d, int n, cswin_reduce_job* deferred, const cswin_reduce_job* pending,
-                                         int npending, const float* const* skip, const int* nsamples, void* stream) {
-    return wgrad_batch_impl(d, n, deferred,
-                            TailExtras{"linear_bwd_weight_batch", nullptr, nullptr, nullptr, 0, 0, 0, pending, npending, skip, nsamples}, stream);
-}
-
 // The tail of a CSWinBlock's backward: dx[M,K] = dy[M,N] @ w[N,K] (the qkv Linear's data gradient, plain fp32, no epilogue extras)
 // and the block's weight gradients as cswin_linear_bwd_weight_batch takes them.  In fp32 with aligned operands both run in ONE
 // launch (gemm_block_tail_kernel); otherwise the data gradient is launched first and the batch follows -- same results either way.
-int cswin_linear_bwd_tail(const float* dy, const float* w, float* dx, int M, int N, int K, const cswin_wgrad_desc* d, int n,
-                          cswin_reduce_job* deferred, const cswin_reduce_job* pending, int npending, void* stream) {
-    return cswin_linear_bwd_tail_masked(dy, w, dx, M, N, K, d, n, deferred, pending, npending, nullptr, nullptr, stream);
-}
-
-// skip / nsamples: masks of the weight gradients as for cswin_linear_bwd_weight_batch_masked; the data gradient has none
-int cswin_linear_bwd_tail_masked(const float* dy, const float* w, float* dx, int M, int N, int K, const cswin_wgrad_desc* d, int n,
-                                 cswin_reduce_job* deferred, const cswin_reduce_job* pending, int npending, const float* const* skip,
-                                 const int* nsamples, void* stream) {
-    CSWIN_REQUIRE(dy && w && dx && M > 0 && N > 0 && K > 0, CSWIN_ERR_SHAPE, "linear_bwd_tail: bad data-gradient arguments");
-    return wgrad_batch_impl(d, n, deferred, TailExtras{"linear_bwd_tail", dy, w, dx, M, N, K, pending, npending, skip, nsamples}, stream);
-}
-
-// order: the data gradient's sample order over order_samples samples of M / order_samples rows (see RowMap); the weight gradients
-// keep their masks.  What the order cannot serve (precision 1, unaligned operands) is refused.
+// skip / nsamples: masks of the weight gradients as for cswin_linear_bwd_weight_batch_masked; the data gradient has none.
+// order: the data gradient's sample order over order_samples samples of M / order_samples rows (see RowMap); what the order cannot
+// serve (precision 1, unaligned operands) is refused.
 int cswin_linear_bwd_tail_skip(const float* dy, const float* w, float* dx, int M, int N, int K, const cswin_wgrad_desc* d, int n,
                                cswin_reduce_job* deferred, const cswin_reduce_job* pending, int npending, const float* const* skip,
                                const int* nsamples, const int* order, int order_samples, void* stream) {
     CSWIN_REQUIRE(dy && w && dx && M > 0 && N > 0 && K > 0, CSWIN_ERR_SHAPE, "linear_bwd_tail_skip: bad data-gradient arguments");
     CSWIN_REQUIRE(order, CSWIN_ERR_SHAPE, "linear_bwd_tail_skip: the order must list 1..%d samples", MASK_MAX_SAMPLES);
     CSWIN_REQUIRE(d && n >= 1 && n <= WGRAD_BATCH, CSWIN_ERR_SHAPE, "linear_bwd_tail_skip: 1..%d weight-gradient problems", WGRAD_BATCH);
-    return wgrad_batch_impl(d, n, deferred, TailExtras{"linear_bwd_tail_skip", dy, w, dx, M, N, K, pending, npending, skip, nsamples, order, order_samples},
-                            stream);
+    TailExtras x = {};
+    x.who = "linear_bwd_tail_skip";
+    x.dy = dy; x.w = w; x.dx = dx; x.M = M; x.N = N; x.K = K;
+    x.jobs = pending; x.njobs = npending;
+    x.skip = skip; x.nsamples = nsamples;
+    x.order = order; x.order_samples = order_samples;
+    return wgrad_batch_impl(d, n, deferred, x, stream);
+}
+
+int cswin_linear_bwd_tail_masked(const float* dy, const float* w, float* dx, int M, int N, int K, const cswin_wgrad_desc* d, int n,
+                                 cswin_reduce_job* deferred, const cswin_reduce_job* pending, int npending, const float* const* skip,
+                                 const int* nsamples, void* stream) {
+    CSWIN_REQUIRE(dy && w && dx && M > 0 && N > 0 && K > 0, CSWIN_ERR_SHAPE, "linear_bwd_tail: bad data-gradient arguments");
+    TailExtras x = {};
+    x.who = "linear_bwd_tail";
+    x.dy = dy; x.w = w; x.dx = dx; x.M = M; x.N = N; x.K = K;
+    x.jobs = pending; x.njobs = npending;
+    x.skip = skip; x.nsamples = nsamples;
+    return wgrad_batch_impl(d, n, deferred, x, stream);
+}
+
+int cswin_linear_bwd_tail(const float* dy, const float* w, float* dx, int M, int N, int K, const cswin_wgrad_desc* d, int n,
+                          cswin_reduce_job* deferred, const cswin_reduce_job* pending, int npending, void* stream) {
+    return cswin_linear_bwd_tail_masked(dy, w, dx, M, N, K, d, n, deferred, pending, npending, nullptr, nullptr, stream);
 }
 
 // -------- convolutions on the (B, H*W, C) token layout (NHWC), implicit GEMM -----------------------------------
@@ -1562,10 +1522,11 @@ int cswin_conv_tok_fwd(const float* x, const float* w_perm, const float* bias, f
     PlainSrc Bm = {w_perm, R, Cout, R, nullptr, 1};
     Epilogue e = plain_epilogue(y, Cout);
     e.bias = bias;
+    const gp::Plan plan = one_split_plan(e, M, Cout, R, precision);
     ConvMagics mg;
     with_fast_div(conv_magics(&mg, M, OH * OW, OW, R, Cin, ks, 0, 0), [&](auto fast) {
         ConvSrcT<decltype(fast)::value> A = {x, B, H, W, Cin, OH, OW, ks, stride, pad, M, R, mg};
-        launch_gemm<true, true, 4, EPI_PLAIN, false>(A, Bm, e, M, Cout, R, 1, one_split(R), precision, (hipStream_t)stream);
+        launch_gemm<true, true, 4, EPI_PLAIN, false>(plan, A, Bm, e, M, Cout, R, precision, (hipStream_t)stream);
     });
     CSWIN_LAUNCH_CHECK();
     return CSWIN_OK;
@@ -1611,13 +1572,13 @@ int cswin_conv_tok_bwd_data(const float* dy, const float* w_permT, float* dx, in
                     ConvMagics mg;
                     conv_magics(&mg, Mc, H2 * W2, W2, Rc, Cout, 1, 0, 0);
                     push(b, ConvTS2SrcT<FAST>{dy, B, H, W, Cout, OH, OW, py, px, H2, W2, kys, kxs, Mc, Rc, mg},
-                         TapRowsSrcT<FAST>{w_permT, Cout, Cin, taps, Rc, Cin, mg.c}, e, Mc, Cin, Rc, one_split(Rc), 1);
+                         TapRowsSrcT<FAST>{w_permT, Cout, Cin, taps, Rc, Cin, mg.c}, e, Mc, Cin, Rc, one_split(Rc), 1, epilogue_vec_ok(e, Cin));
                     rmax = Rc > rmax ? Rc : rmax;
                 }
             if (b.n > 0) {
                 const int blocks = b.first[b.n];
                 hipStream_t st = (hipStream_t)stream;
-                const int kw = k_groups(blocks, rmax);
+                const int kw = gp::s2_dgrad_kw(blocks, rmax, precision);
                 if (precision == 1) hipLaunchKernelGGL((gemm_conv_s2_dgrad_batch_kernel<2, 1, FAST>), dim3(blocks), dim3(512), 0, st, b);
                 else if (kw == 4) hipLaunchKernelGGL((gemm_conv_s2_dgrad_batch_kernel<4, 0, FAST>), dim3(blocks), dim3(1024), 0, st, b);
                 else if (kw == 2) hipLaunchKernelGGL((gemm_conv_s2_dgrad_batch_kernel<2, 0, FAST>), dim3(blocks), dim3(512), 0, st, b);
@@ -1630,10 +1591,11 @@ int cswin_conv_tok_bwd_data(const float* dy, const float* w_permT, float* dx, in
     int M = B * H * W, R = ks * ks * Cout;
     PlainSrc Bm = {w_permT, Cin, R, Cin, nullptr, 1};          // S(i = (tap, co), j = ci)
     Epilogue e = plain_epilogue(dx, Cin);
+    const gp::Plan plan = one_split_plan(e, M, Cin, R, precision);
     ConvMagics mg;
     with_fast_div(conv_magics(&mg, M, H * W, W, R, Cout, ks, (H > W ? H : W) + pad, stride), [&](auto fast) {
         ConvTSrcT<decltype(fast)::value> A = {dy, B, H, W, Cout, OH, OW, ks, stride, pad, M, R, mg};
-        launch_gemm<true, false, 4, EPI_PLAIN, false>(A, Bm, e, M, Cin, R, 1, one_split(R), precision, (hipStream_t)stream);
+        launch_gemm<true, false, 4, EPI_PLAIN, false>(plan, A, Bm, e, M, Cin, R, precision, (hipStream_t)stream);
     });
     CSWIN_LAUNCH_CHECK();
     return CSWIN_OK;
@@ -1641,7 +1603,7 @@ int cswin_conv_tok_bwd_data(const float* dy, const float* w_permT, float* dx, in
 
 size_t cswin_conv_tok_bwd_weight_workspace(int B, int H, int W, int Cin, int Cout, int ks, int stride, int pad) {
     int OH = (H + 2 * pad - ks) / stride + 1, OW = (W + 2 * pad - ks) / stride + 1;
-    return WgradSlabs::bytes(B * OH * OW, Cout, ks * ks * Cin);
+    return gp::wgrad_workspace_bytes(cswin_tuning(), B * OH * OW, Cout, ks * ks * Cin);
 }
 
 int cswin_conv_tok_bwd_weight(const float* dy, const float* x, float* dw_perm, float* dbias, void* workspace,

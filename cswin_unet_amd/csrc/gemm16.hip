@@ -24,6 +24,7 @@
 #include <type_traits>
 #include "common.h"
 #include "gemm_epilogue.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -32,7 +33,7 @@ typedef short g16_s16x4 __attribute__((ext_vector_type(4)));
 typedef short g16_s16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) g16_s16x4 g16_lds_s16x4;
 
-constexpr int G16_T = 64;                 // tile edge (rows, columns) and reduction step
+constexpr int G16_T = gp::G16_T;          // tile edge (rows, columns) and reduction step
 constexpr int G16_IMG = G16_T * 128;      // bytes of one operand image of one step
 constexpr int G16_STAGE = 2 * G16_IMG;
 
@@ -227,14 +228,9 @@ __global__ __launch_bounds__(MODE == 0 ? 256 : 512) void gemm16_kernel(G16Params
     if (stamps && tid == 0) { stamps[8L * bid + 3] = __builtin_amdgcn_s_memtime(); stamps[8L * bid + 6] = __builtin_amdgcn_s_memrealtime(); }
 }
 
+// the launch of plan (gp::gemm16_plan): its tile rows and stage count; 0, or 1 when the kernels' LDS opt-in failed
 template <int EPI, bool BT, bool PRE16>
-int g16_launch(const G16Params& p, hipStream_t st) {
-    const int nsteps = (p.R + G16_T - 1) / G16_T;
-    const int forced = cswin_tuning().gemm16_stages;                                                        // tuning aid: 2 .. 4
-    const int forced_tm = cswin_tuning().gemm16_tm;                                                         // tuning aid: 64 / 128
-    const bool tm128 = forced_tm == 128 || (forced_tm == 0 && p.nblk > 768);
-    int S = nsteps >= 3 ? 3 : 2;          // 48 KB: three workgroups per CU (measured against 2 and 4 stages: profiles/round2_notes.md)
-    if (forced >= 2 && forced <= 4) S = forced;
+int g16_launch(const gp::Plan& plan, const G16Params& p, hipStream_t st) {
     static_assert(2 * G16_STAGE >= 4 * EP_WAVE_FLOATS * (int)sizeof(float), "the smallest ring must hold the epilogue patches");
     // dynamic-LDS opt-in of the instantiations: once per process, thread-safe (a function attribute, not a stream operation)
     static std::once_flag once;
@@ -245,29 +241,27 @@ int g16_launch(const G16Params& p, hipStream_t st) {
         if (status == hipSuccess) status = hipFuncSetAttribute((const void*)gemm16_kernel<EPI, BT, 3, PRE16, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * (3 * G16_IMG));
     });
     if (status != hipSuccess) return 1;
-    if (tm128) {                           // 128 x 64 tiles: three slots of 24 KB, two workgroups per CU
+    if (plan.bm == 2 * G16_T) {            // 128 x 64 tiles: three slots of 24 KB, two workgroups per CU
         G16Params q = p;
         q.tiles_m = cdiv(p.M, 2 * G16_T);
         q.nblk = q.tiles_m * q.tiles_n;
         hipLaunchKernelGGL((gemm16_kernel<EPI, BT, 3, PRE16, 2>), dim3(q.nblk), dim3(512), 3 * (3 * G16_IMG), st, q);
         return 0;
     }
-    const size_t lds = (size_t)S * G16_STAGE;
-    if (S == 4) hipLaunchKernelGGL((gemm16_kernel<EPI, BT, 4, PRE16, 0>), dim3(p.nblk), dim3(256), lds, st, p);
-    else if (S == 3) hipLaunchKernelGGL((gemm16_kernel<EPI, BT, 3, PRE16, 0>), dim3(p.nblk), dim3(256), lds, st, p);
+    const size_t lds = (size_t)plan.stages * G16_STAGE;
+    if (plan.stages == 4) hipLaunchKernelGGL((gemm16_kernel<EPI, BT, 4, PRE16, 0>), dim3(p.nblk), dim3(256), lds, st, p);
+    else if (plan.stages == 3) hipLaunchKernelGGL((gemm16_kernel<EPI, BT, 3, PRE16, 0>), dim3(p.nblk), dim3(256), lds, st, p);
     else hipLaunchKernelGGL((gemm16_kernel<EPI, BT, 2, PRE16, 0>), dim3(p.nblk), dim3(256), lds, st, p);
     return 0;
 }
 
 }  // namespace
 
-// Internal entry used by gemm.hip's cswin_linear_fwd / cswin_linear_bwd_data (precision 1, io_bf16 bits 0 and 2 both set, plain
-// single-source forms).  mode 0: forward (A (M, R), B (NO, R));  mode 1: data gradient (A (M, R), B (R, NO)).
-// Returns 0 when launched, 1 when the shape is not covered (the caller falls back to the tiled family).
-int cswin_gemm16(int mode, int epi_mode, const void* A, const void* B, const void* epilogue, int M, int NO, int R, void* stream) {
-    const bool off = !cswin_tuning().gemm16_on;                                                             // tuning aid
-    if (off || (R % G16_T != 0 && R % G16_T != 32) || R < G16_T || NO % 8 != 0 || M < 1) return 1;    // reduction: n x 64 (+ 32)
-    if ((((uintptr_t)A) | ((uintptr_t)B)) & 15) return 1;
+// Internal entry used by gemm.hip's cswin_linear_fwd / cswin_linear_bwd_data where their plan is Kernel::gemm16 (precision 1,
+// io_bf16 bits 0 and 2 both set, a plain single-source form that gp::gemm16_accepts: a covered shape, aligned operands and the
+// 16-B epilogue, which is all this kernel's own epilogue implements).  mode 0: forward (A (M, R), B (NO, R));  mode 1: data
+// gradient (A (M, R), B (R, NO)).  Returns 0 when launched, 1 on a HIP error.
+int cswin_gemm16(const gp::Plan& plan, int mode, int epi_mode, const void* A, const void* B, const void* epilogue, int M, int NO, int R, void* stream) {
     G16Params p;
     p.A = (const __bf16*)A; p.lda = R;
     p.B = (const __bf16*)B; p.ldb = mode == 0 ? R : NO;
@@ -275,22 +269,20 @@ int cswin_gemm16(int mode, int epi_mode, const void* A, const void* B, const voi
     p.tiles_m = cdiv(M, G16_T); p.tiles_n = cdiv(NO, G16_T);
     p.nblk = p.tiles_m * p.tiles_n;
     p.epi = *(const Epilogue*)epilogue;
-    p.epi.vec_store = epilogue_vec_ok(p.epi, NO);
-    if (!p.epi.vec_store) return 1;          // bf16-stored outputs / auxiliaries need the 16-B epilogue path anyway
-    if (p.epi.rm_on || p.epi.C2 || p.epi.colsum || p.epi.split_stride) return 1;      // forms the kernel's own epilogue does not implement
+    p.epi.vec_store = plan.store == 4;
     hipStream_t st = (hipStream_t)stream;
     const bool pre16 = p.epi.pre_bf16 != 0;
     if (mode == 0) {
         switch (epi_mode) {
-            case EPI_PLAIN: return g16_launch<EPI_PLAIN, false, false>(p, st);
-            case EPI_ACT: return g16_launch<EPI_ACT, false, false>(p, st);
-            case EPI_RES: return g16_launch<EPI_RES, false, false>(p, st);
+            case EPI_PLAIN: return g16_launch<EPI_PLAIN, false, false>(plan, p, st);
+            case EPI_ACT: return g16_launch<EPI_ACT, false, false>(plan, p, st);
+            case EPI_RES: return g16_launch<EPI_RES, false, false>(plan, p, st);
             default: return 1;
         }
     }
     switch (epi_mode) {
-        case EPI_PLAIN: return g16_launch<EPI_PLAIN, true, false>(p, st);
-        case EPI_GELUBWD: return pre16 ? g16_launch<EPI_GELUBWD, true, true>(p, st) : g16_launch<EPI_GELUBWD, true, false>(p, st);
+        case EPI_PLAIN: return g16_launch<EPI_PLAIN, true, false>(plan, p, st);
+        case EPI_GELUBWD: return pre16 ? g16_launch<EPI_GELUBWD, true, true>(plan, p, st) : g16_launch<EPI_GELUBWD, true, false>(plan, p, st);
         default: return 1;
     }
 }

@@ -189,6 +189,12 @@ __device__ __forceinline__ void run_epilogue(const Epilogue& e, f32x16 (&acc)[FM
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// every output / auxiliary operand the epilogue has starts 16-B aligned: what gemm_plan.h's Linear plans ask about the pointers (with
+// the sizes, which they take themselves, this is epilogue_vec_ok)
+inline bool epilogue_ptrs_aligned(const Epilogue& e) {
+    return aligned16(e.C) && aligned16(e.C2) && aligned16(e.bias) && aligned16(e.Cact) && aligned16(e.residual) && aligned16(e.gelu_pre);
+}
+
 // 16-B epilogue accesses are legal when every row of every output / auxiliary operand starts 16-B aligned
 inline int epilogue_vec_ok(const Epilogue& e, int n_out) {
     auto ok = [](const void* p, long ld) { return !p || (aligned16(p) && ld % 4 == 0); };

@@ -15,6 +15,7 @@
 // One workgroup = 4 waves = one 128 (n) x 128 (k) tile of dW over one slice of m; partial tiles go to the same
 // [split][N*K + N] slabs as the fp32 path, reduced by cswin_rows_sum_multi.  fp32 accumulation throughout.
 #include "common.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -23,9 +24,9 @@ typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
-constexpr int W16_T = 128;          // tile edge (n and k)
-constexpr int W16_MS = 32;          // m rows per step
-constexpr int W16_MAXP = 4;
+constexpr int W16_T = gp::W16_T;    // tile edge (n and k)
+constexpr int W16_MS = gp::W16_MS;  // m rows per step
+constexpr int W16_MAXP = gp::WGRAD_BATCH;
 
 struct W16Problem {
     const float* dy; const float* x; const float* row_scale;
@@ -48,7 +49,7 @@ __device__ __forceinline__ int img_off(int row, int ch) { return 256 * row + 16 
 
 constexpr int W16_DMA_S = 3;                                        // LDS-DMA tile: steps in flight
 constexpr int W16_STEP = 2 * W16_MS * 256;                          // bytes of one step's (dy | x) images
-constexpr int W16_SC_SAMPLES = 64;                                  // DropPath factors of the samples a workgroup's rows touch
+constexpr int W16_SC_SAMPLES = gp::W16_SC_SAMPLES;                  // DropPath factors of the samples a workgroup's rows touch
 constexpr int W16_SC_BYTES = (W16_SC_SAMPLES + W16_DMA_S * W16_MS) * 4;
 constexpr int W16_LDS = W16_DMA_S * W16_STEP + W16_SC_BYTES;        // 48.6 KB (register path: 2 stages + bias sums = 36 KB): 3 workgroups per CU
 static_assert(W16_LDS >= 2 * W16_STEP + 8 * W16_T * 4, "the register path's stages and bias sums must fit");
@@ -400,11 +401,12 @@ __global__ __launch_bounds__(256, 3) void wgrad16_kernel(W16Batch b) {
 
 }  // namespace
 
-// Internal entry used by gemm.hip's cswin_linear_bwd_weight_batch in bf16 matmul mode.  Problems must be 16-B aligned with
-// N % 4 == K % 4 == 0 (the caller checks).  splits[i] <= what problem i's workspace holds.  pending[0..npending): reductions of
-// earlier launches that ride as this grid's last workgroups.  Returns 0 (1: a bad pending job).
-int cswin_wgrad16_batch(const cswin_wgrad_desc* d, int n, const int* splits, const int* rows_per_split, const cswin_reduce_job* pending,
-                        int npending, void* stream, long long* stamps) {
+// Internal entry used by gemm.hip's weight-gradient batches in bf16 matmul mode.  Problems must be 16-B aligned with
+// N % 4 == K % 4 == 0; plans[i] (gp::aligned_batch_plans, Kernel::wgrad16) gives problem i's slabs -- no more than its workspace
+// holds -- and whether it takes the LDS-DMA tile.  pending[0..npending): reductions of earlier launches that ride as this grid's
+// last workgroups.  The caller has checked all of it.
+void cswin_wgrad16_batch(const cswin_wgrad_desc* d, int n, const gp::Plan* plans, const cswin_reduce_job* pending, int npending, void* stream,
+                         long long* stamps) {
     W16Batch b = {};
     int blocks = 0;
     for (int i = 0; i < n; ++i) {
@@ -413,18 +415,15 @@ int cswin_wgrad16_batch(const cswin_wgrad_desc* d, int n, const int* splits, con
         P.slab = (float*)d[i].workspace;
         P.M = d[i].M; P.N = d[i].N; P.K = d[i].K;
         P.rows_per_sample = d[i].row_scale ? d[i].rows_per_sample : 1;
-        P.rows_per_split = rows_per_split[i];
+        P.rows_per_split = plans[i].rows;
         P.tiles_n = cdiv(P.N, W16_T); P.tiles_k = cdiv(P.K, W16_T);
         P.has_bias = d[i].dbias != nullptr;
         P.dy_bf16 = d[i].io_bf16 & 1;
         P.x_bf16 = (d[i].io_bf16 >> 1) & 1;
-        P.slab_stride = wgrad_slab_stride(P.N, P.K);
-        const bool dma_off = !cswin_tuning().w16_dma;                                                      // tuning aid
-        P.dma = !dma_off && P.dy_bf16 && P.x_bf16 && P.M % W16_MS == 0 && P.rows_per_split % W16_MS == 0 &&
-                P.N % 8 == 0 && P.K % 8 == 0 && ((((uintptr_t)P.dy) | ((uintptr_t)P.x)) & 15) == 0 &&
-                (!P.row_scale || P.rows_per_split / P.rows_per_sample + 2 <= W16_SC_SAMPLES);
+        P.slab_stride = gp::slab_stride(P.N, P.K);
+        P.dma = plans[i].dma;
         b.first[i] = blocks;
-        blocks += P.tiles_n * P.tiles_k * splits[i];
+        blocks += P.tiles_n * P.tiles_k * plans[i].splits;
     }
     b.first[n] = blocks;
     b.n = n;
@@ -432,10 +431,8 @@ int cswin_wgrad16_batch(const cswin_wgrad_desc* d, int n, const int* splits, con
     int rblocks = 0;
     if (npending > 0) {
         rblocks = fill_reduce_table(pending, npending, b.r.j, b.r.first_block);
-        if (rblocks < 0) return 1;
         b.r.njobs = npending;
     }
     static_assert(sizeof(W16Batch) <= 4096, "kernel argument block");
     hipLaunchKernelGGL(wgrad16_kernel, dim3(blocks + rblocks), dim3(256), 0, (hipStream_t)stream, b);
-    return 0;
 }

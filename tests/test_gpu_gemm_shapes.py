@@ -137,12 +137,13 @@ def linear_loops(x, w, bias, dy, x2, residual, row_scale, rows_per_sample, gelu_
 # ------------------------------------------------------------------------------------------------
 # launch plan
 # ------------------------------------------------------------------------------------------------
-# A transcription of the host rules of cswin_unet_amd/csrc/gemm.hip, gemm16.hip and wgrad16.hip and it MUST FOLLOW THEM: k_groups,
-# one_split, choose_split (stand-alone target 768 workgroups, a batch's per-problem target 1024 / n), launch_gemm (the cost model
-# between the 64x64 and the 64x32 tile at a penalty of 1.20, the k-tile and wave groups of each, the weight gradients' KW >= 2
-# from 256 rows per slab, the bf16 loops' 64x64x64), launch_gemm_vec's loader width as each entry point decides it, epilogue_vec_ok,
-# WgradSlabs::bytes, wgrad_aligned and the ride / fast / w16_path decisions of wgrad_batch_impl, cswin_gemm16's acceptance rule,
-# g16_launch's stage count and 128-row tile, the split count and the dma predicate of the wgrad16 path -- with no tuning variable set.
+# A transcription of the host rules of cswin_unet_amd/csrc/gemm_plan.h, the header gemm.hip, gemm16.hip and wgrad16.hip launch from,
+# with no tuning variable set: k_groups, one_split, choose_split (stand-alone target 768 workgroups, a batch's per-problem target
+# 1024 / n), choose_tile (the cost model between the 64x64 and the 64x32 tile at a penalty of 1.20, the k-tile and wave groups of
+# each, the weight gradients' KW >= 2 from 256 rows per slab, the bf16 loops' 64x64x64), the loader and epilogue widths of each
+# entry point's plan, wgrad_workspace_bytes, wgrad_aligned and batch_route's ride / fast / wgrad16 decisions, gemm16_accepts and
+# gemm16_plan's stage count and 128-row tile, the split count and the dma predicate of the wgrad16 route.
+# tests/test_gemm_plan_host.py holds it to the header line for line (tools/gemm_plan_check.cpp), on these tables and on sweeps.
 def k_groups(blocks, r_len):
     if blocks < 320 and r_len >= 512:
         return 4
@@ -1061,6 +1062,12 @@ def test_linear_refusals_touch_nothing(lin):
     jobs, outs, keep = lin.pending_jobs([one], what="17 pending")
     many = (lin.Job * 17)(*([jobs[0]] * 17))
     lin.batch([one], pending=(many, outs), refused=True, what="17 pending reductions")
+    # the block tail at precision 1 with a bf16-stored problem that is not aligned (N % 4 != 0): refused before the tail's data
+    # gradient is written and before the pending reduction is run
+    bad, tail = (128, 30, 64), dict(dy=det_normal("gshp.refused.tail.dy", (128, 96)), w=det_normal("gshp.refused.tail.w", (96, 32)))
+    b = gemm_inputs(bad, rounded=True)
+    lin.batch([dict(shape=bad, dy=b["dy"], x=b["x"], io=3)], precision=1, pending=(jobs, outs), tail=tail, refused=True,
+              what="bf16-stored unaligned problem under a tail")
     # the same problem, accepted: nothing above left the library in a state that refuses it
     res, _, _ = lin.batch([one], pending=(jobs, outs), what="accepted")
     check(dict(dw=measure(res[0]["dw"], ref_plain(shape)["dw"], "gemmshape.D.accepted.dw")))
