@@ -89,6 +89,8 @@ SIGNATURES = {
     "cswin_seg_metrics_nbins": (I, [I, I, I]),
     "cswin_seg_metrics_workspace": (SZ, [I, I, I, I, I]),
     "cswin_seg_metrics": (I, [P, P, P, P, P, SZ, I, I, I, I, I, P]),
+    "cswin_surface_dist_workspace": (SZ, [I, I, I, I, I]),
+    "cswin_surface_dist": (I, [P, P, P, P, P, L, P, SZ, I, I, I, I, I, D, D, D, P]),
     "cswin_components_workspace": (SZ, [I, I, I]),
     "cswin_components_label": (I, [P, P, P, P, SZ, I, I, I, I, P]),
     "cswin_components_filter": (I, [P, P, P, P, P, P, P, SZ, I, I, I, I, P]),

@@ -405,7 +405,8 @@ def evaluate_tasks(net, loaders, stage_classes, patch_size, *, num_classes=None,
     loader, every task is scored on its own channels (task_class_indices) against its dataset's own label ids.  The model's class
     count is num_classes, or else the num_classes attribute of the first module of net that has one.  A task whose channels reach
     beyond it is refused by name before anything runs (the reference fails with an IndexError inside the first volume).
-    Returns {task: (per_volume, class_mean, mean_dice, mean_hd95)}."""
+    Returns {task: (per_volume, class_mean, mean_dice, mean_hd95)} -- evaluate_volumes' return, so with assd=True among the
+    keyword arguments (which, like voxelspacing, go to evaluate_volumes as they are) a fifth element mean_assd."""
     from .utils import evaluate_volumes
     stage_classes = [int(n) for n in stage_classes]
     if num_classes is None:

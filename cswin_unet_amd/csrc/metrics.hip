@@ -19,6 +19,15 @@
 // The y and z minima are bounded brute force: candidates are visited by growing |dy| and the walk stops once dy^2 >= best, which
 // no farther candidate can beat -- exact, and short because queries sit close to seeds.
 // Classes with an empty side are skipped on the device (every kernel reads counts[c] and leaves): no host round trip.
+//
+// With a voxel spacing (sz, sy, sx) squared distances stop being integers and there is no histogram to index.  The second entry
+// point, cswin_surface_dist, runs the same border and x passes (|dx| stays an integer) and the same y and z walks under another
+// metric (SpacedMetric below, float64): the y pass keeps per voxel the (|dx|, |dy|) of its in-plane argmin, packed in the 32 bits
+// the unit path keeps a squared distance in, and the z pass evaluates (dz sz)^2 + (dy sy)^2 + (dx sx)^2 -- the expression scipy's
+// distance_transform_edt(sampling=...) evaluates, products and sums rounded one by one -- and stores it in a compacted list:
+// segment (c, dir) starts at the exclusive prefix sum of the border counts nq[c][dir] (formed on the device after the border
+// pass), slots inside a segment come from an integer atomic counter.  The multiset of a segment is the same on every run; its
+// order is not, and the caller sorts.
 #include "common.h"
 
 namespace {
@@ -37,6 +46,78 @@ __device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+
+// What the y and z passes minimise.  Best is the running minimum of a walk, cell_t what the y pass leaves per voxel for the z pass.
+// UnitMetric: unit spacing, everything an int32; a row or plane without a seed carries G1_NONE^2.
+struct UnitMetric {
+    using val_t = int;
+    using cell_t = int;
+    struct Best {
+        int v;
+    };
+    __device__ static cell_t no_seed() { return G1_NONE * G1_NONE; }
+    __device__ val_t ystep(int d) const { return d * d; }
+    __device__ Best yinit(int g) const { return {g * g}; }
+    __device__ void ytake(Best& b, int t, int, val_t d2) const { b.v = min(b.v, t * t + d2); }
+    __device__ cell_t ycell(const Best& b) const { return b.v; }
+    __device__ val_t zstep(int d) const { return d * d; }
+    __device__ Best zinit(cell_t q) const { return {q}; }
+    __device__ void ztake(Best& b, cell_t q, val_t d2) const { b.v = min(b.v, q + d2); }
+};
+
+// SpacedMetric: float64 under the spacing (sz, sy, sx).  A cell is |dx| | |dy| << 16 of the in-plane argmin (both < 2048), or
+// NO_SEED, whose distance is +inf.  This file is built with -ffp-contract=off: a product is rounded before it is added, as numpy
+// rounds it.
+struct SpacedMetric {
+    double sz, sy, sx;
+    using val_t = double;
+    using cell_t = unsigned;
+    struct Best {
+        double v;
+        unsigned arg;
+    };
+    static constexpr unsigned NO_SEED = 0xFFFFFFFFu;
+    __device__ static cell_t no_seed() { return NO_SEED; }
+    __device__ static double sq(int d, double w) {
+        const double t = (double)d * w;
+        return t * t;
+    }
+    __device__ static double sum(double a, double b) { return a + b; }
+    __device__ val_t ystep(int d) const { return sq(d, sy); }
+    __device__ Best yinit(int g) const { return g == G1_NONE ? Best{__builtin_inf(), NO_SEED} : Best{sq(g, sx), (unsigned)g}; }
+    __device__ void ytake(Best& b, int t, int d, val_t d2) const {
+        if (t == G1_NONE) return;
+        const double v = sum(d2, sq(t, sx));
+        if (v < b.v) b = {v, (unsigned)t | ((unsigned)d << 16)};
+    }
+    __device__ cell_t ycell(const Best& b) const { return b.arg; }
+    __device__ val_t zstep(int d) const { return sq(d, sz); }
+    __device__ double at(cell_t q, double dz2) const {
+        return q == NO_SEED ? __builtin_inf() : sum(sum(dz2, sq((int)(q >> 16), sy)), sq((int)(q & 0xFFFFu), sx));
+    }
+    __device__ Best zinit(cell_t q) const { return {at(q, 0.0), 0u}; }
+    __device__ void ztake(Best& b, cell_t q, val_t d2) const { b.v = fmin(b.v, at(q, d2)); }
+};
+
+// Where the z pass puts the squared distance of a query of class c, direction dir.
+struct HistSink {
+    unsigned* __restrict__ hist;
+    int nbins;
+    __device__ void put(int c, int, const UnitMetric::Best& b) const {
+        if (b.v < nbins) atomicAdd(&hist[(long)c * nbins + b.v], 1u);
+    }
+};
+// dist2[offs[c][dir] + slot], slot from the segment's counter; a slot at or past cap is dropped (the caller sees nq.sum() > cap)
+struct ListSink {
+    double* __restrict__ dist2;
+    const long long* __restrict__ offs;
+    unsigned long long* __restrict__ cursor;
+    long long cap;
+    __device__ void put(int c, int dir, const SpacedMetric::Best& b) const {
+        const long long slot = offs[c * 2 + dir] + (long long)atomicAdd(&cursor[c * 2 + dir], 1ull);
+        if (slot >= 0 && slot < cap) dist2[slot] = b.v;
+    }
+};
 
 __global__ void seg_box_init_kernel(int* __restrict__ box, int ncls) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -58,14 +139,19 @@ __device__ __forceinline__ bool seg_is_border(const unsigned char* __restrict__ 
 // One sweep over both volumes: byte maps of the borders, the four counts per class, the per-class box of all border voxels.
 // A thread owns 16 consecutive voxels.  Background (id 0) is most of a volume: its counts stay in registers and meet in one
 // wave sum; foreground voxels add to per-workgroup LDS tallies; one 64-bit global atomic per touched class per workgroup.
+// SIDES: also sides[c][0] = |dP_c|, sides[c][1] = |dG_c| of the foreground classes, which counts[c][3] only has the sum of.
+template <bool SIDES>
 __global__ __launch_bounds__(256) void seg_border_count_kernel(const unsigned char* __restrict__ pred,
                                                                const unsigned char* __restrict__ label,
                                                                unsigned char* __restrict__ bmP, unsigned char* __restrict__ bmG,
                                                                unsigned long long* __restrict__ counts, int* __restrict__ box,
-                                                               SegDims s, long N, int vec_ok) {
+                                                               unsigned long long* __restrict__ sides, SegDims s, long N, int vec_ok) {
     __shared__ unsigned tally[(SM_MAX_CLS + 1) * 4];
+    __shared__ unsigned stally[SIDES ? (SM_MAX_CLS + 1) * 2 : 1];
     __shared__ int lbox[(SM_MAX_CLS + 1) * 6];
     for (int i = threadIdx.x; i < s.ncls * 4; i += 256) tally[i] = 0u;
+    if (SIDES)
+        for (int i = threadIdx.x; i < s.ncls * 2; i += 256) stally[i] = 0u;
     for (int i = threadIdx.x; i < s.ncls * 6; i += 256) lbox[i] = (i & 1) ? -1 : 0x7FFFFFFF;
     __syncthreads();
 
@@ -126,6 +212,7 @@ __global__ __launch_bounds__(256) void seg_border_count_kernel(const unsigned ch
                 for (int side = 0; side < 2; ++side) {
                     const int id = side ? ig : ip;
                     if ((side ? bgd : bp) && id != 0) {
+                        if (SIDES) atomicAdd(&stally[id * 2 + side], 1u);
                         int* b = lbox + id * 6;
                         atomicMin(b + 0, z);
                         atomicMax(b + 1, z);
@@ -164,6 +251,9 @@ __global__ __launch_bounds__(256) void seg_border_count_kernel(const unsigned ch
     __syncthreads();
     for (int i = threadIdx.x; i < s.ncls * 4; i += 256)
         if (tally[i]) atomicAdd(&counts[i], (unsigned long long)tally[i]);
+    if (SIDES)
+        for (int i = threadIdx.x; i < s.ncls * 2; i += 256)
+            if (stally[i]) atomicAdd(&sides[i], (unsigned long long)stally[i]);
     for (int i = threadIdx.x; i < s.ncls * 6; i += 256) {
         if (i & 1) {
             if (lbox[i] >= 0) atomicMax(&box[i], lbox[i]);
@@ -228,10 +318,11 @@ __global__ __launch_bounds__(256) void seg_edt_x_kernel(const unsigned char* __r
 
 // y pass: a workgroup takes TX columns of one plane z of the box (TX * H * 2 B of LDS: the host picks TX from H), one column
 // per lane so that the loads of g1 and the stores of g2 are contiguous across lanes.  A plane without any seed is answered
-// with the constant G1_NONE^2 instead of H-long walks.
-__global__ __launch_bounds__(256) void seg_edt_y_kernel(const unsigned short* __restrict__ g1, int* __restrict__ g2,
+// with the metric's "no seed" cell (G1_NONE^2 / NO_SEED) instead of H-long walks.
+template <class M>
+__global__ __launch_bounds__(256) void seg_edt_y_kernel(const unsigned short* __restrict__ g1, typename M::cell_t* __restrict__ g2,
                                                         const unsigned long long* __restrict__ counts, const int* __restrict__ box,
-                                                        SegDims s, long N, int c, int TX) {
+                                                        SegDims s, long N, int c, int TX, M m) {
     extern __shared__ unsigned short col[];          // [hb][TX]
     SegBox b;
     if (!seg_class_box(counts, box, c, b)) return;
@@ -250,35 +341,30 @@ __global__ __launch_bounds__(256) void seg_edt_y_kernel(const unsigned short* __
     any = __syncthreads_or(any);
     if (!live) return;
     if (!any) {
-        for (int yy = yg; yy < hb; yy += G) g2[base + (long)yy * s.W] = G1_NONE * G1_NONE;
+        for (int yy = yg; yy < hb; yy += G) g2[base + (long)yy * s.W] = M::no_seed();
         return;
     }
     for (int yy = yg; yy < hb; yy += G) {
-        const int g = col[yy * TX + cx];
-        int best = g * g;
+        typename M::Best best = m.yinit(col[yy * TX + cx]);
         for (int d = 1;; ++d) {
-            const int d2 = d * d;
+            const typename M::val_t d2 = m.ystep(d);
             const bool lo = yy - d >= 0, hi = yy + d < hb;
-            if (d2 >= best || !(lo || hi)) break;
-            if (lo) {
-                const int t = col[(yy - d) * TX + cx];
-                best = min(best, t * t + d2);
-            }
-            if (hi) {
-                const int t = col[(yy + d) * TX + cx];
-                best = min(best, t * t + d2);
-            }
+            if (d2 >= best.v || !(lo || hi)) break;
+            if (lo) m.ytake(best, col[(yy - d) * TX + cx], d, d2);
+            if (hi) m.ytake(best, col[(yy + d) * TX + cx], d, d2);
         }
-        g2[base + (long)yy * s.W] = best;
+        g2[base + (long)yy * s.W] = m.ycell(best);
     }
 }
 
 // z pass, at the queries only: the other volume's border voxels of class c.  Walks the planes of the box outward from the
-// query's own and stops as for y; adds one to the class's histogram row at the squared distance found.
-__global__ __launch_bounds__(256) void seg_edt_z_hist_kernel(const unsigned char* __restrict__ bmP, const unsigned char* __restrict__ bmG,
-                                                             const int* __restrict__ g2, unsigned* __restrict__ hist,
-                                                             const unsigned long long* __restrict__ counts,
-                                                             const int* __restrict__ box, SegDims s, long N, int c, int nbins) {
+// query's own and stops as for y; the squared distance found goes to the sink: one more in the class's histogram row, or one
+// more entry of the segment's list.
+template <class M, class Sink>
+__global__ __launch_bounds__(256) void seg_edt_z_kernel(const unsigned char* __restrict__ bmP, const unsigned char* __restrict__ bmG,
+                                                        const typename M::cell_t* __restrict__ g2,
+                                                        const unsigned long long* __restrict__ counts,
+                                                        const int* __restrict__ box, SegDims s, long N, int c, M m, Sink sink) {
     SegBox b;
     if (!seg_class_box(counts, box, c, b)) return;
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -286,21 +372,126 @@ __global__ __launch_bounds__(256) void seg_edt_z_hist_kernel(const unsigned char
     if (z < b.z0 || z > b.z1 || y < b.y0 || y > b.y1 || x < b.x0 || x > b.x1) return;
     const long HW = (long)s.H * s.W, v = (long)z * HW + (long)y * s.W + x;
     if ((dir == 0 ? bmP : bmG)[v] != c) return;
-    const int* __restrict__ g = g2 + (long)dir * N + (long)y * s.W + x;
-    int best = g[(long)z * HW];
+    const typename M::cell_t* __restrict__ g = g2 + (long)dir * N + (long)y * s.W + x;
+    typename M::Best best = m.zinit(g[(long)z * HW]);
     for (int d = 1;; ++d) {
-        const int d2 = d * d;
+        const typename M::val_t d2 = m.zstep(d);
         const bool lo = z - d >= b.z0, hi = z + d <= b.z1;
-        if (d2 >= best || !(lo || hi)) break;
-        if (lo) best = min(best, g[(long)(z - d) * HW] + d2);
-        if (hi) best = min(best, g[(long)(z + d) * HW] + d2);
+        if (d2 >= best.v || !(lo || hi)) break;
+        if (lo) m.ztake(best, g[(long)(z - d) * HW], d2);
+        if (hi) m.ztake(best, g[(long)(z + d) * HW], d2);
     }
-    if (best < nbins) atomicAdd(&hist[(long)c * nbins + best], 1u);
+    sink.put(c, dir, best);
+}
+
+// After the border pass: nq[c][dir] = |dP_c| (dir 0) / |dG_c| (dir 1) where class c > 0 has voxels on both sides, else 0 (the
+// border pass left the raw tallies there); offs = exclusive prefix sum of nq in (class, dir) order; the segment counters to 0.
+// One workgroup, a class per thread (ncls <= 255), a Hillis-Steele scan of the per-class totals in LDS.
+__global__ __launch_bounds__(256) void seg_list_offsets_kernel(const unsigned long long* __restrict__ counts, long long* __restrict__ nq,
+                                                               long long* __restrict__ offs, unsigned long long* __restrict__ cursor,
+                                                               int ncls) {
+    __shared__ long long scan[256];
+    const int c = threadIdx.x;
+    const bool both = c > 0 && c < ncls && counts[c * 4 + 0] != 0ull && counts[c * 4 + 1] != 0ull;
+    const long long n0 = both ? nq[c * 2 + 0] : 0, n1 = both ? nq[c * 2 + 1] : 0;
+    long long run = n0 + n1;
+    scan[c] = run;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {
+        const long long add = c >= o ? scan[c - o] : 0;
+        __syncthreads();
+        run += add;
+        scan[c] = run;
+        __syncthreads();
+    }
+    if (c < ncls) {
+        const long long start = run - n0 - n1;
+        nq[c * 2 + 0] = n0;
+        nq[c * 2 + 1] = n1;
+        offs[c * 2 + 0] = start;
+        offs[c * 2 + 1] = start + n0;
+        cursor[c * 2 + 0] = 0ull;
+        cursor[c * 2 + 1] = 0ull;
+    }
 }
 
 bool seg_dims_ok(int D, int H, int W) { return D >= 1 && H >= 1 && W >= 1 && D <= SM_MAX_DIM && H <= SM_MAX_DIM && W <= SM_MAX_DIM; }
 
 size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+// the shape rules of both entry points; `what` names the caller in the message
+bool seg_shape_ok(const char* what, int D, int H, int W, int ndim, int ncls) {
+    if (!seg_dims_ok(D, H, W)) {
+        cswin_set_error("%s: volume %dx%dx%d outside the supported 1..%d per dimension", what, D, H, W, SM_MAX_DIM);
+        return false;
+    }
+    if (!(ndim == 3 || (ndim == 2 && D == 1))) {
+        cswin_set_error("%s: ndim must be 3, or 2 with D == 1 (got ndim=%d, D=%d)", what, ndim, D);
+        return false;
+    }
+    if (ncls < 2 || ncls > SM_MAX_CLS) {
+        cswin_set_error("%s: ncls=%d outside 2..%d", what, ncls, SM_MAX_CLS);
+        return false;
+    }
+    return true;
+}
+
+// One carving for both entry points: two border byte maps, g1 (uint16) and g2 (32-bit cells) for both directions of one class,
+// the per-class boxes -- 14 B per voxel.  The list path appends its segment offsets and counters (16 B per class each).
+struct SegWorkspace {
+    unsigned char *bmP, *bmG;
+    unsigned short* g1;
+    void* g2;
+    int* box;
+    long long* offs;
+    unsigned long long* cursor;
+};
+size_t seg_workspace_bytes(size_t N, int ncls) {
+    return 2 * up16(N) + up16(2 * N * sizeof(unsigned short)) + up16(2 * N * sizeof(int)) + up16((size_t)ncls * 6 * sizeof(int));
+}
+size_t seg_list_bytes(int ncls) { return 2 * up16((size_t)ncls * 2 * sizeof(long long)); }
+SegWorkspace seg_carve(void* workspace, size_t N, int ncls) {
+    SegWorkspace w;
+    w.bmP = (unsigned char*)workspace;
+    w.bmG = w.bmP + up16(N);
+    w.g1 = (unsigned short*)(w.bmG + up16(N));
+    w.g2 = (char*)w.g1 + up16(2 * N * sizeof(unsigned short));
+    w.box = (int*)((char*)w.g2 + up16(2 * N * sizeof(int)));
+    w.offs = (long long*)((char*)w.box + up16((size_t)ncls * 6 * sizeof(int)));
+    w.cursor = (unsigned long long*)((char*)w.offs + up16((size_t)ncls * 2 * sizeof(long long)));
+    return w;
+}
+
+// box reset and the border pass; `sides` (SIDES only) is zeroed by the caller
+template <bool SIDES>
+int seg_border_pass(hipStream_t st, const unsigned char* pred, const unsigned char* label, const SegWorkspace& w, long long* counts,
+                    long long* sides, const SegDims& s, long N) {
+    hipLaunchKernelGGL(seg_box_init_kernel, dim3(cdiv(s.ncls * 6, 256)), dim3(256), 0, st, w.box, s.ncls);
+    CSWIN_LAUNCH_CHECK();
+    const int vec_ok = (uintptr_t)pred % 16 == 0 && (uintptr_t)label % 16 == 0;
+    hipLaunchKernelGGL(seg_border_count_kernel<SIDES>, dim3((unsigned)((N + 256 * BC_VOX - 1) / (256 * BC_VOX))), dim3(256), 0, st, pred,
+                       label, w.bmP, w.bmG, (unsigned long long*)counts, w.box, (unsigned long long*)sides, s, N, vec_ok);
+    CSWIN_LAUNCH_CHECK();
+    return CSWIN_OK;
+}
+
+// x, y and z pass of every foreground class under metric m, distances to `sink`
+template <class M, class Sink>
+int seg_class_passes(hipStream_t st, const SegWorkspace& w, const long long* counts, const SegDims& s, long N, M m, Sink sink) {
+    typename M::cell_t* g2 = (typename M::cell_t*)w.g2;
+    const int TX = s.H <= 512 ? 64 : (s.H <= 1024 ? 32 : 16);          // TX * H * 2 B of LDS <= 64 KiB
+    const long rows = (long)s.D * s.H;
+    for (int c = 1; c < s.ncls; ++c) {                                  // class 0 (background) is never measured
+        hipLaunchKernelGGL(seg_edt_x_kernel, dim3((unsigned)((rows + 3) / 4), 2), dim3(256), 0, st, w.bmP, w.bmG, w.g1,
+                           (const unsigned long long*)counts, w.box, s, N, c);
+        hipLaunchKernelGGL(seg_edt_y_kernel<M>, dim3(cdiv(s.W, TX), s.D, 2), dim3(256), (size_t)TX * s.H * sizeof(unsigned short), st, w.g1,
+                           g2, (const unsigned long long*)counts, w.box, s, N, c, TX, m);
+        hipLaunchKernelGGL((seg_edt_z_kernel<M, Sink>), dim3(cdiv(s.W, 64), cdiv(s.H, 4), 2 * s.D), dim3(256), 0, st, w.bmP, w.bmG, g2,
+                           (const unsigned long long*)counts, w.box, s, N, c, m, sink);
+        CSWIN_LAUNCH_CHECK();
+    }
+    return CSWIN_OK;
+}
 
 }  // namespace
 
@@ -317,20 +508,8 @@ int cswin_seg_metrics_nbins(int D, int H, int W) {
 
 // two border byte maps, g1 (uint16) and g2 (int32) for both directions of one class, the per-class boxes
 size_t cswin_seg_metrics_workspace(int D, int H, int W, int ndim, int ncls) {
-    if (!seg_dims_ok(D, H, W)) {
-        cswin_set_error("seg_metrics: volume %dx%dx%d outside the supported 1..%d per dimension", D, H, W, SM_MAX_DIM);
-        return 0;
-    }
-    if (!(ndim == 3 || (ndim == 2 && D == 1))) {
-        cswin_set_error("seg_metrics: ndim must be 3, or 2 with D == 1 (got ndim=%d, D=%d)", ndim, D);
-        return 0;
-    }
-    if (ncls < 2 || ncls > SM_MAX_CLS) {
-        cswin_set_error("seg_metrics: ncls=%d outside 2..%d", ncls, SM_MAX_CLS);
-        return 0;
-    }
-    const size_t N = (size_t)D * H * W;
-    return 2 * up16(N) + up16(2 * N * sizeof(unsigned short)) + up16(2 * N * sizeof(int)) + up16((size_t)ncls * 6 * sizeof(int));
+    if (!seg_shape_ok("seg_metrics", D, H, W, ndim, ncls)) return 0;
+    return seg_workspace_bytes((size_t)D * H * W, ncls);
 }
 
 int cswin_seg_metrics(const unsigned char* pred, const unsigned char* label, long long* counts, unsigned int* hist,
@@ -345,38 +524,51 @@ int cswin_seg_metrics(const unsigned char* pred, const unsigned char* label, lon
     const long N = (long)D * H * W;
     const int nbins = cswin_seg_metrics_nbins(D, H, W);
     const SegDims s = {D, H, W, ndim, ncls};
-
-    char* w = (char*)workspace;
-    unsigned char* bmP = (unsigned char*)w;
-    unsigned char* bmG = bmP + up16((size_t)N);
-    unsigned short* g1 = (unsigned short*)(bmG + up16((size_t)N));
-    int* g2 = (int*)((char*)g1 + up16(2 * (size_t)N * sizeof(unsigned short)));
-    int* box = (int*)((char*)g2 + up16(2 * (size_t)N * sizeof(int)));
+    const SegWorkspace w = seg_carve(workspace, (size_t)N, ncls);
 
     if (hipMemsetAsync(counts, 0, (size_t)ncls * 4 * sizeof(long long), st) != hipSuccess ||
         hipMemsetAsync(hist, 0, (size_t)ncls * nbins * sizeof(unsigned), st) != hipSuccess) {
         cswin_set_error("seg_metrics: hipMemsetAsync failed");
         return CSWIN_ERR_HIP;
     }
-    hipLaunchKernelGGL(seg_box_init_kernel, dim3(cdiv(ncls * 6, 256)), dim3(256), 0, st, box, ncls);
-    CSWIN_LAUNCH_CHECK();
-    const int vec_ok = (uintptr_t)pred % 16 == 0 && (uintptr_t)label % 16 == 0;
-    hipLaunchKernelGGL(seg_border_count_kernel, dim3((unsigned)((N + 256 * BC_VOX - 1) / (256 * BC_VOX))), dim3(256), 0, st, pred, label,
-                       bmP, bmG, (unsigned long long*)counts, box, s, N, vec_ok);
-    CSWIN_LAUNCH_CHECK();
+    if (int rc = seg_border_pass<false>(st, pred, label, w, counts, nullptr, s, N)) return rc;
+    return seg_class_passes(st, w, counts, s, N, UnitMetric{}, HistSink{hist, nbins});          // row 0 (background) stays zero
+}
 
-    const int TX = H <= 512 ? 64 : (H <= 1024 ? 32 : 16);          // TX * H * 2 B of LDS <= 64 KiB
-    const long rows = (long)D * H;
-    for (int c = 1; c < ncls; ++c) {                                  // row 0 (background) stays zero
-        hipLaunchKernelGGL(seg_edt_x_kernel, dim3((unsigned)((rows + 3) / 4), 2), dim3(256), 0, st, bmP, bmG, g1,
-                           (const unsigned long long*)counts, box, s, N, c);
-        hipLaunchKernelGGL(seg_edt_y_kernel, dim3(cdiv(W, TX), D, 2), dim3(256), (size_t)TX * H * sizeof(unsigned short), st, g1, g2,
-                           (const unsigned long long*)counts, box, s, N, c, TX);
-        hipLaunchKernelGGL(seg_edt_z_hist_kernel, dim3(cdiv(W, 64), cdiv(H, 4), 2 * D), dim3(256), 0, st, bmP, bmG, g2, hist,
-                           (const unsigned long long*)counts, box, s, N, c, nbins);
-        CSWIN_LAUNCH_CHECK();
+// cswin_seg_metrics_workspace plus the list path's segment offsets and counters
+size_t cswin_surface_dist_workspace(int D, int H, int W, int ndim, int ncls) {
+    if (!seg_shape_ok("surface_dist", D, H, W, ndim, ncls)) return 0;
+    return seg_workspace_bytes((size_t)D * H * W, ncls) + seg_list_bytes(ncls);
+}
+
+int cswin_surface_dist(const unsigned char* pred, const unsigned char* label, long long* counts, long long* nq, double* dist2, long cap,
+                       void* workspace, size_t ws_bytes, int D, int H, int W, int ndim, int ncls, double sz, double sy, double sx,
+                       void* stream) {
+    CSWIN_REQUIRE(pred && label && counts && nq && dist2, CSWIN_ERR_SHAPE, "surface_dist: null argument");
+    CSWIN_REQUIRE(cap >= 0, CSWIN_ERR_SHAPE, "surface_dist: cap=%ld is negative", cap);
+    if (ndim == 2) sz = 1.0;                                                          // a plane has no z step
+    CSWIN_REQUIRE(std::isfinite(sz) && std::isfinite(sy) && std::isfinite(sx) && sz > 0 && sy > 0 && sx > 0, CSWIN_ERR_SHAPE,
+                  "surface_dist: voxel spacing (%g, %g, %g) must be finite and positive", sz, sy, sx);
+    const size_t need = cswin_surface_dist_workspace(D, H, W, ndim, ncls);          // sets the message for a bad shape
+    if (need == 0) return CSWIN_ERR_SHAPE;
+    CSWIN_REQUIRE(workspace && ws_bytes >= need, CSWIN_ERR_WORKSPACE, "surface_dist: workspace of %zu bytes, %zu needed", ws_bytes, need);
+    CSWIN_REQUIRE((uintptr_t)workspace % 16 == 0, CSWIN_ERR_ALIGN, "surface_dist: workspace must be 16-B aligned");
+    CSWIN_REQUIRE((uintptr_t)counts % 8 == 0 && (uintptr_t)nq % 8 == 0 && (uintptr_t)dist2 % 8 == 0, CSWIN_ERR_ALIGN,
+                  "surface_dist: counts / nq / dist2 misaligned");
+    hipStream_t st = (hipStream_t)stream;
+    const long N = (long)D * H * W;
+    const SegDims s = {D, H, W, ndim, ncls};
+    const SegWorkspace w = seg_carve(workspace, (size_t)N, ncls);
+
+    if (hipMemsetAsync(counts, 0, (size_t)ncls * 4 * sizeof(long long), st) != hipSuccess ||
+        hipMemsetAsync(nq, 0, (size_t)ncls * 2 * sizeof(long long), st) != hipSuccess) {
+        cswin_set_error("surface_dist: hipMemsetAsync failed");
+        return CSWIN_ERR_HIP;
     }
-    return CSWIN_OK;
+    if (int rc = seg_border_pass<true>(st, pred, label, w, counts, nq, s, N)) return rc;
+    hipLaunchKernelGGL(seg_list_offsets_kernel, dim3(1), dim3(256), 0, st, (const unsigned long long*)counts, nq, w.offs, w.cursor, ncls);
+    CSWIN_LAUNCH_CHECK();
+    return seg_class_passes(st, w, counts, s, N, SpacedMetric{sz, sy, sx}, ListSink{dist2, w.offs, w.cursor, (long long)cap});
 }
 
 }  // extern "C"

@@ -1253,6 +1253,76 @@ def seg_metrics(pred, label, ncls, ndim=None):
     return counts, hist
 
 
+def voxel_spacing(voxelspacing, ndim):
+    """A voxel spacing as a tuple of `ndim` floats in array order, (D, H, W) or (H, W): scipy's `sampling`, medpy's
+    `voxelspacing`.  None is unit spacing, a number is that spacing along every axis, a sequence must have `ndim` entries.
+    ValueError for a wrong length and for an entry that is not finite and positive."""
+    ndim = int(ndim)
+    if voxelspacing is None:
+        return (1.0,) * ndim
+    try:
+        sp = (float(voxelspacing),) * ndim if np.ndim(voxelspacing) == 0 else tuple(float(v) for v in voxelspacing)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"voxelspacing {voxelspacing!r} is not a number or a sequence of numbers") from e
+    if len(sp) != ndim:
+        raise ValueError(f"voxelspacing {voxelspacing!r} has {len(sp)} entries for {ndim} dimensions")
+    if not all(np.isfinite(v) and v > 0 for v in sp):
+        raise ValueError(f"voxelspacing {voxelspacing!r}: every entry must be finite and positive")
+    return sp
+
+
+SURFACE_CAP_EXACT = 1 << 20          # list entries (8 MiB) up to which the default cap is the exact worst case
+SURFACE_CAP_FRACTION = 8             # beyond: one entry per SURFACE_CAP_FRACTION voxels
+
+
+def surface_cap(nvox):
+    """Default capacity of ops.surface_distances' list for a volume of nvox voxels.  Every voxel can be a border voxel on both
+    sides, so 2 nvox entries always suffice; that exact worst case is the default while it stays within SURFACE_CAP_EXACT
+    entries.  Larger volumes get nvox / SURFACE_CAP_FRACTION (at least SURFACE_CAP_EXACT): an organ's surface is a small part
+    of a volume, and utils.volume_metrics calls again with the exact size if it ever is not."""
+    nvox = int(nvox)
+    return 2 * nvox if 2 * nvox <= SURFACE_CAP_EXACT else max(SURFACE_CAP_EXACT, nvox // SURFACE_CAP_FRACTION)
+
+
+def surface_distances(pred, label, ncls, voxelspacing, ndim=None, cap=None):
+    """Per-class surface distances of a prediction / label pair under a voxel spacing (csrc/metrics.hip, cswin_surface_dist): the
+    ingredients of HD95 and ASSD in physical units.  pred, label, ncls, ndim: as for seg_metrics.  voxelspacing: voxel_spacing's,
+    `ndim` entries in array order.  Returns device tensors, no host sync: counts int64 [ncls, 4] (seg_metrics'), nq int64
+    [ncls, 2] = the border voxels of the prediction / of the label per class (0 for a class missing on either side) and dist2
+    float64 [cap]: squared distances in segments ordered class 1 P->G, class 1 G->P, class 2 P->G, ... at the exclusive prefix
+    sums of nq, unordered inside a segment; entries past nq.sum() are uninitialised.  cap: the list's capacity (default
+    surface_cap(voxels)); values that do not fit are dropped, which shows as nq.sum() > cap.  utils.volume_metrics sorts the
+    segments and finishes on the host."""
+    for t, what in ((pred, "surface_distances prediction"), (label, "surface_distances label")):
+        if not t.is_cuda:
+            raise CswinHipError(f"{what} is on {t.device}: the cswin_unet_amd ops run on a HIP device only (no CPU fallback)")
+        if t.dtype != torch.uint8:
+            raise CswinHipError(f"{what} has dtype {t.dtype}; class ids are passed as uint8")
+    if pred.shape != label.shape or pred.dim() not in (2, 3):
+        raise CswinHipError(f"surface_distances: prediction {tuple(pred.shape)} and label {tuple(label.shape)} must be equal (D, H, W) or (H, W) shapes")
+    ndim = pred.dim() if ndim is None else int(ndim)
+    if ndim not in (2, 3):
+        raise CswinHipError(f"surface_distances: ndim must be 2 or 3, got {ndim}")
+    sp = voxel_spacing(voxelspacing, ndim)
+    sz, sy, sx = (1.0,) * (3 - ndim) + sp
+    pred, label = pred.contiguous(), label.contiguous()
+    D, H, W = (1,) * (3 - pred.dim()) + tuple(pred.shape)
+    cap = surface_cap(pred.numel()) if cap is None else int(cap)
+    if cap < 0:
+        raise ValueError(f"surface_distances: cap={cap} is negative")
+    h = lib()
+    nbytes = h.cswin_surface_dist_workspace(D, H, W, ndim, int(ncls))
+    if nbytes == 0:
+        raise CswinHipError(f"surface_distances: {h.cswin_last_error().decode()}")
+    counts = torch.empty(int(ncls), 4, dtype=torch.int64, device=pred.device)
+    nq = torch.empty(int(ncls), 2, dtype=torch.int64, device=pred.device)
+    dist2 = torch.empty(max(cap, 1), dtype=torch.float64, device=pred.device)[:cap]
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=pred.device)
+    call("cswin_surface_dist", ptr(pred), ptr(label), ptr(counts), ptr(nq), ptr(dist2), cap, ptr(ws), nbytes, D, H, W, ndim, int(ncls),
+         sz, sy, sx, stream())
+    return counts, nq, dist2
+
+
 # ------------------------------------------------------------------------------------------------
 # connected components of a label volume and the per-class size filter
 # ------------------------------------------------------------------------------------------------

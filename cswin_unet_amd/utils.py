@@ -12,6 +12,8 @@ Mirrors the reference's utils.py names and call signatures:
     one launch per slice.  ``metrics="hip"`` takes Dice / HD95 of all classes from one device call (``volume_metrics``:
     ops.seg_metrics returns integer counts and an integer histogram of squared surface distances, the host finishes in
     float64) instead of the per-class scipy loop; ``evaluate_volumes`` is the aggregating loop of test.py:155-164.
+    ``voxelspacing`` / ``assd=True`` (not in the reference) score in physical units and add medpy's ASSD, on either path: the
+    device then returns a list of float64 squared surface distances (ops.surface_distances) instead of the histogram.
     ``resize="hip"`` keeps the volume on the device: both zooms are linear maps whose 1-D operators ``zoom_operator`` /
     ``nearest_index`` take from scipy itself, applied by ops.resize_slices / ops.argmax_zoom_back (csrc/resize.hip).
     ``class_indices`` scores a continual model on one dataset's own output channels (universal_test.py:50-54): the argmax runs
@@ -83,16 +85,34 @@ def hd95(result, reference, voxelspacing=None, connectivity=1):
     return float(np.percentile(np.hstack((a, b)), 95))
 
 
-def calculate_metric_percase(pred, gt):
-    """(dice, hd95) of one class; (1, 0) when only the prediction is non-empty, (0, 0) otherwise (utils.py:48-58)."""
+def _hd95_assd(a, b):
+    """(hd95, assd) of the two directed lists of surface distances: the 95th percentile of both together, and the mean of the two
+    directed means (medpy's assd; not the mean of the pooled list, which weighs the longer surface more)."""
+    return float(np.percentile(np.hstack((a, b)), 95)), float(np.mean((a.mean(), b.mean())))
+
+
+def assd(result, reference, voxelspacing=None, connectivity=1):
+    """Average symmetric surface distance: the mean of the two average surface distances result -> reference and
+    reference -> result (medpy.metric.binary.assd / asd)."""
+    a = _surface_distances(result, reference, voxelspacing, connectivity)
+    b = _surface_distances(reference, result, voxelspacing, connectivity)
+    return _hd95_assd(a, b)[1]
+
+
+def calculate_metric_percase(pred, gt, voxelspacing=None, assd=False):
+    """(dice, hd95) of one class; (1, 0) when only the prediction is non-empty, (0, 0) otherwise (utils.py:48-58).
+    voxelspacing (not in the reference, which scores in voxels): medpy's, the spacing per axis in array order; HD95 is then in
+    its units.  assd=True: triples (dice, hd95, assd) -- (1, 0, 0) and (0, 0, 0) in the two degenerate branches."""
     pred, gt = np.asarray(pred).copy(), np.asarray(gt).copy()
     pred[pred > 0] = 1
     gt[gt > 0] = 1
     if pred.sum() > 0 and gt.sum() > 0:
-        return dice_coefficient(pred, gt), hd95(pred, gt)
+        if not assd:
+            return dice_coefficient(pred, gt), hd95(pred, gt, voxelspacing)
+        return (dice_coefficient(pred, gt),) + _hd95_assd(_surface_distances(pred, gt, voxelspacing), _surface_distances(gt, pred, voxelspacing))
     elif pred.sum() > 0 and gt.sum() == 0:
-        return 1, 0
-    return 0, 0
+        return (1, 0, 0) if assd else (1, 0)
+    return (0, 0, 0) if assd else (0, 0)
 
 
 def _hist_percentile(hist, q=95.0):
@@ -130,6 +150,31 @@ def metrics_from_counts_hist(counts, hist):
     return out
 
 
+def metrics_from_surface_lists(counts, nq, dist2, assd=False):
+    """[(dice, hd95)] or, with assd, [(dice, hd95, assd)] for classes 1 .. ncls-1 from what ops.surface_distances returns, as
+    numpy arrays: counts [ncls, 4], nq [ncls, 2] and the first nq.sum() entries of dist2 with every segment sorted ascending
+    (the order makes the sums, and so the result, the same on every run).  One square root of the whole list, then per class the
+    host path's own arithmetic on the two directed lists (_hd95_assd) and the three branches of calculate_metric_percase."""
+    counts, nq = np.asarray(counts), np.asarray(nq)
+    dist2, total = np.asarray(dist2, np.float64), int(nq.sum())
+    if dist2.shape[0] < total:
+        raise ValueError(f"metrics_from_surface_lists: {dist2.shape[0]} distances for nq.sum() = {total}")
+    d = np.sqrt(dist2[:total])
+    starts = np.concatenate(([0], np.cumsum(nq.ravel())))
+    out = []
+    for c in range(1, counts.shape[0]):
+        npred, ngt, inter = int(counts[c, 0]), int(counts[c, 1]), int(counts[c, 2])
+        if npred > 0 and ngt > 0:
+            a, b = d[starts[2 * c]:starts[2 * c + 1]], d[starts[2 * c + 1]:starts[2 * c + 2]]
+            hd, asd = _hd95_assd(a, b)
+            out.append((2.0 * inter / float(npred + ngt), hd) + ((asd,) if assd else ()))
+        elif npred > 0:
+            out.append((1, 0, 0) if assd else (1, 0))
+        else:
+            out.append((0, 0, 0) if assd else (0, 0))
+    return out
+
+
 def _class_ids_u8(a, classes, what, device):
     """Integral class ids in [0, classes) of any dtype (numpy or tensor) -> uint8 tensor on `device`; ValueError otherwise."""
     if isinstance(a, torch.Tensor) and a.is_cuda:
@@ -149,16 +194,41 @@ def _class_ids_u8(a, classes, what, device):
     return torch.from_numpy(np.ascontiguousarray(t.astype(np.uint8))).to(device)
 
 
-def volume_metrics(pred, label, classes, device="cuda"):
+def _sorted_surface_lists(p8, l8, classes, spacing):
+    """ops.surface_distances, again with the exact capacity if the default was too small, every (class, direction) segment sorted
+    with torch.sort; (counts, nq, dist2[:nq.sum()]) as numpy arrays."""
+    counts, nq, dist2 = ops.surface_distances(p8, l8, classes, spacing)
+    nq_host = nq.cpu().numpy()
+    total = int(nq_host.sum())
+    if total > dist2.numel():
+        counts, nq, dist2 = ops.surface_distances(p8, l8, classes, spacing, cap=total)
+    start = 0
+    for n in nq_host.ravel().tolist():
+        if n > 1:
+            dist2[start:start + n] = torch.sort(dist2[start:start + n]).values
+        start += n
+    return counts.cpu().numpy(), nq_host, dist2[:total].cpu().numpy()
+
+
+def volume_metrics(pred, label, classes, device="cuda", voxelspacing=None, assd=False):
     """[(dice, hd95)] for classes 1 .. classes-1 of a (D, H, W) or (H, W) prediction / label pair -- what the loop of
     calculate_metric_percase(pred == i, label == i) returns -- from one ops.seg_metrics call.  pred / label: numpy arrays or
-    tensors of any dtype holding integral ids in [0, classes) (ValueError otherwise).  HIP device only."""
+    tensors of any dtype holding integral ids in [0, classes) (ValueError otherwise).  HIP device only.
+    voxelspacing (a number, or one entry per axis in array order: ops.voxel_spacing) and assd=True (triples with the average
+    symmetric surface distance) are calculate_metric_percase's.  With either, one ops.surface_distances call returns the list of
+    squared distances under the spacing (unit spacing for None) instead of the integer histogram; its segments are sorted on the
+    device, downloaded, and metrics_from_surface_lists finishes.  If the list's default capacity (ops.surface_cap) was too small
+    the call is repeated once with the exact size."""
     classes = int(classes)
     if not 2 <= classes <= 255:
         raise ValueError(f"volume_metrics: classes={classes} outside 2..255")
     if tuple(pred.shape) != tuple(label.shape):
         raise ValueError(f"volume_metrics: prediction {tuple(pred.shape)} and label {tuple(label.shape)} differ in shape")
+    if voxelspacing is not None or assd:
+        voxelspacing = ops.voxel_spacing(voxelspacing, len(pred.shape))
     p8, l8 = _class_ids_u8(pred, classes, "prediction", device), _class_ids_u8(label, classes, "label", device)
+    if voxelspacing is not None:
+        return metrics_from_surface_lists(*_sorted_surface_lists(p8, l8, classes, voxelspacing), assd=assd)
     counts, hist = ops.seg_metrics(p8, l8, classes)
     used = (hist != 0).any(dim=0).nonzero()
     last = int(used.max()) if used.numel() else 0                  # download only the bins in use
@@ -439,7 +509,7 @@ def predict_volume(image, net, patch_size=(224, 224), batch_slices=16, device="c
 
 def test_single_volume(image, label, net, classes, patch_size=[256, 256], test_save_path=None, case=None, z_spacing=1,
                        batch_slices=16, device="cuda", metrics="host", resize="host", class_indices=None, blur_sigma=None,
-                       components=None):
+                       components=None, voxelspacing=None, assd=False):
     """Per-class (dice, hd95) of one volume, classes 1..classes-1 (utils.py:61-102).  image / label: (1, D, H, W) tensors
     as the DataLoader yields them.  With test_save_path the volumes are written as .npz (SimpleITK, which the reference
     uses for .nii.gz, is not installed here).  metrics: "host" = the per-class scipy loop, "hip" = one volume_metrics call on
@@ -448,7 +518,10 @@ def test_single_volume(image, label, net, classes, patch_size=[256, 256], test_s
     channels (ValueError otherwise), the labels being that dataset's own ids 0..classes-1.  blur_sigma: predict_volume's; the
     saved .npz keeps the image as it was passed in.  components: predict_volume's component filter rule, checked against
     `classes` (ValueError for a class id >= classes); the prediction is filtered before it is scored -- on the device with
-    resize="hip", so with metrics="hip" it still never leaves it -- and the saved .npz holds the filtered prediction."""
+    resize="hip", so with metrics="hip" it still never leaves it -- and the saved .npz holds the filtered prediction.
+    voxelspacing, assd: calculate_metric_percase's / volume_metrics', for either value of `metrics`: the spacing of the volume's
+    axes (D, H, W) that HD95 (and ASSD) are measured in, and (dice, hd95, assd) triples.  A bad spacing raises ValueError before
+    the network runs.  z_spacing is unrelated: it only goes into the saved .npz."""
     if class_indices is not None and len(class_indices) != classes:
         raise ValueError(f"test_single_volume: class_indices has {len(class_indices)} entries for classes={classes}")
     if metrics not in ("host", "hip"):
@@ -458,15 +531,17 @@ def test_single_volume(image, label, net, classes, patch_size=[256, 256], test_s
     if components is not None:
         component_rule_tables(components, classes)
     image, label = image.squeeze(0).cpu().detach().numpy(), label.squeeze(0).cpu().detach().numpy()
+    if voxelspacing is not None:
+        voxelspacing = ops.voxel_spacing(voxelspacing, label.ndim)
     on_device = resize == "hip" and metrics == "hip"
     prediction = predict_volume(image, net, tuple(patch_size), batch_slices, device, resize=resize, return_device=on_device,
                                 class_indices=class_indices, blur_sigma=blur_sigma, components=components)
     if not on_device:
         prediction = prediction.astype(label.dtype)
     if metrics == "hip":
-        metric_list = volume_metrics(prediction, label, classes, device)
+        metric_list = volume_metrics(prediction, label, classes, device, voxelspacing=voxelspacing, assd=assd)
     else:
-        metric_list = [calculate_metric_percase(prediction == i, label == i) for i in range(1, classes)]
+        metric_list = [calculate_metric_percase(prediction == i, label == i, voxelspacing=voxelspacing, assd=assd) for i in range(1, classes)]
     if on_device and test_save_path is not None:
         prediction = prediction.cpu().numpy()
     if test_save_path is not None:
@@ -480,27 +555,36 @@ test_single_volume.__test__ = False     # not a pytest test (the name is the ref
 
 
 def evaluate_volumes(loader, net, classes, patch_size, metrics="hip", test_save_path=None, z_spacing=1, batch_slices=16,
-                     device="cuda", resize="host", class_indices=None, blur_sigma=None, components=None):
+                     device="cuda", resize="host", class_indices=None, blur_sigma=None, components=None, voxelspacing=None, assd=False):
     """The volume loop of the reference's inference() (test.py:155-164): test_single_volume per batch of `loader` (dicts with
     "image", "label" (1, D, H, W) and "case_name", batch size 1), the per-volume and final lines it logs.  Returns
     (per_volume, class_mean, mean_dice, mean_hd95): the metric list of every volume, the (classes-1, 2) table of per-class
-    means over the volumes, and that table's column means.  class_indices, blur_sigma, components: test_single_volume's."""
+    means over the volumes, and that table's column means.  class_indices, blur_sigma, components: test_single_volume's.
+    voxelspacing: test_single_volume's, one spacing for every volume or a dict case name -> spacing (KeyError naming a case it
+    lacks).  assd=True: the metric lists hold triples, class_mean is (classes-1, 3), the log lines gain mean_assd and the return
+    a fifth element, mean_assd."""
     per_volume = []
     for i_batch, batch in enumerate(loader):
         name = batch["case_name"]
         name = name if isinstance(name, str) else name[0]
+        spacing = voxelspacing
+        if isinstance(voxelspacing, dict):
+            if name not in voxelspacing:
+                raise KeyError(f"evaluate_volumes: voxelspacing has no entry for case {name!r}")
+            spacing = voxelspacing[name]
         metric_i = test_single_volume(batch["image"], batch["label"], net, classes=classes, patch_size=list(patch_size),
                                       test_save_path=test_save_path, case=name, z_spacing=z_spacing, batch_slices=batch_slices,
                                       device=device, metrics=metrics, resize=resize, class_indices=class_indices,
-                                      blur_sigma=blur_sigma, components=components)
+                                      blur_sigma=blur_sigma, components=components, voxelspacing=spacing, assd=assd)
         per_volume.append(metric_i)
         m = np.mean(metric_i, axis=0)
-        logging.info('idx %d case %s mean_dice %f mean_hd95 %f' % (i_batch, name, m[0], m[1]))
+        logging.info('idx %d case %s mean_dice %f mean_hd95 %f' % (i_batch, name, m[0], m[1]) + (' mean_assd %f' % m[2] if assd else ''))
     if not per_volume:
         raise ValueError("evaluate_volumes: the loader yielded no volume")
     class_mean = sum(np.array(m, dtype=np.float64) for m in per_volume) / len(per_volume)
     for i in range(1, classes):
-        logging.info('Mean class %d mean_dice %f mean_hd95 %f' % (i, class_mean[i - 1][0], class_mean[i - 1][1]))
-    mean_dice, mean_hd95 = (float(v) for v in np.mean(class_mean, axis=0))
-    logging.info('Testing performance in best val model: mean_dice : %f mean_hd95 : %f' % (mean_dice, mean_hd95))
-    return per_volume, class_mean, mean_dice, mean_hd95
+        logging.info('Mean class %d mean_dice %f mean_hd95 %f' % (i, class_mean[i - 1][0], class_mean[i - 1][1])
+                     + (' mean_assd %f' % class_mean[i - 1][2] if assd else ''))
+    means = tuple(float(v) for v in np.mean(class_mean, axis=0))
+    logging.info('Testing performance in best val model: mean_dice : %f mean_hd95 : %f' % means[:2] + (' mean_assd : %f' % means[2] if assd else ''))
+    return (per_volume, class_mean) + means

@@ -30,7 +30,8 @@ extern "C" {
  * cswin_attn_fwd writes y0, cswin_attn_bwd reads it).  cswin_abi_version() returns the value the library was built with: a consumer
  * compiled against another header must refuse to call it.  Entry points that are only ADDED (cswin_seg_metrics*, cswin_resize_banded, cswin_argmax_zoom_back, cswin_augment_*,
  * cswin_chunk_sumsq, cswin_norm_finalize, cswin_adamw_flat, cswin_tpgm_*, cswin_argmax_zoom_back_classes, cswin_class_counts, cswin_gaussian_blur, cswin_eb_tiles,
- * cswin_eb_finalize, cswin_rate_finalize, cswin_adam_flat, cswin_components_*, cswin_drop_path_order, cswin_linear_*_skip) do not bump it: every prototype an older consumer binds is unchanged. */
+ * cswin_eb_finalize, cswin_rate_finalize, cswin_adam_flat, cswin_components_*, cswin_drop_path_order, cswin_linear_*_skip,
+ * cswin_surface_dist*) do not bump it: every prototype an older consumer binds is unchanged. */
 #define CSWIN_ABI_VERSION 4
 
 #define CSWIN_OK 0
@@ -485,6 +486,26 @@ int    cswin_seg_metrics_nbins(int D, int H, int W);
 size_t cswin_seg_metrics_workspace(int D, int H, int W, int ndim, int ncls);
 int    cswin_seg_metrics(const unsigned char* pred, const unsigned char* label, long long* counts, unsigned int* hist,
                          void* workspace, size_t ws_bytes, int D, int H, int W, int ndim, int ncls, void* stream);
+
+/* ---- evaluation: surface distances under a voxel spacing, for HD95 and ASSD in physical units (csrc/metrics.hip;
+ *      medpy.metric.binary hd95 / assd with voxelspacing, connectivity 1) ----
+ * Same volumes, shape rules and counts[ncls][4] as cswin_seg_metrics.  (sz, sy, sx) > 0, finite: the spacing along D, H, W
+ * (scipy's `sampling` in array order); sz is ignored for ndim = 2.  The distance of a border voxel of one volume is the minimum
+ * over the border voxels of the other of (dz sz)^2 + (dy sy)^2 + (dx sx)^2 in float64, the expression
+ * scipy.ndimage.distance_transform_edt(sampling=...) evaluates: exact whenever the products and sums are representable (dyadic
+ * spacings), otherwise within an ulp or two of it (a separable minimisation may pick a candidate that is an ulp worse).
+ * nq[ncls][2] (64-bit): nq[c][0] = |dP_c|, nq[c][1] = |dG_c| for a class c >= 1 with voxels on both sides, else 0.
+ * dist2[cap] (float64): squared distances in segments ordered class 1 P->G, class 1 G->P, class 2 P->G, ...; segment (c, dir)
+ * starts at the exclusive prefix sum of nq and holds nq[c][dir] values in no particular order (sort it: its multiset is the same
+ * on every run).  A value whose slot would be >= cap is dropped and nothing is written outside dist2[0 .. cap): the caller sees
+ * an overflow as sum(nq) > cap and calls again with that capacity.  counts and nq are zeroed by the call; dist2 beyond sum(nq)
+ * is left as it was.  Integer atomics only, no host synchronisation.
+ * Errors: CSWIN_ERR_SHAPE for a bad shape, spacing, null pointer or cap < 0; CSWIN_ERR_WORKSPACE for a short workspace;
+ * CSWIN_ERR_ALIGN for a workspace off 16 B or counts / nq / dist2 off 8 B. */
+size_t cswin_surface_dist_workspace(int D, int H, int W, int ndim, int ncls);
+int    cswin_surface_dist(const unsigned char* pred, const unsigned char* label, long long* counts, long long* nq, double* dist2,
+                          long cap, void* workspace, size_t ws_bytes, int D, int H, int W, int ndim, int ncls, double sz, double sy,
+                          double sx, void* stream);
 
 /* ---- evaluation: connected components of a predicted label volume and the per-class size filter (csrc/components.hip) ----
  * vol: dense (D, H, W) uint8 class ids, N = D H W; ids 0 and >= ncls are background.  A component is a maximal set of voxels of

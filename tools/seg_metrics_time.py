@@ -5,6 +5,7 @@ host path and against inference, and record it in profiles/seg_metrics_timing.tx
     python tools/seg_metrics_time.py [--out FILE] [--repeats 10] [--kernel-stats DIR] [--skip-host]
     python tools/seg_metrics_time.py --one-call          # warm-up + ONE volume_metrics call, for a profiler run of its own:
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o out -- python tools/seg_metrics_time.py --one-call
+    python tools/seg_metrics_time.py --voxelspacing 2.5 0.73 0.73 [--out FILE] [--repeats 10] [--skip-host]
 
 The pair is a seeded nine-class 148 x 512 x 512 blob volume (Synapse-sized).  volume_metrics is timed with device events around
 the whole call (validation, upload, kernels, download of counts and the used histogram bins, float64 finish), which ends in a
@@ -12,7 +13,12 @@ synchronising download; median of --repeats after warm-up.  The host path is the
 classes 1..8, once (about two minutes).  predict_volume of a 148-slice 224 x 224 volume with the tiny network gives the scale
 of inference.  The two metric lists must agree (Dice exactly, HD95 within 1e-12: square roots of the same integers and one
 float64 interpolation on both sides) or the tool exits non-zero without writing.  Run it under `timeout`; every step ends in a
-synchronise and an exception ends the run, so nothing is enqueued after a failed step."""
+synchronise and an exception ends the run, so nothing is enqueued after a failed step.
+
+--voxelspacing times the spacing-aware path on the same pair instead (profiles/surface_metrics_timing.txt):
+volume_metrics(voxelspacing=..., assd=True) whole, ops.surface_distances alone, the finish alone (per-segment torch.sort,
+download, numpy), ops.seg_metrics of the same run for comparison, and once the host loop with voxelspacing, which it must agree
+with (Dice exactly, HD95 and ASSD within 1e-12)."""
 import argparse
 import csv
 import glob
@@ -79,19 +85,106 @@ def kernel_rows(stats_dir):
     return sorted(rows, key=lambda r: -r[2])
 
 
+def surface_main(a, pred, label):
+    from cswin_unet_amd import _lib, ops
+    from cswin_unet_amd.utils import _class_ids_u8, calculate_metric_percase, metrics_from_surface_lists, volume_metrics
+    sp, n = tuple(a.voxelspacing), max(a.repeats, 10)
+    hip = volume_metrics(pred, label, NCLS, voxelspacing=sp, assd=True)
+    vm = device_ms(lambda: volume_metrics(pred, label, NCLS, voxelspacing=sp, assd=True), n)
+    p8, l8 = torch.from_numpy(pred).cuda(), torch.from_numpy(label).cuda()
+    km = device_ms(lambda: ops.surface_distances(p8, l8, NCLS, sp), n)
+    sm = device_ms(lambda: ops.seg_metrics(p8, l8, NCLS), n)
+    counts, nq, dist2 = ops.surface_distances(p8, l8, NCLS, sp)
+    nq_host = nq.cpu().numpy()
+    total = int(nq_host.sum())
+    assert total <= dist2.numel(), "the default capacity overflowed"
+
+    def finish():
+        d = dist2.clone()
+        start = 0
+        for k in nq_host.ravel().tolist():
+            if k > 1:
+                d[start:start + k] = torch.sort(d[start:start + k]).values
+            start += k
+        return metrics_from_surface_lists(counts.cpu().numpy(), nq_host, d[:total].cpu().numpy(), assd=True)
+
+    fm = device_ms(finish, n)
+
+    phases = {}
+
+    def lap(name, t0):
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        phases.setdefault(name, []).append((t1 - t0) * 1e3)
+        return t1
+
+    for _ in range(n + 2):                                            # volume_metrics' own steps, each ended by a synchronise
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        q8, m8 = _class_ids_u8(pred, NCLS, "prediction", "cuda"), _class_ids_u8(label, NCLS, "label", "cuda")
+        t = lap("range check on the host + upload of both volumes", t)
+        lists = ops.surface_distances(q8, m8, NCLS, sp)
+        t = lap("ops.surface_distances", t)
+        finish()
+        t = lap("sort + download + numpy finish", t)
+        del lists
+    phase_lines = [f"  {k}: {statistics.median(v[2:]):.2f} ms" for k, v in phases.items()]
+    ws = _lib.lib().cswin_surface_dist_workspace(*SHAPE, 3, NCLS)
+    print(f"volume_metrics(voxelspacing) {vm[0]:.2f} ms, ops.surface_distances {km[0]:.2f} ms, finish {fm[0]:.2f} ms, ops.seg_metrics {sm[0]:.2f} ms",
+          flush=True)
+    if a.skip_host:
+        print("--skip-host: no agreement check, nothing written")
+        return 0
+    t0 = time.perf_counter()
+    host = [calculate_metric_percase(pred == i, label == i, voxelspacing=sp, assd=True) for i in range(1, NCLS)]
+    host_s = time.perf_counter() - t0
+    ok = len(hip) == len(host) and all(g[0] == h[0] and all(abs(x - y) <= 1e-12 + 1e-12 * abs(y) for x, y in zip(g[1:], h[1:]))
+                                       for g, h in zip(hip, host))
+    lines = [f"surface metrics timing: seeded (seed {SEED}) {NCLS}-class blob pair {SHAPE[0]} x {SHAPE[1]} x {SHAPE[2]}, voxel spacing {sp}, "
+             f"{torch.cuda.get_device_name(0)}",
+             f"agreement hip vs host (Dice exact, HD95 and ASSD within 1e-12): {'PASS' if ok else 'FAIL'}"]
+    lines += [f"  class {c}: hip dice {g[0]:.17g} hd95 {g[1]:.17g} assd {g[2]:.17g} | host dice {h[0]:.17g} hd95 {h[1]:.17g} assd {h[2]:.17g}"
+              for c, (g, h) in enumerate(zip(hip, host), 1)]
+    lines += [f"host path (calculate_metric_percase(voxelspacing=, assd=True) over classes 1..{NCLS - 1}, one repeat): {host_s:.1f} s",
+              f"utils.volume_metrics(voxelspacing=, assd=True) (validate + upload + kernels + sort + download + float64 finish), device events, "
+              f"median of {n}: {vm[0]:.2f} ms (min {vm[1]:.2f}, max {vm[2]:.2f})",
+              f"ops.surface_distances alone (device-resident uint8 inputs, kernels only), median of {n}: {km[0]:.2f} ms (min {km[1]:.2f}, max {km[2]:.2f})",
+              f"finish alone (copy of the list, {int((nq_host > 1).sum())} torch.sort calls, download, numpy sqrt / percentile / means), "
+              f"median of {n}: {fm[0]:.2f} ms (min {fm[1]:.2f}, max {fm[2]:.2f}) = {fm[0] / vm[0]:.2f} of volume_metrics",
+              f"ops.seg_metrics alone (unit spacing, histogram path), same run, median of {n}: {sm[0]:.2f} ms (min {sm[1]:.2f}, max {sm[2]:.2f})",
+              f"wall clock of volume_metrics' steps, each ended by a synchronise, median of {n}:", *phase_lines,
+              f"surface distances in the list: {total} (default capacity {dist2.numel()}, {pred.size} voxels)",
+              f"workspace: {ws} bytes ({ws / 2 ** 20:.1f} MiB)",
+              f"speed-up volume_metrics vs host: {host_s * 1e3 / vm[0]:.0f}x"]
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if not ok:
+        print("FAILED: disagreement; nothing written")
+        return 1
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    open(a.out, "w").write(text)
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "seg_metrics_timing.txt"))
+    ap.add_argument("--out", default=None, help="default: profiles/seg_metrics_timing.txt, with --voxelspacing profiles/surface_metrics_timing.txt")
     ap.add_argument("--repeats", type=int, default=10)
     ap.add_argument("--kernel-stats", default=None, help="output directory of a separate rocprofv3 --kernel-trace --stats run of --one-call")
     ap.add_argument("--skip-host", action="store_true", help="no host timing and no agreement check: nothing is written")
     ap.add_argument("--one-call", action="store_true")
+    ap.add_argument("--voxelspacing", type=float, nargs=3, default=None, metavar=("SZ", "SY", "SX"),
+                    help="time the spacing-aware path (ops.surface_distances) under this spacing instead")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "surface_metrics_timing.txt" if a.voxelspacing else "seg_metrics_timing.txt")
 
     from cswin_unet_amd import _lib, ops
     from cswin_unet_amd.utils import calculate_metric_percase, predict_volume, volume_metrics
     assert torch.cuda.is_available() and _lib.lib().cswin_device_ok() == 1, "needs a gfx950 HIP device"
     pred, label = blob_pair(SHAPE, NCLS, SEED)
+    if a.voxelspacing:
+        return surface_main(a, pred, label)
 
     if a.one_call:
         volume_metrics(pred, label, NCLS)
