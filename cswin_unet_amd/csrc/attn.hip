@@ -22,19 +22,25 @@
 //                               workgroups per CU); S tiles formed while the dO / y0 / v loads are in flight; reduction-free LePE
 //                               weight gradient; one fused dP / dV / dK loop
 //   attn_delta / attn_bwd_kv / attn_bwd_q / lepe_wgrad   N > 112: two passes, 64 x 64 at a time
-// Forward: attn_fwd3_kernel (N <= 128; optional query split over two workgroups), attn_fwd_kernel for larger windows.
+// Forward: attn_fwd3_kernel (N <= 112; optional query split over two workgroups), attn_fwd_kernel for larger windows.
+// Which kernel, instantiation, grid and LDS size a call gets, and the layout of the backward's workspace, are decided in
+// attn_plan.h (host only); the host section at the end of this file launches what that header returns.
 // (Persistent workgroups with cross-unit register prefetch were built and measured in round 3: 7-8 % slower at stages 1-2, equal at
 // stages 3-4; the non-matrix phases need the resident waves that the prefetch registers cost -- profiles/round3_notes.md.)
 // Head dims 8 / 16 / 24 / 32 share the kernels (tiles zero-padded to HD = 32).
 #include "common.h"
+#include "attn_plan.h"
 #include <stdlib.h>
 #include <mutex>
 #include <type_traits>
+#include <utility>
 
 namespace {
 
-constexpr int HD = 32;          // head dim (64/2 = 128/4 = 256/8 = 512/16)
-constexpr int LDT = HD + 4;     // LDS row stride of the [token][d] images
+using ap::HD;                   // head dim the tiles are padded to
+using ap::LDT;                  // LDS row stride of the [token][d] images
+using ap::LW_SUB;               // two-pass backward: slab rows per window
+using ap::LEPE_FLOATS;          // [10][HD]: 9 LePE taps + bias
 
 struct AttnBranch {
     int c0;          // first channel of this branch inside C
@@ -67,7 +73,7 @@ struct AttnParams {
     const unsigned long long* drop_epoch;   // device-resident step counter added to drop_seed (NULL: none)
     int nbranch;
     int ds_stride;         // fused backward: LDS row stride of the dS image (>= N, = 4 mod 8: conflict-free column writes)
-    int slab_rows;         // LePE gradient slab rows per window (1 on every current path)
+    int slab_rows;         // LePE gradient slab rows per window (1 in the fused backward, LW_SUB on the two-pass path)
     int vs_floats;         // fused backward: floats of the V / dS region (see attn_bwd3_kernel)
     long long* stamps;     // debug (cswin_debug_set_attn_stamps): [workgroup][8] s_memtime stamps of wave 0, or NULL
     int qkv_bf16;          // storage mode: bit 0 = qkv and dqkv, bit 1 = y are STORED as bf16 (bf16 activation storage; 0, 1 or 3);
@@ -328,18 +334,18 @@ __device__ __forceinline__ void lepe_wgrad_taps(const AttnBranch& br, const floa
 // issues the loads with the other loads of the unit, lepe_store2 writes the patch when the images are staged
 template <int T>
 __device__ __forceinline__ void lepe_fetch2(const AttnParams& p, const AttnBranch& br, int ch0, int tid, float& wl0, float& wl1) {
-    static_assert(10 * HD <= 2 * T, "LePE taps: at most two per thread");
+    static_assert(LEPE_FLOATS <= 2 * T, "LePE taps: at most two per thread");
     auto value = [&](int i) {
         const int tap = i / HD, ch = i - tap * HD, cb = ch0 - br.c0 + ch;
-        return (i >= 10 * HD || ch >= p.hd) ? 0.f : (tap < 9 ? br.lepe_w[cb * 9 + tap] : br.lepe_b[cb]);
+        return (i >= LEPE_FLOATS || ch >= p.hd) ? 0.f : (tap < 9 ? br.lepe_w[cb * 9 + tap] : br.lepe_b[cb]);
     };
     wl0 = value(tid);
     wl1 = value(tid + T);
 }
 template <int T>
 __device__ __forceinline__ void lepe_store2(float* Wl, int tid, float wl0, float wl1) {
-    if (tid < 10 * HD) Wl[tid] = wl0;
-    if (tid + T < 10 * HD) Wl[tid + T] = wl1;
+    if (tid < LEPE_FLOATS) Wl[tid] = wl0;
+    if (tid + T < LEPE_FLOATS) Wl[tid + T] = wl1;
 }
 
 // =====================================================================================
@@ -384,11 +390,12 @@ __device__ __forceinline__ void softmax_tiles(f32x4 (&s)[NT], const float* Ks, i
 // 384 units on 256 CUs half the CUs would otherwise carry two whole units and set the kernel time; 768 half-units are
 // three per CU.  The two halves are `units` apart in the grid, i.e. on the same XCD / L2 when units % 8 == 0.
 template <int NT, int QS, int ST>
-__global__ __launch_bounds__(64 * (QS == 2 ? (NT + 1) / 2 : (NT < 8 ? NT : 8))) void attn_fwd_kernel(AttnParams p, int units) {
+__global__ __launch_bounds__(64 * ap::fwd_waves(NT, QS)) void attn_fwd_kernel(AttnParams p, int units) {
     constexpr bool Q16 = (ST & 1) != 0, Y16 = (ST & 2) != 0, M16 = (ST & 4) != 0;      // storage of qkv / dqkv and of y, bf16 MFMAs (see AttnParams)
     (void)Q16; (void)Y16; (void)M16;
     constexpr int NP = 16 * NT;
-    constexpr int NW = QS == 2 ? (NT + 1) / 2 : (NT < 8 ? NT : 8);
+    constexpr int NW = ap::fwd_waves(NT, QS);
+    static_assert(ap::fwd_family(NT) == ap::Family::fwd, "windows of more tiles than the one-wave-per-tile kernels take");
     static_assert(QS == 1 || NT <= 18, "query split: one query tile per wave, at most 9 waves");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Ks = smem;                  // [NP][LDT]
@@ -432,7 +439,7 @@ __global__ __launch_bounds__(64 * (QS == 2 ? (NT + 1) / 2 : (NT < 8 ? NT : 8))) 
         *reinterpret_cast<f32x4*>(&Ks[row * LDT + 4 * c4]) = qcv(kv);
         *reinterpret_cast<f32x4*>(&Vs[row * LDT + 4 * c4]) = qcv(vv);
     }
-    for (int i = tid; i < 10 * HD; i += 64 * NW) {
+    for (int i = tid; i < LEPE_FLOATS; i += 64 * NW) {
         const int tap = i / HD, ch = i - tap * HD;
         const int cb = ch0 - br.c0 + ch;        // channel inside the branch
         Wl[i] = ch >= p.hd ? 0.f : (tap < 9 ? br.lepe_w[cb * 9 + tap] : br.lepe_b[cb]);
@@ -514,12 +521,12 @@ __global__ __launch_bounds__(64 * (QS == 2 ? (NT + 1) / 2 : (NT < 8 ? NT : 8))) 
 __device__ __forceinline__ void lds_barrier() { __syncthreads(); }
 
 template <int NT, int QS, int ST>
-__global__ __launch_bounds__(64 * (QS == 2 ? (NT + 1) / 2 : NT), 4) void attn_fwd3_kernel(AttnParams p, int units) {
+__global__ __launch_bounds__(64 * ap::fwd_waves(NT, QS), 4) void attn_fwd3_kernel(AttnParams p, int units) {
     constexpr bool Q16 = (ST & 1) != 0, Y16 = (ST & 2) != 0, M16 = (ST & 4) != 0;
     (void)Q16; (void)Y16; (void)M16;
-    static_assert(NT <= 8, "one query tile per wave");
+    static_assert(ap::fwd_family(NT) == ap::Family::fwd3, "one query tile per wave");
     constexpr int NP = 16 * NT;
-    constexpr int NW = QS == 2 ? (NT + 1) / 2 : NT;
+    constexpr int NW = ap::fwd_waves(NT, QS);
     constexpr int T = 64 * NW;
     constexpr int NLD = (NP * 8 + T - 1) / T;          // 16-B row chunks of K (and of V) staged per thread
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -721,7 +728,7 @@ __global__ __launch_bounds__(64 * NT, 4) void attn_bwd3_kernel(AttnParams p) {
     float* lse_s = VS + p.vs_floats;
     float* del_s = lse_s + NP;
     float* Wl = del_s + NP;                 // [10][HD]
-    float* Gl = Wl + 10 * HD;               // [9 + NT][HD]: LePE weight gradient of this unit (taps by the waves that own them), per-wave bias gradients
+    float* Gl = Wl + LEPE_FLOATS;           // [9 + NT][HD] = ap::bwd3_grad_floats(NT): LePE weight gradient of this unit (taps by the waves that own them), per-wave bias gradients
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, kq = lane >> 4;
@@ -948,7 +955,7 @@ __global__ __launch_bounds__(64 * NT, 4) void attn_bwd3_kernel(AttnParams p) {
             const int cb = br.heads * p.hd;
             float* row = br.dw_part + ((long)w.b * br.nWin + w.win) * p.slab_rows * (cb * 10);
 #pragma unroll
-            for (int i = tid; i < 10 * HD; i += T) {
+            for (int i = tid; i < LEPE_FLOATS; i += T) {
                 if (i < 9 * p.hd) {
                     const int d = i / 9, tap = i - 9 * d;
                     row[w.g * p.hd * 9 + i] = Gl[tap * HD + d];
@@ -1331,7 +1338,6 @@ __global__ __launch_bounds__(256) void attn_bwd_q_kernel(AttnParams p, int nblk)
 // of the slice, so nothing is reduced across lanes; the two halves meet in LDS.  v is re-read nine times by its own window
 // only (L1 / L2 resident).  (The first version -- one thread per (token slot, channel), scalar loads -- took 69 us per launch
 // at 384 x 384, 8 % of that step.)
-constexpr int LW_SUB = 4;
 template <int ST>
 __global__ __launch_bounds__(256) void lepe_wgrad_kernel(AttnParams p) {
     constexpr bool Q16 = (ST & 1) != 0, Y16 = (ST & 2) != 0, M16 = (ST & 4) != 0;      // storage of qkv / dqkv and of y, bf16 MFMAs (see AttnParams)
@@ -1442,129 +1448,102 @@ int reserve_dynamic_lds(size_t bytes, const char* who) {
     return CSWIN_OK;
 }
 
-int fill_params(AttnParams& p, const char* who, int B, int reso, int C, int nbranch, const int* heads,
-                const int* idx, int split, float scale, int* ntile, int* nwg) {
-    CSWIN_REQUIRE(B > 0 && reso > 0 && C > 0 && (nbranch == 1 || nbranch == 2), CSWIN_ERR_SHAPE, "%s: bad arguments", who);
-    const int Cb = C / nbranch;
-    int heads_total = 0, wg = 0, N0 = -1;
+// The geometry of a call (ap::geometry) into AttnParams, with the magic words of the kernels' divisions; a refusal in the entry
+// point's words.
+int fill_params(AttnParams& p, ap::Geometry& g, const char* who, int B, int reso, int C, int nbranch, const int* heads,
+                const int* idx, int split, float scale) {
+    g = ap::geometry(B, reso, C, nbranch, heads, idx, split);
+    const ap::Branch& at = g.br[g.at];
+    switch (g.refusal) {
+        case ap::Refusal::none: break;
+        case ap::Refusal::head_dim:
+            cswin_set_error("%s: head dim %d unsupported (8, 16, 24 or 32, equal in both branches)", who, g.hd);
+            return CSWIN_ERR_UNSUPPORTED;
+        case ap::Refusal::error_mode: cswin_set_error("%s: ERROR MODE %d", who, idx[g.at]); return CSWIN_ERR_SHAPE;
+        case ap::Refusal::divisibility:
+            cswin_set_error("%s: resolution %d not divisible by window %dx%d", who, reso, at.H_sp, at.W_sp);
+            return CSWIN_ERR_SHAPE;
+        case ap::Refusal::index_range:
+            cswin_set_error("%s: %ld units of %d tokens exceed the index arithmetic's range", who, at.units, at.H_sp * at.W_sp);
+            return CSWIN_ERR_UNSUPPORTED;
+        case ap::Refusal::window_sizes: cswin_set_error("%s: branches with different window sizes", who); return CSWIN_ERR_SHAPE;
+        default: cswin_set_error("%s: bad arguments", who); return CSWIN_ERR_SHAPE;
+    }
     for (int i = 0; i < nbranch; ++i) {
-        const int hd = heads[i] > 0 ? Cb / heads[i] : 0;
-        CSWIN_REQUIRE(heads[i] > 0 && Cb == heads[i] * hd && hd >= 8 && hd <= HD && hd % 8 == 0 && (i == 0 || hd == p.hd),
-                      CSWIN_ERR_UNSUPPORTED, "%s: head dim %d unsupported (8, 16, 24 or 32, equal in both branches)", who, hd);
-        p.hd = hd;
-        int H_sp, W_sp;
-        if (idx[i] == -1) { H_sp = reso; W_sp = reso; }
-        else if (idx[i] == 0) { H_sp = reso; W_sp = split; }
-        else if (idx[i] == 1) { H_sp = split; W_sp = reso; }
-        else { cswin_set_error("%s: ERROR MODE %d", who, idx[i]); return CSWIN_ERR_SHAPE; }
-        CSWIN_REQUIRE(reso % H_sp == 0 && reso % W_sp == 0, CSWIN_ERR_SHAPE,
-                      "%s: resolution %d not divisible by window %dx%d", who, reso, H_sp, W_sp);
+        const ap::Branch& b = g.br[i];
         AttnBranch& br = p.br[i];
-        br.c0 = i * Cb;
-        br.heads = heads[i];
-        br.head0 = heads_total;
-        br.H_sp = H_sp; br.W_sp = W_sp;
-        br.nW = reso / W_sp;
-        br.nWin = (reso / H_sp) * (reso / W_sp);
-        br.wg_begin = wg;
-        br.m_heads = fdiv_magic(br.heads); br.m_nWin = fdiv_magic(br.nWin); br.m_nW = fdiv_magic(br.nW); br.m_Wsp = fdiv_magic(W_sp);
-        CSWIN_REQUIRE((long)B * br.nWin * heads[i] < (1 << 20) && H_sp * W_sp < (1 << 12) && br.nWin < (1 << 12) && heads[i] < (1 << 12),
-                      CSWIN_ERR_UNSUPPORTED, "%s: %ld units of %d tokens exceed the index arithmetic's range", who,
-                      (long)B * br.nWin * heads[i], H_sp * W_sp);
-        wg += B * br.nWin * heads[i];
-        heads_total += heads[i];
-        if (N0 < 0) N0 = H_sp * W_sp;
-        CSWIN_REQUIRE(N0 == H_sp * W_sp, CSWIN_ERR_SHAPE, "%s: branches with different window sizes", who);
+        br.c0 = b.c0; br.heads = b.heads; br.head0 = b.head0;
+        br.H_sp = b.H_sp; br.W_sp = b.W_sp; br.nW = b.nW; br.nWin = b.nWin;
+        br.wg_begin = b.wg_begin;
+        br.m_heads = fdiv_magic(b.heads); br.m_nWin = fdiv_magic(b.nWin); br.m_nW = fdiv_magic(b.nW); br.m_Wsp = fdiv_magic(b.W_sp);
     }
-    p.B = B; p.reso = reso; p.C = C; p.heads_total = heads_total; p.nbranch = nbranch;
+    p.B = B; p.reso = reso; p.C = C; p.heads_total = g.heads_total; p.nbranch = nbranch; p.hd = g.hd;
     p.scale = scale > 0.f ? scale : 1.0f / sqrtf((float)p.hd);
-    *ntile = (N0 + 15) / 16;
-    *nwg = wg;
     return CSWIN_OK;
 }
 
-template <int NT, int ST>
-int launch_fwd(const AttnParams& p, int nwg, hipStream_t st) {
-    constexpr int NW = NT < 8 ? NT : 8;
-    constexpr size_t lds = (size_t)(2 * 16 * NT * LDT + 10 * HD) * sizeof(float);
-    if constexpr (lds > 64 * 1024) {            // both query splits, whichever is launched first
-        if (int rc = reserve_dynamic_lds<attn_fwd_kernel<NT, 1, ST>>(lds, "attn_fwd")) return rc;
-        if (int rc = reserve_dynamic_lds<attn_fwd_kernel<NT, 2, ST>>(lds, "attn_fwd")) return rc;
-    }
-    {
-        // few units relative to the 256 CUs: split the query tiles over two workgroups per unit (see the kernel).  Large windows
-        // (NT > 8: 384 x 384 inputs, 128 units at batch 8) otherwise leave half the chip idle and give a wave 2 - 3 query tiles.
-        const int force = cswin_tuning().attn_fwd_qsplit;                                // tuning aid: 1 or 2
-        const bool split = force ? force == 2 : (NT <= 8 ? (nwg < 1024 && nwg % 256 != 0 && NT >= 6)   // measured: pays at N = 98, not at N = 49
-                                                         : nwg <= 256);
-        if (split) {
-            hipLaunchKernelGGL((attn_fwd_kernel<NT, 2, ST>), dim3(2 * nwg), dim3(64 * ((NT + 1) / 2)), lds, st, p, nwg);
-            return CSWIN_OK;
-        }
-    }
-    hipLaunchKernelGGL((attn_fwd_kernel<NT, 1, ST>), dim3(nwg), dim3(64 * NW), lds, st, p, nwg);
-    return CSWIN_OK;
+int no_instantiation(int NT) {
+    cswin_set_error("attn: no kernel instantiated for %d tiles", NT);
+    return CSWIN_ERR_UNSUPPORTED;
 }
 
-// forward for windows of up to 128 tokens: items = units, or 2 x units with the query tiles split over two workgroups
-template <int NT, int ST>
-int launch_fwd3(const AttnParams& p, int nwg, hipStream_t st) {
-    const size_t lds = (size_t)(2 * 16 * NT * LDT + 10 * HD) * sizeof(float);
-    static_assert((2 * 16 * NT * LDT + 10 * HD) * sizeof(float) <= 64 * 1024, "no dynamic-LDS opt-in on this path");
-    if constexpr (NT >= 6) {
-        // few units relative to the CUs (stage 3: 384 units of 7 query tiles): split the query tiles over two workgroups per unit
-        const int force = cswin_tuning().attn_fwd_qsplit;                            // tuning aid: 1 or 2
-        if (force ? force == 2 : (nwg < 1024 && nwg % 256 != 0)) {
-            hipLaunchKernelGGL((attn_fwd3_kernel<NT, 2, ST>), dim3(2 * nwg), dim3(64 * ((NT + 1) / 2)), lds, st, p, nwg);
-            return CSWIN_OK;
-        }
-    }
-    hipLaunchKernelGGL((attn_fwd3_kernel<NT, 1, ST>), dim3(nwg), dim3(64 * NT), lds, st, p, nwg);
-    return CSWIN_OK;
+// f(NT as a compile-time constant) for the tile class a plan names (one of ap::NT_CLASSES)
+template <class F, size_t... I>
+int with_nt(int NT, F f, std::index_sequence<I...>) {
+    int rc = 0;
+    const bool found = ((NT == ap::NT_CLASSES[I] && (rc = f(std::integral_constant<int, ap::NT_CLASSES[I]>{}), true)) || ...);
+    return found ? rc : no_instantiation(NT);
 }
+template <class F> int with_nt(int NT, F f) { return with_nt(NT, f, std::make_index_sequence<ap::N_CLASSES>{}); }
 
-inline int ds_stride_for(int N) {            // smallest stride >= N with stride = 4 (mod 8): 16-B aligned rows, and the four
-    int s = (N + 3) / 4 * 4;                 // row groups of a dS column write land in distinct banks
-    while (s % 8 != 4) s += 4;
-    return s;
-}
-
-inline int vs_floats_for(int NT, int N, int S) {     // V image [16 NT + 1][LDT] (last row zero), later dS [N][S] + 16 NT finite floats behind it
-    const int NP = 16 * NT;
-    const int a = N * S + NP, b = (NP + 1) * LDT;
-    return ((a > b ? a : b) + 3) / 4 * 4;
-}
-
-template <int NT, int ST>
-int launch_bwd3(AttnParams& p, int nwg, hipStream_t st) {
-    constexpr int NP = 16 * NT;
-    p.vs_floats = vs_floats_for(NT, p.br[0].H_sp * p.br[0].W_sp, p.ds_stride);
-    const size_t lds = (size_t)(2 * NP * LDT + p.vs_floats + 2 * NP + (19 + NT) * HD) * sizeof(float);
-    if (lds > 64 * 1024) {
-        // reserve the largest footprint this NT can ask for (N = 16 NT tokens)
-        constexpr int SMAX = ((NP + 3) / 4 * 4) + 8;
-        constexpr size_t lds_max = (size_t)(2 * NP * LDT + (NP * SMAX + NP + 4 > (NP + 1) * LDT ? NP * SMAX + NP + 4 : (NP + 1) * LDT) + 2 * NP + (19 + NT) * HD) * sizeof(float);
-        if (int rc = reserve_dynamic_lds<attn_bwd3_kernel<NT, ST>>(lds_max, "attn_bwd")) return rc;
-    }
-    hipLaunchKernelGGL((attn_bwd3_kernel<NT, ST>), dim3(nwg), dim3(64 * NT), lds, st, p);
-    return CSWIN_OK;
+// the forward instantiation of (NT, QS, mode): the family is NT's
+template <int NT, int QS, int ST> constexpr auto fwd_kernel() {
+    if constexpr (ap::fwd_family(NT) == ap::Family::fwd3) return &attn_fwd3_kernel<NT, QS, ST>;
+    else return &attn_fwd_kernel<NT, QS, ST>;
 }
 
 template <int ST>
-int launch_bwd_two_pass(const AttnParams& p, long items, int nwg, int nblk, hipStream_t st) {
-    hipLaunchKernelGGL(attn_delta_kernel<ST>, dim3((unsigned)((items * 8 + 255) / 256)), dim3(256), 0, st, p);
-    hipLaunchKernelGGL(attn_bwd_kv_kernel<ST>, dim3(nwg * nblk), dim3(256), 0, st, p, nblk);
-    hipLaunchKernelGGL(attn_bwd_q_kernel<ST>, dim3(nwg * nblk), dim3(256), 0, st, p, nblk);
-    hipLaunchKernelGGL(lepe_wgrad_kernel<ST>, dim3(nwg * LW_SUB), dim3(256), 0, st, p);
-    return CSWIN_OK;
+int launch_fwd(const ap::FwdPlan& f, const AttnParams& p, int units, hipStream_t st) {
+    return with_nt(f.NT, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        if constexpr (ap::fwd_opt_in(NT)) {                               // both query splits, whichever is launched first
+            if (int rc = reserve_dynamic_lds<fwd_kernel<NT, 1, ST>()>(ap::fwd_lds_bytes(NT), "attn_fwd")) return rc;
+            if (int rc = reserve_dynamic_lds<fwd_kernel<NT, 2, ST>()>(ap::fwd_lds_bytes(NT), "attn_fwd")) return rc;
+        }
+        if constexpr (ap::fwd_may_split(NT)) {
+            if (f.QS == 2) {
+                hipLaunchKernelGGL((fwd_kernel<NT, 2, ST>()), dim3(f.grid), dim3(f.threads), f.lds, st, p, units);
+                return (int)CSWIN_OK;
+            }
+        }
+        hipLaunchKernelGGL((fwd_kernel<NT, 1, ST>()), dim3(f.grid), dim3(f.threads), f.lds, st, p, units);
+        return (int)CSWIN_OK;
+    });
+}
+
+template <int ST>
+int launch_bwd(const ap::BwdPlan& b, const AttnParams& p, hipStream_t st) {
+    if (b.path == ap::BwdPath::two_pass) {
+        hipLaunchKernelGGL(attn_delta_kernel<ST>, dim3(b.grid[0]), dim3(b.threads), 0, st, p);
+        hipLaunchKernelGGL(attn_bwd_kv_kernel<ST>, dim3(b.grid[1]), dim3(b.threads), 0, st, p, b.nblk);
+        hipLaunchKernelGGL(attn_bwd_q_kernel<ST>, dim3(b.grid[2]), dim3(b.threads), 0, st, p, b.nblk);
+        hipLaunchKernelGGL(lepe_wgrad_kernel<ST>, dim3(b.grid[3]), dim3(b.threads), 0, st, p);
+        return CSWIN_OK;
+    }
+    return with_nt(b.NT, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        if constexpr (ap::fwd_family(NT) == ap::Family::fwd3) {           // the classes with one wave per tile
+            if (b.lds_reserved)
+                if (int rc = reserve_dynamic_lds<attn_bwd3_kernel<NT, ST>>(ap::bwd3_lds_bytes_max(NT), "attn_bwd")) return rc;
+            hipLaunchKernelGGL((attn_bwd3_kernel<NT, ST>), dim3(b.grid[0]), dim3(b.threads), b.lds, st, p);
+            return (int)CSWIN_OK;
+        } else {
+            return no_instantiation(NT);
+        }
+    });
 }
 
 long long* g_attn_stamps = nullptr;     // debug only (cswin_debug_set_attn_stamps)
-
-inline bool force_two_pass() {          // tuning aid: the large-window backward for every window size
-    const bool f = cswin_tuning().attn_bwd_two_pass != 0;
-    return f;
-}
 
 }  // namespace
 
@@ -1579,30 +1558,18 @@ int cswin_attn_fwd(const float* qkv, const float* const* lepe_w, const float* co
                    int B, int reso, int C, int nbranch, const int* heads, const int* idx, int split, float scale, float drop_p,
                    unsigned long long drop_seed, const unsigned long long* drop_epoch, int qkv_bf16, void* stream) {
     AttnParams p = {};
-    int nt, nwg;
+    ap::Geometry g;
     int rc = fill_mode_dropout(p, "attn_fwd", drop_p, drop_seed, drop_epoch, qkv_bf16);
-    if (!rc) rc = fill_params(p, "attn_fwd", B, reso, C, nbranch, heads, idx, split, scale, &nt, &nwg);
+    if (!rc) rc = fill_params(p, g, "attn_fwd", B, reso, C, nbranch, heads, idx, split, scale);
     if (rc) return rc;
     CSWIN_REQUIRE(qkv && y && lse && lepe_w && lepe_b, CSWIN_ERR_SHAPE, "attn_fwd: null pointer");
+    const ap::FwdPlan f = ap::fwd_plan(cswin_tuning(), g);
+    CSWIN_REQUIRE(f.refusal == ap::Refusal::none, CSWIN_ERR_UNSUPPORTED, "attn_fwd: window of %d tokens unsupported", g.N);
     for (int i = 0; i < nbranch; ++i) { p.br[i].lepe_w = lepe_w[i]; p.br[i].lepe_b = lepe_b[i]; }
     p.qkv = qkv; p.y = y; p.y0 = y0; p.lse = lse;
     p.stamps = g_attn_stamps;
     hipStream_t st = (hipStream_t)stream;
-    rc = with_mode(p.qkv_bf16, [&](auto mode) {
-        constexpr int ST = decltype(mode)::value;
-        switch (nt) {
-            case 1: case 2: case 3: case 4: return launch_fwd3<4, ST>(p, nwg, st);
-            case 5: case 6: return launch_fwd3<6, ST>(p, nwg, st);
-            case 7: return launch_fwd3<7, ST>(p, nwg, st);
-            case 8: case 9: return launch_fwd<9, ST>(p, nwg, st);
-            case 10: case 11: case 12: return launch_fwd<12, ST>(p, nwg, st);
-            case 13: case 14: case 15: return launch_fwd<15, ST>(p, nwg, st);
-            case 16: case 17: case 18: return launch_fwd<18, ST>(p, nwg, st);
-            default:
-                cswin_set_error("attn_fwd: window of %d tokens unsupported", p.br[0].H_sp * p.br[0].W_sp);
-                return (int)CSWIN_ERR_UNSUPPORTED;
-        }
-    });
+    rc = with_mode(p.qkv_bf16, [&](auto mode) { return launch_fwd<decltype(mode)::value>(f, p, g.nwg, st); });
     if (rc) return rc;
     CSWIN_LAUNCH_CHECK();
     return CSWIN_OK;
@@ -1610,12 +1577,9 @@ int cswin_attn_fwd(const float* qkv, const float* const* lepe_w, const float* co
 
 size_t cswin_attn_bwd_workspace(int B, int reso, int C, int nbranch, const int* heads, const int* idx, int split) {
     AttnParams p = {};
-    int nt, nwg;
-    if (fill_params(p, "attn_bwd_workspace", B, reso, C, nbranch, heads, idx, split, 0.f, &nt, &nwg)) return 0;
-    // LePE partial slabs (LW_SUB rows per window on the two-pass path) + delta (B, heads, L) (used by the two-pass path)
-    size_t n = (size_t)nwg * 10 * HD * ((nt > 7 || force_two_pass()) ? LW_SUB : 1);
-    n += (size_t)B * p.heads_total * reso * reso;
-    return n * sizeof(float);
+    ap::Geometry g;
+    if (fill_params(p, g, "attn_bwd_workspace", B, reso, C, nbranch, heads, idx, split, 0.f)) return 0;
+    return ap::bwd_plan(cswin_tuning(), g, B, reso, nbranch).ws_bytes;
 }
 
 // dqkv (B, L, 3C) is fully overwritten; dlepe_w[i] (Cb,9) and dlepe_b[i] (Cb) are overwritten.
@@ -1625,39 +1589,28 @@ int cswin_attn_bwd(const float* qkv, const float* const* lepe_w, const float* co
                    int split, float scale, cswin_reduce_job* deferred, float drop_p, unsigned long long drop_seed,
                    const unsigned long long* drop_epoch, int qkv_bf16, void* stream) {
     AttnParams p = {};
-    int nt, nwg;
+    ap::Geometry g;
     int rc = fill_mode_dropout(p, "attn_bwd", drop_p, drop_seed, drop_epoch, qkv_bf16);
-    if (!rc) rc = fill_params(p, "attn_bwd", B, reso, C, nbranch, heads, idx, split, scale, &nt, &nwg);
+    if (!rc) rc = fill_params(p, g, "attn_bwd", B, reso, C, nbranch, heads, idx, split, scale);
     if (rc) return rc;
+    const ap::BwdPlan b = ap::bwd_plan(cswin_tuning(), g, B, reso, nbranch);
     CSWIN_REQUIRE(qkv && lse && dy && dqkv && lepe_w && dlepe_w && dlepe_b, CSWIN_ERR_SHAPE, "attn_bwd: null pointer");
-    CSWIN_REQUIRE(workspace && ws_bytes >= cswin_attn_bwd_workspace(B, reso, C, nbranch, heads, idx, split), CSWIN_ERR_WORKSPACE, "attn_bwd: workspace too small");
+    CSWIN_REQUIRE(workspace && ws_bytes >= b.ws_bytes, CSWIN_ERR_WORKSPACE, "attn_bwd: workspace too small");
     CSWIN_REQUIRE(y0 && lepe_b, CSWIN_ERR_SHAPE, "attn_bwd: y0 (the forward's output without the LePE term) and lepe_b are required");
-    const bool two_pass = nt > 7 || force_two_pass();
-    p.slab_rows = two_pass ? LW_SUB : 1;
-    p.ds_stride = ds_stride_for(p.br[0].H_sp * p.br[0].W_sp);
+    p.slab_rows = b.slab_rows;
+    p.ds_stride = b.ds_stride;
+    p.vs_floats = b.vs_floats;
     for (int i = 0; i < nbranch; ++i) {
         p.br[i].lepe_w = lepe_w[i];
         p.br[i].lepe_b = lepe_b[i];
-        p.br[i].dw_part = (float*)workspace + (size_t)p.br[i].wg_begin * 10 * HD * p.slab_rows;
+        p.br[i].dw_part = (float*)workspace + b.slab_off[i];
     }
     p.stamps = g_attn_stamps;
     p.y_in = y0;
-    p.delta = (float*)workspace + (size_t)nwg * 10 * HD * p.slab_rows;
+    p.delta = (float*)workspace + b.delta_off;
     p.qkv = qkv; p.lse = const_cast<float*>(lse); p.dy = dy; p.dqkv = dqkv;
     hipStream_t st = (hipStream_t)stream;
-    rc = with_mode(p.qkv_bf16, [&](auto mode) {
-        constexpr int ST = decltype(mode)::value;
-        if (two_pass) {
-            // windows of more than 112 tokens (384x384: N = 144, 288): two-pass path
-            const int N = p.br[0].H_sp * p.br[0].W_sp, nblk = (N + 63) / 64;
-            return launch_bwd_two_pass<ST>(p, (long)B * p.heads_total * reso * reso, nwg, nblk, st);
-        }
-        switch (nt) {
-            case 1: case 2: case 3: case 4: return launch_bwd3<4, ST>(p, nwg, st);
-            case 5: case 6: return launch_bwd3<6, ST>(p, nwg, st);
-            default: return launch_bwd3<7, ST>(p, nwg, st);
-        }
-    });
+    rc = with_mode(p.qkv_bf16, [&](auto mode) { return launch_bwd<decltype(mode)::value>(b, p, st); });
     if (rc) return rc;
     CSWIN_LAUNCH_CHECK();
     // the slabs of each branch are a standard reduction job: rows = B * nWin, columns = [Cb * 9 | Cb]; handed to the caller, or

@@ -99,10 +99,11 @@ def attn_ref(qkv, lepe_w, lepe_b, reso, split, idx, heads, scale=None, mask=None
 # ------------------------------------------------------------------------------------------------
 # launch plan
 # ------------------------------------------------------------------------------------------------
-# A transcription of the host rules of cswin_unet_amd/csrc/attn.hip and it MUST FOLLOW THEM: fill_params (window shape, units,
-# *ntile = (N + 15) / 16), the `switch (nt)` of cswin_attn_fwd and of cswin_attn_bwd (two_pass = nt > 7, nblk = (N + 63) / 64),
-# the split rule of launch_fwd3_q (NT >= 6: nwg < 1024 && nwg % 256 != 0) and that of launch_fwd_q (NT > 8: nwg <= 256), with
-# neither tuning variable set.  `thin` is the kernels' own br.H_sp == 1 || br.W_sp == 1.
+# A transcription of the launch rules of cswin_unet_amd/csrc/attn_plan.h, the header attn.hip launches from: ap::geometry (window
+# shape, units, nt = ceil(N / 16)), ap::nt_class (the instantiated tile classes), ap::fwd_plan (the family and the query split:
+# one wave per tile and NT >= 6: nwg < 1024 && nwg % 256 != 0; larger windows: nwg <= 256) and ap::bwd_plan (two_pass = nt > 7,
+# nblk = ceil(N / 64)), with neither tuning variable set.  `thin` is the kernels' own br.H_sp == 1 || br.W_sp == 1.
+# tests/test_attn_plan_host.py (no GPU) holds it to the header, field by field, through tools/attn_plan_check.cpp.
 def attn_plan(B, reso, split, idx, C, heads):
     nwg, N, thin = 0, None, False
     for i, h in zip(idx, heads):
