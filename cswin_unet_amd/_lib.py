@@ -101,6 +101,8 @@ SIGNATURES = {
     "cswin_augment_gather": (I, [P, P, P, I, I, I, I, I, I, P]),
     "cswin_augment_labels": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
     "cswin_gaussian_blur": (I, [P, P, P, I, I, I, I, P]),
+    "cswin_view_batch": (I, [P, P, P, I, I, I, I, P]),
+    "cswin_tta_argmax_zoom_back": (I, [P, P, P, P, P, P, I, P, I, I, I, I, I, I, I, P]),
 }
 
 

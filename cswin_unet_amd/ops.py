@@ -17,7 +17,8 @@ from ._lib import AugmentDesc, ConvImageJob, CswinHipError, ReduceJob, WgradDesc
 
 __all__ = ["layer_norm", "linear", "linear_pair", "mlp", "stripe_attention", "cswin_block", "conv_tokens", "patch_embed_conv", "carafe_reassemble",
            "carafe_reassemble_nchw", "conv_weight_images", "head_compose", "tokens_to_nchw", "matmul_nn", "ce_dice_loss", "continual_loss", "dropout", "img2windows", "windows2img",
-           "seg_metrics", "connected_components", "filter_components", "COMPONENT_TILE", "resize_slices", "argmax_zoom_back", "augment_batch", "class_counts", "gaussian_blur"]
+           "seg_metrics", "connected_components", "filter_components", "COMPONENT_TILE", "resize_slices", "argmax_zoom_back", "augment_batch", "class_counts", "gaussian_blur",
+           "view_batch", "tta_argmax_zoom_back"]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1478,6 +1479,72 @@ def argmax_zoom_back(logits, size, classes=None):
         call("cswin_argmax_zoom_back_classes", ptr(logits), ptr(out), ptr(rows), ptr(cols), ptr(table), table.numel(), B, ncls, h, w,
              H, W, stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# test-time augmentation: the views before the network, their ensemble after it
+# ------------------------------------------------------------------------------------------------
+_view_tables = {}
+
+
+def _view_table(views, what):
+    """The int32 table of a tuple of view codes as the entry points read it -- on the host, before they launch (which is how a bad
+    code is refused without a kernel) -- made once per tuple.  Whether a code is a view, and whether the shape allows it, is the
+    library's decision; here only the count is checked, the table's length being what the library is told."""
+    key = tuple(views)
+    if not 1 <= len(key) <= 8:
+        raise CswinHipError(f"{what}: {len(key)} views; 1..8 are supported")
+    for k, c in enumerate(key):                                         # before the look-up: (True,) hashes as (1,)
+        if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not -2 ** 31 <= c < 2 ** 31:
+            raise CswinHipError(f"{what}: views[{k}] = {c!r} is not a view code (utils.tta_views makes them)")
+    if key not in _view_tables:
+        _view_tables[key] = (ctypes.c_int * len(key))(*(int(c) for c in key))
+    return _view_tables[key]
+
+
+def view_batch(x, views):
+    """The views of a batch of slices: x (B, h, w) fp32 HIP tensor, views a sequence of 1..8 view codes (utils.tta_views) ->
+    (V, B, h', w') fp32, y[v][b] = the numpy expression of utils.apply_view(x[b], views[v]); (h', w') = (h, w), and a transposing
+    view (an odd code) needs h == w (CswinHipError otherwise, as for a code outside 0..7).  One launch (csrc/tta.hip); the values
+    are copied bit for bit."""
+    x = dev_f32(x, "view_batch input")
+    if x.dim() != 3:
+        raise CswinHipError(f"view_batch: input {tuple(x.shape)} must be (B, h, w)")
+    table = _view_table(views, "view_batch")
+    B, h, w = x.shape
+    y = torch.empty((len(table), B, h, w), dtype=torch.float32, device=x.device)
+    call("cswin_view_batch", ptr(x), ptr(y), table, len(table), B, h, w, stream())
+    return y
+
+
+def tta_argmax_zoom_back(logits, views, size, classes=None, return_probs=False):
+    """The ensemble of a network's answers to ops.view_batch's views, its argmax and the order-0 zoom back, in one launch
+    (csrc/tta.hip).  logits (V * B, ncls, h, w) fp32 as the network returns them for the (V * B, 1, h, w) input view_batch made,
+    i.e. (V, B, ...) with slice [v] in the frame of view views[v]; CswinHipError if the batch is no multiple of V.  With
+    P[b, k, r, s] = the mean over v of softmax(logits[v, b, classes])[k] at view v's image of (r, s) -- the mean of probabilities,
+    float32 -- the result is scipy.ndimage.zoom(torch.argmax(P, 1)[b], (H / h, W / w), order=0) as a uint8 (B, H, W) HIP tensor;
+    size = (H, W).  classes: argmax_zoom_back's list, the result being the position in it.  return_probs=True: (out, P) with P
+    (B, nsel, h, w) fp32.  Above 16 candidates the kernel keeps its sums in P, which is then allocated either way."""
+    logits = dev_f32(logits, "tta_argmax_zoom_back logits")
+    if logits.dim() != 4:
+        raise CswinHipError(f"tta_argmax_zoom_back: logits {tuple(logits.shape)} must be (V * B, ncls, h, w)")
+    table = _view_table(views, "tta_argmax_zoom_back")
+    V = len(table)
+    if logits.shape[0] % V or logits.shape[0] == 0:
+        raise CswinHipError(f"tta_argmax_zoom_back: a batch of {logits.shape[0]} logits is not a positive multiple of the {V} views")
+    from .utils import nearest_index_device
+    (VB, ncls, h, w), (H, W) = logits.shape, (int(size[0]), int(size[1]))
+    B = VB // V
+    ctable = None if classes is None else _class_table(classes, ncls, logits.device)
+    nsel = ncls if ctable is None else ctable.numel()
+    if not 1 <= nsel <= 255:
+        raise CswinHipError(f"tta_argmax_zoom_back: {nsel} candidates; 1..255 are supported (the result is a byte)")
+    out = torch.empty((B, H, W), dtype=torch.uint8, device=logits.device)
+    probs = torch.empty((B, nsel, h, w), dtype=torch.float32, device=logits.device) if return_probs or nsel > 16 else None
+    rows, cols = nearest_index_device(h, H, logits.device), nearest_index_device(w, W, logits.device)
+    call("cswin_tta_argmax_zoom_back", ptr(logits), ptr(out), ptr(probs), ptr(rows), ptr(cols), table, V, ptr(ctable), nsel, B, ncls, h, w,
+         H, W, stream())
+    return (out, probs) if return_probs else out
 
 
 # ------------------------------------------------------------------------------------------------

@@ -23,6 +23,10 @@ Mirrors the reference's utils.py names and call signatures:
     ``components`` (not in the reference) drops, per class, the small face-connected components of the finished prediction before
     it is scored: ``filter_components_host`` (scipy.ndimage.label) on the host path, ops.filter_components (csrc/components.hip,
     same result) on the resident volume with ``resize="hip"``.
+    ``tta`` (not in the reference) asks the network for several views of every slice -- symmetries of the square, the group
+    ``random_rot_flip`` trains on (``tta_views``) -- and takes the argmax of the mean of the views' softmax probabilities:
+    numpy in float64 on the host path, which is the definition, ops.view_batch / ops.tta_argmax_zoom_back (csrc/tta.hip) with
+    ``resize="hip"``.
 """
 import functools
 import logging
@@ -423,6 +427,114 @@ def filter_components_host(vol, ncls, rule):
     return out
 
 
+TTA_VIEW_NAMES = {"identity": 0, "transpose": 1, "flip_rows": 2, "rot90": 3, "flip_cols": 4, "rot270": 5, "rot180": 6, "anti_transpose": 7}
+
+
+def tta_views(spec):
+    """The views of a test-time-augmentation spec as a tuple of codes 0..7, or None for None.  A code c is a symmetry of the
+    square: bit 0 transposes, bit 1 reverses the rows, bit 2 the columns, in that order (apply_view) -- the group that training's
+    random_rot_flip draws from.  spec: "flips" = (0, 2, 4, 6), the views that keep a slice's shape; "d4" = all eight; or a
+    sequence of 1..8 distinct codes or names (TTA_VIEW_NAMES: "rot90" = 3 is np.rot90(x, 1), "rot270" = 5 is np.rot90(x, 3)).
+    ValueError naming the entry for anything else (another string, a bool, a code outside 0..7, a repeated view)."""
+    if spec is None:
+        return None
+    if isinstance(spec, str):
+        if spec not in ("flips", "d4"):
+            raise ValueError(f'tta: {spec!r} is not "flips", "d4" or a sequence of view codes or names')
+        return (0, 2, 4, 6) if spec == "flips" else tuple(range(8))
+    try:
+        entries = list(spec)
+    except TypeError:
+        raise ValueError(f'tta: {spec!r} is not "flips", "d4" or a sequence of view codes or names') from None
+    if not 1 <= len(entries) <= 8:
+        raise ValueError(f"tta: {len(entries)} views; 1..8 distinct ones are supported")
+    codes = []
+    for k, e in enumerate(entries):
+        if isinstance(e, str) and e in TTA_VIEW_NAMES:
+            c = TTA_VIEW_NAMES[e]
+        elif not isinstance(e, (bool, str)) and isinstance(e, (int, np.integer)) and 0 <= e <= 7:
+            c = int(e)
+        else:
+            raise ValueError(f"tta: entry {k}, {e!r}, is not a view code in 0..7 or one of {sorted(TTA_VIEW_NAMES)}")
+        if c in codes:
+            raise ValueError(f"tta: entry {k}, {e!r}, repeats view {c}")
+        codes.append(c)
+    return tuple(codes)
+
+
+def apply_view(x, code):
+    """View `code` of the last two axes of a numpy array (a numpy view, nothing is copied)."""
+    a = np.swapaxes(x, -1, -2) if code & 1 else x
+    a = np.flip(a, -2) if code & 2 else a
+    return np.flip(a, -1) if code & 4 else a
+
+
+def undo_view(a, code):
+    """The inverse of apply_view: undo_view(apply_view(x, c), c) is x."""
+    a = np.flip(a, -1) if code & 4 else a
+    a = np.flip(a, -2) if code & 2 else a
+    return np.swapaxes(a, -1, -2) if code & 1 else a
+
+
+def tta_view_position(code, r, s, h, w):
+    """(i, j) of source pixel (r, s) of an (h, w) slice in the frame of view `code`: apply_view(x, code)[i, j] is x[r, s].  The
+    index map of csrc/tta_plan.h (tta_view_pos), which the kernels read the views' logits through."""
+    hv, wv = (w, h) if code & 1 else (h, w)
+    i2, j2 = (s, r) if code & 1 else (r, s)
+    return (hv - 1 - i2 if code & 2 else i2), (wv - 1 - j2 if code & 4 else j2)
+
+
+def _check_tta_patch(views, patch_size):
+    if views is not None and patch_size[0] != patch_size[1] and any(c & 1 for c in views):
+        bad = [c for c in views if c & 1]
+        raise ValueError(f"predict_volume: tta views {bad} transpose the network's input, which needs a square patch_size, "
+                         f"got {tuple(patch_size)}")
+
+
+def ensemble_views_host(logits, views, class_indices):
+    """The definition of the ensemble on downloaded logits (V * b, ncls, h', w'): float64 softmax over the listed channels per
+    view, back to the source frame, the mean over the views, torch.argmax (first index, first NaN).  Returns (cls int64 (b, h, w),
+    P float64 (b, nsel, h, w))."""
+    V = len(views)
+    L = logits.detach().double().cpu().numpy()
+    L = L if class_indices is None else L[:, list(class_indices)]
+    L = L.reshape((V, L.shape[0] // V) + L.shape[1:])
+    P = 0.0
+    with np.errstate(invalid="ignore", over="ignore"):
+        for v, c in enumerate(views):
+            e = np.exp(L[v] - L[v].max(axis=1, keepdims=True))
+            P = P + undo_view(e / e.sum(axis=1, keepdims=True), c)
+        P = np.ascontiguousarray(P / V)
+    return torch.argmax(torch.from_numpy(P), dim=1).numpy(), P
+
+
+def _predict_volume_hip_tta(vol, net, patch_size, batch_slices, device, class_indices, blur_sigma, components, views):
+    """_predict_volume_hip with a view ensemble: per batch (gaussian_blur ->) resize_slices -> view_batch -> ONE network call on
+    V * b samples -> tta_argmax_zoom_back into the resident uint8 volume.  b = max(1, batch_slices // V), so the network's batch
+    stays what the caller sized it for."""
+    D, x, y = vol.shape
+    if blur_sigma is not None and vol.dtype != np.float32:
+        raise ValueError(f'predict_volume: blur_sigma with resize="hip" takes float32 volumes, got {vol.dtype} (scipy blurs in the '
+                         f'volume\'s own dtype); use resize="host"')
+    dvol = torch.from_numpy(np.ascontiguousarray(vol)).to(device)
+    resize = x != patch_size[0] or y != patch_size[1]
+    if not resize:
+        dvol = dvol.float()
+    pred = torch.empty((D, x, y), dtype=torch.uint8, device=dvol.device)
+    b = max(1, batch_slices // len(views))
+    for d0 in range(0, D, b):
+        sl = dvol[d0:d0 + b]
+        if blur_sigma is not None:
+            sl = ops.gaussian_blur(sl, blur_sigma)
+        inp = ops.resize_slices(sl, patch_size) if resize else sl
+        seen = ops.view_batch(inp, views)
+        logits = net(seen.view(-1, 1, seen.shape[2], seen.shape[3]))
+        pred[d0:d0 + b] = ops.tta_argmax_zoom_back(logits, views, (x, y), classes=class_indices)
+    if components is not None and D > 0:
+        ops.filter_components(pred, _class_count(logits, class_indices), components, out=pred)
+    return pred
+
+
 def _predict_volume_hip(vol, net, patch_size, batch_slices, device, class_indices=None, blur_sigma=None, components=None):
     """predict_volume's loop with the volume resident on the device: upload once, per batch (gaussian_blur ->) resize_slices ->
     net -> argmax_zoom_back (over class_indices, if given) into a uint8 (D, H, W) device volume, which filter_components then
@@ -455,7 +567,7 @@ def _class_count(logits, class_indices):
 
 @torch.no_grad()
 def predict_volume(image, net, patch_size=(224, 224), batch_slices=16, device="cuda", resize="host", return_device=False,
-                   class_indices=None, blur_sigma=None, components=None):
+                   class_indices=None, blur_sigma=None, components=None, tta=None):
     """image (D, H, W) or (H, W) numpy -> integer class map of the same shape.  Per slice: cubic zoom to patch_size if the
     size differs, network, argmax over classes (softmax is monotonic, utils.py:75), nearest zoom back (:70-81).
     resize: "host" = scipy's zooms per slice around batched network calls; "hip" = the volume is uploaded once, both zooms and
@@ -471,7 +583,18 @@ def predict_volume(image, net, patch_size=(224, 224), batch_slices=16, device="c
     components: None (nothing is filtered), or a component filter rule (component_rule_tables: "largest" or a mapping per class id)
     applied to the finished class map of the whole volume -- with class_indices that means the dataset's own ids: per class, the
     face-connected components smaller than the rule's threshold become 0.  scipy on the host path (filter_components_host),
-    ops.filter_components on the resident volume with resize="hip".  ValueError for a rule that names a class the map cannot hold."""
+    ops.filter_components on the resident volume with resize="hip".  ValueError for a rule that names a class the map cannot hold.
+    tta: None (one forward pass per slice, the code above call for call), or a test-time-augmentation spec (tta_views: "flips",
+    "d4", or a sequence of view codes / names): the network sees every view of every slice, in one call on V * b samples with
+    b = max(1, batch_slices // V), and the class is the argmax of the MEAN over the views of the softmax probabilities, each
+    taken back to the slice's own frame -- probabilities, not logits: they are bounded, so one over-confident view cannot outvote
+    the rest.  The host path is the definition: np.flip / np.swapaxes around the scipy zooms, softmax and mean in float64 on
+    the downloaded logits, torch.argmax.  resize="hip" makes the views with ops.view_batch and ensembles with
+    ops.tta_argmax_zoom_back in float32 (csrc/tta.hip), which can move a class only where the two best probabilities are
+    within ~1e-6.  A transposing view (an odd code) needs a square patch_size: ValueError before the network runs.
+    class_indices, blur_sigma, components and return_device compose as without tta."""
+    views = tta_views(tta)
+    _check_tta_patch(views, patch_size)
     if resize not in ("host", "hip"):
         raise ValueError(f'predict_volume: resize must be "host" or "hip", got {resize!r}')
     if return_device and resize != "hip":
@@ -485,21 +608,31 @@ def predict_volume(image, net, patch_size=(224, 224), batch_slices=16, device="c
     vol = image[None] if single else image
     net.eval()
     if resize == "hip":
-        pred = _predict_volume_hip(vol, net, tuple(patch_size), batch_slices, device, class_indices, blur_sigma, components)
+        if views is None:
+            pred = _predict_volume_hip(vol, net, tuple(patch_size), batch_slices, device, class_indices, blur_sigma, components)
+        else:
+            pred = _predict_volume_hip_tta(vol, net, tuple(patch_size), batch_slices, device, class_indices, blur_sigma, components, views)
         pred = pred if return_device else pred.cpu().numpy()
         return pred[0] if single else pred
     D, x, y = vol.shape
     resize = x != patch_size[0] or y != patch_size[1]
     pred = np.zeros((D, x, y), np.int64)
+    if views is not None:
+        batch_slices = max(1, batch_slices // len(views))
     for d0 in range(0, D, batch_slices):
         sl = vol[d0:d0 + batch_slices]
         if blur_sigma is not None:
             sl = np.stack([gaussian_filter(s, blur_sigma) for s in sl])
         if resize:
             sl = np.stack([zoom(s, (patch_size[0] / x, patch_size[1] / y), order=3) for s in sl])
-        inp = torch.from_numpy(np.ascontiguousarray(sl)).unsqueeze(1).float().to(device)
-        logits = net(inp)
-        out = torch.argmax(logits if class_indices is None else logits[:, list(class_indices)], dim=1).cpu().numpy()
+        if views is None:
+            inp = torch.from_numpy(np.ascontiguousarray(sl)).unsqueeze(1).float().to(device)
+            logits = net(inp)
+            out = torch.argmax(logits if class_indices is None else logits[:, list(class_indices)], dim=1).cpu().numpy()
+        else:
+            seen = np.concatenate([apply_view(sl, c) for c in views])
+            logits = net(torch.from_numpy(np.ascontiguousarray(seen)).unsqueeze(1).float().to(device))
+            out, _ = ensemble_views_host(logits, views, class_indices)
         for i, o in enumerate(out):
             pred[d0 + i] = zoom(o, (x / patch_size[0], y / patch_size[1]), order=0) if resize else o
     if components is not None and D > 0:
@@ -509,7 +642,7 @@ def predict_volume(image, net, patch_size=(224, 224), batch_slices=16, device="c
 
 def test_single_volume(image, label, net, classes, patch_size=[256, 256], test_save_path=None, case=None, z_spacing=1,
                        batch_slices=16, device="cuda", metrics="host", resize="host", class_indices=None, blur_sigma=None,
-                       components=None, voxelspacing=None, assd=False):
+                       components=None, voxelspacing=None, assd=False, tta=None):
     """Per-class (dice, hd95) of one volume, classes 1..classes-1 (utils.py:61-102).  image / label: (1, D, H, W) tensors
     as the DataLoader yields them.  With test_save_path the volumes are written as .npz (SimpleITK, which the reference
     uses for .nii.gz, is not installed here).  metrics: "host" = the per-class scipy loop, "hip" = one volume_metrics call on
@@ -521,7 +654,9 @@ def test_single_volume(image, label, net, classes, patch_size=[256, 256], test_s
     resize="hip", so with metrics="hip" it still never leaves it -- and the saved .npz holds the filtered prediction.
     voxelspacing, assd: calculate_metric_percase's / volume_metrics', for either value of `metrics`: the spacing of the volume's
     axes (D, H, W) that HD95 (and ASSD) are measured in, and (dice, hd95, assd) triples.  A bad spacing raises ValueError before
-    the network runs.  z_spacing is unrelated: it only goes into the saved .npz."""
+    the network runs.  z_spacing is unrelated: it only goes into the saved .npz.  tta: predict_volume's view ensemble, checked
+    (tta_views, and a square patch for a transposing view) before anything else runs."""
+    _check_tta_patch(tta_views(tta), patch_size)
     if class_indices is not None and len(class_indices) != classes:
         raise ValueError(f"test_single_volume: class_indices has {len(class_indices)} entries for classes={classes}")
     if metrics not in ("host", "hip"):
@@ -535,7 +670,7 @@ def test_single_volume(image, label, net, classes, patch_size=[256, 256], test_s
         voxelspacing = ops.voxel_spacing(voxelspacing, label.ndim)
     on_device = resize == "hip" and metrics == "hip"
     prediction = predict_volume(image, net, tuple(patch_size), batch_slices, device, resize=resize, return_device=on_device,
-                                class_indices=class_indices, blur_sigma=blur_sigma, components=components)
+                                class_indices=class_indices, blur_sigma=blur_sigma, components=components, tta=tta)
     if not on_device:
         prediction = prediction.astype(label.dtype)
     if metrics == "hip":
@@ -555,14 +690,17 @@ test_single_volume.__test__ = False     # not a pytest test (the name is the ref
 
 
 def evaluate_volumes(loader, net, classes, patch_size, metrics="hip", test_save_path=None, z_spacing=1, batch_slices=16,
-                     device="cuda", resize="host", class_indices=None, blur_sigma=None, components=None, voxelspacing=None, assd=False):
+                     device="cuda", resize="host", class_indices=None, blur_sigma=None, components=None, voxelspacing=None, assd=False,
+                     tta=None):
     """The volume loop of the reference's inference() (test.py:155-164): test_single_volume per batch of `loader` (dicts with
     "image", "label" (1, D, H, W) and "case_name", batch size 1), the per-volume and final lines it logs.  Returns
     (per_volume, class_mean, mean_dice, mean_hd95): the metric list of every volume, the (classes-1, 2) table of per-class
-    means over the volumes, and that table's column means.  class_indices, blur_sigma, components: test_single_volume's.
+    means over the volumes, and that table's column means.  class_indices, blur_sigma, components, tta: test_single_volume's
+    (a bad tta raises ValueError before the loader is read).
     voxelspacing: test_single_volume's, one spacing for every volume or a dict case name -> spacing (KeyError naming a case it
     lacks).  assd=True: the metric lists hold triples, class_mean is (classes-1, 3), the log lines gain mean_assd and the return
     a fifth element, mean_assd."""
+    _check_tta_patch(tta_views(tta), patch_size)
     per_volume = []
     for i_batch, batch in enumerate(loader):
         name = batch["case_name"]
@@ -575,7 +713,7 @@ def evaluate_volumes(loader, net, classes, patch_size, metrics="hip", test_save_
         metric_i = test_single_volume(batch["image"], batch["label"], net, classes=classes, patch_size=list(patch_size),
                                       test_save_path=test_save_path, case=name, z_spacing=z_spacing, batch_slices=batch_slices,
                                       device=device, metrics=metrics, resize=resize, class_indices=class_indices,
-                                      blur_sigma=blur_sigma, components=components, voxelspacing=spacing, assd=assd)
+                                      blur_sigma=blur_sigma, components=components, voxelspacing=spacing, assd=assd, tta=tta)
         per_volume.append(metric_i)
         m = np.mean(metric_i, axis=0)
         logging.info('idx %d case %s mean_dice %f mean_hd95 %f' % (i_batch, name, m[0], m[1]) + (' mean_assd %f' % m[2] if assd else ''))

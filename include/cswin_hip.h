@@ -31,7 +31,7 @@ extern "C" {
  * compiled against another header must refuse to call it.  Entry points that are only ADDED (cswin_seg_metrics*, cswin_resize_banded, cswin_argmax_zoom_back, cswin_augment_*,
  * cswin_chunk_sumsq, cswin_norm_finalize, cswin_adamw_flat, cswin_tpgm_*, cswin_argmax_zoom_back_classes, cswin_class_counts, cswin_gaussian_blur, cswin_eb_tiles,
  * cswin_eb_finalize, cswin_rate_finalize, cswin_adam_flat, cswin_components_*, cswin_drop_path_order, cswin_linear_*_skip,
- * cswin_surface_dist*) do not bump it: every prototype an older consumer binds is unchanged. */
+ * cswin_surface_dist*, cswin_view_batch, cswin_tta_argmax_zoom_back) do not bump it: every prototype an older consumer binds is unchanged. */
 #define CSWIN_ABI_VERSION 4
 
 #define CSWIN_OK 0
@@ -577,6 +577,35 @@ int cswin_class_counts(const void* labels, int label_bytes, const int* label_map
  * synchronisation.  Each of D, H, W in 1..2048 (CSWIN_ERR_SHAPE), radius in 0..32 and x != y (CSWIN_ERR_UNSUPPORTED: the filter
  * does not work in place); pointers aligned to their element size. */
 int cswin_gaussian_blur(const float* x, float* y, const double* taps, int radius, int D, int H, int W, void* stream);
+
+/* ---- test-time augmentation of a volume evaluation (csrc/tta.hip): the eight symmetries of the square, which training's
+ *      random_rot_flip draws from (datasets/dataset_synapse.py:12-19), applied before the network and ensembled after it ----
+ * A view is a code c in 0..7: bit 0 transposes, bit 1 reverses the rows, bit 2 the columns, in that order
+ *   (a = x.T if c & 1 else x; a = a[::-1, :] if c & 2 else a; a = a[:, ::-1] if c & 4 else a), so source pixel (r, s) of an (h, w)
+ *   slice sits at (i, j) of the viewed frame (h', w') = (w, h) if c & 1 else (h, w):  (i2, j2) = (s, r) if c & 1 else (r, s),
+ *   i = h'-1-i2 if c & 2 else i2,  j = w'-1-j2 if c & 4 else j2.  np.rot90(x, 1) is code 3, np.rot90(x, 3) code 5.
+ * views: V codes in HOST memory (as the heads / idx of cswin_attn_fwd), V in 1..8, read before the call returns and passed to
+ *   the kernel by value -- so a code outside 0..7, or a transposing code with h != w, is CSWIN_ERR_SHAPE before any launch.
+ * x (B, h, w) fp32 -> y (V, B, h', w') fp32, y[v][b] = view_{views[v]}(x[b]): values are copied, never computed with.  x != y
+ * (CSWIN_ERR_UNSUPPORTED); each of B, h, w in 1..2048.  One launch, no workspace. */
+int cswin_view_batch(const float* x, float* y, const int* views, int V, int B, int h, int w, void* stream);
+/* The ensemble of the network's answers to those views, the argmax and the order-0 zoom back in one launch.
+ * logits (V, B, ncls, h', w') fp32, slice [v] in the frame of view views[v] -> out (B, H, W) uint8, and probs (B, nsel, h, w) fp32
+ * or NULL.  With c_k = classes[k] (device int32 [nsel], clamped into [0, ncls) on the device, as cswin_argmax_zoom_back_classes
+ * takes it) or c_k = k (classes NULL, and then nsel == ncls):
+ *   P[b][k][r][s] = (1 / V) sum_v softmax_k(logits[v][b][c_.][i_v(r, s)][j_v(r, s)]),
+ *   out[b][i][j]  = argmax_k P[b][k][src_row[i]][src_col[j]]  (the first k wins a tie, a NaN wins and the first NaN first),
+ * the mean of the PROBABILITIES of the views.  All of it in float32, in one fixed order: per view in ascending v, m = max_k l_k,
+ * e_k = expf(l_k - m), S = the sum of e_k in ascending k, p_k = e_k / S, added to the sum over views; then the multiplication by
+ * 1 / V.  A +inf or NaN logit in any view makes every P of its pixel NaN (inf - inf), so out is 0 there, as torch.softmax and
+ * torch.argmax give it.  src_row (H), src_col (W) int32, device: as cswin_argmax_zoom_back's (negative: out is 0; past the end:
+ * clamped).  Every source pixel is ensembled once, by the workgroup that also writes every output pixel gathering from it.
+ * probs, if given, receives P.  nsel <= 16 keeps the sums over views in registers; above that they are kept in probs, which is
+ * then required (CSWIN_ERR_WORKSPACE if NULL).  nsel in 1..255, ncls >= 1, each of B, h, w, H, W in 1..2048, V and views as
+ * above (CSWIN_ERR_SHAPE); pointers aligned to their element size.  No atomics: two runs give the same bits. */
+int cswin_tta_argmax_zoom_back(const float* logits, unsigned char* out, float* probs, const int* src_row, const int* src_col,
+                               const int* views, int V, const int* classes, int nsel, int B, int ncls, int h, int w, int H, int W,
+                               void* stream);
 
 /* ---- training augmentation of a batch of raw slices (datasets/dataset_synapse.py:12-47: np.rot90 + np.flip, or
  *      scipy.ndimage.rotate(order=0, reshape=False), then the zooms to the network's size) ----
