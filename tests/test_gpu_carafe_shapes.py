@@ -39,7 +39,7 @@ def cdiv(a, b):
 
 
 # ------------------------------------------------------------------------------------------------
-# launch rules (a transcription of the host code: it MUST FOLLOW csrc/carafe.hip)
+# launch rules (a transcription of csrc/carafe_plan.h, held to it field by field by tests/test_carafe_plan_host.py)
 # ------------------------------------------------------------------------------------------------
 GRID_CLAMP, COLSUM_CLAMP, TILE = 8192, 512, 8
 
