@@ -101,6 +101,9 @@ SIGNATURES = {
     "cswin_augment_gather": (I, [P, P, P, I, I, I, I, I, I, P]),
     "cswin_augment_labels": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
     "cswin_gaussian_blur": (I, [P, P, P, I, I, I, I, P]),
+    "cswin_gaussian_blur_each": (I, [P, P, P, I, P, I, I, I, I, P]),
+    "cswin_intensity_workspace": (SZ, [I, L]),
+    "cswin_intensity_batch": (I, [P, P, P, P, SZ, I, L, I, P]),
     "cswin_view_batch": (I, [P, P, P, I, I, I, I, P]),
     "cswin_tta_argmax_zoom_back": (I, [P, P, P, P, P, P, I, P, I, I, I, I, I, I, I, P]),
 }

@@ -23,6 +23,8 @@ struct BlurArgs {
     const double* taps;                    // taps[0 .. r] = w[-r] .. w[0]
     int radius, H, W, TR, cw_log2;
     unsigned w_magic;                      // fdiv_magic(W)
+    const int* each;                       // EACH only: (taps offset, radius) of every slice; radius is then the largest
+    int ntaps;                             // EACH only: doubles behind taps
 };
 
 __device__ __forceinline__ int bl_reflect(int i, int n) {
@@ -45,16 +47,20 @@ __device__ __forceinline__ int bl_reflect(int i, int n) {
 // Rows of a group beyond the tile's last (a tile remainder) are computed on whatever the LDS holds and not stored.
 // R: the radius at compile time (the tap loops unroll, the taps stay in registers and the stage values of neighbouring taps and
 //   rows are read once), or -1 for any radius.
-template <int VEC, int R>
+// EACH (R == -1 only): slice d has its own radius each[2d + 1] <= a.radius and its own taps at a.taps + each[2d]
+//   (cswin_gaussian_blur_each).  The tile was planned for a.radius, so a smaller halo fits its stage; radius and offset are
+//   clamped here to what the plan and the taps buffer hold, so a bad table cannot send an index out of either.
+template <int VEC, int R, bool EACH = false>
 __global__ __launch_bounds__(256) void gaussian_blur_kernel(BlurArgs a) {
     extern __shared__ __attribute__((aligned(16))) float bl_lds[];
-    const int H = a.H, W = a.W, r = R >= 0 ? R : a.radius, TR = a.TR, cwl = a.cw_log2, CW = 1 << cwl;
-    const int d = blockIdx.y, r0 = blockIdx.x * TR;
+    const int d = blockIdx.y, r0 = blockIdx.x * a.TR;
+    const int r = R >= 0 ? R : EACH ? min(max(a.each[2 * d + 1], 0), min(a.radius, a.ntaps - 1)) : a.radius;
+    const int H = a.H, W = a.W, TR = a.TR, cwl = a.cw_log2, CW = 1 << cwl;
     const int nrow = min(TR, H - r0), nstage = nrow + 2 * r, ngrp = (nrow + BL_RB - 1) / BL_RB;
     float* __restrict__ mid = bl_lds;
     float* __restrict__ stage = bl_lds + TR * W;          // W is even where VEC == 2: 8-B aligned
     const float* __restrict__ xs = a.x + (long)d * H * W;
-    const double* __restrict__ taps = a.taps;
+    const double* __restrict__ taps = EACH ? a.taps + min(max(a.each[2 * d], 0), a.ntaps - 1 - r) : a.taps;
     const double w0 = taps[r];
 
     constexpr int VL = VEC == 2 ? 1 : 0;
@@ -137,6 +143,32 @@ int cswin_gaussian_blur(const float* x, float* y, const double* taps, int radius
         if (vec == 2) hipLaunchKernelGGL((gaussian_blur_kernel<2, -1>), grid, block, lds, st, a);
         else hipLaunchKernelGGL((gaussian_blur_kernel<1, -1>), grid, block, lds, st, a);
     }
+    CSWIN_LAUNCH_CHECK();
+    return CSWIN_OK;
+}
+
+int cswin_gaussian_blur_each(const float* x, float* y, const double* taps, int ntaps, const int* table, int max_radius, int D, int H,
+                             int W, void* stream) {
+    CSWIN_REQUIRE(x && y && taps && table, CSWIN_ERR_SHAPE, "gaussian_blur_each: null argument");
+    CSWIN_REQUIRE(x != y, CSWIN_ERR_UNSUPPORTED, "gaussian_blur_each: x == y (the filter does not work in place)");
+    CSWIN_REQUIRE(bl_dim_ok(D) && bl_dim_ok(H) && bl_dim_ok(W), CSWIN_ERR_SHAPE,
+                  "gaussian_blur_each: (D, H, W) = (%d, %d, %d) outside the supported 1..%d per dimension", D, H, W, BL_MAX_DIM);
+    CSWIN_REQUIRE(max_radius >= 0 && max_radius <= BL_MAX_RADIUS, CSWIN_ERR_UNSUPPORTED, "gaussian_blur_each: max_radius=%d outside 0..%d",
+                  max_radius, BL_MAX_RADIUS);
+    CSWIN_REQUIRE(ntaps > max_radius && ntaps <= BL_MAX_DIM * (BL_MAX_RADIUS + 1), CSWIN_ERR_SHAPE,
+                  "gaussian_blur_each: ntaps=%d does not hold the %d taps of the largest radius (or exceeds %d)", ntaps, max_radius + 1,
+                  BL_MAX_DIM * (BL_MAX_RADIUS + 1));
+    CSWIN_REQUIRE((uintptr_t)x % 4 == 0 && (uintptr_t)y % 4 == 0 && (uintptr_t)taps % 8 == 0 && (uintptr_t)table % 4 == 0, CSWIN_ERR_ALIGN,
+                  "gaussian_blur_each: a pointer is not aligned to its element size");
+    const int vec = (W % 2 == 0 && (uintptr_t)x % 8 == 0) ? 2 : 1;
+    const BlurPlan p = bl_plan(H, W, max_radius, vec);
+    CSWIN_REQUIRE(p.TR >= 1, CSWIN_ERR_UNSUPPORTED, "gaussian_blur_each: no tile of W=%d, radius=%d fits the LDS", W, max_radius);
+    const BlurArgs a = {x, y, taps, max_radius, H, W, p.TR, p.cw_log2, fdiv_magic(W), table, ntaps};
+    const dim3 grid(cdiv(H, p.TR), D), block(256);
+    const size_t lds = (size_t)bl_lds_bytes(p, W, max_radius);
+    hipStream_t st = (hipStream_t)stream;
+    if (vec == 2) hipLaunchKernelGGL((gaussian_blur_kernel<2, -1, true>), grid, block, lds, st, a);
+    else hipLaunchKernelGGL((gaussian_blur_kernel<1, -1, true>), grid, block, lds, st, a);
     CSWIN_LAUNCH_CHECK();
     return CSWIN_OK;
 }

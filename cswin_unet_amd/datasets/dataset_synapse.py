@@ -109,6 +109,93 @@ class RawSliceParams(object):
                 'params': torch.tensor([kind, k, axis, angle], dtype=torch.int32)}
 
 
+# one sample's draw of IntensityAugment: what utils.intensity_host (the definition) and ops.intensity_batch (the device) read
+INTENSITY_DRAW = np.dtype([("do_blur", "?"), ("do_noise", "?"), ("do_brightness", "?"), ("do_contrast", "?"), ("do_gamma", "?"),
+                           ("invert", "?"), ("sigma", "<f8"), ("noise_std", "<f8"), ("brightness", "<f8"), ("contrast", "<f8"),
+                           ("gamma", "<f8"), ("seed", "<u8")])
+
+
+def check_intensity_draws(draws, n=None):
+    """`draws` as a one-dimensional INTENSITY_DRAW array (a single record becomes an array of one), every parameter of a stage
+    that is on checked as IntensityAugment checks its ranges: ValueError for a wrong dtype or count, a sigma outside
+    utils.gaussian_taps' limits, a noise_std that is negative, a gamma that is not positive, or any value that is not finite."""
+    draws = np.atleast_1d(np.asarray(draws))
+    if draws.dtype != INTENSITY_DRAW or draws.ndim != 1:
+        raise ValueError(f"intensity draws must be a one-dimensional array of datasets.INTENSITY_DRAW records, got {draws.dtype} {draws.shape}")
+    if n is not None and len(draws) != n:
+        raise ValueError(f"{len(draws)} intensity draws for {n} samples")
+    from ..utils import gaussian_taps
+    for b, d in enumerate(draws):
+        if d["do_blur"]:
+            gaussian_taps(float(d["sigma"]))
+        for flag, name, ok in (("do_noise", "noise_std", lambda v: v >= 0), ("do_brightness", "brightness", lambda v: True),
+                               ("do_contrast", "contrast", lambda v: True), ("do_gamma", "gamma", lambda v: v > 0)):
+            v = float(d[name])
+            if d[flag] and not (np.isfinite(v) and ok(v)):
+                raise ValueError(f"intensity draw {b}: {name} = {v!r} is outside what the stage takes")
+    return draws
+
+
+class IntensityAugment(object):
+    """Appearance augmentation of a training batch, nnU-Net's: per sample and stage a coin with the stage's probability, then a
+    uniform draw from its range.  Stages in the order they are applied (utils.intensity_host is the definition):
+      blur        scipy.ndimage.gaussian_filter with sigma ~ U(blur_sigma)
+      noise       additive Gaussian noise of variance ~ U(noise_variance), ABSOLUTE (not relative to the image's range)
+      brightness  a factor ~ U(brightness)
+      contrast    a factor ~ U(contrast) about the mean, clipped to the image's own range
+      gamma       a power ~ U(gamma) on the image scaled to [0, 1], mean and deviation restored; with probability p_invert on -image
+    Every argument is (probability, (low, high)).  ValueError at construction for a probability outside [0, 1], low > high, a
+    negative variance, a gamma <= 0 or a sigma outside utils.gaussian_taps' limits.  `nnunet()` is nnU-Net's default set."""
+
+    def __init__(self, noise=(0.0, (0.0, 0.0)), blur=(0.0, (1.0, 1.0)), brightness=(0.0, (1.0, 1.0)), contrast=(0.0, (1.0, 1.0)),
+                 gamma=(0.0, (1.0, 1.0)), p_invert=0.0):
+        from ..utils import gaussian_taps
+        self.stages = {}
+        for name, spec in (("noise", noise), ("blur", blur), ("brightness", brightness), ("contrast", contrast), ("gamma", gamma)):
+            try:
+                p, (lo, hi) = spec
+                p, lo, hi = float(p), float(lo), float(hi)
+            except (TypeError, ValueError):
+                raise ValueError(f"IntensityAugment: {name} = {spec!r} is not (probability, (low, high))") from None
+            if not 0.0 <= p <= 1.0:
+                raise ValueError(f"IntensityAugment: {name} probability {p!r} outside [0, 1]")
+            if not (np.isfinite(lo) and np.isfinite(hi) and lo <= hi):
+                raise ValueError(f"IntensityAugment: {name} range ({lo!r}, {hi!r}) is not finite with low <= high")
+            if name == "noise" and lo < 0:
+                raise ValueError(f"IntensityAugment: noise variance range ({lo!r}, {hi!r}) is negative")
+            if name == "gamma" and lo <= 0:
+                raise ValueError(f"IntensityAugment: gamma range ({lo!r}, {hi!r}) must be positive")
+            if name == "blur":
+                gaussian_taps(lo), gaussian_taps(hi)                        # ValueError for a sigma the blur does not take
+            self.stages[name] = (p, lo, hi)
+        self.p_invert = float(p_invert)
+        if not 0.0 <= self.p_invert <= 1.0:
+            raise ValueError(f"IntensityAugment: p_invert {p_invert!r} outside [0, 1]")
+
+    @classmethod
+    def nnunet(cls):
+        return cls(noise=(0.1, (0.0, 0.1)), blur=(0.2, (0.5, 1.0)), brightness=(0.15, (0.75, 1.25)), contrast=(0.15, (0.75, 1.25)),
+                   gamma=(0.3, (0.7, 1.5)), p_invert=0.25)
+
+    def draw(self, n, generator):
+        """n INTENSITY_DRAW records from `generator`, a numpy.random.Generator (the module-level `random` and `np.random` streams,
+        which RawSliceParams and RandomGenerator share with the reference, are not touched).  The generator is consumed in a fixed
+        pattern -- 12 arrays of n whatever the coins show -- so the records depend on its state and n alone.  A stage that is
+        off keeps its neutral parameter."""
+        if not isinstance(generator, np.random.Generator):
+            raise ValueError(f"IntensityAugment.draw: generator must be a numpy.random.Generator, got {type(generator).__name__}")
+        out = np.zeros(int(n), INTENSITY_DRAW)
+        for name, field, neutral in (("blur", "sigma", 0.0), ("noise", "noise_std", 0.0), ("brightness", "brightness", 1.0),
+                                     ("contrast", "contrast", 1.0), ("gamma", "gamma", 1.0)):
+            p, lo, hi = self.stages[name]
+            on, value = generator.random(len(out)) < p, generator.uniform(lo, hi, len(out))
+            out["do_" + name] = on
+            out[field] = np.where(on, np.sqrt(value) if name == "noise" else value, neutral)
+        out["invert"] = out["do_gamma"] & (generator.random(len(out)) < self.p_invert)
+        out["seed"] = generator.integers(0, 2 ** 64, len(out), dtype=np.uint64)
+        return out
+
+
 def collate_raw_slices(samples):
     """default_collate for RawSliceParams' samples; slices of different shapes in one batch raise a ValueError that names them."""
     from torch.utils.data import default_collate

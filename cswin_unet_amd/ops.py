@@ -18,7 +18,7 @@ from ._lib import AugmentDesc, ConvImageJob, CswinHipError, ReduceJob, WgradDesc
 __all__ = ["layer_norm", "linear", "linear_pair", "mlp", "stripe_attention", "cswin_block", "conv_tokens", "patch_embed_conv", "carafe_reassemble",
            "carafe_reassemble_nchw", "conv_weight_images", "head_compose", "tokens_to_nchw", "matmul_nn", "ce_dice_loss", "continual_loss", "dropout", "img2windows", "windows2img",
            "seg_metrics", "connected_components", "filter_components", "COMPONENT_TILE", "resize_slices", "argmax_zoom_back", "augment_batch", "class_counts", "gaussian_blur",
-           "view_batch", "tta_argmax_zoom_back"]
+           "view_batch", "tta_argmax_zoom_back", "gaussian_blur_each", "intensity_batch"]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1439,6 +1439,94 @@ def gaussian_blur(x, sigma, truncate=4.0):
     y = torch.empty_like(x)
     call("cswin_gaussian_blur", ptr(x), ptr(y), ptr(taps), r, D, H, W, stream())
     return y
+
+
+def _blur_each_tables(sigmas, truncate=4.0):
+    """What cswin_gaussian_blur_each reads for a list of per-slice sigmas (None: the slice is copied): (table int32 (D, 2) of
+    (taps offset, radius), taps float64), the taps of each distinct sigma stored once as w[-r] .. w[0] behind the single tap 1.0
+    of the None slices.  Host only; ValueError for a sigma utils.gaussian_taps does not take."""
+    from .utils import gaussian_taps
+    entries, taps, table = {}, [np.ones(1)], np.zeros((len(sigmas), 2), np.int32)
+    for d, s in enumerate(sigmas):
+        if s is None:
+            continue                                                    # (0, 0): radius 0 at the tap 1.0
+        if float(s) not in entries:
+            w, r = gaussian_taps(s, truncate)
+            entries[float(s)] = (sum(len(t) for t in taps), r)
+            taps.append(w[:r + 1])
+        table[d] = entries[float(s)]
+    return table, np.concatenate(taps)
+
+
+def gaussian_blur_each(x, sigmas, truncate=4.0):
+    """gaussian_blur with a sigma of its own for every slice, in one launch: x (D, H, W) float32 HIP tensor, sigmas a sequence of
+    D entries, each None or a sigma gaussian_blur takes (ValueError otherwise).  Slice d of the result equals
+    gaussian_blur(x[d:d + 1], sigmas[d]) -- scipy's gaussian_filter of that slice -- bit for bit, and x[d] where the entry is None
+    (radius 0 with the single tap 1.0).  The slices' taps and the table of (offset, radius) go up in one pinned buffer per call;
+    the tile plan is the one of the largest radius."""
+    if not x.is_cuda:
+        raise CswinHipError(f"gaussian_blur_each input is on {x.device}: the cswin_unet_amd ops run on a HIP device only (no CPU fallback)")
+    if x.dtype != torch.float32:
+        raise CswinHipError(f"gaussian_blur_each input has dtype {x.dtype}; float32 is blurred")
+    if x.dim() != 3:
+        raise CswinHipError(f"gaussian_blur_each: input {tuple(x.shape)} must be (D, H, W)")
+    sigmas = list(sigmas)
+    if len(sigmas) != x.shape[0]:
+        raise ValueError(f"gaussian_blur_each: {len(sigmas)} sigmas for {x.shape[0]} slices")
+    D, H, W = x.shape
+    table, taps = _blur_each_tables(sigmas, truncate)
+    packed = np.concatenate([table.reshape(-1).view(np.float64), taps])              # D int32 pairs, then the float64 taps
+    x = x.contiguous()
+    buf = _upload(packed.view(np.int64), x.device).view(torch.float64)
+    y = torch.empty_like(x)
+    call("cswin_gaussian_blur_each", ptr(x), ptr(y), ptr(buf[D:]), len(taps), ptr(buf), int(table[:, 1].max()), D, H, W, stream())
+    return y
+
+
+INTENSITY_DESC = np.dtype([("flags", "<i8"), ("seed", "<u8"), ("noise_std", "<f8"), ("brightness", "<f8"), ("contrast", "<f8"),
+                           ("gamma", "<f8")])                                        # cswin_intensity_desc
+IN_NOISE, IN_BRIGHTNESS, IN_CONTRAST, IN_GAMMA, IN_INVERT = 1, 2, 4, 8, 16
+
+
+def _intensity_table(draws):
+    """(cswin_intensity_desc records of checked INTENSITY_DRAW records, the `stages` argument that goes with them).  Host only."""
+    table = np.zeros(len(draws), INTENSITY_DESC)
+    table["flags"] = (IN_NOISE * draws["do_noise"] + IN_BRIGHTNESS * draws["do_brightness"] + IN_CONTRAST * draws["do_contrast"] +
+                      IN_GAMMA * draws["do_gamma"] + IN_INVERT * (draws["invert"] & draws["do_gamma"]))
+    for f in ("seed", "noise_std", "brightness", "contrast", "gamma"):
+        table[f] = draws[f]
+    return table, int(np.bitwise_or.reduce(table["flags"], initial=0)) & (IN_CONTRAST | IN_GAMMA)
+
+
+def intensity_batch(images, draws):
+    """utils.intensity_host of every sample of a batch, on the device: images float32 HIP tensor (B, h, w) or (B, 1, h, w), draws
+    the HOST array of B datasets.INTENSITY_DRAW records (IntensityAugment.draw).  Returns a new float32 tensor of the same shape.
+    The blur stage is gaussian_blur_each (only if a sample blurs), the other four run in float64 in csrc/intensity.hip: one launch
+    for noise and brightness, one more if any sample has contrast, three more if any has gamma, a sample's workgroups leaving
+    at once the launches that do not concern it.  A sample's result is the same bits on every run and in any batch.  Current
+    stream, no synchronisation; the records go up as one pinned table and the workspace is the caching allocator's.  Every check
+    (ValueError for the records, CswinHipError for the tensor) comes before the first launch."""
+    if not images.is_cuda:
+        raise CswinHipError(f"intensity_batch images are on {images.device}: the cswin_unet_amd ops run on a HIP device only (no CPU fallback)")
+    if images.dtype != torch.float32:
+        raise CswinHipError(f"intensity_batch images have dtype {images.dtype}; float32 images are augmented")
+    if images.dim() not in (3, 4) or (images.dim() == 4 and images.shape[1] != 1) or images.numel() == 0:
+        raise CswinHipError(f"intensity_batch: images {tuple(images.shape)} must be (B, h, w) or (B, 1, h, w)")
+    from .datasets.dataset_synapse import check_intensity_draws
+    B, (h, w) = images.shape[0], images.shape[-2:]
+    draws = check_intensity_draws(draws, B)
+    table, stages = _intensity_table(draws)
+    x = images.contiguous().view(B, h, w)
+    if draws["do_blur"].any():
+        x = gaussian_blur_each(x, [float(d["sigma"]) if d["do_blur"] else None for d in draws])
+    y = torch.empty_like(x)
+    nbytes = lib().cswin_intensity_workspace(B, h * w) if stages else 0
+    if stages and not nbytes:
+        raise CswinHipError(f"cswin_intensity_workspace failed: {lib().cswin_last_error().decode()}")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device) if stages else None
+    table = _upload(table.view(np.int64), x.device)
+    call("cswin_intensity_batch", ptr(x), ptr(y), ptr(table), ptr(ws), nbytes, B, h * w, stages, stream())
+    return y.view(images.shape)
 
 
 _class_tables = {}

@@ -24,12 +24,13 @@ protocol with a CPU engine over gloo to check 2-rank == 1-rank-global-batch sema
 import math
 import os
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
 from ._lib import call, ptr, stream
 from .continual import Distill
-from .ops import CeDiceObjective, ContinualObjective, augment_batch, engine_backward
+from .ops import CeDiceObjective, ContinualObjective, augment_batch, engine_backward, intensity_batch
 from .optim import ADAM_MOMENTS, FlatAdamW, FlatSGD
 
 
@@ -490,15 +491,23 @@ class _Prefetcher:
     augment="hip": the loader yields RawSliceParams' raw batches (image, uint8 label, params); they are uploaded and finished by
     ops.augment_batch(..., output_size) on the same side stream, so the augmentation too overlaps the previous step, and the
     (image, label) pair handed out is the one the host path yields.  blur_sigma (augment="hip" only): augment_batch's; on the
-    host path the loader's RandomGenerator blurs."""
+    host path the loader's RandomGenerator blurs.
+    intensity: None, or a datasets.IntensityAugment: after the batch is on the device (and augment_batch has run, with
+    augment="hip") the prefetcher draws one record per sample from a numpy Generator of its own, seeded with intensity_seed (an
+    int or a sequence of ints), and ops.intensity_batch applies them to the images on the side stream; labels are untouched.
+    The draws happen in this process in batch order, so they do not depend on the loader's workers.  intensity_seed may also be
+    a numpy.random.Generator, which is then used and advanced: how one stream of draws spans several prefetchers (epochs)."""
 
-    def __init__(self, loader, device, augment="host", output_size=None, blur_sigma=None):
+    def __init__(self, loader, device, augment="host", output_size=None, blur_sigma=None, intensity=None, intensity_seed=0):
         if augment not in ("host", "hip"):
             raise ValueError(f'_Prefetcher: augment must be "host" or "hip", got {augment!r}')
         if augment == "hip" and (output_size is None or len(output_size) != 2):
             raise ValueError(f'_Prefetcher: augment="hip" needs output_size = (h, w), got {output_size!r}')
         self.it, self.device, self.augment, self.output_size = iter(loader), device, augment, output_size
         self.blur_sigma = blur_sigma if augment == "hip" else None
+        self.intensity = intensity
+        if intensity is not None:
+            self.intensity_rng = intensity_seed if isinstance(intensity_seed, np.random.Generator) else np.random.default_rng(intensity_seed)
         self.stream = torch.cuda.Stream(device)
         self._next()
 
@@ -514,6 +523,8 @@ class _Prefetcher:
                 # the raw uploads and augment_batch's temporaries are allocated, written and read on the side stream only: they
                 # never cross to the consumer's stream, only the two results do (recorded in __next__ like the host path's)
                 img, lab = augment_batch(img, lab, batch['params'], self.output_size, blur_sigma=self.blur_sigma)
+            if self.intensity is not None:                              # its temporaries, too, live and die on the side stream
+                img = intensity_batch(img, self.intensity.draw(img.shape[0], self.intensity_rng))
             self.batch = (img, lab)
 
     def __iter__(self):
@@ -538,7 +549,14 @@ def _step_options(args):
     from .optim import RATE_STATISTICS
     o = dict(optimizer=getattr(args, "optimizer", "sgd"), weight_decay=getattr(args, "weight_decay", 1e-4), w_ce=getattr(args, "w_ce", 0.4),
              w_dice=getattr(args, "w_dice", 0.6), lr_schedule=getattr(args, "lr_schedule", "poly"), moments=getattr(args, "moments", "kept"),
-             auto_rates=getattr(args, "auto_rates", None), subset=getattr(args, "subset_fraction", None))
+             auto_rates=getattr(args, "auto_rates", None), subset=getattr(args, "subset_fraction", None),
+             intensity=getattr(args, "intensity", None))
+    if o["intensity"] is not None:
+        from .datasets import IntensityAugment
+        if o["intensity"] == "nnunet":
+            o["intensity"] = IntensityAugment.nnunet()
+        elif not isinstance(o["intensity"], IntensityAugment):
+            raise ValueError(f'trainer_synapse: intensity must be None, "nnunet" or a datasets.IntensityAugment, got {o["intensity"]!r}')
     if o["optimizer"] not in ENGINE_OPTIMIZERS:
         raise ValueError(f"trainer_synapse: optimizer must be one of {ENGINE_OPTIMIZERS}, got {o['optimizer']!r}")
     if o["lr_schedule"] not in ("poly", "constant"):
@@ -578,6 +596,9 @@ def trainer_synapse(args, model, snapshot_path, group=None, log_every=1, checkpo
     "constant": the rate stays base_lr), moments ("kept" / "fresh": HipEngine's), auto_rates (None, or "grad" / "ratio": per-step
     rates over continual.finetune_groups(model) with that statistic, HipEngine.set_auto_rates), subset_fraction (None, or the part
     of the slices to train on, torch.randperm(n, generator=manual_seed(seed))[:n * fraction], finetune.py:166-169).
+    intensity: None (default), "nnunet" or a datasets.IntensityAugment: appearance augmentation of every batch on the device
+    (ops.intensity_batch on the prefetcher's stream, after either `augment` path), drawn from one numpy Generator seeded with
+    (seed, rank): ranks differ, and a seeded run draws the same records whatever num_workers is.
     checkpoint: None for the schedule above, or a function epoch -> file name or None."""
     import logging
     import random
@@ -649,10 +670,12 @@ def trainer_synapse(args, model, snapshot_path, group=None, log_every=1, checkpo
         from .continual import finetune_groups
         trainer.set_auto_rates(finetune_groups(model), opts["auto_rates"])
     iter_num = 0
+    intensity_rng = np.random.default_rng([int(seed), rank]) if opts["intensity"] is not None else None     # one stream over all epochs
     for epoch_num in range(max_epoch):
         if sampler is not None:
             sampler.set_epoch(epoch_num)
-        for image_batch, label_batch in _Prefetcher(loader, device, augment, (args.img_size, args.img_size), blur_sigma=blur_sigma):
+        for image_batch, label_batch in _Prefetcher(loader, device, augment, (args.img_size, args.img_size), blur_sigma=blur_sigma,
+                                                    intensity=opts["intensity"], intensity_seed=intensity_rng):
             stats = trainer.train_step(image_batch, label_batch)
             iter_num += 1
             if log_every and iter_num % log_every == 0 and rank == 0:

@@ -373,6 +373,65 @@ def gaussian_taps_device(sigma, truncate, device):
     return _device_tables[key]
 
 
+def mix64_host(z):
+    """csrc/layout.hip's mix64 on numpy uint64 (any shape): the whole splitmix64 step, increment included."""
+    z = np.asarray(z, np.uint64)
+    with np.errstate(over="ignore"):
+        z = z + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def intensity_noise_host(seed, n):
+    """The n standard normals n(seed, i), i < n, of the intensity augmentation's noise stage, float64: Box-Muller's cosine branch
+    on the two 24-bit uniforms of r = mix64(mix64(seed) ^ i), u1 = ((r >> 40) + 1) / 2^24 in (0, 1], u2 = ((r >> 16) & 0xFFFFFF)
+    / 2^24 in [0, 1).  csrc/intensity.hip generates the same on the device."""
+    r = mix64_host(mix64_host(np.uint64(seed)) ^ np.arange(n, dtype=np.uint64))
+    u1 = ((r >> np.uint64(40)) + np.uint64(1)).astype(np.float64) / 2.0 ** 24
+    u2 = ((r >> np.uint64(16)) & np.uint64(0xFFFFFF)).astype(np.float64) / 2.0 ** 24
+    return np.sqrt(-2 * np.log(u1)) * np.cos(2 * np.pi * u2)
+
+
+def intensity_host(x, draw):
+    """THE DEFINITION of the intensity augmentation (ops.intensity_batch is held to it): x one float32 image (h, w), draw one
+    datasets.INTENSITY_DRAW record.  The stages in this order, each only if its flag is on:
+      blur        scipy.ndimage.gaussian_filter(x, sigma) on the float32 image, float32 result (ops.gaussian_blur's semantics)
+      noise       z[i] += noise_std * intensity_noise_host(seed, h * w)[i], i the row-major pixel index
+      brightness  z *= brightness
+      contrast    m, lo, hi = mean, min, max of z;  z = clip((z - m) * contrast + m, lo, hi)
+      gamma       (z = -z if invert)  m0, s0 = mean, std (ddof=0);  lo = min, rng = max - lo;
+                  z = ((z - lo) / (rng + 1e-7)) ** gamma * rng + lo;  z = (z - mean(z)) / (std(z) + 1e-8) * s0 + m0  (z = -z again)
+    Apart from the blur everything is float64 from the float32 values, rounded to float32 once at the end; with every flag off the
+    image comes back bit for bit."""
+    from .datasets import check_intensity_draws
+    x = np.asarray(x)
+    if x.dtype != np.float32 or x.ndim != 2:
+        raise ValueError(f"intensity_host: x is {x.dtype} {x.shape}; one float32 image (h, w) is augmented")
+    d = check_intensity_draws(draw, 1)[0]
+    if d["do_blur"]:
+        x = gaussian_filter(x, float(d["sigma"]))
+    z = x.astype(np.float64)
+    if d["do_noise"]:
+        z = z + float(d["noise_std"]) * intensity_noise_host(d["seed"], z.size).reshape(z.shape)
+    if d["do_brightness"]:
+        z = z * float(d["brightness"])
+    if d["do_contrast"]:
+        m, lo, hi = z.mean(), z.min(), z.max()
+        z = np.clip((z - m) * float(d["contrast"]) + m, lo, hi)
+    if d["do_gamma"]:
+        if d["invert"]:
+            z = -z
+        m0, s0 = z.mean(), z.std()
+        lo = z.min()
+        rng = z.max() - lo
+        z = ((z - lo) / (rng + 1e-7)) ** float(d["gamma"]) * rng + lo
+        z = (z - z.mean()) / (z.std() + 1e-8) * s0 + m0
+        if d["invert"]:
+            z = -z
+    return z.astype(np.float32)
+
+
 def component_rule_tables(rule, ncls):
     """The per-class tables of a component filter rule: ``(min_size int64 [ncls], min_fraction float64 [ncls])``.  rule is
     "largest" (min_fraction 1 for every foreground class) or a mapping {class_id: {"min_size": int, "min_fraction": float}} with

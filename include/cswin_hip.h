@@ -31,7 +31,7 @@ extern "C" {
  * compiled against another header must refuse to call it.  Entry points that are only ADDED (cswin_seg_metrics*, cswin_resize_banded, cswin_argmax_zoom_back, cswin_augment_*,
  * cswin_chunk_sumsq, cswin_norm_finalize, cswin_adamw_flat, cswin_tpgm_*, cswin_argmax_zoom_back_classes, cswin_class_counts, cswin_gaussian_blur, cswin_eb_tiles,
  * cswin_eb_finalize, cswin_rate_finalize, cswin_adam_flat, cswin_components_*, cswin_drop_path_order, cswin_linear_*_skip,
- * cswin_surface_dist*, cswin_view_batch, cswin_tta_argmax_zoom_back) do not bump it: every prototype an older consumer binds is unchanged. */
+ * cswin_surface_dist*, cswin_view_batch, cswin_tta_argmax_zoom_back, cswin_gaussian_blur_each, cswin_intensity_*) do not bump it: every prototype an older consumer binds is unchanged. */
 #define CSWIN_ABI_VERSION 4
 
 #define CSWIN_OK 0
@@ -577,6 +577,39 @@ int cswin_class_counts(const void* labels, int label_bytes, const int* label_map
  * synchronisation.  Each of D, H, W in 1..2048 (CSWIN_ERR_SHAPE), radius in 0..32 and x != y (CSWIN_ERR_UNSUPPORTED: the filter
  * does not work in place); pointers aligned to their element size. */
 int cswin_gaussian_blur(const float* x, float* y, const double* taps, int radius, int D, int H, int W, void* stream);
+/* The same filter with a radius and taps of its own for every slice, in one launch.  table (D pairs of int32, device): slice d has
+ * radius table[2d + 1] in 0..max_radius and the taps taps[table[2d] .. table[2d] + radius] (w[-radius] .. w[0] as above) of the
+ * ntaps float64 behind `taps` (device; max_radius < ntaps <= 2048 * 33).  Radius 0 with the single tap 1.0 copies the slice (the
+ * sums above then are x[i] * 1.0).  The tile plan is that of max_radius; a radius or an offset outside what max_radius and ntaps
+ * allow is clamped on the device.  Slice d equals cswin_gaussian_blur of that slice with its taps, bit for bit.  Limits,
+ * alignment and error codes as above. */
+int cswin_gaussian_blur_each(const float* x, float* y, const double* taps, int ntaps, const int* table, int max_radius, int D, int H,
+                             int W, void* stream);
+
+/* ---- intensity augmentation of a batch of images (csrc/intensity.hip): stages 2-5 of cswin_unet_amd.utils.intensity_host ----
+ * One 48-byte record per sample in a device table (8-B aligned).  flags: 1 noise, 2 brightness, 4 contrast, 8 gamma, 16 the gamma
+ * stage works on -z (read only with 8); other bits are ignored.  With z the float64 of the sample's float32 pixels, i the row-major
+ * pixel index within the sample:
+ *   noise       z[i] += noise_std * sqrt(-2 ln u1) cos(2 pi u2),  r = mix64(mix64(seed) ^ i) (splitmix64's step, increment
+ *               included),  u1 = ((r >> 40) + 1) / 2^24,  u2 = ((r >> 16) & 0xFFFFFF) / 2^24
+ *   brightness  z *= brightness
+ *   contrast    m, lo, hi = mean, min, max of z;  z = min(max((z - m) * contrast + m, lo), hi)
+ *   gamma       m0, s0 = mean, population standard deviation;  lo = min, rng = max - lo;
+ *               z = ((z - lo) / (rng + 1e-7)) ** gamma * rng + lo;  z = (z - mean(z)) / (std(z) + 1e-8) * s0 + m0
+ * in this order, each only if its flag is set, all in float64 with separately rounded products and sums, y = float32(z).  The
+ * whole-image sums are formed in a fixed order: a sample's result is the same on every run and whatever else the batch holds.
+ * stages: the OR of the samples' contrast (4) and gamma (8) flags, which decides the launches (1 + 1 + 3 at most); a flag
+ * that `stages` lacks is off for every sample.  workspace: cswin_intensity_workspace(B, slice_elems) bytes, 8-B aligned, needed
+ * only where stages != 0.  x == y is allowed.  B in 1..2048, slice_elems in 1..2048 * 2048 (CSWIN_ERR_SHAPE); the parameters are
+ * the caller's to check (gamma > 0, finite values).  No allocation, no synchronisation, no atomics. */
+typedef struct cswin_intensity_desc {
+    long long flags;
+    unsigned long long seed;
+    double noise_std, brightness, contrast, gamma;
+} cswin_intensity_desc;
+size_t cswin_intensity_workspace(int B, long slice_elems);
+int cswin_intensity_batch(const float* x, float* y, const void* table, void* workspace, size_t ws_bytes, int B, long slice_elems,
+                          int stages, void* stream);
 
 /* ---- test-time augmentation of a volume evaluation (csrc/tta.hip): the eight symmetries of the square, which training's
  *      random_rot_flip draws from (datasets/dataset_synapse.py:12-19), applied before the network and ensembled after it ----
