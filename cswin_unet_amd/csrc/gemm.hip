@@ -400,6 +400,12 @@ __global__ __launch_bounds__(64) void drop_path_order_kernel(const float* __rest
     }
 }
 
+// compile-time switch of the epilogue's early operand request (gemm_body: AHEAD), 0 = every launch keeps the loads behind its last MFMA
+#ifndef CSWIN_EPI_AHEAD
+#define CSWIN_EPI_AHEAD 1
+#endif
+constexpr bool EPI_AHEAD = CSWIN_EPI_AHEAD != 0;
+
 // debug stamps: thread 0 writes s_memtime to `slot` of the workgroup's row; slot 0 also the hardware id and s_memrealtime, slot 3 the latter
 __device__ __forceinline__ void stamp(const Epilogue& epi, int row, int slot) {
     if (!epi.stamps || threadIdx.x != 0) return;
@@ -602,12 +608,76 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
     float csum = 0.f;   // dbias partial (TN, A row-contiguous image: column tid of the A tile)
     const bool do_colsum = !A_RC && epi.colsum && n0 == 0 && tid < BM;
 
+    // AHEAD: the operands of the wave's first epilogue fragment (bias, row factors, residual / gelu_pre chunks; MAPPED: through ord) are
+    // requested where the last k-tile would fetch its successor, in front of that tile's MFMAs, not behind them.  A workgroup with one
+    // k-tile requests before its only tile, a fill tile (no k-loop) before its epilogue.  Forward and data-gradient launches with 16-B
+    // loaders in fp32; the weight gradients' plain epilogue has nothing to request.  Per instantiation, by the kernel traces and the
+    // register table of profiles/gemm_edges_notes.md: the residual and GELU' epilogues, every data gradient and the forward launches
+    // of the concat and gather sources take it; a plain matrix's forward whose epilogue has a bias alone to fetch keeps the old form
+    // (measured 0 to 1.7 us slower per launch), and so does every kernel of four k-groups (the residual forward 4.8 us slower; the
+    // concat and gather sources' would go from 8 to 7 waves per SIMD, one resident workgroup of 16 waves instead of two).
+    constexpr bool AHEAD = EPI_AHEAD && A_RC && VEC == 4 && PREC == 0 && KW != 4 &&
+                           (EPI == EPI_RES || EPI == EPI_GELUBWD || !B_RC || !is_plain<ASrc>);
+    EpiOperands eq;
+    auto request = [&]() {
+        if (KW > 1 && kg != 0) return;               // the k-groups that leave before the epilogue
+        const int mf = m0 + wm0, nf = n0 + wn0;
+        if constexpr (MAPPED) {
+            epilogue_request<EPI, false, true>(eq, epi, M, N, mf, nf, lane, mapped ? ord : nullptr, kept_rows, rm->rows_per_sample, rm->magic);
+        } else {
+            if (!epi.vec_store) return;              // the scalar path loads where it computes
+            if (EPI == EPI_GELUBWD && epi.pre_bf16) epilogue_request<EPI, true, false>(eq, epi, M, N, mf, nf, lane);
+            else epilogue_request<EPI, false, false>(eq, epi, M, N, mf, nf, lane);
+        }
+    };
+
+    // one k-tile's MFMAs as the AHEAD launches run them (fp32, r-contiguous A): the k-loop's fp32 section below, for these alone
+    auto mma_tile = [&]() {
+#pragma unroll
+        for (int kk = kg * (BK / KW); kk < (kg + 1) * (BK / KW); kk += 8) {
+            f32x4 af[FM], bf[FN];
+#pragma unroll
+            for (int i = 0; i < FM; ++i) af[i] = *reinterpret_cast<const f32x4*>(&As[(wm0 + i * 32 + li) * TA::LD + kk + 4 * lh]);
+#pragma unroll
+            for (int j = 0; j < FN; ++j) {
+                if (B_RC) {
+                    bf[j] = *reinterpret_cast<const f32x4*>(&Bs[(wn0 + j * 32 + li) * TB::LD + kk + 4 * lh]);
+                } else {
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) bf[j][s] = Bs[(kk + 4 * lh + s) * TB::LD + wn0 + j * 32 + li];
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+#pragma unroll
+                for (int i = 0; i < FM; ++i)
+#pragma unroll
+                    for (int j = 0; j < FN; ++j)
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][s], bf[j][s], acc[i][j], 0, 0, 0);
+        }
+    };
+
     stamp(epi, stamp_row, 0);
     auto main_loop = [&](auto a16, auto b16) {
         fetch(r_begin, a16, b16);
         stash(a16, b16);
         __syncthreads();
         stamp(epi, stamp_row, 1);
+        if constexpr (AHEAD) {
+            // the last tile stands outside the loop, so that the epilogue's operands are held through that tile alone, where the
+            // prefetch registers are free, not through the loop
+            for (int r0 = r_begin; r0 + BK < r_end; r0 += BK) {
+                fetch(r0 + BK, a16, b16);
+                mma_tile();
+                __syncthreads();
+                stash(a16, b16);
+                __syncthreads();
+            }
+            request();
+            mma_tile();
+            __syncthreads();
+            return;
+        }
         for (int r0 = r_begin; r0 < r_end; r0 += BK) {
             const bool more = r0 + BK < r_end;
             if (more) fetch(r0 + BK, a16, b16);
@@ -709,6 +779,8 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
         } else {
             main_loop(std::false_type{}, std::false_type{});
         }
+    } else if constexpr (AHEAD) {
+        request();
     }
 
     stamp(epi, stamp_row, 2);
@@ -743,17 +815,23 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
     Epilogue e = epi;
     e.C += (long)split * e.split_stride;
     if constexpr (MAPPED) {
-        run_epilogue<EPI, FM, FN, false, false, true>(e, acc, M, N, m0 + wm0, n0 + wn0, lane, lds + wave * EP_WAVE_FLOATS, true, 0, 0,
-                                                      mapped ? ord : nullptr, kept_rows, rm->rows_per_sample, rm->magic);
+        run_epilogue<EPI, FM, FN, false, false, true, AHEAD>(e, acc, M, N, m0 + wm0, n0 + wn0, lane, lds + wave * EP_WAVE_FLOATS, true, 0, 0,
+                                                             mapped ? ord : nullptr, kept_rows, rm->rows_per_sample, rm->magic, &eq);
     } else if constexpr (EPI == EPI_GELUBWD) {
-        if (e.pre_bf16) run_epilogue<EPI, FM, FN, true>(e, acc, M, N, m0 + wm0, n0 + wn0, lane, lds + wave * EP_WAVE_FLOATS, e.vec_store != 0);
-        else run_epilogue<EPI, FM, FN, false>(e, acc, M, N, m0 + wm0, n0 + wn0, lane, lds + wave * EP_WAVE_FLOATS, e.vec_store != 0);
+        if (e.pre_bf16)
+            run_epilogue<EPI, FM, FN, true, false, false, AHEAD>(e, acc, M, N, m0 + wm0, n0 + wn0, lane, lds + wave * EP_WAVE_FLOATS, e.vec_store != 0, 0, 0,
+                                                                 nullptr, 0, 1, 0, &eq);
+        else
+            run_epilogue<EPI, FM, FN, false, false, false, AHEAD>(e, acc, M, N, m0 + wm0, n0 + wn0, lane, lds + wave * EP_WAVE_FLOATS, e.vec_store != 0, 0, 0,
+                                                                  nullptr, 0, 1, 0, &eq);
     } else {
         // a FAST gather source brings the reciprocals of its own row split, which is the epilogue's (rm_on: the parity classes)
         if constexpr (ASrc::fast_div)
-            run_epilogue<EPI, FM, FN, false, true>(e, acc, M, N, m0 + wm0, n0 + wn0, lane, lds + wave * EP_WAVE_FLOATS, e.vec_store != 0, A.m.img, A.m.w);
+            run_epilogue<EPI, FM, FN, false, true, false, AHEAD>(e, acc, M, N, m0 + wm0, n0 + wn0, lane, lds + wave * EP_WAVE_FLOATS, e.vec_store != 0, A.m.img,
+                                                                 A.m.w, nullptr, 0, 1, 0, &eq);
         else
-            run_epilogue<EPI, FM, FN>(e, acc, M, N, m0 + wm0, n0 + wn0, lane, lds + wave * EP_WAVE_FLOATS, e.vec_store != 0);
+            run_epilogue<EPI, FM, FN, false, false, false, AHEAD>(e, acc, M, N, m0 + wm0, n0 + wn0, lane, lds + wave * EP_WAVE_FLOATS, e.vec_store != 0, 0, 0,
+                                                                  nullptr, 0, 1, 0, &eq);
     }
     stamp(epi, stamp_row, 3);
     if (do_colsum && m0 + tid < M) epi.colsum[(long)split * epi.colsum_stride + m0 + tid] = csum;

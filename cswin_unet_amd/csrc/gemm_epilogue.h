@@ -45,6 +45,61 @@ struct Epilogue {
 constexpr int EP_LD = 36;
 constexpr int EP_WAVE_FLOATS = 32 * EP_LD;
 
+// The auxiliary operands of one fragment's vector path, in registers: bias, and per row chunk p the row factor, the residual /
+// gelu_pre chunk (aux16: stored as bf16) and, MAPPED, the row's place in memory.
+struct EpiOperands { f32x4 bias; f32x4 aux[4]; u32x2 aux16[4]; float rs[4]; int pm[4]; };
+
+// MAPPED: the place in memory of logical row m and, in smp, its sample (ord == NULL, the identity, or a row past the end: m and 0)
+__device__ __forceinline__ int epi_mapped_row(int m, int M, const int* ord, int map_rps, unsigned map_magic, int& smp) {
+    smp = 0;
+    if (!ord || m >= M) return m;
+    const int j = fdiv1(m, map_magic);
+    smp = ord[j];
+    return smp * map_rps + (m - j * map_rps);
+}
+
+// The request part of the epilogue: the loads of the fragment at (mf, nf) = (mb + 32 i, nb + 32 j), none of which depends on the
+// accumulators.  gemm.hip's k-loop calls it for a wave's first fragment in front of its last tile's MFMAs (AHEAD below), so that the
+// round trip -- MAPPED: ord[j] -> row_scale[ord[j]] and the aux row's address -> the aux load -- runs under matrix work instead of
+// after it.  Lanes with m >= M or n >= N load nothing and a dropped row's gelu_pre is not read, as before.
+template <int EPI, bool PRE16, bool MAPPED>
+__device__ __forceinline__ void epilogue_request(EpiOperands& q, const Epilogue& e, int M, int N, int mf, int nf, int lane,
+                                                 const int* ord = nullptr, int kept_rows = 0, int map_rps = 1, unsigned map_magic = 0) {
+    const int rrow = lane >> 3, n = nf + (lane & 7) * 4;
+    const bool has_rs = e.row_scale != nullptr;
+    q.bias = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (e.bias && n < N) q.bias = *reinterpret_cast<const f32x4*>(e.bias + n);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const int m = mf + rrow + 8 * p;
+        const bool ok = m < M && n < N;
+        if constexpr (MAPPED) {
+            int smp = 0;
+            q.pm[p] = epi_mapped_row(m, M, ord, map_rps, map_magic, smp);
+            const bool dropped = ord && m >= kept_rows;
+            q.rs[p] = (has_rs && ok) ? e.row_scale[ord ? smp : m / e.rows_per_sample] : 1.0f;
+            if (EPI == EPI_RES || EPI == EPI_GELUBWD) {
+                const float* ap = EPI == EPI_RES ? e.residual : e.gelu_pre;
+                const long ld = EPI == EPI_RES ? e.ldres : e.ldpre;
+                q.aux[p] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (ok && !(EPI == EPI_GELUBWD && dropped)) q.aux[p] = *reinterpret_cast<const f32x4*>(ap + (long)q.pm[p] * ld + n);
+            }
+            continue;
+        }
+        q.rs[p] = (has_rs && ok) ? e.row_scale[m / e.rows_per_sample] : 1.0f;
+        if (EPI == EPI_RES || EPI == EPI_GELUBWD) {
+            const float* ap = EPI == EPI_RES ? e.residual : e.gelu_pre;
+            const long ld = EPI == EPI_RES ? e.ldres : e.ldpre;
+            q.aux[p] = f32x4{0.f, 0.f, 0.f, 0.f};
+            q.aux16[p] = u32x2{0u, 0u};
+            if (ok) {
+                if constexpr (PRE16) q.aux16[p] = *reinterpret_cast<const u32x2*>(reinterpret_cast<const __bf16*>(ap) + (long)m * ld + n);
+                else q.aux[p] = *reinterpret_cast<const f32x4*>(ap + (long)m * ld + n);
+            }
+        }
+    }
+}
+
 // PRE16: gelu_pre is stored as bf16 (EPI_GELUBWD) -- compile-time, so that the four auxiliary loads of a fragment stay in one
 // basic block and are issued back to back.
 // FDIV: the row split of rm_on by multiply-high with the reciprocals m_hw, m_w2 of rm_H2 * rm_W2 and rm_W2 (fdiv, common.h; the
@@ -56,10 +111,14 @@ constexpr int EP_WAVE_FLOATS = 32 * EP_LD;
 // ord[j] * map_rps + (m - j * map_rps) the row of every matrix the epilogue addresses.  Rows from kept_rows on belong to dropped
 // samples: their accumulators are zeros by construction, gelu_pre is not read for them, and a residual epilogue stores their
 // residual row as it is.
-template <int EPI, int FM, int FN, bool PRE16 = false, bool FDIV = false, bool MAPPED = false>
+// The consume part: every fragment goes through the wave's LDS patch, meets its operands and is stored.  AHEAD: `first` already holds
+// the operands of fragment (0, 0) (vector path); a later fragment's are requested while the one before it is computed and stored.
+// Otherwise each fragment requests its own behind its transposition, the order these loads always had.
+template <int EPI, int FM, int FN, bool PRE16 = false, bool FDIV = false, bool MAPPED = false, bool AHEAD = false>
 __device__ __forceinline__ void run_epilogue(const Epilogue& e, f32x16 (&acc)[FM][FN], int M, int N, int mb, int nb,
                                              int lane, float* wbuf, bool vec, unsigned m_hw = 0, unsigned m_w2 = 0,
-                                             const int* ord = nullptr, int kept_rows = 0, int map_rps = 1, unsigned map_magic = 0) {
+                                             const int* ord = nullptr, int kept_rows = 0, int map_rps = 1, unsigned map_magic = 0,
+                                             const EpiOperands* first = nullptr) {
     const int li = lane & 31, lh = lane >> 5;
     const int rrow = lane >> 3, rcol = (lane & 7) * 4;
     const bool has_rs = e.row_scale != nullptr;
@@ -72,6 +131,10 @@ __device__ __forceinline__ void run_epilogue(const Epilogue& e, f32x16 (&acc)[FM
         const int rem = m - b * hw;
         return ((long)b * e.rm_H + 2 * jy + e.rm_py) * e.rm_W + 2 * (rem - jy * e.rm_W2) + e.rm_px;
     };
+    EpiOperands q;                                // the current fragment's operands (vector path)
+    if constexpr (AHEAD) {
+        if (vec) q = *first;
+    }
 #pragma unroll
     for (int i = 0; i < FM; ++i) {
 #pragma unroll
@@ -83,46 +146,24 @@ __device__ __forceinline__ void run_epilogue(const Epilogue& e, f32x16 (&acc)[FM
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             const int n = nb + j * 32 + rcol;
             if (vec) {
-                f32x4 bias_v = {0.f, 0.f, 0.f, 0.f};
-                if (e.bias && n < N) bias_v = *reinterpret_cast<const f32x4*>(e.bias + n);
-                f32x4 v[4], aux[4];
-                u32x2 aux16[4];
-                float rs[4];
-                int pm[4];                                 // MAPPED: the rows' places in memory
+                EpiOperands nq;                            // AHEAD: the next fragment's operands, requested under this one's stores
+                if constexpr (!AHEAD) epilogue_request<EPI, PRE16, MAPPED>(q, e, M, N, mb + i * 32, nb + j * 32, lane, ord, kept_rows, map_rps, map_magic);
+                f32x4 v[4];
+#pragma unroll
+                for (int p = 0; p < 4; ++p) v[p] = *reinterpret_cast<const f32x4*>(&wbuf[(rrow + 8 * p) * EP_LD + rcol]);
+                if constexpr (AHEAD && FM * FN > 1) {
+                    const int f = i * FN + j + 1;
+                    if (f < FM * FN) epilogue_request<EPI, PRE16, MAPPED>(nq, e, M, N, mb + (f / FN) * 32, nb + (f % FN) * 32, lane, ord, kept_rows, map_rps, map_magic);
+                }
+                const f32x4 bias_v = q.bias;
+                const f32x4 (&aux)[4] = q.aux;
+                const u32x2 (&aux16)[4] = q.aux16;
+                const float (&rs)[4] = q.rs;
+                int pm[4];     // MAPPED: the rows' places in memory; AHEAD: made again from ord in LDS, not held through the last k-tile
 #pragma unroll
                 for (int p = 0; p < 4; ++p) {
-                    const int m = mb + i * 32 + rrow + 8 * p;
-                    const bool ok = m < M && n < N;
-                    v[p] = *reinterpret_cast<const f32x4*>(&wbuf[(rrow + 8 * p) * EP_LD + rcol]);
-                    if constexpr (MAPPED) {
-                        pm[p] = m;
-                        int smp = 0;
-                        if (ord && m < M) {
-                            const int j = fdiv1(m, map_magic);
-                            smp = ord[j];
-                            pm[p] = smp * map_rps + (m - j * map_rps);
-                        }
-                        const bool dropped = ord && m >= kept_rows;
-                        rs[p] = (has_rs && ok) ? e.row_scale[ord ? smp : m / e.rows_per_sample] : 1.0f;
-                        if (EPI == EPI_RES || EPI == EPI_GELUBWD) {
-                            const float* ap = EPI == EPI_RES ? e.residual : e.gelu_pre;
-                            const long ld = EPI == EPI_RES ? e.ldres : e.ldpre;
-                            aux[p] = f32x4{0.f, 0.f, 0.f, 0.f};
-                            if (ok && !(EPI == EPI_GELUBWD && dropped)) aux[p] = *reinterpret_cast<const f32x4*>(ap + (long)pm[p] * ld + n);
-                        }
-                        continue;
-                    }
-                    rs[p] = (has_rs && ok) ? e.row_scale[m / e.rows_per_sample] : 1.0f;
-                    if (EPI == EPI_RES || EPI == EPI_GELUBWD) {
-                        const float* ap = EPI == EPI_RES ? e.residual : e.gelu_pre;
-                        const long ld = EPI == EPI_RES ? e.ldres : e.ldpre;
-                        aux[p] = f32x4{0.f, 0.f, 0.f, 0.f};
-                        aux16[p] = u32x2{0u, 0u};
-                        if (ok) {
-                            if constexpr (PRE16) aux16[p] = *reinterpret_cast<const u32x2*>(reinterpret_cast<const __bf16*>(ap) + (long)m * ld + n);
-                            else aux[p] = *reinterpret_cast<const f32x4*>(ap + (long)m * ld + n);
-                        }
-                    }
+                    int smp;
+                    pm[p] = (MAPPED && AHEAD) ? epi_mapped_row(mb + i * 32 + rrow + 8 * p, M, ord, map_rps, map_magic, smp) : q.pm[p];
                 }
 #pragma unroll
                 for (int p = 0; p < 4; ++p) {
@@ -160,6 +201,7 @@ __device__ __forceinline__ void run_epilogue(const Epilogue& e, f32x16 (&acc)[FM
                         epi_store4(e.Cact, (long)m * e.ldact + n, a, e.c_bf16);
                     }
                 }
+                if constexpr (AHEAD && FM * FN > 1) q = nq;
             } else {
 #pragma unroll
                 for (int p = 0; p < 4; ++p) {
