@@ -70,6 +70,12 @@ SIGNATURES = {
     "cswin_cl_loss_sums": (I, [P, P, P, I, P, P, P, P, SZ, I, I, I, L, F, F, F, P]),
     "cswin_cl_loss_finalize": (I, [P, P, P, D, D, I, F, F, F, F, P]),
     "cswin_cl_loss_bwd": (I, [P, P, P, I, P, P, P, P, P, F, F, F, I, I, I, L, F, F, F, P]),
+    "cswin_sdm_workspace": (SZ, [I, I, I, I]),
+    "cswin_signed_distance_maps": (I, [P, P, P, SZ, I, I, I, I, P]),
+    "cswin_bd_loss_workspace": (SZ, [I, I, L]),
+    "cswin_bd_loss_sums": (I, [P, P, P, P, P, P, SZ, I, I, L, P]),
+    "cswin_bd_loss_finalize": (I, [P, P, P, D, I, F, F, P, P, P]),
+    "cswin_bd_loss_bwd": (I, [P, P, P, P, P, P, P, P, F, F, F, I, I, L, P]),
     "cswin_dropout": (I, [P, P, P, P, L, L, F, ctypes.c_ulonglong, P, P]),
     "cswin_sgd_flat": (I, [P, P, P, L, P, F, F, F, P, P]),
     "cswin_multi_copy": (I, [P, I, P]),

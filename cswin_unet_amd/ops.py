@@ -18,7 +18,7 @@ from ._lib import AugmentDesc, ConvImageJob, CswinHipError, ReduceJob, WgradDesc
 __all__ = ["layer_norm", "linear", "linear_pair", "mlp", "stripe_attention", "cswin_block", "conv_tokens", "patch_embed_conv", "carafe_reassemble",
            "carafe_reassemble_nchw", "conv_weight_images", "head_compose", "tokens_to_nchw", "matmul_nn", "ce_dice_loss", "continual_loss", "dropout", "img2windows", "windows2img",
            "seg_metrics", "connected_components", "filter_components", "COMPONENT_TILE", "resize_slices", "argmax_zoom_back", "augment_batch", "class_counts", "gaussian_blur",
-           "view_batch", "tta_argmax_zoom_back", "gaussian_blur_each", "intensity_batch"]
+           "view_batch", "tta_argmax_zoom_back", "gaussian_blur_each", "intensity_batch", "signed_distance_maps", "boundary_loss"]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1062,11 +1062,12 @@ def windows2img(img_splits_hw, H_sp, W_sp, H, W):
 
 
 # ------------------------------------------------------------------------------------------------
-# segmentation objectives: CE + Dice (csrc/loss.hip) and focal CE + Dice + distillation (csrc/cl_loss.hip)
+# segmentation objectives: CE + Dice (csrc/loss.hip), focal CE + Dice + distillation (csrc/cl_loss.hip) and CE + Dice + boundary
+# (csrc/bd_loss.hip, on the signed distance maps of csrc/sdm.hip)
 #
 # An objective has n_sums(ncls), n_stats, sums() (this rank's partial sums, left in device memory: they add across ranks),
 # finalize() (the -- possibly all-reduced -- sums -> stats and the Dice gradient coefficients) and grad() (d loss / d logits).
-# _SegLoss drives either under autograd, HipEngine (trainer.py) calls the same methods inside its captured graphs.  grad_scales()
+# _SegLoss drives any of them under autograd, HipEngine (trainer.py) calls the same methods inside its captured graphs.  grad_scales()
 # alone forms the gradient scales: gradients are averaged over ranks afterwards, so local means keep the local counts and the
 # global Dice gets the world size.
 # ------------------------------------------------------------------------------------------------
@@ -1223,6 +1224,104 @@ def continual_loss(logits, labels, teacher_logits, *, w_focal=0.2, w_dice=0.8, k
     spec = types.SimpleNamespace(w_focal=float(w_focal), w_dice=float(w_dice), kd_weight=float(kd_weight), temperature=float(temperature),
                                  focal_gamma=float(focal_gamma), focal_alpha=float(focal_alpha), class_weight=class_weight, label_map=label_map)
     return _SegLoss.apply(logits, labels, teacher, ContinualObjective(spec), group)
+
+
+def signed_distance_maps(labels, ncls):
+    """The boundary loss's signed distance maps of a label batch on the device (csrc/sdm.hip): labels (B, H, W) int64 HIP tensor ->
+    float32 (B, ncls, H, W), utils.signed_distance_maps_host bit for bit: +distance to the class outside its mask, -(distance to
+    the outside - 1) inside, zeros for a class that is absent from a slice or fills it, Euclidean, in pixels, per 2-D slice.
+    1 <= H, W <= 2047, 2 <= ncls <= 255.  No host sync; the row pass's workspace (half the bytes of the result) is freed on return."""
+    if not labels.is_cuda:
+        raise CswinHipError(f"signed_distance_maps labels are on {labels.device}: the cswin_unet_amd ops run on a HIP device only (no CPU fallback)")
+    if labels.dim() != 3:
+        raise ValueError(f"signed_distance_maps: labels {tuple(labels.shape)} must be (B, H, W)")
+    labels = labels.contiguous()
+    if labels.dtype != torch.int64:
+        labels = labels.long()
+    (B, H, W), ncls = labels.shape, int(ncls)
+    nbytes = lib().cswin_sdm_workspace(B, ncls, H, W)
+    if nbytes == 0:
+        raise ValueError(f"signed_distance_maps: {lib().cswin_last_error().decode()}")
+    phi = torch.empty(B, ncls, H, W, dtype=torch.float32, device=labels.device)
+    call("cswin_signed_distance_maps", ptr(labels), ptr(phi), ptr(_ws(nbytes, labels.device)), nbytes, B, ncls, H, W, stream())
+    return phi
+
+
+class BoundaryObjective:
+    """w_ce * CE + w_dice * Dice + alpha * boundary (Kervadec et al., MIDL 2019), boundary = the mean over pixels of
+    sum_c wb_c * softmax_c * phi_c with phi the labels' signed distance maps; stats = [loss, ce, dice, boundary].  CE and Dice are
+    CeDiceObjective's (class_weight: the Dice's); boundary_class_weight: (ncls,) device tensor, or None for 0 on class 0 and 1 on
+    the rest.  alpha lives in a one-float device tensor that the kernels read, so set_boundary_weight reaches a captured step.
+    sums() makes phi from the labels it is given (which must then be (B, H, W)) and keeps it for grad(); dist_maps: a
+    (B, ncls, H, W) tensor to use instead, for a caller who caches the maps."""
+    n_stats = 4
+
+    def __init__(self, w_ce=0.4, w_dice=0.6, alpha=0.01, class_weight=None, boundary_class_weight=None, dist_maps=None):
+        self.w_ce, self.w_dice, self.class_weight, self.boundary_class_weight = w_ce, w_dice, class_weight, boundary_class_weight
+        self.alpha, self.alpha_dev, self.dist_maps, self._phi = float(alpha), None, dist_maps, None
+
+    @staticmethod
+    def n_sums(ncls):
+        return 2 + 3 * ncls
+
+    def set_boundary_weight(self, alpha):
+        """An eager fill of the device float (as the optimisers' set_lr): the next step, replayed or not, uses it."""
+        self.alpha = float(alpha)
+        if self.alpha_dev is not None:
+            self.alpha_dev.fill_(self.alpha)
+
+    def _alpha(self, device):
+        if self.alpha_dev is None:
+            self.alpha_dev = torch.full((1,), self.alpha, dtype=torch.float32, device=device)
+        return self.alpha_dev
+
+    def sums(self, logits, labels, sums, teacher=None):
+        B, ncls, HW = _pixels(logits)
+        if self.dist_maps is not None:
+            self._phi = self.dist_maps
+        else:
+            if labels.dim() != 3:
+                raise ValueError(f"BoundaryObjective: labels {tuple(labels.shape)} must be (B, H, W) to form the distance maps")
+            self._phi = signed_distance_maps(labels, ncls)
+        nbytes = lib().cswin_bd_loss_workspace(B, ncls, HW)
+        call("cswin_bd_loss_sums", ptr(logits), ptr(labels), ptr(self._phi), ptr(self.boundary_class_weight), ptr(sums),
+             ptr(_ws(nbytes, logits.device)), nbytes, B, ncls, HW, stream())
+
+    def finalize(self, sums, out, coef, n_pixels, batch):
+        call("cswin_bd_loss_finalize", ptr(sums), ptr(out), ptr(coef), float(n_pixels), coef.numel() // 2, self.w_ce, self.w_dice,
+             ptr(self._alpha(sums.device)), ptr(self.class_weight), stream())
+
+    def grad_scales(self, B, HW, ncls, world):
+        """(ce_scale, dice_scale, bd_scale) of cswin_bd_loss_bwd: the boundary mean keeps the local count, as CE does."""
+        return self.w_ce / float(B * HW), self.w_dice / ncls * world, 1.0 / float(B * HW)
+
+    def grad(self, logits, labels, coef, dice_grad_scale, teacher=None, gloss=None):
+        B, ncls, HW = _pixels(logits)
+        dlogits = torch.empty_like(logits)
+        call("cswin_bd_loss_bwd", ptr(logits), ptr(labels), ptr(self._phi), ptr(self.boundary_class_weight), ptr(coef),
+             ptr(self._alpha(logits.device)), ptr(gloss), ptr(dlogits), *self.grad_scales(B, HW, ncls, dice_grad_scale), B, ncls, HW, stream())
+        return dlogits
+
+
+def boundary_loss(logits, labels, alpha, w_ce=0.4, w_dice=0.6, class_weight=None, boundary_class_weight=None, dist_maps=None, group=None):
+    """w_ce * CE + w_dice * Dice + alpha * boundary (Kervadec et al., MIDL 2019) in one fused pass each way.  Returns (loss, stats)
+    with stats = [loss, ce, dice, boundary] (no host sync).  logits (B, ncls, H, W), labels (B, H, W) int64 on the device: their
+    signed distance maps are made there (signed_distance_maps), or pass dist_maps (B, ncls, H, W) to reuse cached ones.
+    class_weight: the Dice's (ncls,) weights; boundary_class_weight: the boundary term's, None = every class but 0.
+    With a process group the 2 + 3*ncls sums are all-reduced: Dice and the two means are the global batch's."""
+    logits, class_weight, wb, dist_maps = dev_f32(logits, "logits"), dev_f32(class_weight), dev_f32(boundary_class_weight), dev_f32(dist_maps, "dist_maps")
+    B, ncls, HW = _pixels(logits)
+    # the kernels index these by pixel and by class: a mismatch would be an out-of-bounds device read
+    if not labels.is_cuda or labels.numel() != B * HW:
+        raise ValueError(f"boundary_loss: labels {tuple(labels.shape)} on {labels.device} do not match logits {tuple(logits.shape)} on {logits.device}")
+    if dist_maps is None and (logits.dim() != 4 or tuple(labels.shape) != (B,) + tuple(logits.shape[2:])):
+        raise ValueError(f"boundary_loss: labels {tuple(labels.shape)} must be (B, H, W) of logits {tuple(logits.shape)} to form the distance maps")
+    if dist_maps is not None and dist_maps.numel() != logits.numel():
+        raise ValueError(f"boundary_loss: dist_maps {tuple(dist_maps.shape)} do not match logits {tuple(logits.shape)}")
+    for w, what in ((class_weight, "class_weight"), (wb, "boundary_class_weight")):
+        if w is not None and w.numel() != ncls:
+            raise ValueError(f"boundary_loss: {what} has {w.numel()} entries for {ncls} classes")
+    return _SegLoss.apply(logits, labels, None, BoundaryObjective(float(w_ce), float(w_dice), float(alpha), class_weight, wb, dist_maps), group)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -30,7 +30,7 @@ import torch.distributed as dist
 
 from ._lib import call, ptr, stream
 from .continual import Distill
-from .ops import CeDiceObjective, ContinualObjective, augment_batch, engine_backward, intensity_batch
+from .ops import BoundaryObjective, CeDiceObjective, ContinualObjective, augment_batch, engine_backward, intensity_batch
 from .optim import ADAM_MOMENTS, FlatAdamW, FlatSGD
 
 
@@ -70,9 +70,22 @@ def cosine_lr(base_lr, epoch, t_max):
     return base_lr * (1.0 + math.cos(math.pi * epoch / t_max)) / 2.0
 
 
+def kervadec_alpha(epoch, start=0.01, step=0.01, cap=1.0):
+    """The boundary loss's weight as Kervadec et al. (MIDL 2019) schedule it: `start` in epoch 0, raised by `step` per epoch, at
+    most `cap`.  The ready-made args.boundary_weight of trainer_synapse."""
+    return min(start + step * epoch, cap)
+
+
 def scale_lr_for_batch(base_lr, batch_size):
     """train.py:104-105: base_lr *= batch_size / 24 only when batch_size != 24 and batch_size % 6 == 0 (per-GPU batch)."""
     return base_lr * batch_size / 24 if (batch_size != 24 and batch_size % 6 == 0) else base_lr
+
+
+def _boundary_alpha(a, who):
+    """The boundary loss's weight as a float; ValueError for anything but a finite number (True is no weight)."""
+    if isinstance(a, bool) or not isinstance(a, (int, float)) or not math.isfinite(a):
+        raise ValueError(f"{who} must be a finite number, got {a!r}")
+    return float(a)
 
 
 ENGINE_OPTIMIZERS = ("sgd", "adamw", "adam")
@@ -96,10 +109,15 @@ class HipEngine:
     "adam" is the reference's finetune.py:183: torch.optim.Adam, whose `weight_decay` is added to the gradient (coupled L2); it
     clips like "adamw" when max_grad_norm is given.  moments ("adamw" and "adam"): "kept" is the optimiser as torch runs it, "fresh"
     takes both moments as zero at every step, which is finetune.py:237's optimiser built anew for every step.  set_auto_rates
-    turns on that loop's per-step learning rates."""
+    turns on that loop's per-step learning rates.
+
+    boundary (None, a float alpha, or a dict of ops.BoundaryObjective's fields): the objective becomes w_ce * CE + w_dice * Dice +
+    alpha * boundary (Kervadec et al., MIDL 2019) -- the labels' signed distance maps are made on the device inside the forward
+    part of the step, `sums` has 2 + 3*ncls entries and `stats` is [loss, ce, dice, boundary].  alpha is a device float:
+    set_boundary_weight changes it between replays of the captured step.  Not together with distill."""
 
     def __init__(self, model, num_classes, lr, momentum, weight_decay, w_ce, w_dice, use_graph=True, distill=None, optimizer="sgd",
-                 max_grad_norm=None, betas=(0.9, 0.999), eps=1e-8, moments="kept"):
+                 max_grad_norm=None, betas=(0.9, 0.999), eps=1e-8, moments="kept", boundary=None):
         if optimizer not in ENGINE_OPTIMIZERS:
             raise ValueError(f"HipEngine: optimizer must be one of {ENGINE_OPTIMIZERS}, got {optimizer!r}")
         if optimizer == "sgd" and max_grad_norm is not None:
@@ -108,6 +126,15 @@ class HipEngine:
             raise ValueError(f'HipEngine: moments must be one of {ADAM_MOMENTS} ("fresh" with optimizer="adamw" or "adam" only), got {moments!r}')
         self.model, self.ncls, self.w_ce, self.w_dice = model, num_classes, w_ce, w_dice
         self.distill = Distill.of(distill)
+        if boundary is not None:
+            if self.distill is not None:
+                raise ValueError("HipEngine: boundary together with distill is not implemented (the continual objective has no boundary term)")
+            boundary = dict(boundary) if isinstance(boundary, dict) else dict(alpha=boundary)
+            # dist_maps is the per-call cache of ops.boundary_loss: in an engine it would pin one batch's maps for every step
+            unknown = set(boundary) - {"w_ce", "w_dice", "alpha", "class_weight", "boundary_class_weight"}
+            if unknown:
+                raise ValueError(f"HipEngine: boundary has no field {sorted(unknown)} (alpha, w_ce, w_dice, class_weight, boundary_class_weight)")
+            boundary["alpha"] = _boundary_alpha(boundary.get("alpha", 0.01), "HipEngine: boundary")
         self.core = model.cswin_unet if hasattr(model, "cswin_unet") else model
         names = [n for n, p in model.named_parameters() if p.requires_grad]
         self.param_names = names                        # aligned with self.opt.params
@@ -123,7 +150,11 @@ class HipEngine:
         # second cut inside the encoder, in front of merge2: parameters [n_mid, n_enc) = merge2, stage3, merge3, stage4, norm
         self.n_mid = next(i for i, n in enumerate(names) if "merge2" in n.split(".")[:2]) if self.split_backward else 0
         dev = self.opt.flat_param.device
-        self.objective = ContinualObjective(self.distill) if self.distill else CeDiceObjective(w_ce, w_dice)
+        if boundary is not None:
+            self.objective = BoundaryObjective(**{"w_ce": w_ce, "w_dice": w_dice, **boundary})
+            self.objective._alpha(dev)                  # the device float exists before any capture: a fill inside a graph would be replayed
+        else:
+            self.objective = ContinualObjective(self.distill) if self.distill else CeDiceObjective(w_ce, w_dice)
         self.sums = torch.zeros(self.objective.n_sums(num_classes), dtype=torch.float32, device=dev)
         self.stats = torch.zeros(self.objective.n_stats, dtype=torch.float32, device=dev)     # [loss, ce, dice] of the last step; distill: [loss, focal, dice, kd, ce]
         self._teacher_logits, self._batch_pixels = None, None
@@ -146,6 +177,12 @@ class HipEngine:
 
     def set_lr(self, lr):
         self.opt.set_lr(lr)
+
+    def set_boundary_weight(self, alpha):
+        """The boundary term's weight from the next step on, captured or not (an eager fill of the objective's device float)."""
+        if not isinstance(self.objective, BoundaryObjective):
+            raise ValueError("HipEngine.set_boundary_weight needs an engine built with boundary=")
+        self.objective.set_boundary_weight(_boundary_alpha(alpha, "HipEngine.set_boundary_weight: boundary weight"))
 
     def set_lr_weights(self, weights, default=0.0):
         """Per-tensor learning-rate multipliers by parameter name (continual.surgical_lr_weights' result); a tensor that is not
@@ -359,7 +396,8 @@ class DataParallelTrainer:
 
     def __init__(self, model=None, num_classes=9, base_lr=0.05, max_iterations=1000, momentum=0.9, weight_decay=1e-4,
                  group=None, use_graph=True, buckets=2, w_ce=0.4, w_dice=0.6, engine=None, force_collectives=False,
-                 allreduce_dtype=None, distill=None, optimizer="sgd", max_grad_norm=None, lr_schedule="poly", moments="kept"):
+                 allreduce_dtype=None, distill=None, optimizer="sgd", max_grad_norm=None, lr_schedule="poly", moments="kept",
+                 boundary=None):
         if lr_schedule not in ("poly", "constant"):
             raise ValueError(f'DataParallelTrainer: lr_schedule must be "poly" or "constant", got {lr_schedule!r}')
         if engine is None and optimizer not in ("sgd", "adamw"):
@@ -372,7 +410,7 @@ class DataParallelTrainer:
         self.base_lr, self.max_iterations, self.iter_num = base_lr, max_iterations, 0
         self.engine = engine if engine is not None else HipEngine(model, num_classes, base_lr, momentum, weight_decay,
                                                                  w_ce, w_dice, use_graph, distill, optimizer, max_grad_norm,
-                                                                 moments=moments)
+                                                                 moments=moments, boundary=boundary)
         self.model = model
         self.nbuckets = max(1, buckets)
         # torch.bfloat16: gradients travel as bf16 (47 MB instead of 94 MB per step, BASELINE configs[2]); the sum is formed
@@ -388,6 +426,10 @@ class DataParallelTrainer:
     @property
     def stats(self):
         return self.engine.stats
+
+    def set_boundary_weight(self, alpha):
+        """HipEngine.set_boundary_weight: every rank sets the same weight."""
+        self.engine.set_boundary_weight(alpha)
 
     def set_auto_rates(self, groups, statistic="grad", default=0.0):
         """HipEngine.set_auto_rates.  The update runs after the all-reduce, so every rank forms the same rates from the same
@@ -550,7 +592,9 @@ def _step_options(args):
     o = dict(optimizer=getattr(args, "optimizer", "sgd"), weight_decay=getattr(args, "weight_decay", 1e-4), w_ce=getattr(args, "w_ce", 0.4),
              w_dice=getattr(args, "w_dice", 0.6), lr_schedule=getattr(args, "lr_schedule", "poly"), moments=getattr(args, "moments", "kept"),
              auto_rates=getattr(args, "auto_rates", None), subset=getattr(args, "subset_fraction", None),
-             intensity=getattr(args, "intensity", None))
+             intensity=getattr(args, "intensity", None), boundary=getattr(args, "boundary_weight", None))
+    if o["boundary"] is not None and not callable(o["boundary"]):
+        o["boundary"] = _boundary_alpha(o["boundary"], "trainer_synapse: boundary_weight (None, a number or a function epoch -> weight)")
     if o["intensity"] is not None:
         from .datasets import IntensityAugment
         if o["intensity"] == "nnunet":
@@ -599,6 +643,9 @@ def trainer_synapse(args, model, snapshot_path, group=None, log_every=1, checkpo
     intensity: None (default), "nnunet" or a datasets.IntensityAugment: appearance augmentation of every batch on the device
     (ops.intensity_batch on the prefetcher's stream, after either `augment` path), drawn from one numpy Generator seeded with
     (seed, rank): ranks differ, and a seeded run draws the same records whatever num_workers is.
+    boundary_weight: None (default), the weight alpha of the boundary loss (HipEngine's boundary=) as a float, or a function
+    epoch -> alpha applied at the start of every epoch (kervadec_alpha is the published schedule); the log line then carries the
+    boundary term.
     checkpoint: None for the schedule above, or a function epoch -> file name or None."""
     import logging
     import random
@@ -659,6 +706,9 @@ def trainer_synapse(args, model, snapshot_path, group=None, log_every=1, checkpo
     logging.info("{} iterations per epoch. {} max iterations ".format(len(loader), max_iterations))
     model.train()
     step = dict(weight_decay=opts["weight_decay"], w_ce=opts["w_ce"], w_dice=opts["w_dice"])
+    boundary = opts["boundary"]
+    if boundary is not None:
+        step.update(boundary=float(boundary(0)) if callable(boundary) else boundary)
     if opts["optimizer"] == "adam":                  # DataParallelTrainer's own `optimizer` keeps its two values: the engine is handed in
         engine = HipEngine(model, args.num_classes, args.base_lr, 0.9, use_graph=True, optimizer="adam", moments=opts["moments"], **step)
         step = dict(engine=engine)
@@ -674,13 +724,20 @@ def trainer_synapse(args, model, snapshot_path, group=None, log_every=1, checkpo
     for epoch_num in range(max_epoch):
         if sampler is not None:
             sampler.set_epoch(epoch_num)
+        if callable(boundary):
+            trainer.set_boundary_weight(float(boundary(epoch_num)))
+            if rank == 0:
+                logging.info('epoch %d : boundary weight : %f' % (epoch_num, trainer.engine.objective.alpha))
         for image_batch, label_batch in _Prefetcher(loader, device, augment, (args.img_size, args.img_size), blur_sigma=blur_sigma,
                                                     intensity=opts["intensity"], intensity_seed=intensity_rng):
             stats = trainer.train_step(image_batch, label_batch)
             iter_num += 1
             if log_every and iter_num % log_every == 0 and rank == 0:
-                loss, loss_ce, _ = stats.tolist()                    # the only host sync of the loop
-                logging.info('iteration %d : loss : %f, loss_ce: %f' % (iter_num, loss, loss_ce))
+                loss, loss_ce, *rest = stats.tolist()                # the only host sync of the loop
+                if boundary is None:
+                    logging.info('iteration %d : loss : %f, loss_ce: %f' % (iter_num, loss, loss_ce))
+                else:
+                    logging.info('iteration %d : loss : %f, loss_ce: %f, loss_dice: %f, loss_boundary: %f' % (iter_num, loss, loss_ce, *rest))
                 if opts["auto_rates"] is not None:                   # finetune.py:236 logs every group's rate; same sync point
                     opt = trainer.engine.opt
                     rates = dict(zip(opt.group_names, (opt.group_stats / opt.group_stats.max() * opt.lr_dev).tolist()))
@@ -708,7 +765,7 @@ def surgical_trainer(args, model, snapshot_path, group=None, log_every=1):
     a constant rate; every step's rate of each of the 22 groups of continual.finetune_groups set to lr * n_k / max_j n_j, n the
     norm of the group's gradient (:116-144, 225-236; auto_rates="grad", formed on the device); a fifth of the slices, drawn once
     from args.seed (:166-169); a checkpoint model_lr{lr}_wd{wd}_epoch{epoch}.pth whenever epoch % args.save_interval == 0 (:250-251,
-    save_interval defaults to 1).  args.moments ("kept" by default) chooses between Adam with running moments and the reference
+    save_interval defaults to 1).  args.boundary_weight is passed on as it is.  args.moments ("kept" by default) chooses between Adam with running moments and the reference
     as written, which builds a new optimiser every step ("fresh").  args.auto_rates and args.subset_fraction override the
     statistic and the part.  Deviations: one forward/backward per step, whose gradient is both measured and
     applied, where the reference measures on a second batch and steps with that batch's gradient; the per-step tune_metrics.pt

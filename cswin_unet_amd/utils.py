@@ -373,6 +373,24 @@ def gaussian_taps_device(sigma, truncate, device):
     return _device_tables[key]
 
 
+def signed_distance_maps_host(labels, ncls):
+    """The boundary loss's signed distance maps (Kervadec et al., MIDL 2019: one_hot2dist), the definition ops.signed_distance_maps
+    is held to bit for bit.  labels (B, H, W) integers -> float32 (B, ncls, H, W): per sample and class, with M = (labels[b] == c),
+    edt(~M) * ~M - (edt(M) - 1) * M in float64 with scipy.ndimage.distance_transform_edt per 2-D slice at unit spacing -- +d(p, M)
+    outside the mask, -(d(p, ~M) - 1) inside -- rounded to float32; zeros where M is empty or the whole slice (no boundary: scipy's
+    transform of an all-true mask is no distance).  A label outside [0, ncls) equals no c: its pixel is outside every mask."""
+    lab = np.asarray(labels.cpu() if torch.is_tensor(labels) else labels)
+    if lab.ndim != 3 or not np.issubdtype(lab.dtype, np.integer):
+        raise ValueError(f"signed_distance_maps_host: labels must be (B, H, W) integers, got {lab.dtype} {lab.shape}")
+    phi = np.zeros((lab.shape[0], int(ncls)) + lab.shape[1:], np.float32)
+    for b in range(lab.shape[0]):
+        for c in range(int(ncls)):
+            m = lab[b] == c
+            if m.any() and not m.all():
+                phi[b, c] = distance_transform_edt(~m) * ~m - (distance_transform_edt(m) - 1.0) * m
+    return phi
+
+
 def mix64_host(z):
     """csrc/layout.hip's mix64 on numpy uint64 (any shape): the whole splitmix64 step, increment included."""
     z = np.asarray(z, np.uint64)

@@ -31,7 +31,7 @@ extern "C" {
  * compiled against another header must refuse to call it.  Entry points that are only ADDED (cswin_seg_metrics*, cswin_resize_banded, cswin_argmax_zoom_back, cswin_augment_*,
  * cswin_chunk_sumsq, cswin_norm_finalize, cswin_adamw_flat, cswin_tpgm_*, cswin_argmax_zoom_back_classes, cswin_class_counts, cswin_gaussian_blur, cswin_eb_tiles,
  * cswin_eb_finalize, cswin_rate_finalize, cswin_adam_flat, cswin_components_*, cswin_drop_path_order, cswin_linear_*_skip,
- * cswin_surface_dist*, cswin_view_batch, cswin_tta_argmax_zoom_back, cswin_gaussian_blur_each, cswin_intensity_*) do not bump it: every prototype an older consumer binds is unchanged. */
+ * cswin_surface_dist*, cswin_view_batch, cswin_tta_argmax_zoom_back, cswin_gaussian_blur_each, cswin_intensity_*, cswin_sdm_workspace, cswin_signed_distance_maps, cswin_bd_loss_*) do not bump it: every prototype an older consumer binds is unchanged. */
 #define CSWIN_ABI_VERSION 4
 
 #define CSWIN_OK 0
@@ -344,6 +344,42 @@ int cswin_cl_loss_bwd(const float* logits, const long long* labels, const int* l
                       const float* class_weight, const float* coef, const float* grad_out, float* dlogits, float focal_scale,
                       float dice_scale, float kd_scale, int B, int ncls, int nold, long HW, float temperature, float focal_alpha,
                       float focal_gamma, void* stream);
+
+/* ---- signed distance maps of label slices, for the boundary loss (Kervadec et al., MIDL 2019: one_hot2dist) ----
+ * labels (B, H, W) int64 -> phi (B, ncls, H, W) fp32.  Per sample b and class c, with M = (labels[b] == c): phi = +d(p, M) outside
+ * M and -(d(p, ~M) - 1) inside it, d the Euclidean distance in pixels (unit spacing, per 2-D slice) to the nearest pixel of the
+ * set; phi[b][c] = 0 everywhere when M is empty or the whole slice (there is no boundary).  A label outside [0, ncls), judged on
+ * the whole int64 value, belongs to no class.  The value is (float)sqrt((double)d2) of the exact integer squared distance
+ * (inside: (float)(1 - sqrt((double)d2))), which is scipy.ndimage.distance_transform_edt's edt(~M) * ~M - (edt(M) - 1) * M bit for
+ * bit; integer atomics only, so two runs give the same bits.  Limits: B >= 1, 1 <= H, W <= 2047 (CSWIN_ERR_SHAPE), 2 <= ncls <= 255
+ * (CSWIN_ERR_UNSUPPORTED); a refused call launches nothing.  cswin_sdm_workspace returns 0 (and sets the error) outside them;
+ * the workspace holds the row pass's uint16 distances (2 bytes per element of phi) and a counter per (b, c). */
+size_t cswin_sdm_workspace(int B, int ncls, int H, int W);
+int cswin_signed_distance_maps(const long long* labels, float* phi, void* workspace, size_t ws_bytes, int B, int ncls, int H,
+                               int W, void* stream);
+
+/* ---- boundary objective: w_ce * CE + w_dice * Dice + alpha * boundary, boundary = 1 / n_pixels * sum over pixels and classes of
+ *      wb_c * softmax(logits)_c * phi_c ----
+ * logits and phi (B, ncls, HW) fp32, labels (B, HW) int64; phi: cswin_signed_distance_maps of the same labels (or any map);
+ * wb: ncls device floats or NULL (= 0 for class 0, 1 for the others).  Logits only: there is no probabilities mode.  ncls as
+ * cswin_loss_sums takes it.
+ * cswin_bd_loss_workspace: bytes of cswin_bd_loss_sums' workspace. */
+size_t cswin_bd_loss_workspace(int B, int ncls, long HW);
+/* sums[2 + 3*ncls]: the first 1 + 3*ncls are cswin_loss_sums', out-of-range labels included (sums[0] NaN);
+ * [1 + 3*ncls] = sum over the local pixels and the classes of (wb_c * p_c) * phi_c, un-normalised: all-reduce across ranks. */
+int cswin_bd_loss_sums(const float* logits, const long long* labels, const float* phi, const float* wb, float* sums,
+                       void* workspace, size_t ws_bytes, int B, int ncls, long HW, void* stream);
+/* out4 = {loss, ce, dice, boundary}: ce, dice and coef[2*ncls] as cswin_loss_finalize forms them (class_weight: the Dice's),
+ * boundary = S_boundary / n_pixels, loss = w_ce * ce + w_dice * dice + alpha * boundary with alpha = alpha_dev[0], ONE DEVICE
+ * FLOAT: the weight is scheduled during training and a captured graph must see its current value.  A term whose weight is 0 is
+ * left out, NaN or not. */
+int cswin_bd_loss_finalize(const float* sums, float* out4, float* coef, double n_pixels, int ncls, float w_ce, float w_dice,
+                           const float* alpha_dev, const float* class_weight, void* stream);
+/* dlogits_c = grad_out (NULL = 1) * [cswin_loss_bwd's two terms + alpha_dev[0] * bd_scale * p_c * (wb_c phi_c - sum_j p_j wb_j phi_j)];
+ * ce_scale and dice_scale as there, bd_scale = 1 / (local pixel count).  Every channel of dlogits is written once. */
+int cswin_bd_loss_bwd(const float* logits, const long long* labels, const float* phi, const float* wb, const float* coef,
+                      const float* alpha_dev, const float* grad_out, float* dlogits, float ce_scale, float dice_scale,
+                      float bd_scale, int B, int ncls, long HW, void* stream);
 
 /* ---- optimiser: torch.optim.SGD(momentum, weight_decay) (trainer.py:42,60) on one flat buffer ---- */
 int cswin_sgd_flat(float* p, const float* g, float* m, long n, const float* lr_dev, float momentum,
