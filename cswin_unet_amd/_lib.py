@@ -87,6 +87,10 @@ SIGNATURES = {
     "cswin_tpgm_chunk_stats": (I, [P, P, P, P, I, I, P, P]),
     "cswin_tpgm_finalize": (I, [P, P, I, I, P, P, P, P, D, D, D, D, I, P, P, P, P]),
     "cswin_tpgm_project": (I, [P, P, P, P, P, I, P, P]),
+    "cswin_importance_accumulate": (I, [P, P, P, I, D, I, P]),
+    "cswin_flat_axpby": (I, [P, P, P, I, D, D, P]),
+    "cswin_consolidate_chunks": (I, [P, P, P, P, P, I, P, P, D, P, P]),
+    "cswin_consolidate_finalize": (I, [P, P, I, P, P, P, P, P]),
     "cswin_eb_tiles": (I, [P, P, I, P, P]),
     "cswin_eb_finalize": (I, [P, P, P, I, P, P]),
     "cswin_pack_bf16": (I, [P, P, L, P]),

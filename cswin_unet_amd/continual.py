@@ -24,6 +24,12 @@ and TPGM, the trainable projection toward the pretrained weights (universal_trai
     if tpgm_due(epoch, start_epoch, frequency): tpgm.iterate(held_out_batches, max_iters)     # learns the radii; the weights are restored
     tpgm.apply()                                                    # once, after training: the weights are projected
 
+and the quadratic penalties that hold every weight near its old-task value in proportion to its importance (EWC, MAS, L2-SP):
+
+    cons = Consolidation(trainer, "ewc", weight=400.0)              # attaches to the engine: every step adds the penalty's gradient
+    cons.estimate(old_task_batches)                                 # the empirical Fisher of a few batches; the anchor is the weights now
+    state = carry_consolidation_state(cons.state_dict(), dict(expanded_model.named_parameters()))     # across expand_classes
+
 and the two ends of a stage that close the loop, label statistics before it and evaluation after it:
 
     counts = scan_labels(raw_label_slices, total_classes, table)    # (N, classes + 1) per-slice class histogram, ops.class_counts
@@ -35,7 +41,7 @@ and the two ends of a stage that close the loop, label statistics before it and 
 (universal_test.py scores a model per dataset on that dataset's own output channels, task_class_indices; checkpoint_num_classes,
 strip_wrapper_prefixes and task_level read a checkpoint's task level.)
 
-surgical_lr_weights, TPGM, scan_labels and evaluate_tasks run kernels; nothing else here does."""
+surgical_lr_weights, TPGM, Consolidation, scan_labels and evaluate_tasks run kernels; nothing else here does."""
 import copy
 import math
 import random
@@ -46,7 +52,7 @@ import numpy as np
 import torch
 from torch import nn
 
-__all__ = ["expand_classes", "new_label_map", "extreme_class_weights", "freeze_teacher", "Distill", "rgn_weights", "eb_weights", "eb_metrics", "surgical_lr_weights", "finetune_groups", "FINETUNE_GROUPS", "FINETUNE_GRID", "TPGM", "tpgm_due",
+__all__ = ["expand_classes", "new_label_map", "extreme_class_weights", "freeze_teacher", "Distill", "rgn_weights", "eb_weights", "eb_metrics", "surgical_lr_weights", "finetune_groups", "FINETUNE_GROUPS", "FINETUNE_GRID", "TPGM", "tpgm_due", "Consolidation", "carry_consolidation_state",
            "task_class_indices", "task_level", "checkpoint_num_classes", "strip_wrapper_prefixes", "evaluate_tasks", "scan_labels",
            "PositiveSampling", "REFERENCE_TASKS", "REFERENCE_STAGE_CLASSES", "KITS23_RULE", "LITS17_RULE"]
 
@@ -336,6 +342,203 @@ class TPGM:
 
     def load_state_dict(self, sd):
         self.flat.load_state_dict(sd)
+
+
+def _drop_kept_activations(model):
+    """None in the place of every activation a forward pass left on the modules (the U-Net's boundary tensors; the next forward
+    writes them again): they hold the pass's autograd graph, and with it the parameters' AccumulateGrad nodes, alive."""
+    for m in model.modules():
+        for k, v in list(vars(m).items()):
+            if any(isinstance(t, torch.Tensor) and t.grad_fn is not None for t in (v if isinstance(v, (list, tuple)) else (v,))):
+                setattr(m, k, None)
+
+
+class Consolidation:
+    """EWC, MAS or L2-SP on a DataParallelTrainer whose engine is a HipEngine: optim.FlatConsolidation on the engine's flat buffers,
+    attached to the engine so that every step's eager tail adds the penalty's gradient to the flat gradient in front of the optimiser
+    launch (HipEngine.apply; the captured hipGraphs are replayed as they are).  The anchor is the weights at construction, or
+    `state`'s (a state_dict() of an earlier stage, carried onto this model's parameters by carry_consolidation_state).
+
+        cons = Consolidation(trainer, "ewc", weight=400.0)              # after the old task is trained, BEFORE the new one
+        cons.estimate(old_task_batches)                                 # importance <- mean of the squared gradients; anchor <- weights
+        ... trainer.train_step(...)                                     # cons.penalty is the device float of the last step's penalty
+        cons.consolidate(new_task_batches, decay=0.9)                   # online EWC: importance <- decay importance + new; anchor <- weights
+
+    method "ewc": the empirical Fisher of the engine's log-likelihood loss, one squared gradient per BATCH: batches of one sample
+    give the per-sample Fisher, larger batches the square of the batch-mean gradient.  "mas": |gradient of the mean squared output
+    norm|, no labels used.  "l2sp": importance 1, nothing to estimate.  names in `exclude` are not penalised."""
+
+    def __init__(self, trainer, method="ewc", weight=1.0, exclude=(), state=None):
+        from .optim import FlatConsolidation, check_consolidation
+        method, weight = check_consolidation(method, weight, "continual.Consolidation")
+        if state is not None and state.get("method") != method:
+            raise ValueError(f"continual.Consolidation: the state is {state.get('method')!r}'s, method is {method!r}")
+        eng = trainer.engine
+        if not hasattr(eng, "opt") or not hasattr(eng, "param_names"):
+            raise TypeError("continual.Consolidation needs a trainer whose engine owns flat buffers (HipEngine)")
+        self.trainer = trainer
+        self.flat = FlatConsolidation(eng.opt, eng.param_names, method=method, weight=weight, exclude=exclude)
+        if state is not None:
+            self._load_tensors(state)
+        eng.consolidation = self.flat
+
+    def detach(self):
+        """The engine steps without the penalty again; this object keeps its buffers."""
+        if self.trainer.engine.consolidation is self.flat:
+            self.trainer.engine.consolidation = None
+
+    @property
+    def penalty(self):
+        """Device view of the last step's (or report()'s) penalty (no sync)."""
+        return self.flat.scalars[0:1]
+
+    def report(self):
+        """FlatConsolidation.report(): [penalty, sum w_t F d^2, ||theta - anchor||] of the weights as they are, on the device."""
+        return self.flat.report()
+
+    def set_weight(self, weight):
+        self.flat.set_weight(weight)
+
+    def _default_loss(self):
+        from . import ops
+        eng = self.trainer.engine
+        if self.flat.method == "mas":
+            return lambda img, logits, lab: logits.square().sum() / logits.shape[0]
+        d = getattr(eng, "distill", None)
+        if d is None:
+            return lambda img, logits, lab: ops.ce_dice_loss(logits, lab, 1.0, 0.0)[0]
+
+        def focal(img, logits, lab):              # surgical_lr_weights' call: the base loss has no instantiation on the widened head
+            with torch.no_grad():
+                teacher_logits = d.teacher(img).contiguous()
+            return ops.continual_loss(logits, lab, teacher_logits, w_focal=1.0, w_dice=0.0, kd_weight=0.0, temperature=d.temperature,
+                                      focal_gamma=d.focal_gamma, focal_alpha=d.focal_alpha, class_weight=d.class_weight, label_map=d.label_map)[0]
+        return focal
+
+    def estimate(self, batches, loss=None, decay=0.0):
+        """importance <- decay importance + (1 / n) sum over `batches` (an iterable of (image, label) device tensors) of the
+        statistic of one eager gradient each; anchor <- the weights.  Per batch one forward in eval() mode, the loss, backward,
+        opt.gather_grads() and one accumulate launch; the engine's cut between encoder and decoder is lifted for it.  loss: a
+        function (logits, labels) -> scalar, or None for the method's own (the class docstring).  Under data parallelism every
+        rank accumulates its own batches, then the sum and the count are all-reduced once.  The training mode is restored and
+        every .grad is None afterwards, also when a batch raises (the importance and the anchor are then as they were); weights,
+        shadow and optimiser state are never touched."""
+        import torch.distributed as dist
+
+        from .optim import check_decay
+        flat, tr = self.flat, self.trainer
+        if flat.method == "l2sp":
+            raise ValueError('continual.Consolidation.estimate: method "l2sp" has importance 1, there is nothing to estimate')
+        decay = check_decay(decay, "continual.Consolidation.estimate")
+        eng = tr.engine
+        model, opt = eng.model, eng.opt
+        fn = self._default_loss() if loss is None else (lambda img, logits, lab: loss(logits, lab))
+        was_training = model.training
+        model.eval()
+        core = _core(model)
+        cut = bool(getattr(core, "detach_decoder_inputs", False))
+        if cut:
+            core.detach_decoder_inputs = False
+        count, done = 0, False
+        flat.begin_estimate()
+        # The loop runs on a side stream, as the eager iterations in front of HipEngine's capture do: autograd binds a parameter's
+        # AccumulateGrad node to the stream of the forward that first uses it, and the node lives as long as a graph that uses it.
+        # Bound to the default stream it would draw that stream into a capture of the step that follows; the activations the
+        # model keeps, which hold the last graph, are dropped at the end for the same reason.
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        try:
+            with torch.cuda.stream(side):
+                for img, lab in batches:
+                    lab = (lab if lab.dtype == torch.int64 else lab.long()).contiguous()
+                    value = fn(img, model(img), lab)
+                    opt.zero_grad()
+                    value.backward()
+                    opt.gather_grads()
+                    flat.accumulate(1.0)
+                    opt.zero_grad()
+                    count += 1
+            done = True
+        finally:
+            torch.cuda.current_stream().wait_stream(side)
+            _drop_kept_activations(model)
+            if cut:
+                core.detach_decoder_inputs = True
+            model.train(was_training)
+            opt.zero_grad()
+            if not done:
+                flat.cancel_estimate()
+        if tr.collectives:
+            total = torch.tensor([float(count)], dtype=torch.float32, device=opt.flat_param.device)
+            dist.all_reduce(flat.scratch, group=tr.group)
+            dist.all_reduce(total, group=tr.group)
+            count = int(total.item())
+        if count == 0:
+            flat.cancel_estimate()
+            raise ValueError("continual.Consolidation.estimate: no batch was given")
+        flat.finish(count, decay)
+
+    def consolidate(self, batches, decay, loss=None):
+        """The online form at the end of a stage: importance <- decay importance + this stage's; anchor <- the weights."""
+        self.estimate(batches, loss=loss, decay=decay)
+
+    def state_dict(self):
+        """{"method", "weight", "exclude", "tensors": {name: {"anchor", "importance"}}}, the tensors in parameter shape (importance
+        None for "l2sp"): keyed by name, so that it outlives the flat layout (carry_consolidation_state)."""
+        flat, opt = self.flat, self.flat.opt
+        tensors = {}
+        for n, p, o in zip(flat.names, opt.params, opt.offsets):
+            cut = slice(o, o + p.numel())
+            tensors[n] = {"anchor": flat.flat_anchor[cut].view(p.shape).clone(),
+                          "importance": None if flat.flat_importance is None else flat.flat_importance[cut].view(p.shape).clone()}
+        return {"method": flat.method, "weight": flat.weight, "exclude": list(flat.exclude), "tensors": tensors}
+
+    def _load_tensors(self, state):
+        flat, opt = self.flat, self.flat.opt
+        carried = carry_consolidation_state(state, {n: p.data for n, p in zip(flat.names, opt.params)})
+        with torch.no_grad():
+            for n, p, o in zip(flat.names, opt.params, opt.offsets):
+                cut, entry = slice(o, o + p.numel()), carried["tensors"][n]
+                flat.flat_anchor[cut].copy_(entry["anchor"].reshape(-1))
+                if flat.flat_importance is not None:
+                    flat.flat_importance[cut].copy_(entry["importance"].reshape(-1))
+
+    def load_state_dict(self, state):
+        """A state_dict() of this method, carried onto this model's parameters (carry_consolidation_state); the weight follows."""
+        if state.get("method") != self.flat.method:
+            raise ValueError(f"continual.Consolidation.load_state_dict: the state is {state.get('method')!r}'s, this object {self.flat.method!r}'s")
+        self._load_tensors(state)
+        self.flat.set_weight(state["weight"])
+
+
+def carry_consolidation_state(state, current):
+    """A Consolidation.state_dict() mapped onto the parameters `current` ({name: tensor}) of a model whose layout has changed since
+    (expand_classes runs between the estimation on the old model and the next trainer): a new state with exactly current's names.
+    Same shape: copied.  First dimension grown with equal trailing dimensions (the widened `output.weight`): the leading rows are
+    carried, the new rows get importance 0 and the current values as anchor.  A name the state does not have: importance 0, anchor
+    the current value.  Any other mismatch: ValueError naming the tensor.  No device work beyond the copies; runs on the CPU."""
+    l2sp = state.get("method") == "l2sp"
+    out = {}
+    for name, cur in current.items():
+        cur = cur.detach()
+        old = state["tensors"].get(name)
+        anchor = cur.clone()
+        importance = None if l2sp else torch.zeros_like(cur)
+        if old is not None:
+            a = old["anchor"]
+            grown = a.dim() >= 1 and a.dim() == cur.dim() and a.shape[0] < cur.shape[0] and a.shape[1:] == cur.shape[1:]
+            if a.shape != cur.shape and not grown:
+                raise ValueError(f"carry_consolidation_state: {name} has shape {tuple(a.shape)} in the state and {tuple(cur.shape)} now "
+                                 f"(only a grown first dimension can be carried)")
+            rows = Ellipsis if a.dim() == 0 else slice(0, a.shape[0])
+            anchor[rows] = a.to(device=cur.device, dtype=cur.dtype)
+            if not l2sp:
+                f = old["importance"]
+                if f is None or f.shape != a.shape:
+                    raise ValueError(f"carry_consolidation_state: {name} has no importance of its anchor's shape in the state")
+                importance[rows] = f.to(device=cur.device, dtype=cur.dtype)
+        out[name] = {"anchor": anchor, "importance": importance}
+    return {"method": state.get("method"), "weight": state.get("weight"), "exclude": list(state.get("exclude", ())), "tensors": out}
 
 
 # ------------------------------------------------------------------------------------------------

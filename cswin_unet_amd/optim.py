@@ -586,3 +586,146 @@ class FlatTPGM:
         self.norm_mode, self.proj_lr = str(sd["norm_mode"]), float(sd["proj_lr"])
         self.l1 = 0 if "l2" in self.norm_mode else 1
         self._ratio_current = False
+
+
+CONSOLIDATION_METHODS = ("ewc", "mas", "l2sp")
+CONSOLIDATION_STATISTIC = {"ewc": 0, "mas": 1}     # cswin_importance_accumulate's `statistic`
+
+
+def check_consolidation(method, weight, who="FlatConsolidation"):
+    """(method, weight) as they are stored; ValueError for an unknown method or a weight that is negative or not finite."""
+    if method not in CONSOLIDATION_METHODS:
+        raise ValueError(f"{who}: method must be one of {CONSOLIDATION_METHODS}, got {method!r}")
+    try:
+        weight = float(weight)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: weight must be a finite number >= 0, got {weight!r}") from None
+    if not (0.0 <= weight < float("inf")):
+        raise ValueError(f"{who}: weight must be a finite number >= 0, got {weight!r}")
+    return method, weight
+
+
+def check_decay(decay, who="FlatConsolidation.finish"):
+    decay = float(decay)
+    if not 0.0 <= decay <= 1.0:
+        raise ValueError(f"{who}: decay must lie in [0, 1], got {decay!r}")
+    return decay
+
+
+class FlatConsolidation:
+    """A quadratic penalty that holds every weight of a FlatSGD / FlatAdamW `opt` near its value when this object was built (the
+    anchor) in proportion to an importance F >= 0 (csrc/consolidate.hip):
+
+        penalty = (weight / 2) sum_t w_t sum_i F_i (theta_i - anchor_i)^2          gradient: weight w_t F_i (theta_i - anchor_i)
+
+    method "ewc": F is the empirical Fisher, the mean over batches of the squared gradient of the log-likelihood loss (a batch of
+    one sample gives the per-sample form; a larger batch the square of the batch-mean gradient); "mas": the mean of |gradient of the
+    squared output norm|, which needs no labels; "l2sp": F = 1 and no importance buffer.  names: the parameter names, aligned with
+    opt.params; names in `exclude` get w_t = 0 (their gradient keeps its bits).
+
+        penalise(grad_scale)     opt.flat_grad += (weight w_t / grad_scale) F d, before opt.apply(grad_scale): clipping, auto rates
+                                 and Adam's moments see it as if it were part of the loss.  Two launches, no host read.
+        report()                 the same two launches with no gradient: scalars and per_tensor alone
+        set_weight(weight)       an eager fill of the device float the kernels read
+        begin_estimate() / accumulate(grad_scale) per batch / finish(count, decay):
+                                 F = decay F + (1 / count) sum over the batches of (grad_scale g)^2 or |grad_scale g|; anchor <- theta
+
+    scalars (device): [penalty, sum_t w_t sum F d^2, ||theta - anchor||]; per_tensor (T, 2): (sum F d^2, sum d^2).
+    Memory: two more flat buffers (one for "l2sp"), a third between begin_estimate() and finish()."""
+
+    def __init__(self, opt, names, method="ewc", weight=1.0, exclude=()):
+        method, weight = check_consolidation(method, weight)
+        names = list(names)
+        if len(names) != len(opt.params):
+            raise ValueError(f"FlatConsolidation: {len(names)} names for {len(opt.params)} parameter tensors")
+        unknown = set(exclude) - set(names)
+        if unknown:
+            raise KeyError(f"FlatConsolidation: no trainable parameter named {sorted(unknown)[:4]}")
+        dev = opt.params[0].device
+        if dev.type != "cuda":
+            raise RuntimeError("FlatConsolidation runs on a HIP device only")
+        self.opt, self.names, self.method, self.weight, self.exclude = opt, names, method, weight, tuple(exclude)
+        T = len(names)
+        self.chunks, self.first_chunk, self.nchunks = opt.chunks, opt.first_chunk, opt.nchunks      # the optimiser's own table
+        self._partial = torch.zeros(self.nchunks, 2, dtype=torch.float32, device=dev)
+        excl = set(exclude)
+        self.tensor_weight = torch.tensor([0.0 if n in excl else 1.0 for n in names], dtype=torch.float32, device=dev)
+        self.lam_dev = torch.full((1,), weight, dtype=torch.float32, device=dev)
+        self.per_tensor = torch.zeros(T, 2, dtype=torch.float32, device=dev)
+        self.scalars = torch.zeros(3, dtype=torch.float32, device=dev)
+        self.flat_anchor = opt.flat_param.clone()
+        self.flat_importance = None if method == "l2sp" else torch.zeros_like(opt.flat_param)
+        self._scratch = None
+
+    # -- the penalty ----------------------------------------------------------------------------------------
+    def _launch(self, g, penalty_scale):
+        call("cswin_consolidate_chunks", ptr(self.opt.flat_param), ptr(self.flat_anchor), ptr(self.flat_importance), ptr(g), ptr(self.chunks),
+             self.nchunks, ptr(self.lam_dev), ptr(self.tensor_weight), float(penalty_scale), ptr(self._partial), stream())
+        call("cswin_consolidate_finalize", ptr(self._partial), ptr(self.first_chunk), len(self.names), ptr(self.lam_dev),
+             ptr(self.tensor_weight), ptr(self.per_tensor), ptr(self.scalars), stream())
+
+    def penalise(self, grad_scale=1.0):
+        """opt.flat_grad += (weight w_t / grad_scale) F (theta - anchor); scalars and per_tensor of theta as it is."""
+        grad_scale = float(grad_scale)
+        if not grad_scale > 0.0:
+            raise ValueError(f"FlatConsolidation.penalise: grad_scale must be positive, got {grad_scale!r}")
+        self._launch(self.opt.flat_grad, 1.0 / grad_scale)
+
+    def report(self):
+        """scalars (a device view, no sync) of theta as it is; the gradient is not touched."""
+        self._launch(None, 1.0)
+        return self.scalars
+
+    def set_weight(self, weight):
+        _, self.weight = check_consolidation(self.method, weight, "FlatConsolidation.set_weight")
+        self.lam_dev.fill_(self.weight)
+
+    # -- the estimation -------------------------------------------------------------------------------------
+    def _need_importance(self, what):
+        if self.flat_importance is None:
+            raise ValueError(f'FlatConsolidation.{what}: method "l2sp" has no importance to estimate')
+
+    def begin_estimate(self):
+        self._need_importance("begin_estimate")
+        self._scratch = torch.zeros_like(self.opt.flat_param)
+
+    def accumulate(self, grad_scale=1.0):
+        """scratch += (grad_scale flat_grad)^2 ("ewc") or |grad_scale flat_grad| ("mas") (one launch)."""
+        self._need_importance("accumulate")
+        if self._scratch is None:
+            raise RuntimeError("FlatConsolidation.accumulate() outside begin_estimate() ... finish()")
+        call("cswin_importance_accumulate", ptr(self.opt.flat_grad), ptr(self._scratch), ptr(self.chunks), self.nchunks, float(grad_scale),
+             CONSOLIDATION_STATISTIC[self.method], stream())
+
+    @property
+    def scratch(self):
+        """The sum accumulate() has formed so far (data parallelism all-reduces it once before finish()); None outside an estimation."""
+        return self._scratch
+
+    def cancel_estimate(self):
+        self._scratch = None
+
+    def finish(self, count, decay=0.0):
+        """importance = decay importance + scratch / count (one launch); anchor <- theta; the scratch buffer is released."""
+        self._need_importance("finish")
+        decay = check_decay(decay)
+        if self._scratch is None:
+            raise RuntimeError("FlatConsolidation.finish() without begin_estimate()")
+        if not count > 0:
+            raise ValueError(f"FlatConsolidation.finish: count must be positive, got {count!r}")
+        call("cswin_flat_axpby", ptr(self.flat_importance), ptr(self._scratch), ptr(self.chunks), self.nchunks, decay, 1.0 / float(count), stream())
+        self.flat_anchor.copy_(self.opt.flat_param)
+        self._scratch = None
+
+    # -- state ----------------------------------------------------------------------------------------------
+    def state_dict(self):
+        return {"method": self.method, "weight": self.weight, "exclude": list(self.exclude), "anchor": self.flat_anchor.clone(),
+                "importance": None if self.flat_importance is None else self.flat_importance.clone()}
+
+    def load_state_dict(self, sd):
+        if sd["method"] != self.method:
+            raise ValueError(f"FlatConsolidation.load_state_dict: the state is {sd['method']!r}'s, this object {self.method!r}'s")
+        self.flat_anchor.copy_(sd["anchor"])
+        if self.flat_importance is not None:
+            self.flat_importance.copy_(sd["importance"])
+        self.set_weight(sd["weight"])

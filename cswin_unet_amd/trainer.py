@@ -114,7 +114,12 @@ class HipEngine:
     boundary (None, a float alpha, or a dict of ops.BoundaryObjective's fields): the objective becomes w_ce * CE + w_dice * Dice +
     alpha * boundary (Kervadec et al., MIDL 2019) -- the labels' signed distance maps are made on the device inside the forward
     part of the step, `sums` has 2 + 3*ncls entries and `stats` is [loss, ce, dice, boundary].  alpha is a device float:
-    set_boundary_weight changes it between replays of the captured step.  Not together with distill."""
+    set_boundary_weight changes it between replays of the captured step.  Not together with distill.
+
+    consolidation (an attribute, None by default): an optim.FlatConsolidation on this engine's flat buffers, attached by
+    continual.Consolidation.  apply() then adds the EWC / MAS / L2-SP penalty's gradient to flat_grad in front of the optimiser
+    launch (two more launches in the eager tail of the step; the captured graphs are untouched); its strength is a device float,
+    set_consolidation_weight changes it between steps.  `stats` keeps its layout: the penalty is consolidation.scalars[0]."""
 
     def __init__(self, model, num_classes, lr, momentum, weight_decay, w_ce, w_dice, use_graph=True, distill=None, optimizer="sgd",
                  max_grad_norm=None, betas=(0.9, 0.999), eps=1e-8, moments="kept", boundary=None):
@@ -165,6 +170,7 @@ class HipEngine:
         self._live_dropout = any(isinstance(m, torch.nn.Dropout) and m.p > 0 for m in model.modules())
         self.use_graph, self._graphs, self._logits = use_graph, None, None
         self._wire = {}
+        self.consolidation = None                       # an optim.FlatConsolidation (continual.Consolidation attaches it): apply() adds its gradient
 
     # flat views the protocol all-reduces / broadcasts
     @property
@@ -373,7 +379,17 @@ class HipEngine:
                     yield r
             self._logits = None
 
+    def set_consolidation_weight(self, weight):
+        """The strength of the attached consolidation penalty from the next step on (an eager fill of its device float)."""
+        if self.consolidation is None:
+            raise ValueError("HipEngine.set_consolidation_weight: no consolidation is attached (continual.Consolidation)")
+        self.consolidation.set_weight(weight)
+
     def apply(self, grad_scale):
+        """The eager tail of the step: the attached consolidation penalty's gradient is added to flat_grad first, so clipping, auto
+        rates and Adam's moments see it as part of the loss."""
+        if self.consolidation is not None:
+            self.consolidation.penalise(grad_scale)
         self.opt.apply(grad_scale)
 
     # bf16 gradient wire (HIP kernels; the wire buffer of a bucket is allocated once and reused every step)
@@ -430,6 +446,10 @@ class DataParallelTrainer:
     def set_boundary_weight(self, alpha):
         """HipEngine.set_boundary_weight: every rank sets the same weight."""
         self.engine.set_boundary_weight(alpha)
+
+    def set_consolidation_weight(self, weight):
+        """HipEngine.set_consolidation_weight: every rank sets the same strength, so the replicas stay bit-identical."""
+        self.engine.set_consolidation_weight(weight)
 
     def set_auto_rates(self, groups, statistic="grad", default=0.0):
         """HipEngine.set_auto_rates.  The update runs after the all-reduce, so every rank forms the same rates from the same
@@ -592,7 +612,22 @@ def _step_options(args):
     o = dict(optimizer=getattr(args, "optimizer", "sgd"), weight_decay=getattr(args, "weight_decay", 1e-4), w_ce=getattr(args, "w_ce", 0.4),
              w_dice=getattr(args, "w_dice", 0.6), lr_schedule=getattr(args, "lr_schedule", "poly"), moments=getattr(args, "moments", "kept"),
              auto_rates=getattr(args, "auto_rates", None), subset=getattr(args, "subset_fraction", None),
-             intensity=getattr(args, "intensity", None), boundary=getattr(args, "boundary_weight", None))
+             intensity=getattr(args, "intensity", None), boundary=getattr(args, "boundary_weight", None),
+             consolidation=getattr(args, "consolidation", None), consolidation_weight=getattr(args, "consolidation_weight", None))
+    cons = o["consolidation"]
+    if cons is None:
+        if o["consolidation_weight"] is not None:
+            raise ValueError("trainer_synapse: consolidation_weight without consolidation (a continual.Consolidation state dict, or a path to one)")
+    else:
+        from .optim import check_consolidation
+        if isinstance(cons, dict):
+            if "method" not in cons or "tensors" not in cons:
+                raise ValueError('trainer_synapse: consolidation must be a continual.Consolidation.state_dict() ("method", "weight", "tensors")')
+            check_consolidation(cons["method"], cons.get("weight", 0.0), "trainer_synapse: consolidation")
+        elif not isinstance(cons, (str, os.PathLike)):
+            raise ValueError(f"trainer_synapse: consolidation must be None, a continual.Consolidation state dict or a path to one, got {type(cons).__name__}")
+        if o["consolidation_weight"] is not None:
+            o["consolidation_weight"] = check_consolidation("ewc", o["consolidation_weight"], "trainer_synapse: consolidation_weight")[1]
     if o["boundary"] is not None and not callable(o["boundary"]):
         o["boundary"] = _boundary_alpha(o["boundary"], "trainer_synapse: boundary_weight (None, a number or a function epoch -> weight)")
     if o["intensity"] is not None:
@@ -646,6 +681,10 @@ def trainer_synapse(args, model, snapshot_path, group=None, log_every=1, checkpo
     boundary_weight: None (default), the weight alpha of the boundary loss (HipEngine's boundary=) as a float, or a function
     epoch -> alpha applied at the start of every epoch (kervadec_alpha is the published schedule); the log line then carries the
     boundary term.
+    consolidation: None (default), or the state_dict() of a continual.Consolidation estimated on the old task (or a path to one
+    saved with torch.save): the EWC / MAS / L2-SP penalty of that state, carried onto this model's parameters
+    (continual.carry_consolidation_state), is attached to the engine for the whole run, and the log gains its value.
+    consolidation_weight: its strength (default: the state's own).
     checkpoint: None for the schedule above, or a function epoch -> file name or None."""
     import logging
     import random
@@ -719,6 +758,14 @@ def trainer_synapse(args, model, snapshot_path, group=None, log_every=1, checkpo
     if opts["auto_rates"] is not None:
         from .continual import finetune_groups
         trainer.set_auto_rates(finetune_groups(model), opts["auto_rates"])
+    cons = None
+    if opts["consolidation"] is not None:
+        from .continual import Consolidation
+        state = opts["consolidation"]
+        if not isinstance(state, dict):
+            state = torch.load(state, map_location=device)
+        weight = state["weight"] if opts["consolidation_weight"] is None else opts["consolidation_weight"]
+        cons = Consolidation(trainer, method=state["method"], weight=weight, exclude=state.get("exclude", ()), state=state)
     iter_num = 0
     intensity_rng = np.random.default_rng([int(seed), rank]) if opts["intensity"] is not None else None     # one stream over all epochs
     for epoch_num in range(max_epoch):
@@ -738,6 +785,8 @@ def trainer_synapse(args, model, snapshot_path, group=None, log_every=1, checkpo
                     logging.info('iteration %d : loss : %f, loss_ce: %f' % (iter_num, loss, loss_ce))
                 else:
                     logging.info('iteration %d : loss : %f, loss_ce: %f, loss_dice: %f, loss_boundary: %f' % (iter_num, loss, loss_ce, *rest))
+                if cons is not None:                                 # the penalty of this step's weights before the update; same sync point
+                    logging.info('iteration %d : consolidation penalty : %f' % (iter_num, float(cons.penalty)))
                 if opts["auto_rates"] is not None:                   # finetune.py:236 logs every group's rate; same sync point
                     opt = trainer.engine.opt
                     rates = dict(zip(opt.group_names, (opt.group_stats / opt.group_stats.max() * opt.lr_dev).tolist()))
@@ -765,7 +814,7 @@ def surgical_trainer(args, model, snapshot_path, group=None, log_every=1):
     a constant rate; every step's rate of each of the 22 groups of continual.finetune_groups set to lr * n_k / max_j n_j, n the
     norm of the group's gradient (:116-144, 225-236; auto_rates="grad", formed on the device); a fifth of the slices, drawn once
     from args.seed (:166-169); a checkpoint model_lr{lr}_wd{wd}_epoch{epoch}.pth whenever epoch % args.save_interval == 0 (:250-251,
-    save_interval defaults to 1).  args.boundary_weight is passed on as it is.  args.moments ("kept" by default) chooses between Adam with running moments and the reference
+    save_interval defaults to 1).  args.boundary_weight, args.consolidation and args.consolidation_weight are passed on as they are.  args.moments ("kept" by default) chooses between Adam with running moments and the reference
     as written, which builds a new optimiser every step ("fresh").  args.auto_rates and args.subset_fraction override the
     statistic and the part.  Deviations: one forward/backward per step, whose gradient is both measured and
     applied, where the reference measures on a second batch and steps with that batch's gradient; the per-step tune_metrics.pt

@@ -29,7 +29,7 @@ extern "C" {
 /* Bumped whenever a prototype or struct below changes (1: round 1; 2: round 2 -- stream / precision / storage arguments; 3: round 3 --
  * cswin_attn_fwd writes y0, cswin_attn_bwd reads it).  cswin_abi_version() returns the value the library was built with: a consumer
  * compiled against another header must refuse to call it.  Entry points that are only ADDED (cswin_seg_metrics*, cswin_resize_banded, cswin_argmax_zoom_back, cswin_augment_*,
- * cswin_chunk_sumsq, cswin_norm_finalize, cswin_adamw_flat, cswin_tpgm_*, cswin_argmax_zoom_back_classes, cswin_class_counts, cswin_gaussian_blur, cswin_eb_tiles,
+ * cswin_chunk_sumsq, cswin_norm_finalize, cswin_adamw_flat, cswin_tpgm_*, cswin_importance_accumulate, cswin_flat_axpby, cswin_consolidate_*, cswin_argmax_zoom_back_classes, cswin_class_counts, cswin_gaussian_blur, cswin_eb_tiles,
  * cswin_eb_finalize, cswin_rate_finalize, cswin_adam_flat, cswin_components_*, cswin_drop_path_order, cswin_linear_*_skip,
  * cswin_surface_dist*, cswin_view_batch, cswin_tta_argmax_zoom_back, cswin_gaussian_blur_each, cswin_intensity_*, cswin_sdm_workspace, cswin_signed_distance_maps, cswin_bd_loss_*) do not bump it: every prototype an older consumer binds is unchanged. */
 #define CSWIN_ABI_VERSION 4
@@ -471,6 +471,27 @@ int cswin_tpgm_finalize(const float* partial, const int* first_chunk, int ntenso
  * shadow 8-B; src == dst is the only overlap allowed. */
 int cswin_tpgm_project(const float* src, const float* anchor, float* dst, const float* ratio, const void* chunks, int nchunks,
                        void* shadow_bf16, void* stream);
+
+/* ---- EWC / MAS / L2-SP: a quadratic penalty that holds every weight near its old-task value (the anchor) in proportion to an
+ * importance F >= 0, on the flat buffers and the chunk table above.  With d = p - anchor, a weight w_t per tensor (0: excluded)
+ * and the strength lambda:  penalty = (lambda / 2) sum_t w_t sum_i F_i d_i^2,  dpenalty/dp_i = lambda w_t F_i d_i.
+ * No host synchronisation, no float atomic; every buffer 16-B aligned; a refused call touches nothing.
+ *
+ * The estimation pass: x = (float)grad_scale * g;  imp += x * x (statistic 0, the empirical Fisher) or imp += |x| (statistic 1, MAS). */
+int cswin_importance_accumulate(const float* g, float* imp, const void* chunks, int nchunks, double grad_scale, int statistic,
+                                void* stream);
+/* dst = a dst + b src over the chunks; src == NULL: dst = a dst.  The 1 / n normalisation and the online decay of the importance. */
+int cswin_flat_axpby(float* dst, const float* src, const void* chunks, int nchunks, double a, double b, void* stream);
+/* Per element t = imp * d (t = d when imp == NULL: importance 1) and g = fma(c, t, g) with c = lam[0] * tensor_weight[tensor] *
+ * penalty_scale; lam is ONE float in device memory, tensor_weight one float per tensor.  partial[c] = (sum t d, sum d^2) over
+ * chunk c (2 * nchunks floats).  A chunk whose c is exactly 0 stores nothing to g (its bits stay, a -0.0 included); g == NULL: the
+ * sums alone.  penalty_scale is 1 / grad_scale of the optimiser launch that follows. */
+int cswin_consolidate_chunks(const float* p, const float* anchor, const float* imp, float* g, const void* chunks, int nchunks,
+                             const float* lam, const float* tensor_weight, double penalty_scale, float* partial, void* stream);
+/* One workgroup.  per_tensor[t] = (sum F d^2, sum d^2), the chunk partials in chunk order;  with W = sum_t w_t per_tensor[t][0] in
+ * tensor order:  scalars = [(lam[0] / 2) W, W, sqrt(sum_t per_tensor[t][1])]. */
+int cswin_consolidate_finalize(const float* partial, const int* first_chunk, int ntensors, const float* lam,
+                               const float* tensor_weight, float* per_tensor, float* scalars, void* stream);
 
 /* ---- the "eb-criterion" statistic of the surgical mode (universal_train.py:669-672) per parameter tensor of the flat gradient
  * buffer: evidence[t] = mean(g * g / (var(g, dim 0, unbiased) + 1e-8)), one variance per column (an index of the dimensions after
