@@ -21,6 +21,7 @@
 #include <stdlib.h>
 
 #include <type_traits>
+#include "bf16_tile.h"
 #include "common.h"
 #include "gemm_epilogue.h"
 #include "gemm_plan.h"
@@ -32,8 +33,6 @@ void cswin_wgrad16_batch(const cswin_wgrad_desc* d, int n, const gp::Plan* plans
                          long long* stamps);
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // matmul precision is an ARGUMENT of every entry point (no library state): 0 = exact fp32 MFMA (the parity path);
 // 1 = operands rounded to bf16 while they are staged into LDS, v_mfma_f32_32x32x16_bf16, fp32 accumulation and fp32
@@ -406,14 +405,8 @@ __global__ __launch_bounds__(64) void drop_path_order_kernel(const float* __rest
 #endif
 constexpr bool EPI_AHEAD = CSWIN_EPI_AHEAD != 0;
 
-// debug stamps: thread 0 writes s_memtime to `slot` of the workgroup's row; slot 0 also the hardware id and s_memrealtime, slot 3 the latter
-__device__ __forceinline__ void stamp(const Epilogue& epi, int row, int slot) {
-    if (!epi.stamps || threadIdx.x != 0) return;
-    long long* s = epi.stamps + 8L * row;
-    s[slot] = __builtin_amdgcn_s_memtime();
-    if (slot == 0) { s[4] = __builtin_amdgcn_s_getreg(6164); s[5] = __builtin_amdgcn_s_memrealtime(); }
-    if (slot == 3) s[6] = __builtin_amdgcn_s_memrealtime();
-}
+// debug stamps (stamp_slot, bf16_tile.h)
+__device__ __forceinline__ void stamp(const Epilogue& epi, int row, int slot) { stamp_slot(epi.stamps, row, slot); }
 
 // T: the tile configuration.  SCALE_A: multiply the A rows by their Row::s (DropPath factor) when staging (weight gradients only).
 // MASKED (weight gradients of plain matrices only): the reduction runs over the kept samples' rows (RowMask); a compile-time variant.
@@ -685,7 +678,7 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
                 if constexpr (PREC == 1) {
 #pragma unroll 8
                     for (int r = 0; r < BK; ++r)
-                        csum += __builtin_bit_cast(float, (unsigned)As16[tid * LD16 + r] << 16);
+                        csum += widen_bf16(As16[tid * LD16 + r]);
                 } else {
 #pragma unroll 8
                     for (int r = 0; r < BK; ++r) csum += As[r * TA::LD + tid];
@@ -703,19 +696,12 @@ __device__ __forceinline__ void gemm_body(float* lds, const ASrc& A, const BSrc&
                         if constexpr (B_RC) {
                             bf[j] = *reinterpret_cast<const bf16x8*>(&Bs16[(wn0 + j * 32 + li) * LD16 + kk + 8 * lh]);
                         } else {
-                            // lane (q, p) of its 16-lane group supplies row r0 + q, columns c0 + 4 p .. + 3; it receives column
-                            // c0 + (lane & 15) of rows r0 .. r0 + 3: two reads give the 8 reduction values of this lane's column
-                            typedef short s16x4 __attribute__((ext_vector_type(4)));
-                            typedef short s16x8 __attribute__((ext_vector_type(8)));
-                            typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+                            // the 8 reduction values of this lane's column (tr16_frag, bf16_tile.h)
                             const int col = wn0 + j * 32 + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
                             const int row = kk + 8 * lh + ((lane & 15) >> 2);
                             const int sw = ((row >> 1) & 1) << 2;               // rows row and row + 4 share bit 1
                             const unsigned short* a0 = &Bs16[row * BN + 8 * ((col >> 3) ^ sw) + (col & 7)];
-                            const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)a0);
-                            const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0 + 4 * BN));
-                            const s16x8 f = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-                            bf[j] = __builtin_bit_cast(bf16x8, f);
+                            bf[j] = tr16_frag(a0, a0 + 4 * BN);
                         }
                     }
 #pragma unroll
@@ -1469,9 +1455,8 @@ int linear_dgrad_impl(const char* who, const float* dy, const float* w, float* d
 // ======================================================================================
 extern "C" {
 
-// debug aid (not part of include/cswin_hip.h): device buffer [workgroups][8] of int64; workgroup w of a GEMM launch stamps row w:
-// slots 0-3 s_memtime at start / first tile staged / main loop done / epilogue done, 4 the hardware id register, 5-6 s_memrealtime
-// at start / end (7 unused)
+// debug aid (not part of include/cswin_hip.h): device buffer [workgroups][8] of int64; workgroup w of a GEMM launch stamps row w
+// (stamp_slot, bf16_tile.h, has the slots)
 void cswin_debug_set_stamps(void* p) { g_stamps = (long long*)p; }
 
 int cswin_linear_fwd(const float* x, const float* x2, int k_split, const float* w, const float* bias, float* y,

@@ -1,15 +1,11 @@
-// Epilogue shared by the GEMM kernels of libcswin_hip (gemm.hip: tiled family; gemm16.hip: LDS-DMA bf16 kernel).
+// Epilogue shared by the GEMM kernels of libcswin_hip (gemm.hip: tiled family; gemm16.hip: LDS-DMA bf16 kernel).  The wave's
+// LDS patch, its put and its constants, and widen_bf16x4 are bf16_tile.h's.
 #pragma once
+#include "bf16_tile.h"
 #include "common.h"
 
 namespace {
 
-// widen 4 bf16 held as two raw dwords.  Raw bf16 bits travel in INTEGER vectors: hipcc 7.2 miscompiles bit casts of the
-// elements of a 2-float vector (element 1 reads element 0).
-__device__ __forceinline__ f32x4 widen_bf16x4(u32x2 raw) {
-    return f32x4{__builtin_bit_cast(float, raw[0] << 16), __builtin_bit_cast(float, raw[0] & 0xffff0000u),
-                 __builtin_bit_cast(float, raw[1] << 16), __builtin_bit_cast(float, raw[1] & 0xffff0000u)};
-}
 __device__ __forceinline__ void epi_store4(float* base, long idx, f32x4 v, int bf16) {
     if (bf16) *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(base) + idx) = __builtin_convertvector(v, bf16x4);
     else *reinterpret_cast<f32x4*>(base + idx) = v;
@@ -37,13 +33,8 @@ struct Epilogue {
     long long* stamps;                        // debug: per-workgroup s_memtime stamps [nblk][8] (NULL in production)
 };
 
-// C/D layout of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5), i.e. a lane owns one
-// COLUMN of the fragment.  Storing from that layout is 16 dword stores per fragment (store-issue bound, measured 20-26 %
-// of a workgroup's life).  Each wave therefore transposes its fragment through a private [32][36] LDS patch so that a
-// lane owns 4 consecutive columns of one row: bias / residual / gelu' operands are read and the result is written
-// with 16-B accesses, 8 full 128-B lines per wave instruction.
-constexpr int EP_LD = 36;
-constexpr int EP_WAVE_FLOATS = 32 * EP_LD;
+// Every fragment leaves the C/D layout through its wave's LDS patch (patch_put, bf16_tile.h), so that a lane owns 4 consecutive
+// columns of one row: bias / residual / gelu' operands are read and the result is written with 16-B accesses.
 
 // The auxiliary operands of one fragment's vector path, in registers: bias, and per row chunk p the row factor, the residual /
 // gelu_pre chunk (aux16: stored as bf16) and, MAPPED, the row's place in memory.
@@ -100,6 +91,36 @@ __device__ __forceinline__ void epilogue_request(EpiOperands& q, const Epilogue&
     }
 }
 
+// The consume step of row chunk p of a fragment (vector path): v, the chunk's four sums from the patch, meets the operands q.
+// epi_value: (v + bias) . gelu'(gelu_pre) . row factor.  epi_consume_row (not MAPPED): + residual, the store of output row m
+// -- row c_row(m) of C -- at columns n .. n + 3, and the activation store.  gemm16.hip's epilogue is this step on one fragment.
+template <int EPI, bool PRE16>
+__device__ __forceinline__ f32x4 epi_value(const EpiOperands& q, int p, f32x4 v, bool has_rs) {
+    f32x4 o = v + q.bias;
+    if (EPI == EPI_GELUBWD) {
+        const f32x4 pre = PRE16 ? widen_bf16x4(q.aux16[p]) : q.aux[p];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) o[c] *= gelu_grad_f(pre[c]);
+    }
+    if (has_rs) o *= q.rs[p];
+    return o;
+}
+template <int EPI, bool PRE16, typename RowFn>
+__device__ __forceinline__ void epi_consume_row(const Epilogue& e, const EpiOperands& q, int p, f32x4 v, bool has_rs, int m, int n, RowFn c_row) {
+    f32x4 o = epi_value<EPI, PRE16>(q, p, v, has_rs);
+    if (EPI == EPI_RES) o += q.aux[p];
+    if (EPI == EPI_SPLIT2 && n >= e.col_split)
+        *reinterpret_cast<f32x4*>(e.C2 + (long)m * e.ldc2 + (n - e.col_split)) = o;
+    else
+        epi_store4(e.C, c_row(m) * e.ldc + n, o, e.c_bf16);
+    if (EPI == EPI_ACT) {
+        f32x4 a;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) a[c] = gelu_f(o[c]);
+        epi_store4(e.Cact, (long)m * e.ldact + n, a, e.c_bf16);
+    }
+}
+
 // PRE16: gelu_pre is stored as bf16 (EPI_GELUBWD) -- compile-time, so that the four auxiliary loads of a fragment stay in one
 // basic block and are issued back to back.
 // FDIV: the row split of rm_on by multiply-high with the reciprocals m_hw, m_w2 of rm_H2 * rm_W2 and rm_W2 (fdiv, common.h; the
@@ -119,7 +140,6 @@ __device__ __forceinline__ void run_epilogue(const Epilogue& e, f32x16 (&acc)[FM
                                              int lane, float* wbuf, bool vec, unsigned m_hw = 0, unsigned m_w2 = 0,
                                              const int* ord = nullptr, int kept_rows = 0, int map_rps = 1, unsigned map_magic = 0,
                                              const EpiOperands* first = nullptr) {
-    const int li = lane & 31, lh = lane >> 5;
     const int rrow = lane >> 3, rcol = (lane & 7) * 4;
     const bool has_rs = e.row_scale != nullptr;
     auto out_row = [&](int m) -> long {           // class-local pixel -> row of the full (B, H*W, C) token matrix
@@ -139,11 +159,7 @@ __device__ __forceinline__ void run_epilogue(const Epilogue& e, f32x16 (&acc)[FM
     for (int i = 0; i < FM; ++i) {
 #pragma unroll
         for (int j = 0; j < FN; ++j) {
-#pragma unroll
-            for (int g = 0; g < 16; ++g) wbuf[((g & 3) + 8 * (g >> 2) + 4 * lh) * EP_LD + li] = acc[i][j][g];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            patch_put(wbuf, acc[i][j], lane);
             const int n = nb + j * 32 + rcol;
             if (vec) {
                 EpiOperands nq;                            // AHEAD: the next fragment's operands, requested under this one's stores
@@ -155,11 +171,7 @@ __device__ __forceinline__ void run_epilogue(const Epilogue& e, f32x16 (&acc)[FM
                     const int f = i * FN + j + 1;
                     if (f < FM * FN) epilogue_request<EPI, PRE16, MAPPED>(nq, e, M, N, mb + (f / FN) * 32, nb + (f % FN) * 32, lane, ord, kept_rows, map_rps, map_magic);
                 }
-                const f32x4 bias_v = q.bias;
-                const f32x4 (&aux)[4] = q.aux;
-                const u32x2 (&aux16)[4] = q.aux16;
-                const float (&rs)[4] = q.rs;
-                int pm[4];     // MAPPED: the rows' places in memory; AHEAD: made again from ord in LDS, not held through the last k-tile
+                int pm[4];    // MAPPED: the rows' places in memory; AHEAD: made again from ord in LDS, not held through the last k-tile
 #pragma unroll
                 for (int p = 0; p < 4; ++p) {
                     int smp;
@@ -169,17 +181,11 @@ __device__ __forceinline__ void run_epilogue(const Epilogue& e, f32x16 (&acc)[FM
                 for (int p = 0; p < 4; ++p) {
                     const int m = mb + i * 32 + rrow + 8 * p;
                     if (m >= M || n >= N) continue;
-                    f32x4 o = v[p] + bias_v;
-                    if (EPI == EPI_GELUBWD) {
-                        const f32x4 pre = PRE16 ? widen_bf16x4(aux16[p]) : aux[p];
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) o[c] *= gelu_grad_f(pre[c]);
-                    }
-                    if (has_rs) o *= rs[p];
                     if constexpr (MAPPED) {
                         static_assert(EPI != EPI_SPLIT2 && !PRE16 && !FDIV, "row-mapped launches: one fp32 output matrix");
+                        f32x4 o = epi_value<EPI, PRE16>(q, p, v[p], has_rs);
                         if (EPI == EPI_RES && ord && m >= kept_rows) o = f32x4{0.f, 0.f, 0.f, 0.f};
-                        if (EPI == EPI_RES) o += aux[p];
+                        if (EPI == EPI_RES) o += q.aux[p];
                         *reinterpret_cast<f32x4*>(e.C + (long)pm[p] * e.ldc + n) = o;
                         if (EPI == EPI_ACT) {
                             f32x4 a;
@@ -187,18 +193,8 @@ __device__ __forceinline__ void run_epilogue(const Epilogue& e, f32x16 (&acc)[FM
                             for (int c = 0; c < 4; ++c) a[c] = gelu_f(o[c]);
                             *reinterpret_cast<f32x4*>(e.Cact + (long)pm[p] * e.ldact + n) = a;
                         }
-                        continue;
-                    }
-                    if (EPI == EPI_RES) o += aux[p];
-                    if (EPI == EPI_SPLIT2 && n >= e.col_split)
-                        *reinterpret_cast<f32x4*>(e.C2 + (long)m * e.ldc2 + (n - e.col_split)) = o;
-                    else
-                        epi_store4(e.C, out_row(m) * e.ldc + n, o, e.c_bf16);
-                    if (EPI == EPI_ACT) {
-                        f32x4 a;
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) a[c] = gelu_f(o[c]);
-                        epi_store4(e.Cact, (long)m * e.ldact + n, a, e.c_bf16);
+                    } else {
+                        epi_consume_row<EPI, PRE16>(e, q, p, v[p], has_rs, m, n, out_row);
                     }
                 }
                 if constexpr (AHEAD && FM * FN > 1) q = nq;

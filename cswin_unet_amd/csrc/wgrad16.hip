@@ -7,22 +7,17 @@
 // index.  The tiled family (gemm.hip) transposes them while staging, with one 2-byte LDS store per element: with bf16
 // MFMAs (16x the fp32 rate) that staging is the whole kernel (profiles/round1_gemm_bench_bf16_operands.txt: 3.07 ms per
 // step against 3.30 ms in fp32).  Here the tiles are stored in LDS the way they arrive -- [m][128 columns] bf16 rows, one
-// ds_write_b64 per 16-B global chunk -- and CDNA4's transposing LDS read (ds_read_b64_tr_b16: a 16-lane group reads a
-// 4-row x 16-column block and each lane receives one COLUMN of it) delivers the m-contiguous fragments that
-// v_mfma_f32_32x32x16_bf16 wants.  256-B rows are XOR-swizzled per 16-B chunk (guide T10, image (b)) so that the
-// transposed reads are bank-conflict free.
+// ds_write_b64 per 16-B global chunk -- and CDNA4's transposing LDS read (tr16_frag, bf16_tile.h) delivers the m-contiguous
+// fragments that v_mfma_f32_32x32x16_bf16 wants.  256-B rows are XOR-swizzled per 16-B chunk (guide T10, image (b)) so that
+// the transposed reads are bank-conflict free.
 //
 // One workgroup = 4 waves = one 128 (n) x 128 (k) tile of dW over one slice of m; partial tiles go to the same
 // [split][N*K + N] slabs as the fp32 path, reduced by cswin_rows_sum_multi.  fp32 accumulation throughout.
+#include "bf16_tile.h"
 #include "common.h"
 #include "gemm_plan.h"
 
 namespace {
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 constexpr int W16_T = gp::W16_T;    // tile edge (n and k)
 constexpr int W16_MS = gp::W16_MS;  // m rows per step
@@ -54,47 +49,62 @@ constexpr int W16_SC_BYTES = (W16_SC_SAMPLES + W16_DMA_S * W16_MS) * 4;
 constexpr int W16_LDS = W16_DMA_S * W16_STEP + W16_SC_BYTES;        // 48.6 KB (register path: 2 stages + bias sums = 36 KB): 3 workgroups per CU
 static_assert(W16_LDS >= 2 * W16_STEP + 8 * W16_T * 4, "the register path's stages and bias sums must fit");
 
-// Partial 64 x 64 wave tile -> slab.  The 32x32 accumulators hold a COLUMN per lane (lane = k, registers = rows n): stored from
-// that layout a wave issues 64 dword stores.  Each fragment goes through a private [32][36] LDS patch instead (as the GEMM
-// epilogue does) so that a lane owns 4 consecutive k of one row: 16 stores of 16 B.  Call after a workgroup barrier (the patches
-// overlay the operand images); K % 4 == 0 and 16-B aligned slabs are the caller's contract.
-constexpr int W16_PATCH = 32 * 36;
-__device__ __forceinline__ void w16_store_tile(f32x16 (&acc)[2][2], float* slab, int N, int K, int n0, int k0, int lane, float* patch) {
-    const int li = lane & 31, lh = lane >> 5, rrow = lane >> 3, rcol = (lane & 7) * 4;
+// What workgroup lb of a problem works on, for both tiles below: its slice [m_begin, m_end) of the reduction (slab `split`), its
+// 128 x 128 tile at (nb, kb) and its place in it -- wave tile n in [nb + 64 wi, +64), k in [kb + 64 wj, +64).
+struct W16Tile {
+    int split, nb, kb, m_begin, m_end, lane, wave, wi, wj, lh;
+    // wave: threadIdx.x >> 6, as the caller holds it (the LDS-DMA tile passes it wave-uniform)
+    __device__ __forceinline__ W16Tile(const W16Problem& P, int lb, int wave_) {
+        const int tiles = P.tiles_n * P.tiles_k;
+        split = lb / tiles;
+        const int tile = lb - split * tiles;
+        nb = (tile / P.tiles_k) * W16_T; kb = (tile % P.tiles_k) * W16_T;
+        m_begin = split * P.rows_per_split;
+        m_end = min(P.M, m_begin + P.rows_per_split);
+        lane = threadIdx.x & 63; wave = wave_;
+        wi = wave >> 1; wj = wave & 1;
+        lh = lane >> 5;
+    }
+    // the m-contiguous fragment of a 32-column block cb (columns cb .. cb + 31) of a [m][128] image for the k16 step at row r16:
+    // group (lane >> 4) & 1 takes columns cb + 16 * that, lane half lh rows r16 + 8 lh + 0 .. 7 (tr16_frag, with img_off's swizzle)
+    __device__ __forceinline__ bf16x8 tr_frag(const unsigned char* img, int cb, int r16) const {
+        const int col = cb + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+        const int row = r16 + 8 * lh + ((lane & 15) >> 2);
+        return tr16_frag(img + img_off(row, col >> 3) + 2 * (col & 7), img + img_off(row + 4, col >> 3) + 2 * (col & 7));
+    }
+    // the workgroup's slab: N x K products, then N bias sums
+    __device__ __forceinline__ float* slab(const W16Problem& P) const { return P.slab + (long)split * P.slab_stride; }
+};
+
+// Partial 64 x 64 wave tile -> the workgroup's slab.  Stored from the accumulators' layout (lane = k, registers = rows n) a wave
+// issues 64 dword stores; through its LDS patch (patch_put) a lane owns 4 consecutive k of one row: 16 stores of 16 B.  Call
+// after a workgroup barrier (the patches overlay the operand images); K % 4 == 0 and 16-B aligned slabs are the caller's
+// contract.  N and K by value: read through the problem they are loaded again between the stores.
+__device__ __forceinline__ void w16_store_tile(f32x16 (&acc)[2][2], float* slab, const int N, const int K, const W16Tile& t, unsigned char* lds) {
+    float* patch = reinterpret_cast<float*>(lds) + t.wave * EP_WAVE_FLOATS;
+    const int n0 = t.nb + 64 * t.wi, k0 = t.kb + 64 * t.wj, rrow = t.lane >> 3, rcol = (t.lane & 7) * 4;
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
-#pragma unroll
-            for (int g = 0; g < 16; ++g) patch[((g & 3) + 8 * (g >> 2) + 4 * lh) * 36 + li] = acc[a][c][g];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            patch_put(patch, acc[a][c], t.lane);
             const int k = k0 + 32 * c + rcol;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int n = n0 + 32 * a + rrow + 8 * q;
-                if (n < N && k < K) *reinterpret_cast<f32x4*>(slab + (long)n * K + k) = *reinterpret_cast<const f32x4*>(&patch[(rrow + 8 * q) * 36 + rcol]);
+                if (n < N && k < K) *reinterpret_cast<f32x4*>(slab + (long)n * K + k) = *reinterpret_cast<const f32x4*>(&patch[(rrow + 8 * q) * EP_LD + rcol]);
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_fence();
         }
 }
 
 // One problem's tile.  DY16 / X16: that operand is STORED as bf16 -- compile-time copies of the body (chosen per workgroup in
 // the kernel below): a run-time choice between 8-B and 16-B loads inside fetch() makes the prefetch loads wait for one another.
 template <bool DY16, bool X16>
-__device__ __forceinline__ void wgrad16_tile(const W16Problem& P, const int lb, unsigned char* lds, long long* st) {
-    const int tiles = P.tiles_n * P.tiles_k;
-    const int split = lb / tiles, tile = lb - split * tiles;
-    const int nb = (tile / P.tiles_k) * W16_T, kb = (tile % P.tiles_k) * W16_T;
-    const int m_begin = split * P.rows_per_split;
-    const int m_end = min(P.M, m_begin + P.rows_per_split);
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wi = wave >> 1, wj = wave & 1;                    // wave tile: n in [64 wi, +64), k in [64 wj, +64)
-    const int li = lane & 31, lh = lane >> 5;
+__device__ __forceinline__ void wgrad16_tile(const W16Problem& P, const int lb, unsigned char* lds, long long* stamps) {
+    const int tid = threadIdx.x;
+    const W16Tile t(P, lb, tid >> 6);
+    const int nb = t.nb, kb = t.kb, m_begin = t.m_begin, m_end = t.m_end, wi = t.wi, wj = t.wj;
 
     // loader: thread -> 16-B fp32 chunk c (4 columns) of rows lr + 8 j, j = 0..3, of both tiles
     const int lc = tid & 31, lr = tid >> 5;
@@ -102,7 +112,7 @@ __device__ __forceinline__ void wgrad16_tile(const W16Problem& P, const int lb, 
     const float* dyp = P.dy + nb + 4 * lc;
     const float* xp = P.x + kb + 4 * lc;
     f32x4 gdy[4], gx[4];
-    u32x2 gdyh[4], gxh[4];          // raw chunks of a bf16-stored operand (INTEGER vectors: see widen_bf16x4 in gemm_epilogue.h)
+    u32x2 gdyh[4], gxh[4];          // raw chunks of a bf16-stored operand (INTEGER vectors: see widen_bf16x4)
     float grs[4];
     auto fetch = [&](int m0) {
 #pragma unroll
@@ -140,9 +150,7 @@ __device__ __forceinline__ void wgrad16_tile(const W16Problem& P, const int lb, 
         for (int j = 0; j < 4; ++j) {
             const int r = lr + 8 * j;
             f32x4 d = gdy[j];
-            if constexpr (DY16)
-                d = f32x4{__builtin_bit_cast(float, gdyh[j][0] << 16), __builtin_bit_cast(float, gdyh[j][0] & 0xffff0000u),
-                          __builtin_bit_cast(float, gdyh[j][1] << 16), __builtin_bit_cast(float, gdyh[j][1] & 0xffff0000u)};
+            if constexpr (DY16) d = widen_bf16x4(gdyh[j]);
             d *= grs[j];
             bsum += d;
             const int off = img_off(r, lc >> 1) + 8 * (lc & 1);
@@ -150,22 +158,6 @@ __device__ __forceinline__ void wgrad16_tile(const W16Problem& P, const int lb, 
             if constexpr (X16) *reinterpret_cast<u32x2*>(ximg + off) = gxh[j];
             else *reinterpret_cast<bf16x4*>(ximg + off) = __builtin_convertvector(gx[j], bf16x4);
         }
-    };
-
-    // transposed-read addresses: lane (q, p) of its 16-lane group supplies row r0 + q, columns c0 + 4 p .. +3 of the block;
-    // it receives column c0 + (lane & 15) of rows r0 .. r0 + 3.  Fragment of a 32-column block cb (columns cb .. cb + 31):
-    // group (lane >> 4) & 1 takes columns cb + 16 * that, lane half lh takes rows 8 lh + 4 t (t = 0, 1) of the k16 step.
-    const int q = (lane & 15) >> 2, pp = lane & 3;
-    auto tr_frag = [&](const unsigned char* img, int cb, int r16) -> bf16x8v {
-        const int col = cb + 16 * ((lane >> 4) & 1) + 4 * pp;
-        s16x4 v0, v1;
-        {
-            const int row = r16 + 8 * lh + q;
-            v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + img_off(row, col >> 3) + 2 * (col & 7)));
-            v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + img_off(row + 4, col >> 3) + 2 * (col & 7)));
-        }
-        s16x8 f = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-        return __builtin_bit_cast(bf16x8v, f);
     };
 
     f32x16 acc[2][2];
@@ -180,7 +172,7 @@ __device__ __forceinline__ void wgrad16_tile(const W16Problem& P, const int lb, 
         fetch(m_begin);
         stash(0);
         __syncthreads();
-        if (st && threadIdx.x == 0) st[1] = __builtin_amdgcn_s_memtime();
+        stamp_slot(stamps, blockIdx.x, 1);
         int stage = 0;
         for (int m0 = m_begin; m0 < m_end; m0 += W16_MS) {
             const bool more = m0 + W16_MS < m_end;
@@ -189,11 +181,11 @@ __device__ __forceinline__ void wgrad16_tile(const W16Problem& P, const int lb, 
             const unsigned char* ximg = dimg + W16_MS * 256;
 #pragma unroll
             for (int r16 = 0; r16 < W16_MS; r16 += 16) {
-                bf16x8v af[2], bf[2];
+                bf16x8 af[2], bf[2];
 #pragma unroll
-                for (int a = 0; a < 2; ++a) af[a] = tr_frag(dimg, 64 * wi + 32 * a, r16);
+                for (int a = 0; a < 2; ++a) af[a] = t.tr_frag(dimg, 64 * wi + 32 * a, r16);
 #pragma unroll
-                for (int c = 0; c < 2; ++c) bf[c] = tr_frag(ximg, 64 * wj + 32 * c, r16);
+                for (int c = 0; c < 2; ++c) bf[c] = t.tr_frag(ximg, 64 * wj + 32 * c, r16);
 #pragma unroll
                 for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -205,11 +197,11 @@ __device__ __forceinline__ void wgrad16_tile(const W16Problem& P, const int lb, 
         }
     }
 
-    if (st && threadIdx.x == 0) st[2] = __builtin_amdgcn_s_memtime();
+    stamp_slot(stamps, blockIdx.x, 2);
     // ---- partial tile -> slab ----
-    float* slab = P.slab + (long)split * P.slab_stride;
     __syncthreads();                        // every wave is done with the operand images: they become the store patches
-    w16_store_tile(acc, slab, P.N, P.K, nb + 64 * wi, kb + 64 * wj, lane, reinterpret_cast<float*>(lds) + wave * W16_PATCH);
+    float* slab = t.slab(P);
+    w16_store_tile(acc, slab, P.N, P.K, t, lds);
     // ---- bias gradient partial: column sums of the dy tile (only the k-tile 0 workgroups own them) ----
     if (P.has_bias && kb == 0) {
         float* red = reinterpret_cast<float*>(lds + 2 * 2 * W16_MS * 256);      // [8][128]
@@ -227,32 +219,19 @@ __device__ __forceinline__ void wgrad16_tile(const W16Problem& P, const int lb, 
 // ---- LDS-DMA tile: both operands stored as bf16 and used as they are (no row scale) ----------------------------------------
 // The register path above spends ~3 k cycles per 32-row step on 256 cycles of MFMA work (tools/wgrad16_stamps.py): one
 // global-load round trip per step, its prefetch reaching one step ahead, and a second register set costs a workgroup per CU.
-// Here the [m][128] images are written by global_load_lds_dwordx4 (no registers: three steps in flight at the same occupancy),
-// the XOR swizzle of img_off applied to the SOURCE chunk, one counted s_waitcnt vmcnt + s_barrier per step.  The bias gradient
+// Here the [m][128] images are written by LDS-DMA (lds_dma, bf16_tile.h; no registers: three steps in flight at the same
+// occupancy), the XOR swizzle of img_off applied to the SOURCE chunk, one counted dma_wait + dma_barrier per step.  The bias gradient
 // (column sums of dy) is one more MFMA per fragment against a constant ones operand instead of a pass over the tile.
 // SCALE (DropPath row factors on dy): the factors of the samples this workgroup's rows touch are read once, a 32-entry per-row
 // table is refreshed per step in LDS, and the dy fragments are scaled as they leave LDS (widen, multiply, round: the same
 // arithmetic, element by element, as the register path's scale-then-round).
-__device__ __forceinline__ void w16_dma(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-template <int N> __device__ __forceinline__ void w16_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void w16_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 template <bool SCALE>
-__device__ __forceinline__ void wgrad16_dma_tile(const W16Problem& P, const int lb, unsigned char* lds, long long* st) {
-    const int tiles = P.tiles_n * P.tiles_k;
-    const int split = lb / tiles, tile = lb - split * tiles;
-    const int nb = (tile / P.tiles_k) * W16_T, kb = (tile % P.tiles_k) * W16_T;
-    const int m_begin = split * P.rows_per_split;
-    const int m_end = min(P.M, m_begin + P.rows_per_split);
+__device__ __forceinline__ void wgrad16_dma_tile(const W16Problem& P, const int lb, unsigned char* lds, long long* stamps) {
+    const int tid = threadIdx.x;
+    const W16Tile t(P, lb, __builtin_amdgcn_readfirstlane(tid >> 6));
+    const int nb = t.nb, kb = t.kb, m_begin = t.m_begin, m_end = t.m_end, lane = t.lane, wave = t.wave, wi = t.wi, wj = t.wj, lh = t.lh;
     const int nsteps = (m_end - m_begin) / W16_MS;              // whole steps: M and the split size are multiples of 32
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wi = wave >> 1, wj = wave & 1;                    // wave tile: n in [64 wi, +64), k in [64 wj, +64)
-    const int li = lane & 31, lh = lane >> 5;
+    const int li = lane & 31;
     const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds;
 
     // DMA: a wave instruction moves 4 image rows (1 KB); wave w moves row groups 2 w, 2 w + 1 of both images of a step
@@ -270,19 +249,9 @@ __device__ __forceinline__ void wgrad16_dma_tile(const W16Problem& P, const int 
     auto issue = [&](int step) {
         const unsigned stg = lds0 + (unsigned)(step % W16_DMA_S) * W16_STEP + (unsigned)wave * 2048;
 #pragma unroll
-        for (int g = 0; g < 2; ++g) w16_dma(dy_src[g] + (long)step * W16_MS * P.N * 2, stg + g * 1024);
+        for (int g = 0; g < 2; ++g) lds_dma(dy_src[g] + (long)step * W16_MS * P.N * 2, stg + g * 1024);
 #pragma unroll
-        for (int g = 0; g < 2; ++g) w16_dma(x_src[g] + (long)step * W16_MS * P.K * 2, stg + W16_MS * 256 + g * 1024);
-    };
-
-    const int q = (lane & 15) >> 2, pp = lane & 3;
-    auto tr_frag = [&](const unsigned char* img, int cb, int r16) -> bf16x8v {
-        const int col = cb + 16 * ((lane >> 4) & 1) + 4 * pp;
-        const int row = r16 + 8 * lh + q;
-        const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + img_off(row, col >> 3) + 2 * (col & 7)));
-        const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + img_off(row + 4, col >> 3) + 2 * (col & 7)));
-        const s16x8 f = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-        return __builtin_bit_cast(bf16x8v, f);
+        for (int g = 0; g < 2; ++g) lds_dma(x_src[g] + (long)step * W16_MS * P.K * 2, stg + W16_MS * 256 + g * 1024);
     };
 
     f32x16 acc[2][2], accb[2];
@@ -309,7 +278,7 @@ __device__ __forceinline__ void wgrad16_dma_tile(const W16Problem& P, const int 
         if (tid < W16_MS) sc_row[(step % W16_DMA_S) * W16_MS + tid] = sc_tab[(m_begin + step * W16_MS + tid) / P.rows_per_sample - b0];
     };
     const s16x8 ones_s = {0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80};      // bf16 1.0
-    const bf16x8v ones = __builtin_bit_cast(bf16x8v, ones_s);
+    const bf16x8 ones = __builtin_bit_cast(bf16x8, ones_s);
 
     for (int s = 0; s < W16_DMA_S - 1 && s < nsteps; ++s) {
         issue(s);
@@ -317,23 +286,23 @@ __device__ __forceinline__ void wgrad16_dma_tile(const W16Problem& P, const int 
     }
     for (int step = 0; step < nsteps; ++step) {
         const int later = min(W16_DMA_S - 2, nsteps - 1 - step);
-        if (later >= 1) w16_wait<4>();
-        else w16_wait<0>();
-        w16_barrier();                      // the step is in LDS for every wave; the stage read one step ago is free again
+        if (later >= 1) dma_wait<4>();      // this step's 4 DMAs (per wave) have landed when only the next step's 4 are outstanding
+        else dma_wait<0>();
+        dma_barrier();                      // the step is in LDS for every wave; the stage read one step ago is free again
         if (step + W16_DMA_S - 1 < nsteps) {
             issue(step + W16_DMA_S - 1);
             if constexpr (SCALE) fill_rows(step + W16_DMA_S - 1);
         }
-        if (st && threadIdx.x == 0 && step == 0) st[1] = __builtin_amdgcn_s_memtime();
+        if (step == 0) stamp_slot(stamps, blockIdx.x, 1);
         const unsigned char* dimg = lds + (step % W16_DMA_S) * W16_STEP;
         const unsigned char* ximg = dimg + W16_MS * 256;
 #pragma unroll
         for (int r16 = 0; r16 < W16_MS; r16 += 16) {
-            bf16x8v af[2], bf[2];
+            bf16x8 af[2], bf[2];
 #pragma unroll
-            for (int a = 0; a < 2; ++a) af[a] = tr_frag(dimg, 64 * wi + 32 * a, r16);
+            for (int a = 0; a < 2; ++a) af[a] = t.tr_frag(dimg, 64 * wi + 32 * a, r16);
 #pragma unroll
-            for (int c = 0; c < 2; ++c) bf[c] = tr_frag(ximg, 64 * wj + 32 * c, r16);
+            for (int c = 0; c < 2; ++c) bf[c] = t.tr_frag(ximg, 64 * wj + 32 * c, r16);
             if constexpr (SCALE) {
                 // a lane's 8 values are rows r16 + 8 lh + 0 .. 7 of its column
                 const float* sr = &sc_row[(step % W16_DMA_S) * W16_MS + r16 + 8 * lh];
@@ -341,10 +310,7 @@ __device__ __forceinline__ void wgrad16_dma_tile(const W16Problem& P, const int 
 #pragma unroll
                 for (int a = 0; a < 2; ++a) {
                     const u32x4 raw = __builtin_bit_cast(u32x4, af[a]);
-                    f32x4 lo = {__builtin_bit_cast(float, raw[0] << 16), __builtin_bit_cast(float, raw[0] & 0xffff0000u),
-                                __builtin_bit_cast(float, raw[1] << 16), __builtin_bit_cast(float, raw[1] & 0xffff0000u)};
-                    f32x4 hi = {__builtin_bit_cast(float, raw[2] << 16), __builtin_bit_cast(float, raw[2] & 0xffff0000u),
-                                __builtin_bit_cast(float, raw[3] << 16), __builtin_bit_cast(float, raw[3] & 0xffff0000u)};
+                    const f32x4 lo = widen_bf16x4(u32x2{raw[0], raw[1]}), hi = widen_bf16x4(u32x2{raw[2], raw[3]});
                     af[a] = __builtin_shufflevector(__builtin_convertvector(lo * s0, bf16x4), __builtin_convertvector(hi * s1, bf16x4), 0, 1, 2, 3, 4, 5, 6, 7);
                 }
             }
@@ -358,10 +324,10 @@ __device__ __forceinline__ void wgrad16_dma_tile(const W16Problem& P, const int 
             }
         }
     }
-    if (st && threadIdx.x == 0) st[2] = __builtin_amdgcn_s_memtime();
-    float* slab = P.slab + (long)split * P.slab_stride;
-    w16_barrier();                          // every wave is done with the operand images: they become the store patches
-    w16_store_tile(acc, slab, P.N, P.K, nb + 64 * wi, kb + 64 * wj, lane, reinterpret_cast<float*>(lds) + wave * W16_PATCH);
+    stamp_slot(stamps, blockIdx.x, 2);
+    dma_barrier();                          // every wave is done with the operand images: they become the store patches
+    float* slab = t.slab(P);
+    w16_store_tile(acc, slab, P.N, P.K, t, lds);
     if (do_bias && li == 0) {               // every column of the ones product holds the row sums: take column 0
 #pragma unroll
         for (int a = 0; a < 2; ++a)
@@ -384,19 +350,18 @@ __global__ __launch_bounds__(256, 3) void wgrad16_kernel(W16Batch b) {
     while (pi + 1 < b.n && (int)blockIdx.x >= b.first[pi + 1]) ++pi;
     const W16Problem& P = b.p[pi];
     const int lb = (int)blockIdx.x - b.first[pi];
-    long long* st = b.stamps ? b.stamps + 8L * blockIdx.x : nullptr;
-    if (st && threadIdx.x == 0) { st[0] = __builtin_amdgcn_s_memtime(); st[4] = __builtin_amdgcn_s_getreg(6164); st[5] = __builtin_amdgcn_s_memrealtime(); }
-    if (P.dma) {
-        if (P.row_scale) wgrad16_dma_tile<true>(P, lb, lds, st);
-        else wgrad16_dma_tile<false>(P, lb, lds, st);
+    stamp_slot(b.stamps, blockIdx.x, 0);
+    if (P.dma) {            // SCALE, like DY16 / X16, is compile-time: the unscaled tile carries no table, no LDS reads and no rounding
+        if (P.row_scale) wgrad16_dma_tile<true>(P, lb, lds, b.stamps);
+        else wgrad16_dma_tile<false>(P, lb, lds, b.stamps);
     } else if (P.dy_bf16) {
-        if (P.x_bf16) wgrad16_tile<true, true>(P, lb, lds, st);
-        else wgrad16_tile<true, false>(P, lb, lds, st);
+        if (P.x_bf16) wgrad16_tile<true, true>(P, lb, lds, b.stamps);
+        else wgrad16_tile<true, false>(P, lb, lds, b.stamps);
     } else {
-        if (P.x_bf16) wgrad16_tile<false, true>(P, lb, lds, st);
-        else wgrad16_tile<false, false>(P, lb, lds, st);
+        if (P.x_bf16) wgrad16_tile<false, true>(P, lb, lds, b.stamps);
+        else wgrad16_tile<false, false>(P, lb, lds, b.stamps);
     }
-    if (st && threadIdx.x == 0) { st[3] = __builtin_amdgcn_s_memtime(); st[6] = __builtin_amdgcn_s_memrealtime(); }
+    stamp_slot(b.stamps, blockIdx.x, 3);
 }
 
 }  // namespace

@@ -256,11 +256,8 @@ def test_golden_file_holds_every_record_and_nothing_else():
     assert os.path.getsize(GOLDEN) < 1_000_000
 
 
-@gpu
-@pytest.mark.parametrize("name", list(RECORDS))
-def test_gemm_bits_equal_the_build_before_the_device_half_was_tidied(lin, name):
-    """Every recorded array of this record, word for word."""
-    want, got = unpack(), recorded(lin, name)
+def assert_same_bits(want, got, name):
+    """got holds exactly the arrays that the golden file `want` has for record `name`, word for word."""
     assert sorted(got) == sorted(k for k in want if k.startswith(name + ":"))
     for key, a in got.items():
         ref = want[key]
@@ -271,13 +268,20 @@ def test_gemm_bits_equal_the_build_before_the_device_half_was_tidied(lin, name):
                                  f"{int(a[k]):#x} for {int(ref[k]):#x}")
 
 
-if __name__ == "__main__" and sys.argv[1:2] == ["record"]:
-    dest = sys.argv[2] if len(sys.argv) > 2 else GOLDEN
+@gpu
+@pytest.mark.parametrize("name", list(RECORDS))
+def test_gemm_bits_equal_the_build_before_the_device_half_was_tidied(lin, name):
+    """Every recorded array of this record, word for word."""
+    assert_same_bits(unpack(), recorded(lin, name), name)
+
+
+def record(names, recorded, dest):
+    """The recorder (also test_gpu_bf16_parent's): every record twice on this build, nothing written when the two runs differ."""
     os.makedirs(os.path.dirname(dest), exist_ok=True)
     make = getattr(lin, "_get_wrapped_function", None)
     L = (make() if make else lin.__wrapped__)()
     arrays = {}
-    for rec in RECORDS:
+    for rec in names:
         first, second = recorded(L, rec), recorded(L, rec)
         assert sorted(first) == sorted(second), rec
         for key in first:
@@ -287,3 +291,7 @@ if __name__ == "__main__" and sys.argv[1:2] == ["record"]:
         print(rec, len(first), "arrays", flush=True)
     np.savez_compressed(dest, **pack(arrays))
     print("wrote", dest, os.path.getsize(dest), "bytes,", len(arrays), "arrays")
+
+
+if __name__ == "__main__" and sys.argv[1:2] == ["record"]:
+    record(RECORDS, recorded, sys.argv[2] if len(sys.argv) > 2 else GOLDEN)
